@@ -8,9 +8,16 @@ src/mapping/pose_graph_optimization.rs:269-301): linearise + assemble, factor, s
 same work on the same pattern).  Headline workload = BASELINE.json configs[1]: intel.g2o, fp64.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload intel|m3500|dlr|sphere2500|torus3d|parking-garage|grid:WxH[:E]]
-                  [--precision f64|f32|mixed] [--shard [--emulate P]] [--no-secondary] [--no-cpu-baseline]
+                  [--precision f64|f32|mixed] [--shard [--emulate P]] [--dump-outputs DIR]
+                  [--full [--no-secondary] [--no-cpu-baseline]]
 
-Prints ONE JSON line (rank 0): the contract keys for the headline workload plus
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the contract keys of the
+headline workload (metric, value, unit, higher_is_better, dtype, ms_per_step, ...), nothing more.
+--dump-outputs DIR  after the timed steps: what the last rr_pgo_optimize call of the timed loop returned to its caller,
+                    as DIR/state.npy (the poses), DIR/errors.npy (its chi2 list), DIR/norm_dx.npy (its |dx| list), float64
+--full adds the figures and checks that take runs of their own:
+  iterate_async  the same K steps enqueued back to back; optimize(10) and new() + optimize(10) closure times
+  errors         the reference's loop from the initial state, compared with the oracle fixture where there is one
   roofline       dominant kernel class of the headline, HIP-event timing on the library's own stream
   cpu_baseline   the CPU oracle (1 thread, bounded sample; `nproc` = cores of the box), N = 1 only
   secondary      the other BASELINE configs, each timed with the SAME timed_steps contract (W warm-up steps,
@@ -317,6 +324,32 @@ def measure_single(ctx, workload, precision, steps, warmup, through="optimize"):
     return g, state0, dt
 
 
+def last_call_outputs(g):
+    """What the last rr_pgo_optimize call of optimize_steps returned to its caller: the poses it left in the handle, its
+    chi2 list and its |dx| list (PoseGraph.optimize_count keeps both lists in the buffers of that call)."""
+    errors, norms, n = g._opt_buf[:3]
+    return {"state": g.state(), "errors": errors[:n.value].copy(), "norm_dx": norms[:n.value - 1].copy()}
+
+
+DUMP_LIMIT_BYTES = 60 << 20   # the data of all files, so that the .npy headers keep the whole dump under 64 MB
+DUMP_WHOLE = 4096             # arrays up to this many entries are always written whole
+
+
+def dump_outputs(directory, arrays, limit=DUMP_LIMIT_BYTES):
+    """DIRECTORY/<name>.npy in float64 for every array.  If the data exceed `limit`, every array longer than DUMP_WHOLE is
+    cut to the same share of its entries by a fixed, seeded sample (the same indices from run to run, in order)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, np.float64).ravel() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    small = sum(a.nbytes for a in arrays.values() if a.size <= DUMP_WHOLE)
+    for name, a in arrays.items():
+        if total > limit and a.size > DUMP_WHOLE:
+            keep = a.size * (limit - small) // (total - small)
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def measure_sharded(ctx, workload, precision, steps, warmup, force_collectives=False):
     """ONE graph sharded over the ranks: rr_pgo_stage + RCCL collectives issued on the library's own stream
     (rustrobotics_amd.sharding.TorchShardDriver); no host synchronisation inside an iteration."""
@@ -465,8 +498,14 @@ def main():
     ap.add_argument("--workload", default="intel")
     ap.add_argument("--precision", default="f64", choices=["f64", "f32", "mixed"],
                     help="f64 (reference arithmetic), f32, or mixed = f64 state/linearisation + f32 factor/solve")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="headline workload only")
+    ap.add_argument("--full", action="store_true",
+                    help="also the figures and checks that take runs of their own: iterate_async, optimize(10) and closure "
+                         "times, the correctness leg, roofline, CPU baseline, the secondary BASELINE configs")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last optimize() call of the timed loop returned "
+                         "(state, errors, norm_dx) as DIR/<name>.npy, float64")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU oracle runs")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: headline workload only")
     ap.add_argument("--emulate", type=int, default=0, metavar="P",
                     help="with --shard on ONE GPU: P ranks emulated in this process (P handles, device copies as the two "
                          "collectives) -- exercises the N > 1 record shape and the sharded numerics; the time is P ranks "
@@ -482,6 +521,10 @@ def main():
                     help="shard ONE graph (--workload) over the ranks as the headline line (strong scaling); with one rank "
                          "the collectives still run, over a one-rank RCCL group")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.shard:
+        ap.error("--dump-outputs writes the outputs of the single-graph headline, not of --shard")
 
     # The contract is ONE JSON line on stdout.  RCCL / HIP libraries print banners through C stdio, which no Python
     # redirection catches: from here on file descriptor 1 IS stderr, the JSON line goes to the saved descriptor.
@@ -541,13 +584,33 @@ def main():
     else:
         g, state0, dt = measure_single(ctx, args.workload, args.precision, args.steps, args.warmup)
         value = args.steps * world / dt
-
-        def sync_g():
-            g.sync()
-            ctx.torch.cuda.synchronize()
-        # secondary figure: the same K iterations enqueued back to back by rr_pgo_iterate_async (no stop rule, nothing read back)
-        dt_async = timed_steps(g.iterate_async, sync_g, ctx.barrier, ctx.all_max, args.steps, args.warmup, reset=lambda: g.set_state(state0))
         if rank == 0:
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, last_call_outputs(g))
+            out = {
+                "metric": "GN iterations/s", "value": value, "unit": "GN iterations/s", "n_gpus": world,
+                "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps,
+                "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+                "dtype": args.precision, "data": "reference dataset file" if not args.workload.startswith("grid:") else "synthetic",
+                "config": {"workload": f"{args.workload} ({g.num_nodes} poses / {g.num_edges} edges / dim {g.len}), "
+                                       f"Gauss-Newton, " + ("one graph on one GPU" if world == 1 else
+                                                            f"{world} independent replicas, one per GPU: replicas (no communication)"),
+                           "solver": "GaussNewton",
+                           "timed_through": f"rr_pgo_optimize (= PoseGraph::optimize): optimize({OPTIMIZE_CALL}) from the initial state, "
+                                            f"restarted until {args.steps} iterations have run -- the reference's loop with its stop "
+                                            f"rule, its chi2 list and the restarts are inside the timed region",
+                           "parallelism": "single" if world == 1 else "replicas (no communication)"},
+                "edges_iters_per_s": value * g.num_edges,
+                "min_steps_for_a_stable_value": "the timed region is whole optimize() calls: below ~60 steps (ten calls on intel) "
+                                                "the value moves by a few per cent from run to run",
+            }
+        if args.full:
+            def sync_g():
+                g.sync()
+                ctx.torch.cuda.synchronize()
+            # secondary figure: the same K iterations enqueued back to back by rr_pgo_iterate_async (no stop rule, nothing read back)
+            dt_async = timed_steps(g.iterate_async, sync_g, ctx.barrier, ctx.all_max, args.steps, args.warmup, reset=lambda: g.set_state(state0))
+        if args.full and rank == 0:
             stats = g.stats()
             # correctness leg: the reference's bench shape, optimize(10) from the initial state
             g.set_state(state0)
@@ -584,25 +647,10 @@ def main():
                     del os.environ["RR_PGO_ANALYSIS_CACHE"]
             g.set_state(state0)
             roofline, mfma_kernel, class_bytes = roofline_of(g, args.workload, args.precision)
-            out = {
-                "metric": "GN iterations/s", "value": value, "unit": "GN iterations/s", "n_gpus": world,
-                "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps,
-                "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-                "dtype": args.precision, "data": "reference dataset file" if not args.workload.startswith("grid:") else "synthetic",
-                "config": {"workload": f"{args.workload} ({g.num_nodes} poses / {g.num_edges} edges / dim {g.len}), "
-                                       f"Gauss-Newton, " + ("one graph on one GPU" if world == 1 else
-                                                            f"{world} independent replicas, one per GPU: replicas (no communication)"),
-                           "solver": "GaussNewton",
-                           "timed_through": f"rr_pgo_optimize (= PoseGraph::optimize): optimize({OPTIMIZE_CALL}) from the initial state, "
-                                            f"restarted until {args.steps} iterations have run -- the reference's loop with its stop "
-                                            f"rule, its chi2 list and the restarts are inside the timed region",
-                           "parallelism": "single" if world == 1 else "replicas (no communication)"},
-                "edges_iters_per_s": value * g.num_edges,
+            out.update({
                 "iterate_async": {"value": args.steps * world / dt_async, "ms_per_step": 1e3 * dt_async / args.steps,
                                   "what": "the same K iterations through rr_pgo_iterate_async: enqueued back to back, no stop rule, "
                                           "nothing read back (the r01 - r05 headline)"},
-                "min_steps_for_a_stable_value": "the timed region is whole optimize() calls: below ~60 steps (ten calls on intel) "
-                                                "the value moves by a few per cent from run to run",
                 "optimize10_ms": opt_ms,
                 # like for like with earlier rounds and with cpu_baseline.closure_ms (the oracle analyses on every construction, as
                 # the reference's UMFPACK path does): the UNCACHED closure.  The steady state of the reference's bench loop, where
@@ -618,7 +666,7 @@ def main():
                 "stored_factor_bytes": stats["stored_factor_bytes"],
                 "big_fronts": stats["n_big_fronts"], "max_front": stats["max_front"],
                 "roofline": roofline, "mfma_kernel": mfma_kernel,
-            }
+            })
             gold = golden_chi2(args.workload)
             if gold is not None:
                 out["chi2_rel_diff_vs_oracle"] = abs(min(errors) - gold) / gold
@@ -637,8 +685,8 @@ def main():
     if out is not None and host_staged:
         out["rehearsal"] = (f"--collectives host-staged: {world} ranks on {torch.cuda.device_count()} GPU(s), gloo group, the sharded legs' "
                             f"collectives staged through host memory -- the N > 1 plan end to end, NOT a scaling measurement")
-    # ---- the other BASELINE configs, same contract (skipped when a non-default workload was asked for)
-    if not args.no_secondary and not args.shard and args.workload == "intel" and args.precision == "f64":
+    # ---- --full: the other BASELINE configs, same contract (skipped when a non-default workload was asked for)
+    if args.full and not args.no_secondary and not args.shard and args.workload == "intel" and args.precision == "f64":
         sec = []
         # The sharded legs (N > 1) are collectives that have never run on real multi-GPU hardware: if one of them
         # hangs, every rank leaves through this watchdog and rank 0 still prints the headline line (with whatever

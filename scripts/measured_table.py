@@ -30,7 +30,7 @@ for key, label in rows:
 dflt = json.load(open(os.path.join(ROOT, "profiles", f"{tag}_bench_default.json")))
 cb = dflt.get("cpu_baseline") or {}
 print()
-print(f"Default line (`python bench.py`, what the driver runs): {dflt['value']:.0f} {dflt['unit']}, CPU oracle on one core of the same box "
+print(f"Full line (`python bench.py --full`): {dflt['value']:.0f} {dflt['unit']}, CPU oracle on one core of the same box "
       f"{cb.get('value', 0):.0f} {cb.get('unit', '')} ({cb.get('kind')}; {cb.get('sample', '')[:120]}).")
 for s in dflt.get("secondary", []):
     cbs = s.get("cpu_baseline") or {}

@@ -180,3 +180,31 @@ def test_optimize_steps_runs_exactly_k_iterations_through_optimize_calls():
         for n, d in g.calls:   # every call asks for optimize(10), or for what is left of K
             assert n == min(left, bench.OPTIMIZE_CALL)
             left -= d
+
+
+def test_dump_outputs_writes_the_last_calls_arrays_and_caps_the_size(tmp_path):
+    """bench.py --dump-outputs: the state and the chi2 / |dx| lists of the last optimize() call, float64; above the size limit
+    the long arrays become the same seeded sample in every run and the short ones stay whole."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+
+    class Stub:
+        _opt_buf = (np.array([9.0, 5.0, 4.0, 0.0]), np.array([3.0, 1.0, 0.0]), type("N", (), {"value": 3})())
+
+        def state(self):
+            return np.arange(6.0)
+
+    bench.dump_outputs(str(tmp_path / "a"), bench.last_call_outputs(Stub()))
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in ("state", "errors", "norm_dx")}
+    assert got["state"].tolist() == list(range(6)) and got["errors"].tolist() == [9, 5, 4] and got["norm_dx"].tolist() == [3, 1]
+    assert all(a.dtype == np.float64 for a in got.values())
+
+    big = {"state": np.arange(100000, dtype=np.float32), "errors": np.arange(7.0)}
+    limit = 8 * 20000
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), big, limit=limit)
+    s_b, s_c = np.load(tmp_path / "b" / "state.npy"), np.load(tmp_path / "c" / "state.npy")
+    assert s_b.dtype == np.float64 and np.array_equal(s_b, s_c) and np.all(np.diff(s_b) > 0)
+    assert s_b.nbytes + 7 * 8 <= limit and len(s_b) > 19000
+    assert np.load(tmp_path / "b" / "errors.npy").tolist() == list(range(7))

@@ -1679,7 +1679,7 @@ def test_bench_py_runs_its_multi_rank_plan_under_torchrun_on_one_gpu(tmp_path):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", RR_PGO_BENCH_SECONDARY_LIMIT="400")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", port, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "12", "--warmup", "2",
-           "--collectives", "host-staged", "--lattice", "grid:120x80"]
+           "--collectives", "host-staged", "--lattice", "grid:120x80", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT, env=env, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -1699,3 +1699,29 @@ def test_bench_py_runs_its_multi_rank_plan_under_torchrun_on_one_gpu(tmp_path):
     ref = PoseGraph.synthetic_grid(120, 80, precision="mixed").optimize(10)
     assert abs(sec[0]["chi2_final"] - ref[-1]) <= 1e-9 * ref[-1] and sec[0]["stopped_by_reference_rule"]
     assert abs(sec[2]["chi2_final"] - 727.149667) <= 1e-5
+
+
+def test_bench_py_plain_run_times_k_steps_and_dumps_the_last_calls_outputs(tmp_path):
+    """bench.py without --full: the headline line alone, K timed steps, and --dump-outputs writes what the last optimize()
+    call of the timed loop returned.  K = 12 on intel.g2o is optimize(10) (the stop rule ends it after 6 iterations), then
+    optimize(6) from the initial state: the same 6 iterations a fresh graph's optimize(10) runs."""
+    import json
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "12", "--warmup", "2",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, cwd=ROOT, timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["metric"] == "GN iterations/s" and d["unit"] == "GN iterations/s" and d["higher_is_better"] and d["dtype"] == "f64"
+    assert d["steps"] == 12 and abs(d["value"] - 12 / (d["ms_per_step"] * 12e-3)) <= 1e-6 * d["value"]
+    assert not {"secondary", "roofline", "cpu_baseline", "iterate_async"} & set(d)
+    from rustrobotics_amd import PoseGraph
+    g = PoseGraph.new(g2o_path("intel"))
+    errors, norms = g.optimize(10, return_norms=True)
+    assert len(errors) == 7
+    # the module's fp64 tolerances (another process: the device's sums may run in another order)
+    np.testing.assert_allclose(np.load(tmp_path / "errors.npy"), errors, rtol=1e-9)
+    np.testing.assert_allclose(np.load(tmp_path / "norm_dx.npy"), norms, rtol=1e-9, atol=1e-8)
+    np.testing.assert_allclose(np.load(tmp_path / "state.npy"), g.state(), rtol=0, atol=1e-8)
