@@ -136,8 +136,8 @@ int rr_pgo_get_graph(const rr_pgo *h, rr_pgo_graph_desc *out);
 
 /* ---- the hot path -------------------------------------------------------- */
 
-/* global_error(graph)  (:537-574): sum_e e^T Omega e at the current state.
- * f64 result also in f32 mode. */
+/* global_error(graph)  (:537-574): sum_e e^T Omega e at the current state (sum_e rho(s_e) while a robust kernel is
+ * set, see below).  f64 result also in f32 mode. */
 int rr_pgo_chi2(rr_pgo *h, double *out);
 
 /* build_linear_system(lambda)?.solve()?  (:271 ; linearize_and_solve :371-373
@@ -170,6 +170,27 @@ int rr_pgo_get_state(rr_pgo *h, double *out);
  * stream (everything else the handle does is ordered behind it); setting the state of the previous call again costs a
  * comparison and one device-side copy. */
 int rr_pgo_set_state(rr_pgo *h, const double *state);
+
+/* ---- robust kernels (build-defined; the reference has none) -------------
+ * s_e = e^T Omega e of edge e at the current state (the term global_error sums, :537-574).  A kernel rho with
+ * parameter delta > 0 (g2o's convention: delta is in the units of sqrt(s)):
+ *   RR_PGO_ROBUST_NONE    rho(s) = s, w = 1: the default, plain least squares
+ *   RR_PGO_ROBUST_HUBER   rho(s) = s if s <= delta^2, else 2 delta sqrt(s) - delta^2;  w = rho'(s) = 1 or delta / sqrt(s)
+ *   RR_PGO_ROBUST_CAUCHY  rho(s) = delta^2 log(1 + s / delta^2);                       w = 1 / (1 + s / delta^2)
+ *   s < 0 (an indefinite Omega): rho(s) = s, w = 1.
+ * IRLS as g2o does it, without the rho'' term: every robustified edge adds w J^T Omega J to H and w J^T Omega e to b,
+ * w taken at the state being linearised; its term in chi2 is rho(s_e).  The anchor prior (1e7) and the LM lambda are
+ * never weighted.  So while a kernel is set, rr_pgo_chi2, the errors_out of rr_pgo_optimize and the values
+ * Levenberg-Marquardt compares are the robust cost sum_e rho(s_e); the stop rule |dx| < 1e-4 is unchanged.
+ * The setting is per handle (a new handle starts with NONE) and holds from the next linearisation on, for every entry
+ * point that linearises (rr_pgo_stage on sharded handles included).  Arithmetic in the linearisation's type: f64 in the
+ * f64 and mixed modes, f32 in the f32 mode; chi2 sums in f64. */
+enum { RR_PGO_ROBUST_NONE = 0, RR_PGO_ROBUST_HUBER = 1, RR_PGO_ROBUST_CAUCHY = 2 };
+/* edge_mask: [n_edges], nonzero = robustified; NULL = every edge.  Copied.  EINVAL: unknown kind, delta not finite or <= 0
+ * (NONE ignores delta), mask length implied by n_edges. */
+int rr_pgo_set_robust_kernel(rr_pgo *h, int32_t kind, double delta, const int32_t *edge_mask);
+/* s_e = e^T Omega e and w_e at the current state, file order; weight_out may be NULL.  EUNSUPPORTED on sharded handles. */
+int rr_pgo_edge_errors(rr_pgo *h, double *chi2_out, double *weight_out);
 
 /* ---- inspection of the assembled system (parity tests) ------------------- */
 

@@ -6,6 +6,9 @@
         (the reference picks file / solver / plot from interactive menus; --plot writes img/{name}-{iteration}-{solver}.svg
         before the first and after every iteration, like :266-268, :294-296)
 
+  --robust huber:DELTA | cauchy:DELTA  (both modes): a robust kernel on every edge (include/rr_pgo.h); the errors printed
+      are then the robust cost
+
   python -m rustrobotics_amd <file.g2o> --bench [--repeats 20]
       = benches/graph_slam.rs:9-10   PoseGraph::new("dataset/g2o/intel.g2o", GaussNewton)?.optimize(10, false, false)
         timed end to end like criterion does: parsing, symbolic analysis, device setup and the ten
@@ -19,6 +22,18 @@ import time
 from .mapping import PoseGraph, PoseGraphSolver
 
 
+def _robust_arg(text):
+    kind, sep, delta = text.partition(":")
+    kind = kind.strip().lower()
+    try:
+        d = float(delta)
+    except ValueError:
+        d = float("nan")
+    if kind not in ("huber", "cauchy") or not sep or not (d > 0 and d != float("inf")):
+        raise argparse.ArgumentTypeError(f"expected huber:DELTA or cauchy:DELTA with DELTA > 0, got {text!r}")
+    return kind, d
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m rustrobotics_amd", description=__doc__,
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -29,22 +44,33 @@ def main(argv=None):
     ap.add_argument("--plot", action="store_true", help="the example's third menu: write ./img/{name}-{iteration}-{solver}.svg")
     ap.add_argument("--bench", action="store_true", help="time new() + optimize(10, false, false) like benches/graph_slam.rs")
     ap.add_argument("--repeats", type=int, default=20)
+    ap.add_argument("--robust", type=_robust_arg, default=None, metavar="KIND:DELTA",
+                    help="robust kernel on every edge: huber:DELTA or cauchy:DELTA")
     a = ap.parse_args(argv)
     solver = PoseGraphSolver[a.solver]
+
+    def new():
+        g = PoseGraph.new(a.file, solver, precision=a.precision)
+        if a.robust:
+            g.set_robust_kernel(*a.robust)
+        return g
+
     if not a.bench:
-        graph = PoseGraph.new(a.file, solver, precision=a.precision)
-        graph.optimize(50 if a.iterations is None else a.iterations, True, a.plot)
+        if a.robust:
+            print(f"robust kernel {a.robust[0]}, delta {a.robust[1]:g}")
+        new().optimize(50 if a.iterations is None else a.iterations, True, a.plot)
         return 0
     iters = 10 if a.iterations is None else a.iterations
-    PoseGraph.new(a.file, solver, precision=a.precision).optimize(iters, False, False)   # warm-up: library load, HIP context
+    new().optimize(iters, False, False)   # warm-up: library load, HIP context
     ms = []
     for _ in range(a.repeats):
         t0 = time.perf_counter()
-        errors = PoseGraph.new(a.file, solver, precision=a.precision).optimize(iters, False, False)
+        errors = new().optimize(iters, False, False)
         ms.append((time.perf_counter() - t0) * 1e3)
-    print(f"graph_slam: new() + optimize({iters}, false, false) on {a.file}: mean {statistics.mean(ms):.3f} ms, "
+    rob = f" with {a.robust[0]}:{a.robust[1]:g}" if a.robust else ""
+    print(f"graph_slam: new() + optimize({iters}, false, false){rob} on {a.file}: mean {statistics.mean(ms):.3f} ms, "
           f"median {statistics.median(ms):.3f} ms, min {min(ms):.3f} ms over {a.repeats} runs; "
-          f"{len(errors) - 1} iterations run, final chi2 {errors[-1]:.9g}")
+          f"{len(errors) - 1} iterations run, final {'robust cost' if a.robust else 'chi2'} {errors[-1]:.9g}")
     return 0
 
 

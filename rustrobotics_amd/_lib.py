@@ -16,6 +16,8 @@ LIB_PATH = os.path.join(_HERE, "librr_pgo.so")
 OK, EINVAL, EIO, EPARSE, ENODEVICE, ENOTSPD, ENOMEM, EUNSUPPORTED, ETIMEOUT = 0, -1, -2, -3, -4, -5, -6, -7, -8
 ABI_VERSION = 4   # RR_PGO_ABI_VERSION this mirror was written against (load() checks the library's)
 F64, F32, MIXED = 0, 1, 2
+ROBUST_NONE, ROBUST_HUBER, ROBUST_CAUCHY = 0, 1, 2   # RR_PGO_ROBUST_* (rr_pgo_set_robust_kernel)
+ROBUST_KERNELS = {None: ROBUST_NONE, "none": ROBUST_NONE, "huber": ROBUST_HUBER, "cauchy": ROBUST_CAUCHY}
 PRECISIONS = {"f64": F64, "f32": F32, "mixed": MIXED}
 NUM_KCLASS = 11
 KCLASS_NAMES = ("linearize", "factor", "solve", "update", "reduce", "big_assembly", "big_panel", "big_update",
@@ -29,7 +31,7 @@ EXPORTS = (
     "rr_pgo_get_state", "rr_pgo_set_state", "rr_pgo_assemble", "rr_pgo_iterate_async", "rr_pgo_sync",
     "rr_pgo_get_stats", "rr_pgo_analyze_g2o", "rr_pgo_abi_version", "rr_pgo_debug_withhold", "rr_pgo_profile", "rr_pgo_synth_grid", "rr_pgo_synth_free",
     "rr_pgo_exchange_buffer", "rr_pgo_set_exchange_buffer", "rr_pgo_stage", "rr_pgo_stage_scalars", "rr_pgo_stream",
-    "rr_pgo_node_owner", "rr_pgo_trim",
+    "rr_pgo_node_owner", "rr_pgo_trim", "rr_pgo_set_robust_kernel", "rr_pgo_edge_errors",
 )
 
 
@@ -126,6 +128,8 @@ def load():
     L.rr_pgo_analyze_g2o.argtypes = [C.c_char_p, C.POINTER(Options), C.POINTER(Stats)]
     L.rr_pgo_abi_version.restype = C.c_int32
     L.rr_pgo_debug_withhold.argtypes = [vp, C.c_int32]
+    L.rr_pgo_set_robust_kernel.argtypes = [vp, C.c_int32, C.c_double, ip]
+    L.rr_pgo_edge_errors.argtypes = [vp, dp, dp]
     if L.rr_pgo_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH} speaks ABI version {L.rr_pgo_abi_version()}, this mirror {ABI_VERSION}: rebuild the library")
     _lib = L

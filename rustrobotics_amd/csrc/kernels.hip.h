@@ -188,6 +188,8 @@ template <typename T, typename TC = T> struct LinArgs {
                                          //      2: a chi2-only item: always published from here (and kept as OptCtrl::last_error)
   OptSlot *ring_host;
   int *blocks_done;                      // zero between launches
+  TC robust_delta, robust_delta2;        // robust kernel (k_linearize's RK): delta and delta^2
+  const uint8_t *robust_mask;            // per edge: 1 = robustified; null = every edge
 };
 template <typename A> __device__ __forceinline__ void opt_reset_in_first_thread(const A &a) {
   if (a.reset_ctrl && blockIdx.x == 0 && threadIdx.x == 0) {
@@ -241,6 +243,28 @@ __device__ __forceinline__ void edge_linearize_2d(int kind, const typename VecT<
     B[1][0] = -i; B[1][1] = r;  B[1][2] = 0;
     B[2][0] = 0;  B[2][1] = 0;  B[2][2] = 0;
   }
+}
+
+// e^T W e of one 2D edge (the reference's chi2 term, :555,568)
+template <typename T> __device__ __forceinline__ T edge_chi2_2d(const T W[3][3], const T e[3]) {
+  const T we0 = W[0][0] * e[0] + W[0][1] * e[1] + W[0][2] * e[2];
+  const T we1 = W[1][0] * e[0] + W[1][1] * e[1] + W[1][2] * e[2];
+  const T we2 = W[2][0] * e[0] + W[2][1] * e[1] + W[2][2] * e[2];
+  return e[0] * we0 + e[1] * we1 + e[2] * we2;
+}
+
+// Robust kernels (include/rr_pgo.h, rr_pgo_set_robust_kernel): rho(s) and the IRLS weight w = rho'(s) at s = e^T W e.
+// A template argument of the linearisation kernels: the NONE instantiation is the plain least-squares code.
+enum : int { ROBUST_NONE = 0, ROBUST_HUBER = 1, ROBUST_CAUCHY = 2 };
+template <int RK, typename T> __device__ __forceinline__ T robust_weight(T s, T delta, T delta2) {
+  if (RK == ROBUST_HUBER) return s > delta2 ? delta / sqrt(s) : (T)1;
+  if (RK == ROBUST_CAUCHY) return s > (T)0 ? (T)1 / ((T)1 + s / delta2) : (T)1;
+  return (T)1;
+}
+template <int RK, typename T> __device__ __forceinline__ T robust_rho(T s, T delta, T delta2) {
+  if (RK == ROBUST_HUBER) return s > delta2 ? (T)2 * delta * sqrt(s) - delta2 : s;
+  if (RK == ROBUST_CAUCHY) return s > (T)0 ? delta2 * log1p(s / delta2) : s;
+  return s;
 }
 
 template <typename T> __device__ __forceinline__ T group_sum8(T v) {   // sum over the LIN_GROUP lanes of a node
@@ -383,7 +407,10 @@ template <typename A> __device__ __forceinline__ void opt_publish_chi2_in_last_b
 // (deterministic: no atomics, fixed summation order), builds the node's
 // diagonal block and right-hand side; the lane holding an edge in its `from`
 // role also writes the off-diagonal block and the edge's chi2 term.
-template <typename TO, typename T>
+// RK: the robust kernel (ROBUST_*).  Every incidence of a robustified edge computes s = e^T W e and scales W by w(s) before
+// J^T W is formed, so the diagonal block, the right-hand side and the off-diagonal block all carry the weight; both endpoints'
+// lanes compute e from the same operands, hence the same w.  The from-role lane adds rho(s) to chi2.
+template <typename TO, typename T, int RK = ROBUST_NONE>
 __global__ void __launch_bounds__(LIN_THREADS) k_linearize(LinArgs<TO, T> a) {
   using V4 = typename VecT<T>::V4;
   using V2 = typename VecT<T>::V2;
@@ -417,9 +444,22 @@ __global__ void __launch_bounds__(LIN_THREADS) k_linearize(LinArgs<TO, T> a) {
       const V4 z = rec.meas;
       const V4 wa = rec.info_a;
       const V2 wb = rec.info_b;
-      const T W[3][3] = {{wa.x, wa.y, wa.z}, {wa.y, wa.w, wb.x}, {wa.z, wb.x, wb.y}};
+      T W[3][3] = {{wa.x, wa.y, wa.z}, {wa.y, wa.w, wb.x}, {wa.z, wb.x, wb.y}};
       T e[3], A[3][3], B[3][3];
       edge_linearize_2d<T>(kind, role ? other : self, role ? self : other, z, e, A, B);
+      T s_rob = 0;
+      bool rob = false;
+      if constexpr (RK != ROBUST_NONE) {
+        s_rob = edge_chi2_2d<T>(W, e);
+        rob = !a.robust_mask || a.robust_mask[k];
+        if (rob) {   // masked-off edges keep W as it is
+          const T w = robust_weight<RK, T>(s_rob, a.robust_delta, a.robust_delta2);
+#pragma unroll
+          for (int i = 0; i < 3; i++)
+#pragma unroll
+            for (int j = 0; j < 3; j++) W[i][j] *= w;
+        }
+      }
       // J = A (from role) or B (to role);  JW = J^T W
       T JW[3][3];
 #pragma unroll
@@ -446,11 +486,12 @@ __global__ void __launch_bounds__(LIN_THREADS) k_linearize(LinArgs<TO, T> a) {
         for (int i = 0; i < 3; i++) bv[i] += JW[i][0] * e[0] + JW[i][1] * e[1] + JW[i][2] * e[2];
       }
       if (role == 0) {
-        // chi2 term e^T W e (:555,568), accumulated in f64
-        T we0 = W[0][0] * e[0] + W[0][1] * e[1] + W[0][2] * e[2];
-        T we1 = W[1][0] * e[0] + W[1][1] * e[1] + W[1][2] * e[2];
-        T we2 = W[2][0] * e[0] + W[2][1] * e[1] + W[2][2] * e[2];
-        if (owns) chi += (double)(e[0] * we0 + e[1] * we1 + e[2] * we2);   // every edge's term is owned by one rank
+        // chi2 term e^T W e (:555,568), accumulated in f64; rho(e^T W e) under a robust kernel
+        if constexpr (RK == ROBUST_NONE) {
+          if (owns) chi += (double)edge_chi2_2d<T>(W, e);   // every edge's term is owned by one rank
+        } else {
+          if (owns) chi += (double)(rob ? robust_rho<RK, T>(s_rob, a.robust_delta, a.robust_delta2) : s_rob);
+        }
         if (a.write_system && (ent & 8)) {
           // off-diagonal block H[from rows, to cols] = A^T W B
           const int64_t so = rec.slot;
@@ -799,7 +840,22 @@ template <typename T, typename TC = T> struct LinArgs3 {
   int publish;
   OptSlot *ring_host;
   int *blocks_done;
+  TC robust_delta, robust_delta2;       // as LinArgs
+  const uint8_t *robust_mask;
 };
+
+// e^T W e of one SE(3) edge
+template <typename T> __device__ __forceinline__ T edge_chi2_3d(const T W[6][6], const T e[6]) {
+  T c2 = 0;
+#pragma unroll
+  for (int i = 0; i < 6; i++) {
+    T we = 0;
+#pragma unroll
+    for (int r = 0; r < 6; r++) we += W[i][r] * e[r];
+    c2 += e[i] * we;
+  }
+  return c2;
+}
 
 template <typename T> __device__ __forceinline__ void q_mul(const T a[4], const T b[4], T r[4]) {
   r[0] = a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1];
@@ -878,7 +934,7 @@ __device__ void edge_linearize_3d(int role, const T ti[3], const T qi[4], const 
   }
 }
 
-template <typename TO, typename T>
+template <typename TO, typename T, int RK = ROBUST_NONE>   // RK: as k_linearize
 __global__ void __launch_bounds__(LIN_THREADS) k_linearize_se3(LinArgs3<TO, T> a) {
   using V4 = typename VecT<T>::V4;
   __shared__ double red[LIN_THREADS / 64];
@@ -922,6 +978,19 @@ __global__ void __launch_bounds__(LIN_THREADS) k_linearize_se3(LinArgs3<TO, T> a
       T e[6], J[6][6];
       if (role) edge_linearize_3d<T>(1, to, qo, ts, qs, tz, qz, e, J);
       else edge_linearize_3d<T>(0, ts, qs, to, qo, tz, qz, e, J);
+      T s_rob = 0;
+      bool rob = false;
+      if constexpr (RK != ROBUST_NONE) {
+        s_rob = edge_chi2_3d<T>(W, e);
+        rob = !a.robust_mask || a.robust_mask[k];
+        if (rob) {
+          const T w = robust_weight<RK, T>(s_rob, a.robust_delta, a.robust_delta2);
+#pragma unroll
+          for (int i = 0; i < 6; i++)
+#pragma unroll
+            for (int j = 0; j < 6; j++) W[i][j] *= w;
+        }
+      }
       T JW[6][6];   // J^T W
 #pragma unroll
       for (int i = 0; i < 6; i++)
@@ -952,15 +1021,11 @@ __global__ void __launch_bounds__(LIN_THREADS) k_linearize_se3(LinArgs3<TO, T> a
         }
       }
       if (role == 0) {
-        T c2 = 0;
-#pragma unroll
-        for (int i = 0; i < 6; i++) {
-          T we = 0;
-#pragma unroll
-          for (int r = 0; r < 6; r++) we += W[i][r] * e[r];
-          c2 += e[i] * we;
+        if constexpr (RK == ROBUST_NONE) {
+          if (owns) chi += (double)edge_chi2_3d<T>(W, e);
+        } else {
+          if (owns) chi += (double)(rob ? robust_rho<RK, T>(s_rob, a.robust_delta, a.robust_delta2) : s_rob);
         }
-        if (owns) chi += (double)c2;
         if (a.write_system && (ent & 8)) {
           // off-diagonal block H[from rows, to cols] = A^T W B: B of the same edge
           T e2[6], Bm[6][6];
@@ -1008,6 +1073,58 @@ __global__ void __launch_bounds__(LIN_THREADS) k_linearize_se3(LinArgs3<TO, T> a
   double tot = block_sum<double, LIN_THREADS>(chi, red);
   if (threadIdx.x == 0) a.chi2_partial[blockIdx.x] = tot;
   opt_publish_chi2_in_last_block(a, red);
+}
+
+// rr_pgo_edge_errors: one thread per edge, s = e^T W e and the robust weight w(s) at the current state, in f64 (file order).
+// The same error code as the linearisation kernels (edge_linearize_2d / edge_linearize_3d), in TC.
+template <typename TC> struct EdgeErrArgs {
+  int n_edges, is3d, kind;               // kind: ROBUST_*
+  const EdgeRec<TC> *e_rec;              // SE(2)
+  const typename VecT<TC>::V4 *pose;     // SE(2): 1 per node; SE(3): 2 per node
+  const int2 *e_idx;                     // SE(3)
+  const typename VecT<TC>::V4 *e_meas;   // SE(3): 2 per edge
+  const TC *e_info;                      // SE(3): 21 per edge
+  const uint8_t *node_dim;               // SE(2): 3 (pose) or 2 (landmark: the edge into it is pose-landmark)
+  TC delta, delta2;
+  const uint8_t *mask;                   // null: every edge
+  double *s_out, *w_out;
+};
+template <typename TC> __global__ void __launch_bounds__(256) k_edge_errors(EdgeErrArgs<TC> a) {
+  using V4 = typename VecT<TC>::V4;
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  if (k >= a.n_edges) return;
+  TC s;
+  if (!a.is3d) {
+    const EdgeRec<TC> rec = a.e_rec[k];
+    const V4 wa = rec.info_a;
+    const typename VecT<TC>::V2 wb = rec.info_b;
+    const TC W[3][3] = {{wa.x, wa.y, wa.z}, {wa.y, wa.w, wb.x}, {wa.z, wb.x, wb.y}};
+    TC e[3], A[3][3], B[3][3];
+    edge_linearize_2d<TC>(a.node_dim[rec.to] == 2 ? 1 : 0, a.pose[rec.from], a.pose[rec.to], rec.meas, e, A, B);
+    s = edge_chi2_2d<TC>(W, e);
+  } else {
+    const int2 ft = a.e_idx[k];
+    const V4 it = a.pose[2 * ft.x], iq = a.pose[2 * ft.x + 1], jt = a.pose[2 * ft.y], jq = a.pose[2 * ft.y + 1];
+    const V4 zt = a.e_meas[2 * k], zq = a.e_meas[2 * k + 1];
+    const TC ti[3] = {it.x, it.y, it.z}, qi[4] = {iq.x, iq.y, iq.z, iq.w};
+    const TC tj[3] = {jt.x, jt.y, jt.z}, qj[4] = {jq.x, jq.y, jq.z, jq.w};
+    const TC tz[3] = {zt.x, zt.y, zt.z}, qz[4] = {zq.x, zq.y, zq.z, zq.w};
+    TC W[6][6];
+    const TC *w = a.e_info + (int64_t)k * 21;
+    int t = 0;
+    for (int i = 0; i < 6; i++)
+      for (int j = i; j < 6; j++) { W[i][j] = w[t]; W[j][i] = w[t]; t++; }
+    TC e[6], J[6][6];
+    edge_linearize_3d<TC>(0, ti, qi, tj, qj, tz, qz, e, J);
+    s = edge_chi2_3d<TC>(W, e);
+  }
+  TC wt = 1;
+  if (!a.mask || a.mask[k]) {
+    if (a.kind == ROBUST_HUBER) wt = robust_weight<ROBUST_HUBER, TC>(s, a.delta, a.delta2);
+    else if (a.kind == ROBUST_CAUCHY) wt = robust_weight<ROBUST_CAUCHY, TC>(s, a.delta, a.delta2);
+  }
+  a.s_out[k] = (double)s;
+  if (a.w_out) a.w_out[k] = (double)wt;
 }
 
 template <typename T, typename TC = T> struct UpdArgs3 {

@@ -249,6 +249,8 @@ struct EngineBase {
   virtual void stage(int stage, double lambda, int lm) = 0;
   virtual void read_last_scalars(double *chi, double *norm) = 0;
   virtual void debug_withhold(int mode) = 0;   // failure injection for the dataflow launches (rr_pgo_debug_withhold)
+  virtual void set_robust(int kind, double delta, const int32_t *mask) = 0;   // rr_pgo_set_robust_kernel (arguments checked)
+  virtual void edge_errors(double *s_out, double *w_out) = 0;                  // rr_pgo_edge_errors
   int n_launches_per_iter = 0;
 };
 
@@ -428,6 +430,12 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   bool no_graph_ = false, force_graph_ = false;   // RR_PGO_NO_GRAPH=1 / RR_PGO_FORCE_GRAPH=1 (read when the handle is created): plain launches / replays of the captured hipGraph everywhere
   bool edge_lin_ = false;           // RR_PGO_EDGE_LINEARIZE=1: k_linearize_edges (one thread per edge, atomics) instead of the pull form
   bool edge_lin_wave_ = false;      // RR_PGO_EDGE_LINEARIZE=2: k_linearize_wave_edges (one WAVEFRONT per edge, operands staged in LDS, LDS-reduced scatter-add)
+  bool edge_lin_env_ = false, edge_lin_wave_env_ = false;   // what the knob asked for (a robust kernel runs the pull form)
+  int lin_blocks_pull_ = 0, lin_blocks_edge_ = 0;            // n_lin_blocks_ of the pull form / of the edge-parallel form
+  // robust kernel (rr_pgo_set_robust_kernel): ROBUST_* of kernels.hip.h, delta, per-edge mask (empty: every edge)
+  int robust_kind_ = ROBUST_NONE;
+  double robust_delta_ = 1.0;
+  DevBuf<uint8_t> robust_mask_;
   int host_counter_ = 0;             // mirrors the device slot counter
 
  public:
@@ -603,11 +611,15 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     if (const char *e = getenv("RR_PGO_SOLVE_FLOW")) solve_flow_on_ = std::atoi(e) != 0;
     if (const char *e = getenv("RR_PGO_FLOW_SCHUR_MIN")) flow_schur_min_ = std::atoi(e);
     n_lin_blocks_ = (int)(((int64_t)n_list_ * LIN_GROUP + LIN_THREADS - 1) / LIN_THREADS);
+    lin_blocks_pull_ = n_lin_blocks_;
     edge_lin_ = getenv("RR_PGO_EDGE_LINEARIZE") != nullptr && !is3d_ && !sharded_ && g_.n_edges() > 0;
     edge_lin_wave_ = edge_lin_ && std::atoi(getenv("RR_PGO_EDGE_LINEARIZE")) == 2;
     if (edge_lin_) n_lin_blocks_ = std::max(1, (g_.n_edges() + (edge_lin_wave_ ? WE_EDGES : LIN_THREADS) - 1) / (edge_lin_wave_ ? WE_EDGES : LIN_THREADS));
+    edge_lin_env_ = edge_lin_;
+    edge_lin_wave_env_ = edge_lin_wave_;
+    lin_blocks_edge_ = n_lin_blocks_;
     n_upd_blocks_ = (n_list_ + UPD_THREADS - 1) / UPD_THREADS;
-    chi_partial_.alloc((size_t)n_lin_blocks_);
+    chi_partial_.alloc((size_t)(edge_lin_ ? std::max(lin_blocks_pull_, lin_blocks_edge_) : n_lin_blocks_));   // (a robust kernel switches to the pull form)
     norm_partial_.alloc((size_t)n_upd_blocks_);
     hist_.alloc(2 * HIST);
     hist_.zero();
@@ -1512,7 +1524,13 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     a.fill_words = lds_flow_ ? reinterpret_cast<unsigned *>(x_ptr_) : nullptr;
     a.n_fill_words = lds_flow_ ? (int)((size_t)g_.dim * sizeof(T) / 4) : 0;
     opt_lin_fields(a, lm);
+    robust_fields(a);
     return a;
+  }
+  template <typename A> void robust_fields(A &a) const {
+    a.robust_delta = (S)robust_delta_;
+    a.robust_delta2 = (S)(robust_delta_ * robust_delta_);
+    a.robust_mask = robust_mask_.n ? robust_mask_.p : nullptr;
   }
   // what a linearisation inside a pipelined rr_pgo_optimize call carries: the reset of the loop state (first launch of
   // the call), lambda from the device (Levenberg-Marquardt)
@@ -1613,8 +1631,15 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
       else hipLaunchKernelGGL((k_linearize_edges<T, S>), dim3(n_lin_blocks_), dim3(LIN_THREADS), 0, stream_, la, g_.n_edges());
       if (write_system) hipLaunchKernelGGL((k_lin_finish<T, S>), dim3(nb), dim3(256), 0, stream_, la);
     } else if (!is3d_) {
-      hipLaunchKernelGGL((k_linearize<T, S>), dim3(n_lin_blocks_), dim3(LIN_THREADS), 0, stream_,
-                         lin_args(lambda, lm, write_system, reference_prior));
+      if (robust_kind_ == ROBUST_HUBER)
+        hipLaunchKernelGGL((k_linearize<T, S, ROBUST_HUBER>), dim3(n_lin_blocks_), dim3(LIN_THREADS), 0, stream_,
+                           lin_args(lambda, lm, write_system, reference_prior));
+      else if (robust_kind_ == ROBUST_CAUCHY)
+        hipLaunchKernelGGL((k_linearize<T, S, ROBUST_CAUCHY>), dim3(n_lin_blocks_), dim3(LIN_THREADS), 0, stream_,
+                           lin_args(lambda, lm, write_system, reference_prior));
+      else
+        hipLaunchKernelGGL((k_linearize<T, S>), dim3(n_lin_blocks_), dim3(LIN_THREADS), 0, stream_,
+                           lin_args(lambda, lm, write_system, reference_prior));
     } else {
       LinArgs3<T, S> a;
       a.n_nodes = n_list_;
@@ -1640,7 +1665,10 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
       a.fill_words = lds_flow_ ? reinterpret_cast<unsigned *>(x_ptr_) : nullptr;
       a.n_fill_words = lds_flow_ ? (int)((size_t)g_.dim * sizeof(T) / 4) : 0;
       opt_lin_fields(a, lm);
-      hipLaunchKernelGGL((k_linearize_se3<T, S>), dim3(n_lin_blocks_), dim3(LIN_THREADS), 0, stream_, a);
+      robust_fields(a);
+      if (robust_kind_ == ROBUST_HUBER) hipLaunchKernelGGL((k_linearize_se3<T, S, ROBUST_HUBER>), dim3(n_lin_blocks_), dim3(LIN_THREADS), 0, stream_, a);
+      else if (robust_kind_ == ROBUST_CAUCHY) hipLaunchKernelGGL((k_linearize_se3<T, S, ROBUST_CAUCHY>), dim3(n_lin_blocks_), dim3(LIN_THREADS), 0, stream_, a);
+      else hipLaunchKernelGGL((k_linearize_se3<T, S>), dim3(n_lin_blocks_), dim3(LIN_THREADS), 0, stream_, a);
     }
     check_launch("k_linearize");
     pend(RR_PGO_K_LINEARIZE);
@@ -2491,6 +2519,55 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   // is looked for in a word nobody sets; 2: k_solve_flow -- the same for the parent flag of one front; 3: k_big_flow --
   // the first PANEL task of the first flow level publishes its X blocks in the dead words behind the live flags;
   // 0: everything back.  The captured graphs hold pointers, not contents: no re-capture.
+  // ---- robust kernels (include/rr_pgo.h, rr_pgo_set_robust_kernel)
+  void set_robust(int kind, double delta, const int32_t *mask) override {
+    std::vector<uint8_t> m;
+    if (kind != ROBUST_NONE && mask) {
+      m.resize((size_t)g_.n_edges());
+      for (int k = 0; k < g_.n_edges(); k++) m[k] = mask[k] != 0 ? 1 : 0;
+    }
+    HIPCHK(hipStreamSynchronize(stream_));   // launches already enqueued read the old mask
+    robust_mask_.upload(m);                  // (empty: freed, every edge)
+    robust_kind_ = kind;
+    robust_delta_ = kind != ROBUST_NONE ? delta : 1.0;
+    // the captured graphs hold the old kernel and its arguments
+    if (gn_exec_) { (void)hipGraphExecDestroy(gn_exec_); gn_exec_ = nullptr; }
+    for (hipGraphExec_t &e : stage_exec_) if (e) { (void)hipGraphExecDestroy(e); e = nullptr; }
+    // the edge-parallel experiment forms have no robust instantiation: the pull form runs while a kernel is set
+    edge_lin_ = edge_lin_env_ && kind == ROBUST_NONE;
+    edge_lin_wave_ = edge_lin_wave_env_ && kind == ROBUST_NONE;
+    n_lin_blocks_ = edge_lin_ ? lin_blocks_edge_ : lin_blocks_pull_;
+  }
+  void edge_errors(double *s_out, double *w_out) override {
+    if (sharded_) throw ApiError(RR_PGO_EUNSUPPORTED, "rr_pgo_edge_errors on a sharded handle");
+    const int E = g_.n_edges();
+    if (E == 0) return;
+    DevBuf<double> out;
+    out.alloc(2 * (size_t)E);
+    EdgeErrArgs<S> a;
+    a.n_edges = E;
+    a.is3d = is3d_ ? 1 : 0;
+    a.kind = robust_kind_;
+    a.e_rec = e_rec_.p;
+    a.pose = pose_.p;
+    a.e_idx = e_idx_.p;
+    a.e_meas = e_meas_.p;
+    a.e_info = e_info3_.p;
+    a.node_dim = node_dim_.p;
+    a.delta = (S)robust_delta_;
+    a.delta2 = (S)(robust_delta_ * robust_delta_);
+    a.mask = robust_mask_.n ? robust_mask_.p : nullptr;
+    a.s_out = out.p;
+    a.w_out = out.p + E;
+    hipLaunchKernelGGL((k_edge_errors<S>), dim3((E + 255) / 256), dim3(256), 0, stream_, a);
+    check_launch("k_edge_errors");
+    std::vector<double> host(2 * (size_t)E);
+    HIPCHK(hipMemcpyAsync(host.data(), out.p, host.size() * sizeof(double), hipMemcpyDeviceToHost, stream_));
+    HIPCHK(hipStreamSynchronize(stream_));
+    std::memcpy(s_out, host.data(), E * sizeof(double));
+    if (w_out) std::memcpy(w_out, host.data() + E, E * sizeof(double));
+  }
+
   void debug_withhold(int mode) override {
     HIPCHK(hipStreamSynchronize(stream_));
     if (mode == 0) {
@@ -3078,6 +3155,25 @@ int rr_pgo_assemble(rr_pgo *h, double lambda, int lm, int32_t *n_blocks, int32_t
     std::memcpy(bvals, hv.data(), hv.size() * sizeof(double));
     if (b_out) std::memcpy(b_out, b.data(), b.size() * sizeof(double));
   });
+}
+
+int rr_pgo_set_robust_kernel(rr_pgo *h, int32_t kind, double delta, const int32_t *edge_mask) {
+  if (!h) { g_last_error = "null argument"; return RR_PGO_EINVAL; }
+  if (kind != RR_PGO_ROBUST_NONE && kind != RR_PGO_ROBUST_HUBER && kind != RR_PGO_ROBUST_CAUCHY) {
+    g_last_error = "unknown robust kernel " + std::to_string(kind);
+    return RR_PGO_EINVAL;
+  }
+  if (kind != RR_PGO_ROBUST_NONE && !(std::isfinite(delta) && delta > 0.0)) {
+    g_last_error = "robust kernel delta must be finite and > 0";
+    return RR_PGO_EINVAL;
+  }
+  static_assert(RR_PGO_ROBUST_HUBER == ROBUST_HUBER && RR_PGO_ROBUST_CAUCHY == ROBUST_CAUCHY, "robust kernel numbering");
+  return guarded([&] { h->engine->set_robust(kind, delta, edge_mask); });
+}
+
+int rr_pgo_edge_errors(rr_pgo *h, double *chi2_out, double *weight_out) {
+  if (!h || !chi2_out) { g_last_error = "null argument"; return RR_PGO_EINVAL; }
+  return guarded([&] { h->engine->edge_errors(chi2_out, weight_out); });
 }
 
 int rr_pgo_iterate_async(rr_pgo *h, int32_t iters) {

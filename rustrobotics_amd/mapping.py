@@ -215,6 +215,28 @@ class PoseGraph:
                 break
         return (errors, norms) if return_norms else errors
 
+    # -- robust kernels (include/rr_pgo.h, "robust kernels") ----------------------------
+    def set_robust_kernel(self, kind, delta=1.0, edge_mask=None):
+        """Robust kernel of every later linearisation: kind None (plain least squares), "huber" or "cauchy"; delta in the
+        units of sqrt(e^T Omega e); edge_mask: per edge, nonzero = robustified (None: every edge).  chi2 and the errors
+        optimize() returns are then the robust cost sum rho(e^T Omega e)."""
+        key = kind.lower() if isinstance(kind, str) else kind
+        if key not in _lib.ROBUST_KERNELS:
+            raise ValueError(f"unknown robust kernel {kind!r}: None, 'huber' or 'cauchy'")
+        mask = None
+        if edge_mask is not None:
+            mask = np.ascontiguousarray(edge_mask).astype(np.int32)
+            if mask.shape != (self.num_edges,):
+                raise ValueError("edge_mask needs one entry per edge")
+        _check(_lib.load().rr_pgo_set_robust_kernel(self._h, _lib.ROBUST_KERNELS[key], float(delta),
+                                                    None if mask is None else _ip(mask)))
+
+    def edge_errors(self):
+        """(s, w): e^T Omega e of every edge at the current state and its robust weight (1 without a kernel), file order."""
+        s, w = np.zeros(self.num_edges), np.zeros(self.num_edges)
+        _check(_lib.load().rr_pgo_edge_errors(self._h, _dp(s), _dp(w)))
+        return s, w
+
     # -- PoseGraph::plot, :375-431 -------------------------------------------------------
     def plot_data(self):
         """What the reference's figure shows: the poses (blue circles), the same poses joined in the order of their ids
