@@ -233,6 +233,13 @@ typedef struct rr_pgo_stats {
 } rr_pgo_stats;
 int rr_pgo_get_stats(const rr_pgo *h, rr_pgo_stats *out);
 
+/* Form of the back substitution of the fronts that live in LDS.  *kform = 1: the K form -- the factorisation also forms, per
+ * front with rows below its pivot block, K = L11^-T L21^T and c = L11^-T y (stored like the factor), and the back
+ * substitution of such a front is one product with them; 0: the chain over 16-column blocks.  k_bytes / k_flops (may be
+ * NULL): what the K steps of one factorisation read and write, and their flops (2 per multiply-add); 0 in the chain form.
+ * Not part of bytes_factor / bytes_solve, which count every datum of the factor once. */
+int rr_pgo_solve_form(const rr_pgo *h, int32_t *kform, double *k_bytes, double *k_flops);
+
 /* Host-only: parse + symbolic analysis of a g2o file, the rr_pgo_stats a handle on it would report (fields that depend
  * on the device -- n_launches_per_iter, big_update_flops, big_flow_flops -- are 0).  Needs no HIP device. */
 int rr_pgo_analyze_g2o(const char *path, const rr_pgo_options *opt, rr_pgo_stats *out);

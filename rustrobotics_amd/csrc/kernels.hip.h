@@ -1247,6 +1247,8 @@ template <typename T> struct FactorArgs {
   int parent_dep_self;         // S: a front's own solve flag is dep_flags[S + s]
   unsigned long long wait_ticks;   // bound of one wait, 100 MHz ticks
   int solve_lds;                   // k_solve_flow: scalars of dynamic LDS (decides, front by front, whether its L11 image fits)
+  T *kvals;                        // K form of the back substitution (kform_front): [K^T; c^T] of every LDS front with rows below
+                                   // its pivot block, laid out like its panel in lvals; null = the chain form
 };
 
 // ---- hand-offs between workgroups of ONE launch (lds_flow.hip.h; flow.hip.h has the same policy for the fronts beyond
@@ -2078,6 +2080,113 @@ __device__ void process_front(const FactorArgs<T> &a, int s, const SnMeta &m, T 
   RRPGO_STAMP(a, s, 6);
 }
 
+// ---- K form of the back substitution (FactorArgs::kvals).  For a front with rows below its pivot block
+//   L11^T x_P = y_P - L21^T x_R   <=>   x_P = c - K x_R,   K = L11^-T L21^T,   c = L11^-T y_P,
+// and neither K nor c depends on x: the factorisation forms X = B L11^-1 = [K^T; c^T] (B: rows nc .. M-1 of the factored
+// panel, L21 and the rhs row) and stores it in the panel's own layout (kvals + loff, ld M, rows nc ..), so that the back
+// substitution of the front is ONE GEMV behind its wait (solve_front) instead of a chain over 16-column blocks.
+// By 16-column blocks from the right, X_b = (B_b - sum_{b' > b} X_b' L(b', b)) W_b (W_b = L_bb^-1, kept in winv), on 16 x 16
+// MFMA tiles in transposed form (tile rows = panel columns, tile columns = rows of B: contiguous in LDS).  Step b subtracts
+// X_b from every block to its left; the tile of block b - 1, complete then, is multiplied by W_(b-1) in the same registers
+// (k-step s of a lane takes k = row(lane, s) on both operands, which is where the accumulator holds it).  One barrier per
+// block; the waves own disjoint tiles and every entry gets its terms in one fixed order, whatever the workgroup size or the
+// schedule.  P: the factored panel in LDS (column-major, ld M); rows nc .. are overwritten with X.
+template <typename T, int THREADS>
+__device__ void kform_front(const FactorArgs<T> &a, const SnMeta &m, T *P) {
+  using MM = Mfma16<T>;
+  constexpr int NW = THREADS / 64;
+  const int nc = m.nc, M = nc + m.nr + 1;
+  const int lane = threadIdx.x & 63, li = lane & 15;
+  const int wave = wave_index();
+  const int nblk = (nc + 15) >> 4, ntr = (M - nc + 15) >> 4;
+  const T *Wg = a.winv + (int64_t)m.wblk * 256;
+  T *Kg = a.kvals + m.loff;
+  auto w_load = [&](int b, T (&wq)[4]) {   // A operand of X_b = B'_b W_b: (tile row i, k) = W_b(k, i)
+#pragma unroll
+    for (int s = 0; s < 4; s++) wq[s] = Wg[b * 256 + MM::row(lane, s) * 16 + li];
+  };
+  auto w_tile = [&](int b, int ib, const T (&bq)[4], const T (&wq)[4]) {   // bq[s] = B'(row, 16 b + row(lane, s))
+    const int c0 = 16 * b, cw = min(16, nc - c0);
+    const int r = nc + 16 * ib + li;
+    typename MM::Acc x = {0, 0, 0, 0};
+#pragma unroll
+    for (int s = 0; s < 4; s++) x = MM::mma(wq[s], MM::row(lane, s) < cw ? bq[s] : (T)0, x);
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      const int c = MM::row(lane, q);
+      if (r < M && c < cw) {
+        P[(c0 + c) * M + r] = x[q];
+        Kg[(int64_t)(c0 + c) * M + r] = x[q];
+      }
+    }
+  };
+  T wq[4];
+  {   // the last block: nothing to its right
+    const int b = nblk - 1, c0 = 16 * b, cw = nc - c0;
+    w_load(b, wq);
+    for (int ib = wave; ib < ntr; ib += NW) {
+      const int rc = min(nc + 16 * ib + li, M - 1);
+      T bq[4];
+#pragma unroll
+      for (int s = 0; s < 4; s++) bq[s] = P[(c0 + min(MM::row(lane, s), cw - 1)) * M + rc];
+      w_tile(b, ib, bq, wq);
+    }
+  }
+  for (int b = nblk - 1; b >= 1; b--) {
+    lds_barrier();   // X_b is in LDS
+    const int c0 = 16 * b, cw = min(16, nc - c0);
+    w_load(b - 1, wq);
+    // tiles (ib, bb < b), the block b - 1 first: its waves go on to the W product
+    for (int t = wave; t < ntr * b; t += NW) {
+      const int bb = b - 1 - t / ntr, ib = t % ntr;
+      const int j0 = 16 * bb;
+      const int r = nc + 16 * ib + li, rc = min(r, M - 1);
+      typename MM::Acc acc;
+      T av[4], bv[4];
+#pragma unroll
+      for (int q = 0; q < 4; q++) acc[q] = P[(j0 + MM::row(lane, q)) * M + rc];
+#pragma unroll
+      for (int s = 0; s < 4; s++) {
+        const int k = MM::row(lane, s), kc = min(k, cw - 1);
+        av[s] = P[(j0 + li) * M + c0 + kc];   // L(c0 + k, j0 + i)
+        bv[s] = P[(c0 + kc) * M + rc];        // X(row, c0 + k)
+      }
+#pragma unroll
+      for (int s = 0; s < 4; s++) acc = MM::mma(MM::row(lane, s) < cw ? -av[s] : (T)0, bv[s], acc);
+      if (bb == b - 1) {
+        T bq[4];
+#pragma unroll
+        for (int q = 0; q < 4; q++) bq[q] = acc[q];
+        w_tile(bb, ib, bq, wq);
+      } else if (r < M) {
+#pragma unroll
+        for (int q = 0; q < 4; q++) P[(j0 + MM::row(lane, q)) * M + r] = acc[q];
+      }
+    }
+  }
+}
+
+// The K step of a task's fronts, behind the last front's flag (k_factor_flow) -- nothing of it is on the way to the parent's
+// factorisation: the last front's panel is still in LDS, the earlier ones are read back from lvals (written by this
+// workgroup, read past the L1).  Root fronts (no rows below the pivot block) keep the chain form.
+template <typename T, int THREADS>
+__device__ void kform_task(const FactorArgs<T> &a, int sn_begin, int sn_end, T *P) {
+  for (int si = sn_end - 1; si >= sn_begin; si--) {
+    const SnMeta m = a.sn_meta[a.task_sn[si]];
+    if (m.nr == 0) continue;
+    if (si == sn_end - 1) {
+      kform_front<T, THREADS>(a, m, P);
+      continue;
+    }
+    const int psize = (m.nc + m.nr + 1) * m.nc;
+    const T *Lg = a.lvals + m.loff;
+    __syncthreads();   // the K step before is done with LDS
+    for (int t = threadIdx.x; t < psize; t += THREADS) P[t] = mem_ld<true>(Lg + t);
+    __syncthreads();
+    kform_front<T, THREADS>(a, m, P);
+  }
+}
+
 // One workgroup per task; a task is a list of supernodes in elimination order
 // whose fronts are assembled, factored and pushed to global memory one after
 // the other, entirely out of LDS.
@@ -2106,6 +2215,7 @@ __global__ void __launch_bounds__(THREADS) k_factor_tasks(FactorArgs<T> a) {
     }
     process_front<T, THREADS, false>(a, s, m, smem, smem + (m.nc + m.nr + 1) * m.nc, 0, dinv);
   }
+  if (a.kvals) kform_task<T, THREADS>(a, sbeg, send, smem);   // as in k_factor_flow: the same bits
 }
 
 // ---- huge fronts: many workgroups per front, one launch per phase, the huge fronts of one
@@ -3105,7 +3215,11 @@ __device__ void solve_front(const FactorArgs<T> &a, int s, const SnMeta &m, T *w
     T *Ll = t1 + ncp;
     const int ldl = ncp + 1;
     constexpr int CBLK = 2 * 16 * 17;
-    const bool img = FLOW && nrp + ncp + ncp * ldl + 2 <= a.solve_lds;
+    // K form (kform_front): x_P = c - K x_R is the GEMV below on the columns of [K^T; c^T] instead of [L21; y_P^T]; no image,
+    // no chain
+    const bool kf = a.kvals != nullptr && nr > 0;
+    const T *Gc = kf ? a.kvals + m.loff : Lg;   // the GEMV's columns: col = Gc + j M + nc, col[nr] = the rhs entry
+    const bool img = FLOW && !kf && nrp + ncp + ncp * ldl + 2 <= a.solve_lds;
     __syncthreads();
     RRPGO_STAMP_SOLVE(a, s, 0);
     // t = y1 - L21^T x[rows]: the 16 lanes of a row take one column, lane q the rows q, q + 16, ... (a row of lanes reads
@@ -3122,7 +3236,7 @@ __device__ void solve_front(const FactorArgs<T> &a, int s, const SnMeta &m, T *w
 #pragma unroll
       for (int p = 0; p < PM; p++)
         if (p < P) {
-          const T *col = Lg + (int64_t)min(jl + p * CPP, nc - 1) * M + nc;
+          const T *col = Gc + (int64_t)min(jl + p * CPP, nc - 1) * M + nc;
 #pragma unroll
           for (int r = 0; r < RM; r++)
             if (r < R) lv[p][r] = col[min(q16 + 16 * r, nr)];   // past the rows: the rhs entry, times the zero padding of x2
@@ -3166,7 +3280,7 @@ __device__ void solve_front(const FactorArgs<T> &a, int s, const SnMeta &m, T *w
 #pragma unroll
       for (int u = 0; u < 4; u++) wstore(tid + u * THREADS, w4[u]);
       for (int i = tid + 4 * THREADS; i < nblk * 256; i += THREADS) wstore(i, Wsrc[i]);
-    } else {
+    } else if (!kf) {
       // entry e of the chain image: block b = e >> 9, then the 256 entries of W_b and the 256 of L(b+1, b), both in memory
       // order; lane m of the chain finds its 16 operands k = 0 .. 15 at m * 17 + k
       constexpr int SC = 8;
@@ -3228,7 +3342,7 @@ __device__ void solve_front(const FactorArgs<T> &a, int s, const SnMeta &m, T *w
       // the same sums with the loads behind the wait: two columns per lane row and eight rows at a time in flight
       for (int j0 = 0; j0 < nc; j0 += 2 * CPP) {
         const int jA = j0 + jl, jB = jA + CPP;
-        const T *colA = Lg + (int64_t)min(jA, nc - 1) * M + nc, *colB = Lg + (int64_t)min(jB, nc - 1) * M + nc;
+        const T *colA = Gc + (int64_t)min(jA, nc - 1) * M + nc, *colB = Gc + (int64_t)min(jB, nc - 1) * M + nc;
         T accA = 0, accB = 0;
         for (int r0 = 0; r0 < R; r0 += 8) {
           T la8[8], lb8[8], x8[8];
@@ -3364,7 +3478,8 @@ __device__ void solve_front(const FactorArgs<T> &a, int s, const SnMeta &m, T *w
         }
       }
     };
-    if (img) chain(std::true_type{});
+    if (kf) {}   // t1 is x_P
+    else if (img) chain(std::true_type{});
     else chain(std::false_type{});
     __syncthreads();
     RRPGO_STAMP_SOLVE(a, s, 3);

@@ -75,6 +75,8 @@ __global__ void __launch_bounds__(THREADS) k_factor_flow(FactorArgs<T> a, const 
       }
       process_front<T, THREADS, false, true>(a, s, m, smem, smem + (m.nc + m.nr + 1) * m.nc, 0, dinv);
     }
+    // K form: the task's K steps, behind the flag of its last front (kernels.hip.h, kform_front)
+    if (a.kvals) kform_task<T, THREADS>(a, tr.sn_begin, tr.sn_end, smem);
   }
 }
 

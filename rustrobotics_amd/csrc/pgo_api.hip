@@ -242,6 +242,7 @@ struct EngineBase {
   virtual void read_stamps(std::vector<unsigned long long> &out) = 0;
   virtual void mark_flow_fronts(std::vector<char> &in_flow) = 0;   // fronts whose level runs as k_big_flow
   virtual int schur_tile() const = 0;                              // tile edge of k_big_schur, 0 = no Schur split
+  virtual void solve_form(int32_t *kform, double *k_bytes, double *k_flops) const = 0;   // rr_pgo_solve_form
   virtual int flow_trace(int level, std::vector<int32_t> &tasks, std::vector<unsigned long long> &stamps, int *nf, double *est_us) = 0;
   // sharded runs
   virtual void exchange_buffer(int which, void **ptr, int64_t *n, int32_t *esize) = 0;
@@ -401,6 +402,13 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   int n_pack_ = 0, pack_max_nu_ = 0;
   // numeric
   DevBuf<T> hvals_, b_, x_, dx_ref_, lvals_, uvals_, winv_, xnew_, gemv_part_;
+  // K form of the back substitution (kernels.hip.h, kform_front): [K^T; c^T] of the LDS fronts, laid out like lvals up to the
+  // last LDS panel.  On for the handles whose LDS fronts qualify for the dataflow launches (Symbolic::flow_eligible, one rank,
+  // not sharded) -- in the level schedule of such a handle too (RR_PGO_LDS_FLOW=0: the same bits); RR_PGO_SOLVE_KFORM=0: the
+  // chain form (read at creation)
+  DevBuf<T> kvals_;
+  bool kform_ = false;
+  double kform_bytes_ = 0, kform_flops_ = 0;   // one factorisation's K steps: panel rows read + X written, 2 per multiply-add
   static constexpr int kGemvSlices = 16;   // row slices of the multi-workgroup L21^T x product
   DevBuf<double> chi_partial_, norm_partial_, hist_;
   DevBuf<int> counter_, err_, blocks_done_;
@@ -696,6 +704,20 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
       if (wblk_total > 0x7fffff00LL) throw ApiError(RR_PGO_EUNSUPPORTED, "too many diagonal blocks");
       winv_.alloc((size_t)wblk_total * 256 + 4);
       winv_.zero();
+      kform_ = sym.flow_eligible && !sharded_ && world_ <= 1;
+      if (const char *e = getenv("RR_PGO_SOLVE_KFORM")) kform_ = kform_ && std::atoi(e) != 0;
+      if (kform_) {
+        int64_t kend = 0;
+        for (int f = 0; f < sym.S; f++)
+          if (!sym.sn_big[f] && sym.sn_nrows[f] > 0) {
+            const double nc = sym.sn_ncols[f], nu = sym.sn_nrows[f] + 1;
+            kend = std::max<int64_t>(kend, sym.sn_loff[f] + (int64_t)(nc + nu) * sym.sn_ncols[f]);
+            kform_bytes_ += (nc * (nc + 1) / 2 + 2 * nu * nc) * sizeof(T);   // L11, then B read and X written once each
+            kform_flops_ += nu * nc * nc;                                    // X = B L11^-1: nu nc^2 / 2 multiply-adds
+          }
+        kvals_.alloc((size_t)kend + 4);
+        kvals_.zero();
+      }
       {
         bool any_big = false;
         for (const Step &st : sym.steps) any_big = any_big || st.kind == STEP_BIG;
@@ -1584,6 +1606,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     a.parent_dep_self = sym_.S;
     a.wait_ticks = wait_ticks_;
     a.solve_lds = 0;
+    a.kvals = kform_ ? kvals_.p : nullptr;
     return a;
   }
 
@@ -2376,6 +2399,11 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   }
 
   int schur_tile() const override { return schur_split_ ? schur_tile_ : 0; }
+  void solve_form(int32_t *kform, double *k_bytes, double *k_flops) const override {
+    *kform = kform_ ? 1 : 0;
+    if (k_bytes) *k_bytes = kform_bytes_;
+    if (k_flops) *k_flops = kform_flops_;
+  }
   void mark_flow_fronts(std::vector<char> &in_flow) override {
     for (size_t si = 0; si < flow_levels_.size(); si++)
       if (flow_levels_[si])
@@ -3174,6 +3202,11 @@ int rr_pgo_set_robust_kernel(rr_pgo *h, int32_t kind, double delta, const int32_
 int rr_pgo_edge_errors(rr_pgo *h, double *chi2_out, double *weight_out) {
   if (!h || !chi2_out) { g_last_error = "null argument"; return RR_PGO_EINVAL; }
   return guarded([&] { h->engine->edge_errors(chi2_out, weight_out); });
+}
+
+int rr_pgo_solve_form(const rr_pgo *h, int32_t *kform, double *k_bytes, double *k_flops) {
+  if (!h || !kform) { g_last_error = "null argument"; return RR_PGO_EINVAL; }
+  return guarded([&] { h->engine->solve_form(kform, k_bytes, k_flops); });
 }
 
 int rr_pgo_iterate_async(rr_pgo *h, int32_t iters) {

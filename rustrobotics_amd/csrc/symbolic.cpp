@@ -2053,7 +2053,8 @@ std::string analyze(const HostGraph &g, const SymbolicOptions &opt, Symbolic &sy
   // 521 + 122 us of level launches; sphere2500, 545 LDS fronts: 91 + 38 against 126 + 56 us)
   int n_lds_fronts = 0;
   for (int f = 0; f < S; f++) n_lds_fronts += !sym.sn_big[f];
-  if (opt.lds_flow && opt.n_parts <= 1 && S > 0 && !big_below_lds && n_lds_fronts <= 8 * opt.n_cus) {
+  sym.flow_eligible = opt.n_parts <= 1 && S > 0 && !big_below_lds && n_lds_fronts <= 8 * opt.n_cus;
+  if (opt.lds_flow && sym.flow_eligible) {
     if (sym.n_big > 0) {   // the levels of the fronts beyond LDS: from the level schedule
       double best = 1e300, best_t = 90;
       for (double t = 10.0; t < 260.0; t *= 1.12) {

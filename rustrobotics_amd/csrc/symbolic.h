@@ -155,6 +155,10 @@ struct Symbolic {
   // comes after the tasks of its fronts' children -- and the back substitution draws its tasks in solve_order (parents
   // before children).  Leaf subtrees cheaper than the threshold are one task, every front above them a task of its own.
   bool lds_flow = false;
+  // the LDS fronts qualify for the dataflow launches (all the conditions of lds_flow but SymbolicOptions::lds_flow itself):
+  // the engine gives such a handle the K form of the back substitution (kernels.hip.h, kform_front) -- in the level
+  // schedule too when that was asked for, so that the two schedules stay bit-identical
+  bool flow_eligible = false;
   std::vector<int32_t> solve_order;  // ticket -> task for k_solve_flow
   double est_factor_us = 0.0, est_solve_us = 0.0;   // the cost model's makespans of the two launches
   // ---- sharding over ranks (n_parts > 1): steps [0, n_local_steps) are this rank's own subtrees,

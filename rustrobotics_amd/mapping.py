@@ -378,7 +378,12 @@ class PoseGraph:
     def stats(self):
         s = _lib.Stats()
         _check(_lib.load().rr_pgo_get_stats(self._h, C.byref(s)))
-        return {k: getattr(s, k) for k, _ in _lib.Stats._fields_ if k != "reserved"}
+        out = {k: getattr(s, k) for k, _ in _lib.Stats._fields_ if k != "reserved"}
+        # form of the back substitution of the LDS fronts (rr_pgo_solve_form): kept apart from bytes_factor / bytes_solve
+        kform, kb, kf = C.c_int32(0), C.c_double(0), C.c_double(0)
+        _check(_lib.load().rr_pgo_solve_form(self._h, C.byref(kform), C.byref(kb), C.byref(kf)))
+        out.update(solve_kform=int(kform.value), kform_bytes=float(kb.value), kform_flops=float(kf.value))
+        return out
 
     @staticmethod
     def analyze(file_path, precision="f64"):
