@@ -192,6 +192,25 @@ int rr_pgo_set_robust_kernel(rr_pgo *h, int32_t kind, double delta, const int32_
 /* s_e = e^T Omega e and w_e at the current state, file order; weight_out may be NULL.  EUNSUPPORTED on sharded handles. */
 int rr_pgo_edge_errors(rr_pgo *h, double *chi2_out, double *weight_out);
 
+/* ---- marginal covariances (build-defined; the reference has none) ----------
+ * Blocks of Sigma = H^-1 at the current state (H as rr_pgo_linearize_solve(h, 0, 0) builds it: anchor prior 1e7 included,
+ * lambda = 0, robust weights included while a kernel is set).
+ * Query q asks for block (node_a[q], node_b[q]): d_a x d_b, row-major, tangent coordinates in the order
+ * rr_pgo_linearize_solve's dx uses for the node.  node_b == NULL: diagonal blocks of node_a.
+ * node_a == NULL too: n_query must be rr_pgo_num_nodes, all diagonal blocks in node order.
+ * out_offset (may be NULL): [n_query + 1] offsets into out.  Call with out == NULL to get *n_vals (and the offsets).
+ * A pair a != b is answered when both nodes lie in one front of the factor -- guaranteed for every pair joined by an edge;
+ * any other pair is RR_PGO_EINVAL (the message names it) and nothing is written.  Out-of-range node: RR_PGO_EINVAL.
+ * The call linearises, factors, runs the selected inverse (the Takahashi recursion over the supernode tree) and gathers on
+ * the handle's stream, then synchronises; the state, the Levenberg-Marquardt lambda and rr_pgo_optimize's results are
+ * untouched.  A non-positive pivot: RR_PGO_ENOTSPD.
+ * RR_PGO_EUNSUPPORTED (the message says which): sharded handles, RR_PGO_F32 / RR_PGO_MIXED handles, graphs with fronts
+ * beyond LDS (rr_pgo_stats::n_big_fronts != 0). */
+int rr_pgo_marginals(rr_pgo *h, int32_t n_query, const int32_t *node_a, const int32_t *node_b,
+                     double *out, int64_t *out_offset, int64_t *n_vals);
+/* ms[3]: HIP-event times of the last rr_pgo_marginals call -- linearise + factor, selected inverse, gather. */
+int rr_pgo_marginals_times(const rr_pgo *h, double *ms);
+
 /* ---- inspection of the assembled system (parity tests) ------------------- */
 
 /* Runs the linearisation kernels only and returns the assembled normal matrix

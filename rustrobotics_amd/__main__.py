@@ -9,6 +9,9 @@
   --robust huber:DELTA | cauchy:DELTA  (both modes): a robust kernel on every edge (include/rr_pgo.h); the errors printed
       are then the robust cost
 
+  --marginals FILE  (example mode): after the optimisation, one line per node -- id, d, the upper triangle of its d x d
+      covariance block (rr_pgo_marginals; f64 handles whose fronts all live in LDS)
+
   python -m rustrobotics_amd <file.g2o> --bench [--repeats 20]
       = benches/graph_slam.rs:9-10   PoseGraph::new("dataset/g2o/intel.g2o", GaussNewton)?.optimize(10, false, false)
         timed end to end like criterion does: parsing, symbolic analysis, device setup and the ten
@@ -34,6 +37,22 @@ def _robust_arg(text):
     return kind, d
 
 
+def write_marginals(g, path):
+    import ctypes as C
+
+    import numpy as np
+    from . import _lib
+    d = _lib.GraphDesc()
+    _lib.load().rr_pgo_get_graph(g._h, C.byref(d))
+    n = d.n_nodes
+    ids = np.ctypeslib.as_array(d.node_id, (n,)) if (n and d.node_id) else np.arange(n)
+    with open(path, "w") as f:
+        for i, blk in zip(ids, g.marginals()):
+            k = len(blk)
+            f.write(f"{int(i)} {k} " + " ".join(f"{v:.17g}" for v in blk[np.triu_indices(k)]) + "\n")
+    print(f"marginal covariances of {n} nodes written to {path}")
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m rustrobotics_amd", description=__doc__,
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -46,6 +65,8 @@ def main(argv=None):
     ap.add_argument("--repeats", type=int, default=20)
     ap.add_argument("--robust", type=_robust_arg, default=None, metavar="KIND:DELTA",
                     help="robust kernel on every edge: huber:DELTA or cauchy:DELTA")
+    ap.add_argument("--marginals", metavar="FILE", default=None,
+                    help="after the optimisation write every node's covariance block: id, d, upper triangle")
     a = ap.parse_args(argv)
     solver = PoseGraphSolver[a.solver]
 
@@ -58,7 +79,10 @@ def main(argv=None):
     if not a.bench:
         if a.robust:
             print(f"robust kernel {a.robust[0]}, delta {a.robust[1]:g}")
-        new().optimize(50 if a.iterations is None else a.iterations, True, a.plot)
+        g = new()
+        g.optimize(50 if a.iterations is None else a.iterations, True, a.plot)
+        if a.marginals:
+            write_marginals(g, a.marginals)
         return 0
     iters = 10 if a.iterations is None else a.iterations
     new().optimize(iters, False, False)   # warm-up: library load, HIP context

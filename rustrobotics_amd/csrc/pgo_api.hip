@@ -27,6 +27,7 @@
 #include "kernels.hip.h"
 #include "flow.hip.h"
 #include "lds_flow.hip.h"
+#include "selinv.hip.h"
 #include "symbolic.h"
 #include "host_threads.h"
 
@@ -252,6 +253,9 @@ struct EngineBase {
   virtual void debug_withhold(int mode) = 0;   // failure injection for the dataflow launches (rr_pgo_debug_withhold)
   virtual void set_robust(int kind, double delta, const int32_t *mask) = 0;   // rr_pgo_set_robust_kernel (arguments checked)
   virtual void edge_errors(double *s_out, double *w_out) = 0;                  // rr_pgo_edge_errors
+  // rr_pgo_marginals (arguments checked; off: [nq + 1] offsets of the blocks in out) / rr_pgo_marginals_times
+  virtual void marginals(int nq, const int32_t *na, const int32_t *nb, const int64_t *off, double *out) = 0;
+  virtual void marginals_times(double *ms) const = 0;
   int n_launches_per_iter = 0;
 };
 
@@ -409,6 +413,16 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   DevBuf<T> kvals_;
   bool kform_ = false;
   double kform_bytes_ = 0, kform_flops_ = 0;   // one factorisation's K steps: panel rows read + X written, 2 per multiply-add
+  // marginal covariances (selinv.hip.h; rr_pgo_marginals): everything made on the first call
+  DevBuf<T> svals_;                  // the selected inverse, a front's image laid out like its factor image (less the rhs row)
+  DevBuf<SelMeta> sel_meta_;
+  DevBuf<int32_t> sel_order_;        // fronts by tree level, root level first
+  std::vector<int32_t> sel_level_ptr_, sel_col_sn_;   // ranges of sel_order_; permuted scalar column -> supernode
+  std::vector<int64_t> sel_soff_;
+  size_t sel_lds_ = 0;
+  bool sel_ready_ = false;
+  EventHolder sel_ev_[4];
+  double sel_ms_[3] = {0, 0, 0};     // the last call: linearise + factor, selected inverse, gather
   static constexpr int kGemvSlices = 16;   // row slices of the multi-workgroup L21^T x product
   DevBuf<double> chi_partial_, norm_partial_, hist_;
   DevBuf<int> counter_, err_, blocks_done_;
@@ -2596,6 +2610,155 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     if (w_out) std::memcpy(w_out, host.data() + E, E * sizeof(double));
   }
 
+
+  // ---- marginal covariances (include/rr_pgo.h, rr_pgo_marginals)
+  void marginals_prepare() {
+    if (sel_ready_) return;
+    const Symbolic &sym = sym_;
+    const int S_ = sym.S;
+    std::vector<SelMeta> meta((size_t)S_);
+    sel_soff_.assign((size_t)S_ + 1, 0);
+    std::vector<int32_t> depth((size_t)S_, 0);
+    int max_depth = 0;
+    size_t lds_elems = 0;
+    sel_col_sn_.assign((size_t)g_.dim, -1);
+    for (int f = S_ - 1; f >= 0; f--) {   // children precede parents
+      if (sym.sn_parent[f] >= 0) depth[f] = depth[sym.sn_parent[f]] + 1;
+      max_depth = std::max(max_depth, depth[f]);
+    }
+    for (int f = 0; f < S_; f++) {
+      const int64_t nc = sym.sn_ncols[f], nr = sym.sn_nrows[f];
+      if (nc + nr > SELINV_MAX_ROWS) throw ApiError(RR_PGO_EUNSUPPORTED, "rr_pgo_marginals: a front of " + std::to_string(nc + nr) + " rows exceeds what one workgroup holds");
+      const int64_t image = (nc + nr) * nc + nr * (nr + 1) / 2;
+      lds_elems = std::max(lds_elems, (size_t)image);
+      sel_soff_[f + 1] = sel_soff_[f] + ((image + 3) & ~(int64_t)3);
+      for (int c = 0; c < nc; c++) sel_col_sn_[sym.sn_col0[f] + c] = f;
+    }
+    for (int f = 0; f < S_; f++) {
+      SelMeta &m = meta[f];
+      const int p = sym.sn_parent[f];
+      m.nc = sym.sn_ncols[f];
+      m.nr = sym.sn_nrows[f];
+      m.wblk = host_sn_meta_[f].wblk;
+      m.has_parent = p >= 0 ? 1 : 0;
+      m.pnc = p >= 0 ? sym.sn_ncols[p] : 0;
+      m.pn = p >= 0 ? sym.sn_ncols[p] + sym.sn_nrows[p] : 0;
+      m.pad0 = m.pad1 = 0;
+      m.loff = sym.sn_loff[f];
+      m.soff = sel_soff_[f];
+      m.psoff = p >= 0 ? sel_soff_[p] : 0;
+      m.rel_ptr = sym.rel_ptr[f];
+      if (p < 0 && m.nr != 0) throw ApiError(RR_PGO_EUNSUPPORTED, "rr_pgo_marginals: a root front with rows below its pivot block");
+    }
+    sel_lds_ = lds_elems * sizeof(T);
+    if (sel_lds_ + (size_t)(256 + SELINV_GPART * 256) * sizeof(T) > (size_t)160 * 1024)
+      throw ApiError(RR_PGO_EUNSUPPORTED, "rr_pgo_marginals: fronts beyond LDS");
+    std::vector<int32_t> order;
+    sel_level_ptr_.assign(1, 0);
+    for (int d = 0; d <= max_depth; d++) {
+      for (int f = S_ - 1; f >= 0; f--)
+        if (depth[f] == d) order.push_back(f);
+      sel_level_ptr_.push_back((int32_t)order.size());
+    }
+    DeviceArena *prev = t_arena;
+    t_arena = &arena_;   // like every other buffer of the handle: back to the pool with it
+    try {
+      sel_meta_.upload(meta);
+      sel_order_.upload(order);
+      svals_.alloc((size_t)sel_soff_[S_] + 4);
+    } catch (...) {
+      t_arena = prev;
+      throw;
+    }
+    t_arena = prev;
+    for (EventHolder &e : sel_ev_) e.create(hipEventDefault);
+    if constexpr (std::is_same<T, double>::value)
+      HIPCHK(hipFuncSetAttribute((const void *)k_selinv_level<T, SELINV_THREADS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sel_lds_));
+    sel_ready_ = true;
+  }
+
+  void marginals(int nq, const int32_t *na, const int32_t *nb, const int64_t *off, double *out) override {
+    if (sharded_ || world_ > 1) throw ApiError(RR_PGO_EUNSUPPORTED, "rr_pgo_marginals: sharded handle (a rank holds a part of the factor only)");
+    if constexpr (!(std::is_same<T, double>::value && std::is_same<S, double>::value)) {
+      throw ApiError(RR_PGO_EUNSUPPORTED, "rr_pgo_marginals: F32 / MIXED handle (a single-precision factor of a matrix of condition ~1e10 has no meaningful inverse): create the handle with RR_PGO_F64");
+    } else {
+      if (sym_.n_big > 0) throw ApiError(RR_PGO_EUNSUPPORTED, "rr_pgo_marginals: " + std::to_string(sym_.n_big) + " fronts beyond LDS (n_big_fronts must be 0)");
+      marginals_prepare();
+      const Symbolic &sym = sym_;
+      // ---- where every output scalar lives in svals
+      const int64_t n_vals = off[nq];
+      std::vector<int64_t> src((size_t)n_vals);
+      int32_t pc_a[6], pc_b[6];
+      auto node_cols = [&](int v, int32_t *pc) {   // reference scalar r of node v -> permuted column
+        const int d = node_dim(g_.node_kind[v]), p0 = sym.node_pcol[v];
+        for (int i = 0; i < d; i++) pc[sym.perm[p0 + i] - g_.node_offset[v]] = p0 + i;
+        return d;
+      };
+      for (int q = 0; q < nq; q++) {
+        const int va = na ? na[q] : q, vb = nb ? nb[q] : va;
+        const int da = node_cols(va, pc_a), db = node_cols(vb, pc_b);
+        const int ve = sym.node_pcol[va] <= sym.node_pcol[vb] ? va : vb;   // eliminated first: its front holds the pair, or none does
+        const int f = sel_col_sn_[sym.node_pcol[ve]];
+        const int nc = sym.sn_ncols[f], nr = sym.sn_nrows[f], n = nc + nr, c0 = sym.sn_col0[f];
+        const int32_t *rows = sym.sn_rows.data() + sym.sn_rows_ptr[f];
+        auto local = [&](int pcol) -> int {
+          if (pcol >= c0 && pcol < c0 + nc) return pcol - c0;
+          const int32_t *it = std::lower_bound(rows, rows + nr, pcol);
+          return it != rows + nr && *it == pcol ? nc + (int)(it - rows) : -1;
+        };
+        for (int i = 0; i < da; i++)
+          for (int j = 0; j < db; j++) {
+            const int li = local(pc_a[i]), lj = local(pc_b[j]);
+            if (li < 0 || lj < 0)
+              throw ApiError(RR_PGO_EINVAL, "rr_pgo_marginals: nodes " + std::to_string(va) + " and " + std::to_string(vb) +
+                                                " (query " + std::to_string(q) + ") share no front of the factor: only pairs joined by an edge are guaranteed");
+            const int hi = std::max(li, lj), lo = std::min(li, lj);
+            if (lo >= nc) throw ApiError(RR_PGO_ENODEVICE, "rr_pgo_marginals: internal: pair outside its front's panel");
+            src[(size_t)(off[q] + (int64_t)i * db + j)] = sel_soff_[f] + (int64_t)lo * n + hi;
+          }
+      }
+      DevBuf<int64_t> d_src;
+      DevBuf<double> d_out;
+      d_src.alloc((size_t)n_vals);
+      d_out.alloc((size_t)n_vals);
+      HIPCHK(hipMemcpyAsync(d_src.p, src.data(), src.size() * sizeof(int64_t), hipMemcpyHostToDevice, stream_));
+      HIPCHK(hipEventRecord(sel_ev_[0], stream_));
+      launch_linearize(0.0, 0, 1);
+      launch_factor();
+      HIPCHK(hipEventRecord(sel_ev_[1], stream_));
+      SelArgs<T> a;
+      a.meta = sel_meta_.p;
+      a.order = sel_order_.p;
+      a.rel = rel_.p;
+      a.lvals = lvals_.p;
+      a.winv = winv_.p;
+      a.svals = svals_.p;
+      for (size_t l = 0; l + 1 < sel_level_ptr_.size(); l++) {
+        const int begin = sel_level_ptr_[l], count = sel_level_ptr_[l + 1] - begin;
+        if (count <= 0) continue;
+        hipLaunchKernelGGL((k_selinv_level<T, SELINV_THREADS>), dim3((unsigned)count), dim3(SELINV_THREADS), sel_lds_, stream_, a, begin);
+      }
+      check_launch("k_selinv_level");
+      HIPCHK(hipEventRecord(sel_ev_[2], stream_));
+      if (n_vals > 0) {
+        hipLaunchKernelGGL((k_marg_gather<T>), dim3((unsigned)((n_vals + 255) / 256)), dim3(256), 0, stream_, (const T *)svals_.p, (const int64_t *)d_src.p, d_out.p, n_vals);
+        check_launch("k_marg_gather");
+      }
+      HIPCHK(hipEventRecord(sel_ev_[3], stream_));
+      std::vector<double> host((size_t)n_vals);
+      if (n_vals > 0) HIPCHK(hipMemcpyAsync(host.data(), d_out.p, host.size() * sizeof(double), hipMemcpyDeviceToHost, stream_));
+      HIPCHK(hipStreamSynchronize(stream_));
+      check_device_error();
+      for (int k = 0; k < 3; k++) {
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, sel_ev_[k], sel_ev_[k + 1]));
+        sel_ms_[k] = ms;
+      }
+      if (n_vals > 0) std::memcpy(out, host.data(), host.size() * sizeof(double));
+    }
+  }
+  void marginals_times(double *ms) const override { for (int k = 0; k < 3; k++) ms[k] = sel_ms_[k]; }
+
   void debug_withhold(int mode) override {
     HIPCHK(hipStreamSynchronize(stream_));
     if (mode == 0) {
@@ -3207,6 +3370,38 @@ int rr_pgo_edge_errors(rr_pgo *h, double *chi2_out, double *weight_out) {
 int rr_pgo_solve_form(const rr_pgo *h, int32_t *kform, double *k_bytes, double *k_flops) {
   if (!h || !kform) { g_last_error = "null argument"; return RR_PGO_EINVAL; }
   return guarded([&] { h->engine->solve_form(kform, k_bytes, k_flops); });
+}
+
+int rr_pgo_marginals(rr_pgo *h, int32_t n_query, const int32_t *node_a, const int32_t *node_b, double *out,
+                     int64_t *out_offset, int64_t *n_vals) {
+  if (!h || n_query < 0 || (!node_a && node_b)) { g_last_error = "bad argument"; return RR_PGO_EINVAL; }
+  const int N = h->g.n_nodes();
+  if (!node_a && n_query != N) {
+    g_last_error = "rr_pgo_marginals: node_a == NULL asks for every node: n_query must be rr_pgo_num_nodes";
+    return RR_PGO_EINVAL;
+  }
+  std::vector<int64_t> off((size_t)n_query + 1, 0);
+  for (int q = 0; q < n_query; q++) {
+    const int va = node_a ? node_a[q] : q, vb = node_b ? node_b[q] : va;
+    if (va < 0 || va >= N || vb < 0 || vb >= N) {
+      g_last_error = "rr_pgo_marginals: query " + std::to_string(q) + ": node index out of range";
+      return RR_PGO_EINVAL;
+    }
+    off[q + 1] = off[q] + (int64_t)node_dim(h->g.node_kind[va]) * node_dim(h->g.node_kind[vb]);
+  }
+  if (n_vals) *n_vals = off[n_query];
+  if (!out) {   // size query
+    if (out_offset) std::copy(off.begin(), off.end(), out_offset);
+    return RR_PGO_OK;
+  }
+  const int rc = guarded([&] { h->engine->marginals(n_query, node_a, node_b, off.data(), out); });
+  if (rc == RR_PGO_OK && out_offset) std::copy(off.begin(), off.end(), out_offset);
+  return rc;
+}
+
+int rr_pgo_marginals_times(const rr_pgo *h, double *ms) {
+  if (!h || !ms) { g_last_error = "null argument"; return RR_PGO_EINVAL; }
+  return guarded([&] { h->engine->marginals_times(ms); });
 }
 
 int rr_pgo_iterate_async(rr_pgo *h, int32_t iters) {

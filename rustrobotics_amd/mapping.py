@@ -237,6 +237,49 @@ class PoseGraph:
         _check(_lib.load().rr_pgo_edge_errors(self._h, _dp(s), _dp(w)))
         return s, w
 
+    # -- marginal covariances (include/rr_pgo.h, "marginal covariances") -----------------
+    def marginal_blocks(self, node_a=None, node_b=None):
+        """rr_pgo_marginals as it is: (values, offsets) of the queried blocks of Sigma = H^-1 at the current state.
+        node_a None: every node's diagonal block; node_b None: the diagonal blocks of node_a."""
+        L = _lib.load()
+        a = None if node_a is None else np.ascontiguousarray(node_a, np.int32)
+        b = None if node_b is None else np.ascontiguousarray(node_b, np.int32)
+        if b is not None and (a is None or a.shape != b.shape):
+            raise ValueError("node_a and node_b need the same length")
+        nq = self.num_nodes if a is None else len(a)
+        off = np.zeros(nq + 1, np.int64)
+        nv = C.c_int64()
+        pa, pb = (None if a is None else _ip(a)), (None if b is None else _ip(b))
+        po = off.ctypes.data_as(C.POINTER(C.c_int64))
+        _check(L.rr_pgo_marginals(self._h, nq, pa, pb, None, po, C.byref(nv)))
+        vals = np.zeros(nv.value)
+        _check(L.rr_pgo_marginals(self._h, nq, pa, pb, _dp(vals), po, C.byref(nv)))
+        return vals, off
+
+    def marginals(self, nodes=None):
+        """Covariance of every node (or of `nodes`): a list of d x d arrays, tangent coordinates in dx's order."""
+        vals, off = self.marginal_blocks(nodes)
+        out = []
+        for q in range(len(off) - 1):
+            d = int(round(np.sqrt(off[q + 1] - off[q])))
+            out.append(vals[off[q]:off[q + 1]].reshape(d, d).copy())
+        return out
+
+    def joint_marginal(self, a, b):
+        """[[S_aa, S_ab], [S_ab^T, S_bb]] of two nodes that share a front of the factor (every pair joined by an edge
+        does), from one call."""
+        vals, off = self.marginal_blocks([a, b, a], [a, b, b])
+        da, db = int(round(np.sqrt(off[1] - off[0]))), int(round(np.sqrt(off[2] - off[1])))
+        saa, sbb = vals[off[0]:off[1]].reshape(da, da), vals[off[1]:off[2]].reshape(db, db)
+        sab = vals[off[2]:off[3]].reshape(da, db)
+        return np.block([[saa, sab], [sab.T, sbb]])
+
+    def marginals_times(self):
+        """HIP-event milliseconds of the last marginals call: (linearise + factor, selected inverse, gather)."""
+        ms = np.zeros(3)
+        _check(_lib.load().rr_pgo_marginals_times(self._h, _dp(ms)))
+        return tuple(float(v) for v in ms)
+
     # -- PoseGraph::plot, :375-431 -------------------------------------------------------
     def plot_data(self):
         """What the reference's figure shows: the poses (blue circles), the same poses joined in the order of their ids
