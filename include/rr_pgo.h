@@ -211,6 +211,25 @@ int rr_pgo_marginals(rr_pgo *h, int32_t n_query, const int32_t *node_a, const in
 /* ms[3]: HIP-event times of the last rr_pgo_marginals call -- linearise + factor, selected inverse, gather. */
 int rr_pgo_marginals_times(const rr_pgo *h, double *ms);
 
+/* Covariance blocks of ARBITRARY node pairs: block q is Sigma(node_a[q], node_b[q]), d_a x d_b row-major, for any two
+ * valid nodes -- joined by an edge or far apart in the elimination tree (a == b: the node's diagonal block).  Same H, same
+ * coordinates, same out / out_offset / n_vals conventions as rr_pgo_marginals (out == NULL: size query; out_offset may
+ * be NULL), with these differences: node_a and node_b are both required; every pair is answered; a node may appear in
+ * any number of queries.
+ * Computed as Sigma_ab = Z_a^T Z_b with Z_s = L^-1 E_s, a multi-column forward solve over the fronts between the queried
+ * nodes and the root: Sigma(b, a) is the transpose of Sigma(a, b) bit for bit, diagonal blocks are symmetric bit for bit,
+ * and a block's bits do not depend on what else the call asks for.  Cost grows with the number of DISTINCT nodes (32
+ * columns per pass over their root paths); for all diagonal blocks or edge pairs rr_pgo_marginals is the cheaper call.
+ * The call linearises, factors, solves and gathers on the handle's stream, then synchronises; the state, the
+ * Levenberg-Marquardt lambda, rr_pgo_optimize's results and captured graphs are untouched.
+ * RR_PGO_EINVAL: an out-of-range node or n_query < 0 (nothing is written).  RR_PGO_ENOTSPD: a non-positive pivot.
+ * RR_PGO_EUNSUPPORTED (the message says which): sharded handles, RR_PGO_F32 / RR_PGO_MIXED handles, graphs with fronts
+ * beyond LDS (rr_pgo_stats::n_big_fronts != 0). */
+int rr_pgo_covariances(rr_pgo *h, int32_t n_query, const int32_t *node_a, const int32_t *node_b,
+                       double *out, int64_t *out_offset, int64_t *n_vals);
+/* ms[3]: HIP-event times of the last rr_pgo_covariances call -- linearise + factor, tree solve, products + gather. */
+int rr_pgo_covariances_times(const rr_pgo *h, double *ms);
+
 /* ---- inspection of the assembled system (parity tests) ------------------- */
 
 /* Runs the linearisation kernels only and returns the assembled normal matrix

@@ -12,6 +12,9 @@
   --marginals FILE  (example mode): after the optimisation, one line per node -- id, d, the upper triangle of its d x d
       covariance block (rr_pgo_marginals; f64 handles whose fronts all live in LDS)
 
+  --joint ID,ID,...  (example mode): after the optimisation, the joint covariance of the listed g2o vertex ids -- any
+      nodes, joined by an edge or not (rr_pgo_covariances) -- one matrix row per line
+
   python -m rustrobotics_amd <file.g2o> --bench [--repeats 20]
       = benches/graph_slam.rs:9-10   PoseGraph::new("dataset/g2o/intel.g2o", GaussNewton)?.optimize(10, false, false)
         timed end to end like criterion does: parsing, symbolic analysis, device setup and the ten
@@ -53,6 +56,35 @@ def write_marginals(g, path):
     print(f"marginal covariances of {n} nodes written to {path}")
 
 
+def _ids_arg(text):
+    try:
+        ids = [int(t) for t in text.split(",")]
+    except ValueError:
+        ids = []
+    if not ids or min(ids) < 0:
+        raise argparse.ArgumentTypeError(f"expected ID,ID,... (g2o vertex ids), got {text!r}")
+    return ids
+
+
+def print_joint(g, ids):
+    import ctypes as C
+
+    import numpy as np
+    from . import _lib
+    d = _lib.GraphDesc()
+    _lib.load().rr_pgo_get_graph(g._h, C.byref(d))
+    n = d.n_nodes
+    file_ids = np.ctypeslib.as_array(d.node_id, (n,)) if (n and d.node_id) else np.arange(n)
+    index = {int(v): k for k, v in enumerate(file_ids)}
+    missing = [i for i in ids if i not in index]
+    if missing:
+        raise SystemExit(f"--joint: no vertex with id {missing[0]} in the file")
+    J = g.covariance([index[i] for i in ids])
+    print(f"joint covariance of vertices {','.join(str(i) for i in ids)} ({J.shape[0]} x {J.shape[0]}):")
+    for row in J:
+        print(" ".join(f"{v:.17g}" for v in row))
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m rustrobotics_amd", description=__doc__,
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -67,6 +99,8 @@ def main(argv=None):
                     help="robust kernel on every edge: huber:DELTA or cauchy:DELTA")
     ap.add_argument("--marginals", metavar="FILE", default=None,
                     help="after the optimisation write every node's covariance block: id, d, upper triangle")
+    ap.add_argument("--joint", type=_ids_arg, metavar="ID,ID,...", default=None,
+                    help="after the optimisation print the joint covariance of these g2o vertex ids (any nodes)")
     a = ap.parse_args(argv)
     solver = PoseGraphSolver[a.solver]
 
@@ -83,6 +117,8 @@ def main(argv=None):
         g.optimize(50 if a.iterations is None else a.iterations, True, a.plot)
         if a.marginals:
             write_marginals(g, a.marginals)
+        if a.joint:
+            print_joint(g, a.joint)
         return 0
     iters = 10 if a.iterations is None else a.iterations
     new().optimize(iters, False, False)   # warm-up: library load, HIP context

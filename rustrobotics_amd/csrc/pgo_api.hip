@@ -28,6 +28,7 @@
 #include "flow.hip.h"
 #include "lds_flow.hip.h"
 #include "selinv.hip.h"
+#include "treesolve.hip.h"
 #include "symbolic.h"
 #include "host_threads.h"
 
@@ -256,6 +257,9 @@ struct EngineBase {
   // rr_pgo_marginals (arguments checked; off: [nq + 1] offsets of the blocks in out) / rr_pgo_marginals_times
   virtual void marginals(int nq, const int32_t *na, const int32_t *nb, const int64_t *off, double *out) = 0;
   virtual void marginals_times(double *ms) const = 0;
+  // rr_pgo_covariances (arguments checked; off as for marginals) / rr_pgo_covariances_times
+  virtual void covariances(int nq, const int32_t *na, const int32_t *nb, const int64_t *off, double *out) = 0;
+  virtual void covariances_times(double *ms) const = 0;
   int n_launches_per_iter = 0;
 };
 
@@ -423,6 +427,19 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   bool sel_ready_ = false;
   EventHolder sel_ev_[4];
   double sel_ms_[3] = {0, 0, 0};     // the last call: linearise + factor, selected inverse, gather
+  // covariances of arbitrary pairs (treesolve.hip.h; rr_pgo_covariances): the per-front records are made on the first call,
+  // in the arena; the plan of a call and its workspace live in buffers of their own that only grow
+  DevBuf<TsMeta> ts_meta_;
+  std::vector<int32_t> ts_depth_, ts_col_sn_;   // depth of a front (a root: 0); permuted scalar column -> supernode
+  size_t ts_lds_ = 0;
+  bool ts_ready_ = false;
+  DevBuf<TsTask> ts_tasks_;
+  DevBuf<int32_t> ts_child_, ts_unit_, ts_czrow_;
+  DevBuf<CovQuery> ts_query_;
+  DevBuf<T> ts_z_, ts_u_;
+  DevBuf<double> ts_out_;
+  EventHolder ts_ev_[4];
+  double ts_ms_[3] = {0, 0, 0};      // the last call: linearise + factor, tree solve, products + gather
   static constexpr int kGemvSlices = 16;   // row slices of the multi-workgroup L21^T x product
   DevBuf<double> chi_partial_, norm_partial_, hist_;
   DevBuf<int> counter_, err_, blocks_done_;
@@ -2759,6 +2776,264 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   }
   void marginals_times(double *ms) const override { for (int k = 0; k < 3; k++) ms[k] = sel_ms_[k]; }
 
+  // ---- covariances of arbitrary node pairs (include/rr_pgo.h, rr_pgo_covariances; treesolve.hip.h)
+  struct TsPlan {
+    std::vector<TsTask> tasks;                 // by level, deepest first
+    std::vector<int32_t> child, unit, czrow, level_ptr;
+    std::vector<CovQuery> query;
+    int64_t zrows = 0, urows = 0;
+    int n_chunks = 0;
+  };
+
+  void covariances_prepare() {
+    if (ts_ready_) return;
+    const Symbolic &sym = sym_;
+    const int S_ = sym.S;
+    std::vector<TsMeta> meta((size_t)S_);
+    ts_depth_.assign((size_t)S_, 0);
+    ts_col_sn_.assign((size_t)g_.dim, -1);
+    int64_t max_n = 1;
+    for (int f = S_ - 1; f >= 0; f--)   // children precede parents
+      if (sym.sn_parent[f] >= 0) ts_depth_[f] = ts_depth_[sym.sn_parent[f]] + 1;
+    for (int f = 0; f < S_; f++) {
+      TsMeta &m = meta[f];
+      m.nc = sym.sn_ncols[f];
+      m.nr = sym.sn_nrows[f];
+      m.wblk = host_sn_meta_[f].wblk;
+      m.parent = sym.sn_parent[f];
+      m.loff = sym.sn_loff[f];
+      m.rel_ptr = sym.rel_ptr[f];
+      if (m.parent < 0 && m.nr != 0) throw ApiError(RR_PGO_EUNSUPPORTED, "rr_pgo_covariances: a root front with rows below its pivot block");
+      max_n = std::max<int64_t>(max_n, (int64_t)m.nc + m.nr);
+      for (int c = 0; c < m.nc; c++) ts_col_sn_[sym.sn_col0[f] + c] = f;
+    }
+    ts_lds_ = (size_t)max_n * TS_LD * sizeof(T);
+    if (ts_lds_ + 256 * sizeof(T) > (size_t)160 * 1024)
+      throw ApiError(RR_PGO_EUNSUPPORTED, "rr_pgo_covariances: a front of " + std::to_string(max_n) + " rows exceeds what one workgroup holds beside a chunk of columns");
+    DeviceArena *prev = t_arena;
+    t_arena = &arena_;   // like every other buffer of the handle: back to the pool with it
+    try {
+      ts_meta_.upload(meta);
+    } catch (...) {
+      t_arena = prev;
+      throw;
+    }
+    t_arena = prev;
+    for (EventHolder &e : ts_ev_) e.create(hipEventDefault);
+    if constexpr (std::is_same<T, double>::value)
+      HIPCHK(hipFuncSetAttribute((const void *)k_tree_fwd<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ts_lds_));
+    ts_ready_ = true;
+  }
+
+  // the plan of queries [q0, q1): columns, chunks, active fronts by level, the pairs' common paths
+  void covariances_plan(int q0, int q1, const int32_t *na, const int32_t *nb, const int64_t *off, TsPlan &pl) const {
+    const Symbolic &sym = sym_;
+    const int S_ = sym.S;
+    auto front_of = [&](int v) { return ts_col_sn_[sym.node_pcol[v]]; };
+    // distinct nodes by permuted column: fronts own consecutive column ranges in elimination order, so this is the order
+    // of (front, column) and neighbours share most of their paths
+    std::vector<int32_t> nodes;
+    nodes.reserve(2 * (size_t)(q1 - q0));
+    for (int q = q0; q < q1; q++) {
+      nodes.push_back(na[q]);
+      nodes.push_back(nb[q]);
+    }
+    std::sort(nodes.begin(), nodes.end(), [&](int32_t x, int32_t y) { return sym.node_pcol[x] < sym.node_pcol[y]; });
+    nodes.erase(std::unique(nodes.begin(), nodes.end()), nodes.end());
+    std::vector<int32_t> node_chunk((size_t)g_.n_nodes(), -1), node_col((size_t)g_.n_nodes(), 0);
+    std::vector<size_t> chunk_ptr{0};   // into nodes: whole nodes, at most TS_MC columns
+    int used = 0;
+    for (size_t k = 0; k < nodes.size(); k++) {
+      const int v = nodes[k], d = node_dim(g_.node_kind[v]);
+      if (used + d > TS_MC) {
+        chunk_ptr.push_back(k);
+        used = 0;
+      }
+      node_chunk[v] = (int32_t)chunk_ptr.size() - 1;
+      node_col[v] = used;
+      used += d;
+    }
+    chunk_ptr.push_back(nodes.size());
+    pl.n_chunks = (int)chunk_ptr.size() - 1;
+    pl.czrow.assign((size_t)pl.n_chunks * S_, -1);
+    std::vector<TsTask> tmp;            // tasks in (chunk, front) order; pl.child holds indices into it until the sort below
+    std::vector<int32_t> mark((size_t)S_, -1), task_of((size_t)S_, -1), fronts;
+    for (int c = 0; c < pl.n_chunks; c++) {
+      fronts.clear();
+      for (size_t k = chunk_ptr[c]; k < chunk_ptr[c + 1]; k++)
+        for (int f = front_of(nodes[k]); f >= 0 && mark[f] != c; f = sym.sn_parent[f]) {
+          mark[f] = c;
+          fronts.push_back(f);
+        }
+      std::sort(fronts.begin(), fronts.end());
+      const size_t base = tmp.size();
+      for (int f : fronts) {
+        TsTask t{};
+        t.front = f;
+        t.zrow = (int32_t)pl.zrows;   // (a plan beyond the workspace bound is dropped before these are read)
+        t.urow = (int32_t)pl.urows;
+        pl.zrows += sym.sn_ncols[f];
+        pl.urows += sym.sn_nrows[f];
+        pl.czrow[(size_t)c * S_ + f] = t.zrow;
+        task_of[f] = (int32_t)tmp.size();
+        tmp.push_back(t);
+      }
+      for (int f : fronts)
+        if (sym.sn_parent[f] >= 0) tmp[task_of[sym.sn_parent[f]]].n_child++;
+      size_t cp = pl.child.size();
+      for (size_t i = base; i < tmp.size(); i++) {
+        tmp[i].child_ptr = (int32_t)cp;
+        cp += tmp[i].n_child;
+        tmp[i].n_child = 0;
+      }
+      pl.child.resize(cp);
+      for (int f : fronts)   // ascending: the fixed child order of the gather
+        if (sym.sn_parent[f] >= 0) {
+          TsTask &pt = tmp[task_of[sym.sn_parent[f]]];
+          pl.child[pt.child_ptr + pt.n_child++] = task_of[f];
+        }
+      for (size_t k = chunk_ptr[c]; k < chunk_ptr[c + 1]; k++) {   // (the nodes of one front follow each other)
+        const int v = nodes[k], f = front_of(v), d = node_dim(g_.node_kind[v]), p0 = sym.node_pcol[v];
+        TsTask &t = tmp[task_of[f]];
+        if (t.n_unit == 0) t.unit_ptr = (int32_t)pl.unit.size();
+        for (int i = 0; i < d; i++) pl.unit.push_back(((p0 + i - sym.sn_col0[f]) << 5) | (node_col[v] + i));
+        t.n_unit += d;
+      }
+    }
+    const int nt = (int)tmp.size();
+    std::vector<int32_t> order((size_t)nt), newidx((size_t)nt);
+    for (int i = 0; i < nt; i++) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return ts_depth_[tmp[x].front] > ts_depth_[tmp[y].front]; });
+    pl.tasks.resize((size_t)nt);
+    pl.level_ptr.assign(1, 0);
+    for (int i = 0; i < nt; i++) {
+      newidx[order[i]] = i;
+      pl.tasks[i] = tmp[order[i]];
+      if (i > 0 && ts_depth_[pl.tasks[i].front] != ts_depth_[pl.tasks[i - 1].front]) pl.level_ptr.push_back(i);
+    }
+    pl.level_ptr.push_back(nt);
+    for (int32_t &c : pl.child) c = newidx[c];
+    pl.query.resize((size_t)(q1 - q0));
+    for (int q = q0; q < q1; q++) {
+      CovQuery &cq = pl.query[q - q0];
+      std::memset(&cq, 0, sizeof(cq));
+      const int va = na[q], vb = nb[q];
+      int fa = front_of(va), fb = front_of(vb);
+      while (fa != fb && fa >= 0 && fb >= 0) {
+        if (ts_depth_[fa] >= ts_depth_[fb]) fa = sym.sn_parent[fa];
+        else fb = sym.sn_parent[fb];
+      }
+      cq.lca = fa == fb ? fa : -1;
+      cq.chunk_a = node_chunk[va];
+      cq.chunk_b = node_chunk[vb];
+      cq.da = node_dim(g_.node_kind[va]);
+      cq.db = node_dim(g_.node_kind[vb]);
+      for (int i = 0; i < cq.da; i++) cq.ca[sym.perm[sym.node_pcol[va] + i] - g_.node_offset[va]] = (uint8_t)(node_col[va] + i);
+      for (int i = 0; i < cq.db; i++) cq.cb[sym.perm[sym.node_pcol[vb] + i] - g_.node_offset[vb]] = (uint8_t)(node_col[vb] + i);
+      cq.ooff = off[q] - off[q0];
+    }
+  }
+
+  template <typename U> void ts_grow(DevBuf<U> &b, size_t count) {
+    if (b.p && b.n >= count) return;
+    DeviceArena *prev = t_arena;
+    t_arena = nullptr;   // a buffer of its own: freed when it grows and with the handle
+    try {
+      b.alloc(std::max<size_t>(std::max(count, b.n + b.n / 2), 4));
+    } catch (...) {
+      t_arena = prev;
+      throw;
+    }
+    t_arena = prev;
+  }
+  template <typename U> void ts_fill(DevBuf<U> &b, const std::vector<U> &v) {
+    ts_grow(b, v.size());
+    if (!v.empty()) HIPCHK(hipMemcpyAsync(b.p, v.data(), v.size() * sizeof(U), hipMemcpyHostToDevice, stream_));
+  }
+
+  // queries [q0, q1) over the factor in lvals / winv; `first`: the factorisation of this call has not been waited for yet
+  void covariances_run(int q0, int q1, const int32_t *na, const int32_t *nb, const int64_t *off, double *out, bool &first) {
+    if constexpr (std::is_same<T, double>::value && std::is_same<S, double>::value) {
+      TsPlan pl;
+      covariances_plan(q0, q1, na, nb, off, pl);
+      const size_t ws = (size_t)(pl.zrows + pl.urows) * TS_MC * sizeof(T);
+      if (ws > TS_WS_BYTES) {
+        if (q1 - q0 <= 1) throw ApiError(RR_PGO_ENOMEM, "rr_pgo_covariances: one pair needs " + std::to_string(ws) + " bytes of workspace");
+        const int mid = q0 + (q1 - q0) / 2;
+        covariances_run(q0, mid, na, nb, off, out, first);
+        covariances_run(mid, q1, na, nb, off, out, first);
+        return;
+      }
+      const int64_t n_vals = off[q1] - off[q0];
+      ts_fill(ts_tasks_, pl.tasks);
+      ts_fill(ts_child_, pl.child);
+      ts_fill(ts_unit_, pl.unit);
+      ts_fill(ts_czrow_, pl.czrow);
+      ts_fill(ts_query_, pl.query);
+      ts_grow(ts_z_, (size_t)pl.zrows * TS_MC);
+      ts_grow(ts_u_, (size_t)pl.urows * TS_MC);
+      ts_grow(ts_out_, (size_t)n_vals);
+      if (!first) HIPCHK(hipEventRecord(ts_ev_[1], stream_));
+      TsArgs<T> a;
+      a.meta = ts_meta_.p;
+      a.tasks = ts_tasks_.p;
+      a.child = ts_child_.p;
+      a.unit = ts_unit_.p;
+      a.rel = rel_.p;
+      a.lvals = lvals_.p;
+      a.winv = winv_.p;
+      a.Z = ts_z_.p;
+      a.U = ts_u_.p;
+      for (size_t l = 0; l + 1 < pl.level_ptr.size(); l++) {
+        const int begin = pl.level_ptr[l], count = pl.level_ptr[l + 1] - begin;
+        if (count <= 0) continue;
+        hipLaunchKernelGGL((k_tree_fwd<T>), dim3((unsigned)count), dim3(TS_THREADS), ts_lds_, stream_, a, begin);
+      }
+      check_launch("k_tree_fwd");
+      HIPCHK(hipEventRecord(ts_ev_[2], stream_));
+      CovArgs<T> c;
+      c.meta = ts_meta_.p;
+      c.query = ts_query_.p;
+      c.czrow = ts_czrow_.p;
+      c.Z = ts_z_.p;
+      c.out = ts_out_.p;
+      c.S = sym_.S;
+      hipLaunchKernelGGL((k_cov_pairs<T>), dim3((unsigned)(q1 - q0)), dim3(COV_THREADS), 0, stream_, c);
+      check_launch("k_cov_pairs");
+      HIPCHK(hipEventRecord(ts_ev_[3], stream_));
+      std::vector<double> host((size_t)n_vals);
+      if (n_vals > 0) HIPCHK(hipMemcpyAsync(host.data(), ts_out_.p, host.size() * sizeof(double), hipMemcpyDeviceToHost, stream_));
+      HIPCHK(hipStreamSynchronize(stream_));
+      if (first) check_device_error();   // a non-positive pivot: nothing has been written
+      for (int k = first ? 0 : 1; k < 3; k++) {
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, ts_ev_[k], ts_ev_[k + 1]));
+        ts_ms_[k] += ms;
+      }
+      first = false;
+      if (n_vals > 0) std::memcpy(out + off[q0], host.data(), host.size() * sizeof(double));
+    }
+  }
+
+  void covariances(int nq, const int32_t *na, const int32_t *nb, const int64_t *off, double *out) override {
+    if (sharded_ || world_ > 1) throw ApiError(RR_PGO_EUNSUPPORTED, "rr_pgo_covariances: sharded handle (a rank holds a part of the factor only)");
+    if constexpr (!(std::is_same<T, double>::value && std::is_same<S, double>::value)) {
+      throw ApiError(RR_PGO_EUNSUPPORTED, "rr_pgo_covariances: F32 / MIXED handle (a single-precision factor of a matrix of condition ~1e10 has no meaningful inverse): create the handle with RR_PGO_F64");
+    } else {
+      if (sym_.n_big > 0) throw ApiError(RR_PGO_EUNSUPPORTED, "rr_pgo_covariances: " + std::to_string(sym_.n_big) + " fronts beyond LDS (n_big_fronts must be 0)");
+      covariances_prepare();
+      for (double &v : ts_ms_) v = 0;
+      if (nq == 0) return;
+      HIPCHK(hipEventRecord(ts_ev_[0], stream_));
+      launch_linearize(0.0, 0, 1);
+      launch_factor();
+      HIPCHK(hipEventRecord(ts_ev_[1], stream_));
+      bool first = true;
+      covariances_run(0, nq, na, nb, off, out, first);
+    }
+  }
+  void covariances_times(double *ms) const override { for (int k = 0; k < 3; k++) ms[k] = ts_ms_[k]; }
+
   void debug_withhold(int mode) override {
     HIPCHK(hipStreamSynchronize(stream_));
     if (mode == 0) {
@@ -3402,6 +3677,34 @@ int rr_pgo_marginals(rr_pgo *h, int32_t n_query, const int32_t *node_a, const in
 int rr_pgo_marginals_times(const rr_pgo *h, double *ms) {
   if (!h || !ms) { g_last_error = "null argument"; return RR_PGO_EINVAL; }
   return guarded([&] { h->engine->marginals_times(ms); });
+}
+
+int rr_pgo_covariances(rr_pgo *h, int32_t n_query, const int32_t *node_a, const int32_t *node_b, double *out,
+                       int64_t *out_offset, int64_t *n_vals) {
+  if (!h || n_query < 0 || (n_query > 0 && (!node_a || !node_b))) { g_last_error = "rr_pgo_covariances: bad argument (node_a and node_b are both required)"; return RR_PGO_EINVAL; }
+  const int N = h->g.n_nodes();
+  std::vector<int64_t> off((size_t)n_query + 1, 0);
+  for (int q = 0; q < n_query; q++) {
+    const int va = node_a[q], vb = node_b[q];
+    if (va < 0 || va >= N || vb < 0 || vb >= N) {
+      g_last_error = "rr_pgo_covariances: query " + std::to_string(q) + ": node index out of range";
+      return RR_PGO_EINVAL;
+    }
+    off[q + 1] = off[q] + (int64_t)node_dim(h->g.node_kind[va]) * node_dim(h->g.node_kind[vb]);
+  }
+  if (n_vals) *n_vals = off[n_query];
+  if (!out) {   // size query
+    if (out_offset) std::copy(off.begin(), off.end(), out_offset);
+    return RR_PGO_OK;
+  }
+  const int rc = guarded([&] { h->engine->covariances(n_query, node_a, node_b, off.data(), out); });
+  if (rc == RR_PGO_OK && out_offset) std::copy(off.begin(), off.end(), out_offset);
+  return rc;
+}
+
+int rr_pgo_covariances_times(const rr_pgo *h, double *ms) {
+  if (!h || !ms) { g_last_error = "null argument"; return RR_PGO_EINVAL; }
+  return guarded([&] { h->engine->covariances_times(ms); });
 }
 
 int rr_pgo_iterate_async(rr_pgo *h, int32_t iters) {

@@ -280,6 +280,53 @@ class PoseGraph:
         _check(_lib.load().rr_pgo_marginals_times(self._h, _dp(ms)))
         return tuple(float(v) for v in ms)
 
+    # -- covariances of arbitrary pairs (include/rr_pgo.h, rr_pgo_covariances) -----------
+    def covariance_blocks(self, node_a, node_b):
+        """rr_pgo_covariances as it is: (values, offsets) of the blocks Sigma(node_a[q], node_b[q]) at the current state,
+        for ANY pairs of nodes (a == b: the diagonal block); a node may appear in any number of queries."""
+        L = _lib.load()
+        a = np.ascontiguousarray(node_a, np.int32)
+        b = np.ascontiguousarray(node_b, np.int32)
+        if a.ndim != 1 or a.shape != b.shape:
+            raise ValueError("node_a and node_b need the same length")
+        nq = len(a)
+        off = np.zeros(nq + 1, np.int64)
+        nv = C.c_int64()
+        po = off.ctypes.data_as(C.POINTER(C.c_int64))
+        _check(L.rr_pgo_covariances(self._h, nq, _ip(a), _ip(b), None, po, C.byref(nv)))
+        vals = np.zeros(nv.value)
+        _check(L.rr_pgo_covariances(self._h, nq, _ip(a), _ip(b), _dp(vals), po, C.byref(nv)))
+        return vals, off
+
+    def covariance(self, nodes):
+        """Dense joint covariance of a set of nodes, (sum d) x (sum d), blocks in the order of `nodes`: the lower block
+        triangle from one rr_pgo_covariances call, mirrored (so the result is symmetric bit for bit)."""
+        nodes = [int(v) for v in nodes]
+        k = len(nodes)
+        ia, ib = np.tril_indices(k)
+        a = np.array([nodes[i] for i in ia], np.int32)
+        b = np.array([nodes[j] for j in ib], np.int32)
+        vals, off = self.covariance_blocks(a, b)
+        dims = [0] * k
+        for q in range(len(ia)):
+            if ia[q] == ib[q]:
+                dims[ia[q]] = int(round(np.sqrt(off[q + 1] - off[q])))
+        start = np.concatenate([[0], np.cumsum(dims)]).astype(int)
+        out = np.zeros((start[-1], start[-1]))
+        for q in range(len(ia)):
+            i, j = int(ia[q]), int(ib[q])
+            blk = vals[off[q]:off[q + 1]].reshape(dims[i], dims[j])
+            out[start[i]:start[i + 1], start[j]:start[j + 1]] = blk
+            if i != j:
+                out[start[j]:start[j + 1], start[i]:start[i + 1]] = blk.T
+        return out
+
+    def covariances_times(self):
+        """HIP-event milliseconds of the last covariance call: (linearise + factor, tree solve, products + gather)."""
+        ms = np.zeros(3)
+        _check(_lib.load().rr_pgo_covariances_times(self._h, _dp(ms)))
+        return tuple(float(v) for v in ms)
+
     # -- PoseGraph::plot, :375-431 -------------------------------------------------------
     def plot_data(self):
         """What the reference's figure shows: the poses (blue circles), the same poses joined in the order of their ids
