@@ -230,6 +230,33 @@ int rr_pgo_covariances(rr_pgo *h, int32_t n_query, const int32_t *node_a, const 
 /* ms[3]: HIP-event times of the last rr_pgo_covariances call -- linearise + factor, tree solve, products + gather. */
 int rr_pgo_covariances_times(const rr_pgo *h, double *ms);
 
+/* ---- Mahalanobis gate of candidate loop closures (build-defined; the reference has none) ----
+ * For candidate c -- an edge of kind edge_kind[c] from node edge_from[c] to node edge_to[c] with measurement z and
+ * information Omega, in rr_pgo_graph_desc packing (measurements and packed upper triangles follow each other in candidate
+ * order) -- that is NOT part of the graph:
+ *   e, A = de/d(from), B = de/d(to)   what the linearisation computes for such an edge at the current state (dx's coordinates)
+ *   S = Omega^-1 + [A B] Sigma_{ab,ab} [A B]^T     the innovation covariance; Sigma = H^-1, H as for rr_pgo_covariances
+ *   d2_out[c] = e^T S^-1 e                         compare with a chi-square quantile of d_e = 3 / 2 / 6 degrees of freedom
+ *   chi2_out[c] = e^T Omega e                      the term the edge would add to rr_pgo_chi2 (may be NULL)
+ *   innov_out (may be NULL): S per candidate, d_e x d_e row-major, packed; innov_offset (may be NULL): [n_cand + 1] offsets.
+ * [A B] Sigma [A B]^T is formed as G^T G with G = Z_a A^T + Z_b B^T, Z_s = L^-1 E_s of rr_pgo_covariances: the blocks of
+ * Sigma of two poses that move together cancel to many digits, and here they cancel row by row before the square.  S is
+ * symmetric bit for bit and positive definite; a candidate's bits do not depend on what else the call asks for.
+ * One linearisation, one factorisation and one tree solve per call on the handle's stream, then one synchronisation; the
+ * state, the Levenberg-Marquardt lambda, rr_pgo_optimize's results, captured graphs and the robust setting are untouched.
+ * RR_PGO_EINVAL, decided before anything is launched or written, the message names the candidate: n_cand < 0, a null
+ * required pointer, a node out of range, from == to, an unknown kind, a kind that does not fit its nodes (SE2: two SE2
+ * poses; SE2_XY: from an SE2 pose to an XY landmark; SE3: two SE3 poses), Omega not positive definite, a non-finite
+ * measurement.  n_cand == 0: RR_PGO_OK.  RR_PGO_ENOTSPD: a non-positive pivot of H.
+ * RR_PGO_EUNSUPPORTED (the message says which): sharded handles, RR_PGO_F32 / RR_PGO_MIXED handles, graphs with fronts
+ * beyond LDS (rr_pgo_stats::n_big_fronts != 0). */
+int rr_pgo_gate_edges(rr_pgo *h, int32_t n_cand,
+                      const int32_t *edge_kind, const int32_t *edge_from, const int32_t *edge_to,
+                      const double *edge_meas, const double *edge_info,
+                      double *d2_out, double *chi2_out, double *innov_out, int64_t *innov_offset);
+/* ms[3]: HIP-event times of the last rr_pgo_gate_edges call -- linearise + factor, tree solve, gate kernel + copy. */
+int rr_pgo_gate_times(const rr_pgo *h, double *ms);
+
 /* ---- inspection of the assembled system (parity tests) ------------------- */
 
 /* Runs the linearisation kernels only and returns the assembled normal matrix

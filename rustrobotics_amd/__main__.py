@@ -15,6 +15,11 @@
   --joint ID,ID,...  (example mode): after the optimisation, the joint covariance of the listed g2o vertex ids -- any
       nodes, joined by an edge or not (rr_pgo_covariances) -- one matrix row per line
 
+  --gate FILE  (example mode): after the optimisation, gate the candidate edges of FILE -- EDGE_SE2 / EDGE_SE2_XY /
+      EDGE_SE3:QUAT lines in the loader's field order, between vertex ids of the loaded graph, not part of it -- and print
+      one line per candidate: ids, Mahalanobis distance d2, e^T Omega e, accept / reject at the 0.95 chi-square quantile
+      (rr_pgo_gate_edges)
+
   python -m rustrobotics_amd <file.g2o> --bench [--repeats 20]
       = benches/graph_slam.rs:9-10   PoseGraph::new("dataset/g2o/intel.g2o", GaussNewton)?.optimize(10, false, false)
         timed end to end like criterion does: parsing, symbolic analysis, device setup and the ten
@@ -85,6 +90,60 @@ def print_joint(g, ids):
         print(" ".join(f"{v:.17g}" for v in row))
 
 
+GATE_TAGS = {"EDGE_SE2": 0, "EDGE_SE2_XY": 1, "EDGE_SE3:QUAT": 2}
+
+
+def parse_gate_file(path, index):
+    """Candidate edges of a --gate file as (kind, from, to, meas, info, ids) in rr_pgo_graph_desc packing; `index` maps a
+    g2o vertex id to the node's index.  Needs no device.  An unknown tag or id is a SystemExit that names the line."""
+    from .mapping import GATE_INFO_LEN, GATE_MEAS_LEN
+    kind, a, b, meas, info, ids = [], [], [], [], [], []
+    with open(path) as f:
+        for no, line in enumerate(f, 1):
+            tok = line.split()
+            if not tok or tok[0].startswith("#"):
+                continue
+            if tok[0] not in GATE_TAGS:
+                raise SystemExit(f"--gate: {path}:{no}: unknown tag {tok[0]!r} (EDGE_SE2, EDGE_SE2_XY or EDGE_SE3:QUAT)")
+            k = GATE_TAGS[tok[0]]
+            nm, ni = GATE_MEAS_LEN[k], GATE_INFO_LEN[k]
+            try:
+                i, j = int(tok[1]), int(tok[2])
+                vals = [float(t) for t in tok[3:]]
+            except (ValueError, IndexError):
+                raise SystemExit(f"--gate: {path}:{no}: expected two vertex ids and {nm + ni} numbers after {tok[0]}")
+            if len(vals) != nm + ni:
+                raise SystemExit(f"--gate: {path}:{no}: expected {nm + ni} values after the ids, got {len(vals)}")
+            for v in (i, j):
+                if v not in index:
+                    raise SystemExit(f"--gate: {path}:{no}: no vertex with id {v} in the graph")
+            kind.append(k)
+            a.append(index[i])
+            b.append(index[j])
+            meas.extend(vals[:nm])
+            info.extend(vals[nm:])
+            ids.append((i, j))
+    return kind, a, b, meas, info, ids
+
+
+def print_gate(g, path):
+    import ctypes as C
+
+    import numpy as np
+    from . import _lib
+    from .mapping import gate_thresholds
+    d = _lib.GraphDesc()
+    _lib.load().rr_pgo_get_graph(g._h, C.byref(d))
+    n = d.n_nodes
+    file_ids = np.ctypeslib.as_array(d.node_id, (n,)) if (n and d.node_id) else np.arange(n)
+    kind, a, b, meas, info, ids = parse_gate_file(path, {int(v): k for k, v in enumerate(file_ids)})
+    d2, chi2 = g.gate_edges(kind, a, b, meas, info)
+    thr = gate_thresholds(kind)
+    print(f"gate of {len(kind)} candidate edges from {path} (accept: d2 <= the 0.95 chi-square quantile):")
+    for c, (i, j) in enumerate(ids):
+        print(f"{i} {j} d2 {d2[c]:.9g} chi2 {chi2[c]:.9g} threshold {thr[c]:g} {'accept' if d2[c] <= thr[c] else 'reject'}")
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m rustrobotics_amd", description=__doc__,
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -101,6 +160,8 @@ def main(argv=None):
                     help="after the optimisation write every node's covariance block: id, d, upper triangle")
     ap.add_argument("--joint", type=_ids_arg, metavar="ID,ID,...", default=None,
                     help="after the optimisation print the joint covariance of these g2o vertex ids (any nodes)")
+    ap.add_argument("--gate", metavar="FILE", default=None,
+                    help="after the optimisation gate the candidate EDGE_* lines of FILE: d2, e^T Omega e, accept / reject")
     a = ap.parse_args(argv)
     solver = PoseGraphSolver[a.solver]
 
@@ -119,6 +180,8 @@ def main(argv=None):
             write_marginals(g, a.marginals)
         if a.joint:
             print_joint(g, a.joint)
+        if a.gate:
+            print_gate(g, a.gate)
         return 0
     iters = 10 if a.iterations is None else a.iterations
     new().optimize(iters, False, False)   # warm-up: library load, HIP context

@@ -33,6 +33,7 @@ EXPORTS = (
     "rr_pgo_exchange_buffer", "rr_pgo_set_exchange_buffer", "rr_pgo_stage", "rr_pgo_stage_scalars", "rr_pgo_stream",
     "rr_pgo_node_owner", "rr_pgo_trim", "rr_pgo_set_robust_kernel", "rr_pgo_edge_errors", "rr_pgo_solve_form",
     "rr_pgo_marginals", "rr_pgo_marginals_times", "rr_pgo_covariances", "rr_pgo_covariances_times",
+    "rr_pgo_gate_edges", "rr_pgo_gate_times",
 )
 
 
@@ -136,6 +137,8 @@ def load():
     L.rr_pgo_marginals_times.argtypes = [vp, dp]
     L.rr_pgo_covariances.argtypes = [vp, C.c_int32, ip, ip, dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.rr_pgo_covariances_times.argtypes = [vp, dp]
+    L.rr_pgo_gate_edges.argtypes = [vp, C.c_int32, ip, ip, ip, dp, dp, dp, dp, dp, C.POINTER(C.c_int64)]
+    L.rr_pgo_gate_times.argtypes = [vp, dp]
     if L.rr_pgo_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH} speaks ABI version {L.rr_pgo_abi_version()}, this mirror {ABI_VERSION}: rebuild the library")
     _lib = L

@@ -260,6 +260,11 @@ struct EngineBase {
   // rr_pgo_covariances (arguments checked; off as for marginals) / rr_pgo_covariances_times
   virtual void covariances(int nq, const int32_t *na, const int32_t *nb, const int64_t *off, double *out) = 0;
   virtual void covariances_times(double *ms) const = 0;
+  // rr_pgo_gate_edges (arguments checked; cand: kind, nodes, measurement, Omega and Omega^-1 filled in; soff: [n + 1] offsets
+  // of the innovation covariances in innov; chi2 and innov may be null) / rr_pgo_gate_times
+  virtual void gate_edges(int n, const int32_t *from, const int32_t *to, const int64_t *soff, std::vector<GateCand> &cand,
+                          double *d2, double *chi2, double *innov) = 0;
+  virtual void gate_times(double *ms) const = 0;
   int n_launches_per_iter = 0;
 };
 
@@ -440,6 +445,10 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   DevBuf<double> ts_out_;
   EventHolder ts_ev_[4];
   double ts_ms_[3] = {0, 0, 0};      // the last call: linearise + factor, tree solve, products + gather
+  // the gate of candidate edges (rr_pgo_gate_edges): the covariance plan and workspace above, plus its own records
+  DevBuf<GateCand> gate_cand_;
+  EventHolder gate_ev_[4];
+  double gate_ms_[3] = {0, 0, 0};    // the last call: linearise + factor, tree solve, gate kernel + copy
   static constexpr int kGemvSlices = 16;   // row slices of the multi-workgroup L21^T x product
   DevBuf<double> chi_partial_, norm_partial_, hist_;
   DevBuf<int> counter_, err_, blocks_done_;
@@ -2951,6 +2960,35 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     if (!v.empty()) HIPCHK(hipMemcpyAsync(b.p, v.data(), v.size() * sizeof(U), hipMemcpyHostToDevice, stream_));
   }
 
+  // a plan's tables and workspace on the device; the forward solve of its columns, one launch per level (Z, U)
+  void ts_stage(const TsPlan &pl) {
+    ts_fill(ts_tasks_, pl.tasks);
+    ts_fill(ts_child_, pl.child);
+    ts_fill(ts_unit_, pl.unit);
+    ts_fill(ts_czrow_, pl.czrow);
+    ts_grow(ts_z_, (size_t)pl.zrows * TS_MC);
+    ts_grow(ts_u_, (size_t)pl.urows * TS_MC);
+  }
+  void ts_forward(const TsPlan &pl) {
+    TsArgs<T> a;
+    a.meta = ts_meta_.p;
+    a.tasks = ts_tasks_.p;
+    a.child = ts_child_.p;
+    a.unit = ts_unit_.p;
+    a.rel = rel_.p;
+    a.lvals = lvals_.p;
+    a.winv = winv_.p;
+    a.Z = ts_z_.p;
+    a.U = ts_u_.p;
+    if constexpr (std::is_same<T, double>::value)
+      for (size_t l = 0; l + 1 < pl.level_ptr.size(); l++) {
+        const int begin = pl.level_ptr[l], count = pl.level_ptr[l + 1] - begin;
+        if (count <= 0) continue;
+        hipLaunchKernelGGL((k_tree_fwd<T>), dim3((unsigned)count), dim3(TS_THREADS), ts_lds_, stream_, a, begin);
+      }
+    check_launch("k_tree_fwd");
+  }
+
   // queries [q0, q1) over the factor in lvals / winv; `first`: the factorisation of this call has not been waited for yet
   void covariances_run(int q0, int q1, const int32_t *na, const int32_t *nb, const int64_t *off, double *out, bool &first) {
     if constexpr (std::is_same<T, double>::value && std::is_same<S, double>::value) {
@@ -2965,31 +3003,11 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
         return;
       }
       const int64_t n_vals = off[q1] - off[q0];
-      ts_fill(ts_tasks_, pl.tasks);
-      ts_fill(ts_child_, pl.child);
-      ts_fill(ts_unit_, pl.unit);
-      ts_fill(ts_czrow_, pl.czrow);
+      ts_stage(pl);
       ts_fill(ts_query_, pl.query);
-      ts_grow(ts_z_, (size_t)pl.zrows * TS_MC);
-      ts_grow(ts_u_, (size_t)pl.urows * TS_MC);
       ts_grow(ts_out_, (size_t)n_vals);
       if (!first) HIPCHK(hipEventRecord(ts_ev_[1], stream_));
-      TsArgs<T> a;
-      a.meta = ts_meta_.p;
-      a.tasks = ts_tasks_.p;
-      a.child = ts_child_.p;
-      a.unit = ts_unit_.p;
-      a.rel = rel_.p;
-      a.lvals = lvals_.p;
-      a.winv = winv_.p;
-      a.Z = ts_z_.p;
-      a.U = ts_u_.p;
-      for (size_t l = 0; l + 1 < pl.level_ptr.size(); l++) {
-        const int begin = pl.level_ptr[l], count = pl.level_ptr[l + 1] - begin;
-        if (count <= 0) continue;
-        hipLaunchKernelGGL((k_tree_fwd<T>), dim3((unsigned)count), dim3(TS_THREADS), ts_lds_, stream_, a, begin);
-      }
-      check_launch("k_tree_fwd");
+      ts_forward(pl);
       HIPCHK(hipEventRecord(ts_ev_[2], stream_));
       CovArgs<T> c;
       c.meta = ts_meta_.p;
@@ -3033,6 +3051,103 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     }
   }
   void covariances_times(double *ms) const override { for (int k = 0; k < 3; k++) ms[k] = ts_ms_[k]; }
+
+  // ---- Mahalanobis gate of candidate edges (include/rr_pgo.h, rr_pgo_gate_edges; treesolve.hip.h, k_gate_pairs)
+  // candidates [c0, c1): the plan of their nodes' columns is the covariance plan of the pairs (from, to)
+  void gate_run(int c0, int c1, const int32_t *from, const int32_t *to, const int64_t *soff, std::vector<GateCand> &cand,
+                double *d2, double *chi2, double *innov, bool &first) {
+    if constexpr (std::is_same<T, double>::value && std::is_same<S, double>::value) {
+      TsPlan pl;
+      covariances_plan(c0, c1, from, to, soff, pl);
+      const size_t ws = (size_t)(pl.zrows + pl.urows) * TS_MC * sizeof(T);
+      if (ws > TS_WS_BYTES) {
+        if (c1 - c0 <= 1) throw ApiError(RR_PGO_ENOMEM, "rr_pgo_gate_edges: one candidate needs " + std::to_string(ws) + " bytes of workspace");
+        const int mid = c0 + (c1 - c0) / 2;
+        gate_run(c0, mid, from, to, soff, cand, d2, chi2, innov, first);
+        gate_run(mid, c1, from, to, soff, cand, d2, chi2, innov, first);
+        return;
+      }
+      const int n = c1 - c0;
+      const int64_t n_s = soff[c1] - soff[c0];
+      auto front_of = [&](int v) { return ts_col_sn_[sym_.node_pcol[v]]; };
+      for (int c = c0; c < c1; c++) {
+        GateCand &gc = cand[c];
+        const CovQuery &cq = pl.query[c - c0];
+        gc.lca = cq.lca;
+        gc.fa = front_of(from[c]);
+        gc.fb = front_of(to[c]);
+        gc.chunk_a = cq.chunk_a;
+        gc.chunk_b = cq.chunk_b;
+        std::memcpy(gc.ca, cq.ca, sizeof(gc.ca));
+        std::memcpy(gc.cb, cq.cb, sizeof(gc.cb));
+        gc.ooff = cq.ooff;
+      }
+      ts_stage(pl);
+      ts_grow(gate_cand_, (size_t)n);
+      HIPCHK(hipMemcpyAsync(gate_cand_.p, cand.data() + c0, (size_t)n * sizeof(GateCand), hipMemcpyHostToDevice, stream_));
+      const size_t n_out = 2 * (size_t)n + (innov ? (size_t)n_s : 0);
+      ts_grow(ts_out_, n_out);
+      if (!first) HIPCHK(hipEventRecord(gate_ev_[1], stream_));
+      ts_forward(pl);
+      HIPCHK(hipEventRecord(gate_ev_[2], stream_));
+      GateArgs<T> a;
+      a.meta = ts_meta_.p;
+      a.cand = gate_cand_.p;
+      a.czrow = ts_czrow_.p;
+      a.Z = ts_z_.p;
+      a.pose = pose_.p;
+      a.d2 = ts_out_.p;
+      a.chi2 = ts_out_.p + n;
+      a.sout = innov ? ts_out_.p + 2 * (size_t)n : nullptr;
+      a.S = sym_.S;
+      if (is3d_) hipLaunchKernelGGL((k_gate_pairs<T, 6>), dim3((unsigned)n), dim3(COV_THREADS), 0, stream_, a);
+      else hipLaunchKernelGGL((k_gate_pairs<T, 3>), dim3((unsigned)n), dim3(COV_THREADS), 0, stream_, a);
+      check_launch("k_gate_pairs");
+      std::vector<double> host(n_out);
+      HIPCHK(hipMemcpyAsync(host.data(), ts_out_.p, n_out * sizeof(double), hipMemcpyDeviceToHost, stream_));
+      HIPCHK(hipEventRecord(gate_ev_[3], stream_));
+      HIPCHK(hipStreamSynchronize(stream_));
+      if (first) check_device_error();   // a non-positive pivot of H: nothing has been written
+      for (int k = first ? 0 : 1; k < 3; k++) {
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, gate_ev_[k], gate_ev_[k + 1]));
+        gate_ms_[k] += ms;
+      }
+      first = false;
+      std::memcpy(d2 + c0, host.data(), (size_t)n * sizeof(double));
+      if (chi2) std::memcpy(chi2 + c0, host.data() + n, (size_t)n * sizeof(double));
+      if (innov && n_s > 0) std::memcpy(innov + soff[c0], host.data() + 2 * (size_t)n, (size_t)n_s * sizeof(double));
+    }
+  }
+
+  void gate_edges(int n, const int32_t *from, const int32_t *to, const int64_t *soff, std::vector<GateCand> &cand, double *d2,
+                  double *chi2, double *innov) override {
+    if (sharded_ || world_ > 1) throw ApiError(RR_PGO_EUNSUPPORTED, "rr_pgo_gate_edges: sharded handle (a rank holds a part of the factor only)");
+    if constexpr (!(std::is_same<T, double>::value && std::is_same<S, double>::value)) {
+      throw ApiError(RR_PGO_EUNSUPPORTED, "rr_pgo_gate_edges: F32 / MIXED handle (a single-precision factor of a matrix of condition ~1e10 has no meaningful inverse): create the handle with RR_PGO_F64");
+    } else {
+      if (sym_.n_big > 0) throw ApiError(RR_PGO_EUNSUPPORTED, "rr_pgo_gate_edges: " + std::to_string(sym_.n_big) + " fronts beyond LDS (n_big_fronts must be 0)");
+      try {
+        covariances_prepare();
+      } catch (const ApiError &e) {   // the same limits, under this entry point's name
+        std::string msg = e.what();
+        const std::string other = "rr_pgo_covariances";
+        const size_t at = msg.find(other);
+        if (at != std::string::npos) msg.replace(at, other.size(), "rr_pgo_gate_edges");
+        throw ApiError(e.code, msg);
+      }
+      for (EventHolder &e : gate_ev_) e.create(hipEventDefault);
+      for (double &v : gate_ms_) v = 0;
+      if (n == 0) return;
+      HIPCHK(hipEventRecord(gate_ev_[0], stream_));
+      launch_linearize(0.0, 0, 1);
+      launch_factor();
+      HIPCHK(hipEventRecord(gate_ev_[1], stream_));
+      bool first = true;
+      gate_run(0, n, from, to, soff, cand, d2, chi2, innov, first);
+    }
+  }
+  void gate_times(double *ms) const override { for (int k = 0; k < 3; k++) ms[k] = gate_ms_[k]; }
 
   void debug_withhold(int mode) override {
     HIPCHK(hipStreamSynchronize(stream_));
@@ -3705,6 +3820,102 @@ int rr_pgo_covariances(rr_pgo *h, int32_t n_query, const int32_t *node_a, const 
 int rr_pgo_covariances_times(const rr_pgo *h, double *ms) {
   if (!h || !ms) { g_last_error = "null argument"; return RR_PGO_EINVAL; }
   return guarded([&] { h->engine->covariances_times(ms); });
+}
+
+// Cholesky of the d x d matrix in w (row stride ld), in place in the lower triangle; false: not positive definite
+static bool small_cholesky(double *w, int d, int ld) {
+  for (int c = 0; c < d; c++) {
+    double v = w[c * ld + c];
+    for (int k = 0; k < c; k++) v -= w[c * ld + k] * w[c * ld + k];
+    if (!(v > 0.0) || !std::isfinite(v)) return false;
+    const double l = std::sqrt(v);
+    w[c * ld + c] = l;
+    for (int r = c + 1; r < d; r++) {
+      double x = w[r * ld + c];
+      for (int k = 0; k < c; k++) x -= w[r * ld + k] * w[c * ld + k];
+      w[r * ld + c] = x / l;
+    }
+  }
+  return true;
+}
+
+int rr_pgo_gate_edges(rr_pgo *h, int32_t n_cand, const int32_t *edge_kind, const int32_t *edge_from, const int32_t *edge_to,
+                      const double *edge_meas, const double *edge_info, double *d2_out, double *chi2_out, double *innov_out,
+                      int64_t *innov_offset) {
+  if (!h || n_cand < 0) { g_last_error = "rr_pgo_gate_edges: bad argument (n_cand < 0 or no handle)"; return RR_PGO_EINVAL; }
+  if (n_cand > 0 && (!edge_kind || !edge_from || !edge_to || !edge_meas || !edge_info || !d2_out)) {
+    g_last_error = "rr_pgo_gate_edges: null argument (edge_kind, edge_from, edge_to, edge_meas, edge_info and d2_out are required)";
+    return RR_PGO_EINVAL;
+  }
+  const HostGraph &g = h->g;
+  const int N = g.n_nodes(), D = g.has_se3 ? 6 : 3;
+  std::vector<GateCand> cand((size_t)n_cand);
+  std::vector<int64_t> soff((size_t)n_cand + 1, 0);
+  int64_t mo = 0, io = 0;
+  for (int c = 0; c < n_cand; c++) {
+    const std::string who = "rr_pgo_gate_edges: candidate " + std::to_string(c) + ": ";
+    auto bad = [&](const std::string &what) { g_last_error = who + what; return RR_PGO_EINVAL; };
+    const int kind = edge_kind[c], a = edge_from[c], b = edge_to[c];
+    if (kind != EDGE_SE2 && kind != EDGE_SE2_XY && kind != EDGE_SE3) return bad("unknown edge kind " + std::to_string(kind));
+    if (a < 0 || a >= N || b < 0 || b >= N) return bad("node index out of range");
+    if (a == b) return bad("from == to");
+    const int ka = g.node_kind[a], kb = g.node_kind[b];
+    if (kind == EDGE_SE2 && (ka != NODE_SE2 || kb != NODE_SE2)) return bad("an SE2 edge needs two SE2 poses");
+    if (kind == EDGE_SE2_XY && (ka != NODE_SE2 || kb != NODE_XY)) return bad("an SE2_XY edge goes from an SE2 pose to an XY landmark");
+    if (kind == EDGE_SE3 && (ka != NODE_SE3 || kb != NODE_SE3)) return bad("an SE3 edge needs two SE3 poses");
+    const int nm = edge_meas_len(kind), ni = edge_info_len(kind), de = kind == EDGE_SE2 ? 3 : kind == EDGE_SE2_XY ? 2 : 6;
+    const double *m = edge_meas + mo, *w = edge_info + io;
+    mo += nm;
+    io += ni;
+    for (int t = 0; t < nm; t++)
+      if (!std::isfinite(m[t])) return bad("non-finite measurement");
+    GateCand &gc = cand[c];
+    std::memset(&gc, 0, sizeof(gc));
+    gc.kind = kind;
+    gc.na = a;
+    gc.nb = b;
+    if (kind == EDGE_SE2) {
+      gc.meas[0] = m[0]; gc.meas[1] = m[1]; gc.meas[2] = std::cos(m[2]); gc.meas[3] = std::sin(m[2]);
+    } else if (kind == EDGE_SE2_XY) {
+      gc.meas[0] = m[0]; gc.meas[1] = m[1];
+    } else {   // the quaternion normalised like UnitQuaternion::from_quaternion, as the handle's own measurements are
+      const double nq = std::sqrt(m[3] * m[3] + m[4] * m[4] + m[5] * m[5] + m[6] * m[6]);
+      if (!(nq > 0.0)) return bad("zero quaternion in the measurement");
+      gc.meas[0] = m[0]; gc.meas[1] = m[1]; gc.meas[2] = m[2];
+      for (int t = 0; t < 4; t++) gc.meas[4 + t] = m[3 + t] / nq;
+    }
+    // Omega from its packed upper triangle; Omega^-1 = L^-T L^-1 from its Cholesky factor
+    double L[36] = {0}, Li[36] = {0};
+    for (int i = 0, t = 0; i < de; i++)
+      for (int j = i; j < de; j++, t++) {
+        if (!std::isfinite(w[t])) return bad("non-finite information matrix");
+        gc.info[i * D + j] = gc.info[j * D + i] = w[t];
+        L[j * 6 + i] = w[t];
+        L[i * 6 + j] = w[t];
+      }
+    if (!small_cholesky(L, de, 6)) return bad("information matrix not positive definite");
+    for (int j = 0; j < de; j++)     // Li = L^-1, column by column
+      for (int i = j; i < de; i++) {
+        double x = i == j ? 1.0 : 0.0;
+        for (int k = j; k < i; k++) x -= L[i * 6 + k] * Li[k * 6 + j];
+        Li[i * 6 + j] = x / L[i * 6 + i];
+      }
+    for (int i = 0; i < de; i++)
+      for (int j = 0; j <= i; j++) {
+        double x = 0.0;
+        for (int k = i; k < de; k++) x += Li[k * 6 + i] * Li[k * 6 + j];
+        gc.cov[i * D + j] = gc.cov[j * D + i] = x;
+      }
+    soff[c + 1] = soff[c] + de * de;
+  }
+  const int rc = guarded([&] { h->engine->gate_edges(n_cand, edge_from, edge_to, soff.data(), cand, d2_out, chi2_out, innov_out); });
+  if (rc == RR_PGO_OK && innov_offset) std::copy(soff.begin(), soff.end(), innov_offset);
+  return rc;
+}
+
+int rr_pgo_gate_times(const rr_pgo *h, double *ms) {
+  if (!h || !ms) { g_last_error = "null argument"; return RR_PGO_EINVAL; }
+  return guarded([&] { h->engine->gate_times(ms); });
 }
 
 int rr_pgo_iterate_async(rr_pgo *h, int32_t iters) {

@@ -7,6 +7,7 @@
 //
 //   k_tree_fwd    one workgroup per (chunk of TS_MC columns, active front), one launch per level of the tree, deepest first
 //   k_cov_pairs   one workgroup per query: Sigma_ab = sum over the common path's pivot rows of Z_a[row]^T Z_b[row]
+//   k_gate_pairs  one workgroup per candidate edge: its Mahalanobis distance from the same Z (the end of this file)
 //
 // Columns.  The distinct queried nodes are ordered by (front, pivot column) -- fronts are numbered in elimination order, so
 // neighbours share paths -- and packed, whole nodes at a time, into chunks of TS_MC = 32 columns (unused columns stay zero).
@@ -213,6 +214,182 @@ __global__ void __launch_bounds__(COV_THREADS) k_cov_pairs(CovArgs<T> a) {
 #pragma unroll
     for (int k = 1; k < NS; k++) s += part[k * 64 + tid];
     a.out[q->ooff + tid] = (double)s;
+  }
+}
+
+// ---- Mahalanobis gate of candidate edges (rr_pgo_gate_edges)
+//
+// For a candidate edge between nodes a and b with error e, Jacobians A, B and information Omega at the current state:
+//   P = [A B] Sigma_{ab,ab} [A B]^T = G^T G,   G = Z_a A^T + Z_b B^T   (one row per pivot row on the two root paths),
+//   S = Omega^-1 + P,   d2 = e^T S^-1 e,   s = e^T Omega e.
+// The four blocks of Sigma_{ab,ab} are large against P (the two poses move together): G forms the difference row by row,
+// on the common path, BEFORE it is squared, and P is positive semi-definite by construction.
+struct GateCand {
+  int32_t lca, fa, fb;            // lowest common front (-1: different trees), the fronts of a and of b
+  int32_t chunk_a, chunk_b;
+  int32_t na, nb, kind;           // the two nodes; RR_PGO_EDGE_*
+  uint8_t ca[8], cb[8];           // as CovQuery
+  int64_t ooff;                   // offset of S (d_e x d_e, row-major) in sout
+  double meas[8];                 // 2-D: x, y, cos, sin | SE(3): t (3), -, q (4, normalised)
+  double info[36], cov[36];       // Omega and Omega^-1, row stride D (3 or 6), zero padded
+};
+static_assert(sizeof(GateCand) == 696, "GateCand is one 696-byte record");
+
+template <typename T> struct GateArgs {
+  const TsMeta *meta;
+  const GateCand *cand;
+  const int32_t *czrow;           // as CovArgs
+  const T *Z;
+  const typename VecT<T>::V4 *pose;
+  double *d2, *chi2, *sout;       // sout null: S is not asked for
+  int32_t S;
+};
+
+// the rows of the fronts from f up to (not including) `stop`, slice by slice: acc += G_r[i] G_r[j]
+template <typename T, int D, bool UA, bool UB>
+__device__ __forceinline__ T gate_walk(const TsMeta *meta, const T *Z, const int32_t *za_tab, const int32_t *zb_tab, int f, int stop,
+                                       int slice, int ns, const int (&cola)[D], const int (&colb)[D], const T (&Ai)[D],
+                                       const T (&Aj)[D], const T (&Bi)[D], const T (&Bj)[D], T acc) {
+  for (; f >= 0 && f != stop; f = meta[f].parent) {
+    const int nc = meta[f].nc, za = UA ? za_tab[f] : 0, zb = UB ? zb_tab[f] : 0;
+    if (za < 0 || zb < 0) continue;
+    for (int r = slice; r < nc; r += ns) {
+      T gi = 0, gj = 0;
+      if (UA) {
+        const T *p = Z + (int64_t)(za + r) * TS_MC;
+#pragma unroll
+        for (int k = 0; k < D; k++) {
+          const T z = p[cola[k]];
+          gi = fma(z, Ai[k], gi);
+          gj = fma(z, Aj[k], gj);
+        }
+      }
+      if (UB) {
+        const T *p = Z + (int64_t)(zb + r) * TS_MC;
+#pragma unroll
+        for (int k = 0; k < D; k++) {
+          const T z = p[colb[k]];
+          gi = fma(z, Bi[k], gi);
+          gj = fma(z, Bj[k], gj);
+        }
+      }
+      acc = fma(gi, gj, acc);
+    }
+  }
+  return acc;
+}
+
+// One workgroup per candidate; D = 3 (a 2-D graph: SE2 and SE2_XY candidates) or 6 (SE3).  Lanes 0 of waves 0 and 1 evaluate
+// (e, A) and B with the linearisation's own code.  A wave is one slice of rows (row = slice, slice + 8, ... of every front);
+// lane t of it accumulates entry t of P's lower triangle.  The eight slices are added in slice order, then lane 0 of wave 0
+// factors S = Omega^-1 + P in LDS.  A non-positive pivot of S (Omega is checked on the host: rounding only) gives d2 = NaN.
+template <typename T, int D>
+__global__ void __launch_bounds__(COV_THREADS) k_gate_pairs(GateArgs<T> a) {
+  constexpr int NS = COV_THREADS / 64;
+  using V4 = typename VecT<T>::V4;
+  __shared__ T part[NS * 32], sA[D * D], sB[D * D], se[D], sS[D * D];
+  const GateCand *q = a.cand + blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63, slice = wave_index();
+  const int kind = q->kind;
+  const int de = kind == 1 ? 2 : D, db = kind == 1 ? 2 : D, ntri = de * (de + 1) / 2;
+  if (lane == 0 && slice < 2) {
+    if constexpr (D == 3) {
+      if (slice == 0) {
+        const V4 z = {(T)q->meas[0], (T)q->meas[1], (T)q->meas[2], (T)q->meas[3]};
+        T e[3], A[3][3], B[3][3];
+        edge_linearize_2d<T>(kind, a.pose[q->na], a.pose[q->nb], z, e, A, B);
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+          se[i] = e[i];
+#pragma unroll
+          for (int j = 0; j < 3; j++) {
+            sA[i * 3 + j] = A[i][j];
+            sB[i * 3 + j] = B[i][j];
+          }
+        }
+      }
+    } else {
+      const V4 it = a.pose[2 * q->na], iq = a.pose[2 * q->na + 1], jt = a.pose[2 * q->nb], jq = a.pose[2 * q->nb + 1];
+      const T ti[3] = {it.x, it.y, it.z}, qi[4] = {iq.x, iq.y, iq.z, iq.w};
+      const T tj[3] = {jt.x, jt.y, jt.z}, qj[4] = {jq.x, jq.y, jq.z, jq.w};
+      const T tz[3] = {(T)q->meas[0], (T)q->meas[1], (T)q->meas[2]};
+      const T qz[4] = {(T)q->meas[4], (T)q->meas[5], (T)q->meas[6], (T)q->meas[7]};
+      T e[6], J[6][6];
+      edge_linearize_3d<T>(slice, ti, qi, tj, qj, tz, qz, e, J);
+      T *dst = slice ? sB : sA;
+#pragma unroll
+      for (int i = 0; i < 6; i++) {
+        if (slice == 0) se[i] = e[i];
+#pragma unroll
+        for (int j = 0; j < 6; j++) dst[i * 6 + j] = J[i][j];
+      }
+    }
+  }
+  __syncthreads();
+  // ---- entry t = (i, j), j <= i, of the lower triangle; lanes past the triangle repeat its last entry
+  const int t = min(lane, ntri - 1);
+  int i = 0;
+  while ((i + 1) * (i + 2) / 2 <= t) i++;
+  const int j = t - i * (i + 1) / 2;
+  T Ai[D], Aj[D], Bi[D], Bj[D];
+  int cola[D], colb[D];
+#pragma unroll
+  for (int k = 0; k < D; k++) {
+    Ai[k] = sA[i * D + k];
+    Aj[k] = sA[j * D + k];
+    Bi[k] = sB[i * D + k];   // (the columns of B past d_b are zero: pose-landmark)
+    Bj[k] = sB[j * D + k];
+    cola[k] = q->ca[k];
+    colb[k] = q->cb[min(k, db - 1)];
+  }
+  const int32_t *za_tab = a.czrow + (int64_t)q->chunk_a * a.S, *zb_tab = a.czrow + (int64_t)q->chunk_b * a.S;
+  const int lca = q->lca;
+  T acc = 0;
+  acc = gate_walk<T, D, true, false>(a.meta, a.Z, za_tab, zb_tab, q->fa, lca, slice, NS, cola, colb, Ai, Aj, Bi, Bj, acc);
+  acc = gate_walk<T, D, false, true>(a.meta, a.Z, za_tab, zb_tab, q->fb, lca, slice, NS, cola, colb, Ai, Aj, Bi, Bj, acc);
+  if (lca >= 0) acc = gate_walk<T, D, true, true>(a.meta, a.Z, za_tab, zb_tab, lca, -1, slice, NS, cola, colb, Ai, Aj, Bi, Bj, acc);
+  if (lane < 32) part[slice * 32 + lane] = acc;
+  __syncthreads();
+  if (tid < ntri) {
+    T s = part[tid];
+#pragma unroll
+    for (int k = 1; k < NS; k++) s += part[k * 32 + tid];
+    s += (T)q->cov[i * D + j];
+    sS[i * D + j] = s;
+    sS[j * D + i] = s;
+  }
+  __syncthreads();
+  if (a.sout && tid < de * de) a.sout[q->ooff + tid] = (double)sS[(tid / de) * D + tid % de];   // both halves from the lower triangle
+  __syncthreads();
+  if (tid == 0) {
+    T c2 = 0;   // e^T Omega e, the sum order of edge_chi2_2d / edge_chi2_3d
+    for (int r = 0; r < de; r++) {
+      T we = 0;
+      for (int c = 0; c < de; c++) we += (T)q->info[r * D + c] * se[c];
+      c2 += se[r] * we;
+    }
+    a.chi2[blockIdx.x] = (double)c2;
+    // S = L L^T in place (lower triangle), y = L^-1 e, d2 = y^T y
+    bool ok = true;
+    T d2 = 0;
+    for (int c = 0; c < de; c++) {
+      T d = sS[c * D + c];
+      for (int k = 0; k < c; k++) d = fma(-sS[c * D + k], sS[c * D + k], d);
+      if (!(d > (T)0)) { ok = false; break; }
+      const T l = sqrt(d), inv = (T)1 / l;
+      sS[c * D + c] = l;
+      for (int r = c + 1; r < de; r++) {
+        T v = sS[r * D + c];
+        for (int k = 0; k < c; k++) v = fma(-sS[r * D + k], sS[c * D + k], v);
+        sS[r * D + c] = v * inv;
+      }
+      T y = se[c];
+      for (int k = 0; k < c; k++) y = fma(-sS[c * D + k], se[k], y);
+      y *= inv;
+      se[c] = y;
+      d2 = fma(y, y, d2);
+    }
+    a.d2[blockIdx.x] = ok ? (double)d2 : __builtin_nan("");
   }
 }
 

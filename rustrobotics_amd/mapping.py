@@ -33,6 +33,25 @@ class PoseGraphError(RuntimeError):
         self.code = code
 
 
+# 0.95 quantiles of the chi-square distribution with 2, 3 and 6 degrees of freedom (the default gate), and the error
+# dimension, measurement length and packed information length of an edge by kind (RR_PGO_EDGE_SE2, _SE2_XY, _SE3)
+CHI2_95_2, CHI2_95_3, CHI2_95_6 = 5.991, 7.815, 12.592
+GATE_DEFAULT_THRESHOLD = {0: CHI2_95_3, 1: CHI2_95_2, 2: CHI2_95_6}
+GATE_EDGE_DIM = (3, 2, 6)
+GATE_MEAS_LEN = (3, 2, 7)
+GATE_INFO_LEN = (6, 3, 21)
+
+
+def gate_thresholds(edge_kind, threshold=None):
+    """per-candidate threshold of PoseGraph.gate: a scalar, a per-kind mapping, or None (the 0.95 quantiles)"""
+    kind = np.asarray(edge_kind, np.int64)
+    if threshold is None:
+        threshold = GATE_DEFAULT_THRESHOLD
+    if hasattr(threshold, "keys"):
+        return np.array([float(threshold[int(k)]) for k in kind])
+    return np.full(kind.shape, float(threshold))
+
+
 def _check(rc):
     if rc != 0:
         raise PoseGraphError(rc, _lib.load().rr_pgo_last_error().decode())
@@ -325,6 +344,48 @@ class PoseGraph:
         """HIP-event milliseconds of the last covariance call: (linearise + factor, tree solve, products + gather)."""
         ms = np.zeros(3)
         _check(_lib.load().rr_pgo_covariances_times(self._h, _dp(ms)))
+        return tuple(float(v) for v in ms)
+
+    # -- Mahalanobis gate of candidate loop closures (include/rr_pgo.h, rr_pgo_gate_edges) ----
+    def gate_edges(self, edge_kind, edge_from, edge_to, edge_meas, edge_info, return_innovation=False):
+        """rr_pgo_gate_edges: (d2, chi2) of candidate edges that are not part of the graph, in rr_pgo_graph_desc packing --
+        d2 = e^T S^-1 e with S = Omega^-1 + J Sigma J^T at the current state, chi2 = e^T Omega e.  With return_innovation
+        also the list of the d_e x d_e matrices S."""
+        L = _lib.load()
+        kind = np.ascontiguousarray(edge_kind, np.int32)
+        a = np.ascontiguousarray(edge_from, np.int32)
+        b = np.ascontiguousarray(edge_to, np.int32)
+        meas = np.ascontiguousarray(edge_meas, np.float64).ravel()
+        info = np.ascontiguousarray(edge_info, np.float64).ravel()
+        if kind.ndim != 1 or a.shape != kind.shape or b.shape != kind.shape:
+            raise ValueError("edge_kind, edge_from and edge_to need the same length")
+        known = np.isin(kind, (0, 1, 2))   # (an unknown kind is the library's to refuse: the lengths are then not checked)
+        if np.all(known):
+            if len(meas) != int(np.sum(np.take(GATE_MEAS_LEN, kind))) or len(info) != int(np.sum(np.take(GATE_INFO_LEN, kind))):
+                raise ValueError("edge_meas / edge_info do not have the length the edge kinds ask for")
+        n = len(kind)
+        d2, chi2 = np.zeros(n), np.zeros(n)
+        off = np.zeros(n + 1, np.int64)
+        vals = None
+        if return_innovation:
+            vals = np.zeros(36 * max(n, 1))
+        _check(L.rr_pgo_gate_edges(self._h, n, _ip(kind), _ip(a), _ip(b), _dp(meas), _dp(info), _dp(d2), _dp(chi2),
+                                   None if vals is None else _dp(vals), off.ctypes.data_as(C.POINTER(C.c_int64))))
+        if not return_innovation:
+            return d2, chi2
+        dims = [int(round(np.sqrt(off[c + 1] - off[c]))) for c in range(n)]
+        return d2, chi2, [vals[off[c]:off[c + 1]].reshape(dims[c], dims[c]).copy() for c in range(n)]
+
+    def gate(self, edge_kind, edge_from, edge_to, edge_meas, edge_info, threshold=None):
+        """Boolean mask d2 <= threshold of the candidates (True: accept).  threshold: a scalar, a mapping from edge kind
+        (0 SE2, 1 SE2_XY, 2 SE3) to a scalar, or None: the 0.95 chi-square quantile of the edge's dimension."""
+        d2, _ = self.gate_edges(edge_kind, edge_from, edge_to, edge_meas, edge_info)
+        return d2 <= gate_thresholds(edge_kind, threshold)
+
+    def gate_times(self):
+        """HIP-event milliseconds of the last gate_edges call: (linearise + factor, tree solve, gate kernel + copy)."""
+        ms = np.zeros(3)
+        _check(_lib.load().rr_pgo_gate_times(self._h, _dp(ms)))
         return tuple(float(v) for v in ms)
 
     # -- PoseGraph::plot, :375-431 -------------------------------------------------------
