@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -130,6 +131,13 @@ struct DeviceArena {
   }
 };
 static thread_local DeviceArena *t_arena = nullptr;   // set while an engine allocates
+struct ArenaScope {   // every DevBuf::alloc of the scope draws from `a` (null: a buffer of its own, freed when it grows and with the handle)
+  DeviceArena *const prev = t_arena;
+  explicit ArenaScope(DeviceArena *a) { t_arena = a; }
+  ArenaScope(const ArenaScope &) = delete;
+  ArenaScope &operator=(const ArenaScope &) = delete;
+  ~ArenaScope() { t_arena = prev; }
+};
 
 // hipStreamCreate costs ~2 ms (a hardware queue) and hipStreamDestroy about as much: more than the ten
 // Gauss-Newton iterations of the reference's bench on intel.g2o.  Streams of destroyed handles are kept
@@ -422,32 +430,34 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   DevBuf<T> kvals_;
   bool kform_ = false;
   double kform_bytes_ = 0, kform_flops_ = 0;   // one factorisation's K steps: panel rows read + X written, 2 per multiply-add
+  // queries over the factor (rr_pgo_marginals, rr_pgo_covariances, rr_pgo_gate_edges): the tree tables and the events are made
+  // by the first such call
+  static constexpr bool f64_ = std::is_same<T, double>::value && std::is_same<S, double>::value;
+  std::vector<int32_t> front_depth_, col_front_;   // depth of a front (a root: 0); permuted scalar column -> front
+  EventHolder query_ev_[4];
   // marginal covariances (selinv.hip.h; rr_pgo_marginals): everything made on the first call
   DevBuf<T> svals_;                  // the selected inverse, a front's image laid out like its factor image (less the rhs row)
   DevBuf<SelMeta> sel_meta_;
   DevBuf<int32_t> sel_order_;        // fronts by tree level, root level first
-  std::vector<int32_t> sel_level_ptr_, sel_col_sn_;   // ranges of sel_order_; permuted scalar column -> supernode
+  std::vector<int32_t> sel_level_ptr_;   // ranges of sel_order_
   std::vector<int64_t> sel_soff_;
   size_t sel_lds_ = 0;
   bool sel_ready_ = false;
-  EventHolder sel_ev_[4];
   double sel_ms_[3] = {0, 0, 0};     // the last call: linearise + factor, selected inverse, gather
   // covariances of arbitrary pairs (treesolve.hip.h; rr_pgo_covariances): the per-front records are made on the first call,
   // in the arena; the plan of a call and its workspace live in buffers of their own that only grow
   DevBuf<TsMeta> ts_meta_;
-  std::vector<int32_t> ts_depth_, ts_col_sn_;   // depth of a front (a root: 0); permuted scalar column -> supernode
   size_t ts_lds_ = 0;
+  size_t ts_ws_bytes_ = TS_WS_BYTES;   // bound of Z + U of one pass (RR_PGO_TS_WS_BYTES=<n>, read at creation)
   bool ts_ready_ = false;
   DevBuf<TsTask> ts_tasks_;
   DevBuf<int32_t> ts_child_, ts_unit_, ts_czrow_;
   DevBuf<CovQuery> ts_query_;
   DevBuf<T> ts_z_, ts_u_;
   DevBuf<double> ts_out_;
-  EventHolder ts_ev_[4];
   double ts_ms_[3] = {0, 0, 0};      // the last call: linearise + factor, tree solve, products + gather
   // the gate of candidate edges (rr_pgo_gate_edges): the covariance plan and workspace above, plus its own records
   DevBuf<GateCand> gate_cand_;
-  EventHolder gate_ev_[4];
   double gate_ms_[3] = {0, 0, 0};    // the last call: linearise + factor, tree solve, gate kernel + copy
   static constexpr int kGemvSlices = 16;   // row slices of the multi-workgroup L21^T x product
   DevBuf<double> chi_partial_, norm_partial_, hist_;
@@ -489,10 +499,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
  public:
   Engine(const HostGraph &g, const Symbolic &sym, int rank, int world, bool sharded)
       : g_(g), sym_(sym), rank_(rank), world_(world), sharded_(sharded || world > 1) {
-    struct ArenaScope {   // every DevBuf::alloc of this constructor draws from arena_
-      explicit ArenaScope(DeviceArena *a) { t_arena = a; }
-      ~ArenaScope() { t_arena = nullptr; }
-    } scope(&arena_);
+    ArenaScope scope(&arena_);
     const bool ctimes = getenv("RR_PGO_ANALYZE_TIMES") != nullptr;   // wall time of the phases of this constructor on stderr
     double ct0 = now_ms();
     auto cmark = [&](const char *what) {
@@ -658,6 +665,8 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     if (const char *e = getenv("RR_PGO_FLOW_TASKS")) flow_max_tasks_ = std::atoi(e);
     if (const char *e = getenv("RR_PGO_SOLVE_FLOW")) solve_flow_on_ = std::atoi(e) != 0;
     if (const char *e = getenv("RR_PGO_FLOW_SCHUR_MIN")) flow_schur_min_ = std::atoi(e);
+    if (const char *e = getenv("RR_PGO_TS_WS_BYTES"))
+      if (const long long v = std::atoll(e); v > 0) ts_ws_bytes_ = (size_t)v;
     n_lin_blocks_ = (int)(((int64_t)n_list_ * LIN_GROUP + LIN_THREADS - 1) / LIN_THREADS);
     lin_blocks_pull_ = n_lin_blocks_;
     edge_lin_ = getenv("RR_PGO_EDGE_LINEARIZE") != nullptr && !is3d_ && !sharded_ && g_.n_edges() > 0;
@@ -2637,28 +2646,54 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   }
 
 
+  // ---- queries over the factor: what rr_pgo_marginals, rr_pgo_covariances and rr_pgo_gate_edges share
+  void require_f64_unsharded_lds_factor(const char *who) const {
+    const std::string w = who;
+    if (sharded_ || world_ > 1) throw ApiError(RR_PGO_EUNSUPPORTED, w + ": sharded handle (a rank holds a part of the factor only)");
+    if (!f64_) throw ApiError(RR_PGO_EUNSUPPORTED, w + ": F32 / MIXED handle (a single-precision factor of a matrix of condition ~1e10 has no meaningful inverse): create the handle with RR_PGO_F64");
+    if (sym_.n_big > 0) throw ApiError(RR_PGO_EUNSUPPORTED, w + ": " + std::to_string(sym_.n_big) + " fronts beyond LDS (n_big_fronts must be 0)");
+  }
+  // depth of every front, front of every permuted column, the four events of a call: made once
+  void tree_tables(const char *who) {
+    if (!front_depth_.empty()) return;
+    const Symbolic &sym = sym_;
+    for (int f = 0; f < sym.S; f++)
+      if (sym.sn_parent[f] < 0 && sym.sn_nrows[f] != 0) throw ApiError(RR_PGO_EUNSUPPORTED, std::string(who) + ": a root front with rows below its pivot block");
+    for (EventHolder &e : query_ev_) e.create(hipEventDefault);
+    col_front_.assign((size_t)g_.dim, -1);
+    std::vector<int32_t> depth((size_t)sym.S, 0);
+    for (int f = sym.S - 1; f >= 0; f--) {   // children precede parents
+      if (sym.sn_parent[f] >= 0) depth[f] = depth[sym.sn_parent[f]] + 1;
+      for (int c = 0; c < sym.sn_ncols[f]; c++) col_front_[sym.sn_col0[f] + c] = f;
+    }
+    front_depth_ = std::move(depth);
+  }
+  int front_of(int v) const { return col_front_[sym_.node_pcol[v]]; }
+  // the three intervals between the events in ms.  accumulate: a later pass of the same call -- event 0 belongs to the first
+  // pass, so intervals 1 and 2 are added
+  void query_times(double *ms, bool accumulate) {
+    for (int k = accumulate ? 1 : 0; k < 3; k++) {
+      float t = 0;
+      HIPCHK(hipEventElapsedTime(&t, query_ev_[k], query_ev_[k + 1]));
+      ms[k] = accumulate ? ms[k] + t : t;
+    }
+  }
+
   // ---- marginal covariances (include/rr_pgo.h, rr_pgo_marginals)
-  void marginals_prepare() {
+  void marginals_prepare(const char *who) {
     if (sel_ready_) return;
+    tree_tables(who);
     const Symbolic &sym = sym_;
     const int S_ = sym.S;
     std::vector<SelMeta> meta((size_t)S_);
     sel_soff_.assign((size_t)S_ + 1, 0);
-    std::vector<int32_t> depth((size_t)S_, 0);
-    int max_depth = 0;
     size_t lds_elems = 0;
-    sel_col_sn_.assign((size_t)g_.dim, -1);
-    for (int f = S_ - 1; f >= 0; f--) {   // children precede parents
-      if (sym.sn_parent[f] >= 0) depth[f] = depth[sym.sn_parent[f]] + 1;
-      max_depth = std::max(max_depth, depth[f]);
-    }
     for (int f = 0; f < S_; f++) {
       const int64_t nc = sym.sn_ncols[f], nr = sym.sn_nrows[f];
-      if (nc + nr > SELINV_MAX_ROWS) throw ApiError(RR_PGO_EUNSUPPORTED, "rr_pgo_marginals: a front of " + std::to_string(nc + nr) + " rows exceeds what one workgroup holds");
+      if (nc + nr > SELINV_MAX_ROWS) throw ApiError(RR_PGO_EUNSUPPORTED, std::string(who) + ": a front of " + std::to_string(nc + nr) + " rows exceeds what one workgroup holds");
       const int64_t image = (nc + nr) * nc + nr * (nr + 1) / 2;
       lds_elems = std::max(lds_elems, (size_t)image);
       sel_soff_[f + 1] = sel_soff_[f] + ((image + 3) & ~(int64_t)3);
-      for (int c = 0; c < nc; c++) sel_col_sn_[sym.sn_col0[f] + c] = f;
     }
     for (int f = 0; f < S_; f++) {
       SelMeta &m = meta[f];
@@ -2674,42 +2709,34 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
       m.soff = sel_soff_[f];
       m.psoff = p >= 0 ? sel_soff_[p] : 0;
       m.rel_ptr = sym.rel_ptr[f];
-      if (p < 0 && m.nr != 0) throw ApiError(RR_PGO_EUNSUPPORTED, "rr_pgo_marginals: a root front with rows below its pivot block");
     }
     sel_lds_ = lds_elems * sizeof(T);
     if (sel_lds_ + (size_t)(256 + SELINV_GPART * 256) * sizeof(T) > (size_t)160 * 1024)
-      throw ApiError(RR_PGO_EUNSUPPORTED, "rr_pgo_marginals: fronts beyond LDS");
+      throw ApiError(RR_PGO_EUNSUPPORTED, std::string(who) + ": fronts beyond LDS");
     std::vector<int32_t> order;
     sel_level_ptr_.assign(1, 0);
+    const int max_depth = *std::max_element(front_depth_.begin(), front_depth_.end());
     for (int d = 0; d <= max_depth; d++) {
       for (int f = S_ - 1; f >= 0; f--)
-        if (depth[f] == d) order.push_back(f);
+        if (front_depth_[f] == d) order.push_back(f);
       sel_level_ptr_.push_back((int32_t)order.size());
     }
-    DeviceArena *prev = t_arena;
-    t_arena = &arena_;   // like every other buffer of the handle: back to the pool with it
-    try {
+    {
+      ArenaScope scope(&arena_);   // like every other buffer of the handle: back to the pool with it
       sel_meta_.upload(meta);
       sel_order_.upload(order);
       svals_.alloc((size_t)sel_soff_[S_] + 4);
-    } catch (...) {
-      t_arena = prev;
-      throw;
     }
-    t_arena = prev;
-    for (EventHolder &e : sel_ev_) e.create(hipEventDefault);
     if constexpr (std::is_same<T, double>::value)
       HIPCHK(hipFuncSetAttribute((const void *)k_selinv_level<T, SELINV_THREADS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sel_lds_));
     sel_ready_ = true;
   }
 
   void marginals(int nq, const int32_t *na, const int32_t *nb, const int64_t *off, double *out) override {
-    if (sharded_ || world_ > 1) throw ApiError(RR_PGO_EUNSUPPORTED, "rr_pgo_marginals: sharded handle (a rank holds a part of the factor only)");
-    if constexpr (!(std::is_same<T, double>::value && std::is_same<S, double>::value)) {
-      throw ApiError(RR_PGO_EUNSUPPORTED, "rr_pgo_marginals: F32 / MIXED handle (a single-precision factor of a matrix of condition ~1e10 has no meaningful inverse): create the handle with RR_PGO_F64");
-    } else {
-      if (sym_.n_big > 0) throw ApiError(RR_PGO_EUNSUPPORTED, "rr_pgo_marginals: " + std::to_string(sym_.n_big) + " fronts beyond LDS (n_big_fronts must be 0)");
-      marginals_prepare();
+    static constexpr const char *who = "rr_pgo_marginals";
+    require_f64_unsharded_lds_factor(who);
+    if constexpr (f64_) {
+      marginals_prepare(who);
       const Symbolic &sym = sym_;
       // ---- where every output scalar lives in svals
       const int64_t n_vals = off[nq];
@@ -2724,7 +2751,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
         const int va = na ? na[q] : q, vb = nb ? nb[q] : va;
         const int da = node_cols(va, pc_a), db = node_cols(vb, pc_b);
         const int ve = sym.node_pcol[va] <= sym.node_pcol[vb] ? va : vb;   // eliminated first: its front holds the pair, or none does
-        const int f = sel_col_sn_[sym.node_pcol[ve]];
+        const int f = front_of(ve);
         const int nc = sym.sn_ncols[f], nr = sym.sn_nrows[f], n = nc + nr, c0 = sym.sn_col0[f];
         const int32_t *rows = sym.sn_rows.data() + sym.sn_rows_ptr[f];
         auto local = [&](int pcol) -> int {
@@ -2748,10 +2775,10 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
       d_src.alloc((size_t)n_vals);
       d_out.alloc((size_t)n_vals);
       HIPCHK(hipMemcpyAsync(d_src.p, src.data(), src.size() * sizeof(int64_t), hipMemcpyHostToDevice, stream_));
-      HIPCHK(hipEventRecord(sel_ev_[0], stream_));
+      HIPCHK(hipEventRecord(query_ev_[0], stream_));
       launch_linearize(0.0, 0, 1);
       launch_factor();
-      HIPCHK(hipEventRecord(sel_ev_[1], stream_));
+      HIPCHK(hipEventRecord(query_ev_[1], stream_));
       SelArgs<T> a;
       a.meta = sel_meta_.p;
       a.order = sel_order_.p;
@@ -2765,27 +2792,23 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
         hipLaunchKernelGGL((k_selinv_level<T, SELINV_THREADS>), dim3((unsigned)count), dim3(SELINV_THREADS), sel_lds_, stream_, a, begin);
       }
       check_launch("k_selinv_level");
-      HIPCHK(hipEventRecord(sel_ev_[2], stream_));
+      HIPCHK(hipEventRecord(query_ev_[2], stream_));
       if (n_vals > 0) {
         hipLaunchKernelGGL((k_marg_gather<T>), dim3((unsigned)((n_vals + 255) / 256)), dim3(256), 0, stream_, (const T *)svals_.p, (const int64_t *)d_src.p, d_out.p, n_vals);
         check_launch("k_marg_gather");
       }
-      HIPCHK(hipEventRecord(sel_ev_[3], stream_));
+      HIPCHK(hipEventRecord(query_ev_[3], stream_));
       std::vector<double> host((size_t)n_vals);
       if (n_vals > 0) HIPCHK(hipMemcpyAsync(host.data(), d_out.p, host.size() * sizeof(double), hipMemcpyDeviceToHost, stream_));
       HIPCHK(hipStreamSynchronize(stream_));
       check_device_error();
-      for (int k = 0; k < 3; k++) {
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, sel_ev_[k], sel_ev_[k + 1]));
-        sel_ms_[k] = ms;
-      }
+      query_times(sel_ms_, false);
       if (n_vals > 0) std::memcpy(out, host.data(), host.size() * sizeof(double));
     }
   }
   void marginals_times(double *ms) const override { for (int k = 0; k < 3; k++) ms[k] = sel_ms_[k]; }
 
-  // ---- covariances of arbitrary node pairs (include/rr_pgo.h, rr_pgo_covariances; treesolve.hip.h)
+  // ---- the multi-column tree solve (treesolve.hip.h) under rr_pgo_covariances and rr_pgo_gate_edges
   struct TsPlan {
     std::vector<TsTask> tasks;                 // by level, deepest first
     std::vector<int32_t> child, unit, czrow, level_ptr;
@@ -2794,16 +2817,13 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     int n_chunks = 0;
   };
 
-  void covariances_prepare() {
+  void covariances_prepare(const char *who) {
     if (ts_ready_) return;
+    tree_tables(who);
     const Symbolic &sym = sym_;
     const int S_ = sym.S;
     std::vector<TsMeta> meta((size_t)S_);
-    ts_depth_.assign((size_t)S_, 0);
-    ts_col_sn_.assign((size_t)g_.dim, -1);
     int64_t max_n = 1;
-    for (int f = S_ - 1; f >= 0; f--)   // children precede parents
-      if (sym.sn_parent[f] >= 0) ts_depth_[f] = ts_depth_[sym.sn_parent[f]] + 1;
     for (int f = 0; f < S_; f++) {
       TsMeta &m = meta[f];
       m.nc = sym.sn_ncols[f];
@@ -2812,23 +2832,15 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
       m.parent = sym.sn_parent[f];
       m.loff = sym.sn_loff[f];
       m.rel_ptr = sym.rel_ptr[f];
-      if (m.parent < 0 && m.nr != 0) throw ApiError(RR_PGO_EUNSUPPORTED, "rr_pgo_covariances: a root front with rows below its pivot block");
       max_n = std::max<int64_t>(max_n, (int64_t)m.nc + m.nr);
-      for (int c = 0; c < m.nc; c++) ts_col_sn_[sym.sn_col0[f] + c] = f;
     }
     ts_lds_ = (size_t)max_n * TS_LD * sizeof(T);
     if (ts_lds_ + 256 * sizeof(T) > (size_t)160 * 1024)
-      throw ApiError(RR_PGO_EUNSUPPORTED, "rr_pgo_covariances: a front of " + std::to_string(max_n) + " rows exceeds what one workgroup holds beside a chunk of columns");
-    DeviceArena *prev = t_arena;
-    t_arena = &arena_;   // like every other buffer of the handle: back to the pool with it
-    try {
+      throw ApiError(RR_PGO_EUNSUPPORTED, std::string(who) + ": a front of " + std::to_string(max_n) + " rows exceeds what one workgroup holds beside a chunk of columns");
+    {
+      ArenaScope scope(&arena_);   // like every other buffer of the handle: back to the pool with it
       ts_meta_.upload(meta);
-    } catch (...) {
-      t_arena = prev;
-      throw;
     }
-    t_arena = prev;
-    for (EventHolder &e : ts_ev_) e.create(hipEventDefault);
     if constexpr (std::is_same<T, double>::value)
       HIPCHK(hipFuncSetAttribute((const void *)k_tree_fwd<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ts_lds_));
     ts_ready_ = true;
@@ -2838,7 +2850,6 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   void covariances_plan(int q0, int q1, const int32_t *na, const int32_t *nb, const int64_t *off, TsPlan &pl) const {
     const Symbolic &sym = sym_;
     const int S_ = sym.S;
-    auto front_of = [&](int v) { return ts_col_sn_[sym.node_pcol[v]]; };
     // distinct nodes by permuted column: fronts own consecutive column ranges in elimination order, so this is the order
     // of (front, column) and neighbours share most of their paths
     std::vector<int32_t> nodes;
@@ -2912,13 +2923,13 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     const int nt = (int)tmp.size();
     std::vector<int32_t> order((size_t)nt), newidx((size_t)nt);
     for (int i = 0; i < nt; i++) order[i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return ts_depth_[tmp[x].front] > ts_depth_[tmp[y].front]; });
+    std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return front_depth_[tmp[x].front] > front_depth_[tmp[y].front]; });
     pl.tasks.resize((size_t)nt);
     pl.level_ptr.assign(1, 0);
     for (int i = 0; i < nt; i++) {
       newidx[order[i]] = i;
       pl.tasks[i] = tmp[order[i]];
-      if (i > 0 && ts_depth_[pl.tasks[i].front] != ts_depth_[pl.tasks[i - 1].front]) pl.level_ptr.push_back(i);
+      if (i > 0 && front_depth_[pl.tasks[i].front] != front_depth_[pl.tasks[i - 1].front]) pl.level_ptr.push_back(i);
     }
     pl.level_ptr.push_back(nt);
     for (int32_t &c : pl.child) c = newidx[c];
@@ -2929,7 +2940,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
       const int va = na[q], vb = nb[q];
       int fa = front_of(va), fb = front_of(vb);
       while (fa != fb && fa >= 0 && fb >= 0) {
-        if (ts_depth_[fa] >= ts_depth_[fb]) fa = sym.sn_parent[fa];
+        if (front_depth_[fa] >= front_depth_[fb]) fa = sym.sn_parent[fa];
         else fb = sym.sn_parent[fb];
       }
       cq.lca = fa == fb ? fa : -1;
@@ -2945,15 +2956,8 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
 
   template <typename U> void ts_grow(DevBuf<U> &b, size_t count) {
     if (b.p && b.n >= count) return;
-    DeviceArena *prev = t_arena;
-    t_arena = nullptr;   // a buffer of its own: freed when it grows and with the handle
-    try {
-      b.alloc(std::max<size_t>(std::max(count, b.n + b.n / 2), 4));
-    } catch (...) {
-      t_arena = prev;
-      throw;
-    }
-    t_arena = prev;
+    ArenaScope scope(nullptr);   // a buffer of its own: freed when it grows and with the handle
+    b.alloc(std::max<size_t>(std::max(count, b.n + b.n / 2), 4));
   }
   template <typename U> void ts_fill(DevBuf<U> &b, const std::vector<U> &v) {
     ts_grow(b, v.size());
@@ -2989,162 +2993,124 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     check_launch("k_tree_fwd");
   }
 
-  // queries [q0, q1) over the factor in lvals / winv; `first`: the factorisation of this call has not been waited for yet
-  void covariances_run(int q0, int q1, const int32_t *na, const int32_t *nb, const int64_t *off, double *out, bool &first) {
-    if constexpr (std::is_same<T, double>::value && std::is_same<S, double>::value) {
+  // What a pass's kernel left in ts_out_, in order: n doubles for `to` (null: dropped)
+  struct TsDest { double *to; size_t n; };
+
+  // One call over the pairs (a[q], b[q]), q < n: linearise and factor, then the plan of the pairs, stage(q0, q1, plan), which
+  // uploads the pairs' records and sizes ts_out_, the forward solve of the plan's columns, and launch(q0, q1), which launches
+  // the pairs' kernel into ts_out_ and returns the TsDest list of what it writes.  A plan beyond the workspace bound is cut
+  // in halves by index, and the parts run one after the other over the same factor.  ms: the call's three intervals (every
+  // upload lies in the second); time_copy: the third ends behind the copy to the host.
+  template <typename Stage, typename Launch>
+  void tree_query(const char *who, const char *what, int n, const int32_t *a, const int32_t *b, const int64_t *off, double *ms,
+                  bool time_copy, Stage &&stage, Launch &&launch) {
+    for (int k = 0; k < 3; k++) ms[k] = 0;
+    if (n == 0) return;
+    HIPCHK(hipEventRecord(query_ev_[0], stream_));
+    launch_linearize(0.0, 0, 1);
+    launch_factor();
+    HIPCHK(hipEventRecord(query_ev_[1], stream_));
+    bool first = true;   // the factorisation of this call has not been waited for yet
+    std::vector<std::pair<int, int>> todo{{0, n}};   // ranges still to run, the next one last
+    std::vector<double> host;
+    while (!todo.empty()) {
+      const int q0 = todo.back().first, q1 = todo.back().second;
+      todo.pop_back();
       TsPlan pl;
-      covariances_plan(q0, q1, na, nb, off, pl);
+      covariances_plan(q0, q1, a, b, off, pl);
       const size_t ws = (size_t)(pl.zrows + pl.urows) * TS_MC * sizeof(T);
-      if (ws > TS_WS_BYTES) {
-        if (q1 - q0 <= 1) throw ApiError(RR_PGO_ENOMEM, "rr_pgo_covariances: one pair needs " + std::to_string(ws) + " bytes of workspace");
+      if (ws > ts_ws_bytes_) {
+        if (q1 - q0 <= 1) throw ApiError(RR_PGO_ENOMEM, std::string(who) + ": one " + what + " needs " + std::to_string(ws) + " bytes of workspace");
         const int mid = q0 + (q1 - q0) / 2;
-        covariances_run(q0, mid, na, nb, off, out, first);
-        covariances_run(mid, q1, na, nb, off, out, first);
-        return;
+        todo.emplace_back(mid, q1);
+        todo.emplace_back(q0, mid);
+        continue;
       }
-      const int64_t n_vals = off[q1] - off[q0];
       ts_stage(pl);
-      ts_fill(ts_query_, pl.query);
-      ts_grow(ts_out_, (size_t)n_vals);
-      if (!first) HIPCHK(hipEventRecord(ts_ev_[1], stream_));
+      stage(q0, q1, pl);
+      if (!first) HIPCHK(hipEventRecord(query_ev_[1], stream_));
       ts_forward(pl);
-      HIPCHK(hipEventRecord(ts_ev_[2], stream_));
-      CovArgs<T> c;
-      c.meta = ts_meta_.p;
-      c.query = ts_query_.p;
-      c.czrow = ts_czrow_.p;
-      c.Z = ts_z_.p;
-      c.out = ts_out_.p;
-      c.S = sym_.S;
-      hipLaunchKernelGGL((k_cov_pairs<T>), dim3((unsigned)(q1 - q0)), dim3(COV_THREADS), 0, stream_, c);
-      check_launch("k_cov_pairs");
-      HIPCHK(hipEventRecord(ts_ev_[3], stream_));
-      std::vector<double> host((size_t)n_vals);
-      if (n_vals > 0) HIPCHK(hipMemcpyAsync(host.data(), ts_out_.p, host.size() * sizeof(double), hipMemcpyDeviceToHost, stream_));
+      HIPCHK(hipEventRecord(query_ev_[2], stream_));
+      const auto dest = launch(q0, q1);
+      size_t n_out = 0;
+      for (const TsDest &d : dest) n_out += d.n;
+      host.resize(n_out);
+      if (!time_copy) HIPCHK(hipEventRecord(query_ev_[3], stream_));
+      if (n_out > 0) HIPCHK(hipMemcpyAsync(host.data(), ts_out_.p, n_out * sizeof(double), hipMemcpyDeviceToHost, stream_));
+      if (time_copy) HIPCHK(hipEventRecord(query_ev_[3], stream_));
       HIPCHK(hipStreamSynchronize(stream_));
       if (first) check_device_error();   // a non-positive pivot: nothing has been written
-      for (int k = first ? 0 : 1; k < 3; k++) {
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, ts_ev_[k], ts_ev_[k + 1]));
-        ts_ms_[k] += ms;
-      }
+      query_times(ms, !first);
       first = false;
-      if (n_vals > 0) std::memcpy(out + off[q0], host.data(), host.size() * sizeof(double));
+      const double *src = host.data();
+      for (const TsDest &d : dest) {
+        if (d.to && d.n > 0) std::memcpy(d.to, src, d.n * sizeof(double));
+        src += d.n;
+      }
     }
   }
 
+  // ---- covariances of arbitrary node pairs (include/rr_pgo.h, rr_pgo_covariances; treesolve.hip.h, k_cov_pairs)
   void covariances(int nq, const int32_t *na, const int32_t *nb, const int64_t *off, double *out) override {
-    if (sharded_ || world_ > 1) throw ApiError(RR_PGO_EUNSUPPORTED, "rr_pgo_covariances: sharded handle (a rank holds a part of the factor only)");
-    if constexpr (!(std::is_same<T, double>::value && std::is_same<S, double>::value)) {
-      throw ApiError(RR_PGO_EUNSUPPORTED, "rr_pgo_covariances: F32 / MIXED handle (a single-precision factor of a matrix of condition ~1e10 has no meaningful inverse): create the handle with RR_PGO_F64");
-    } else {
-      if (sym_.n_big > 0) throw ApiError(RR_PGO_EUNSUPPORTED, "rr_pgo_covariances: " + std::to_string(sym_.n_big) + " fronts beyond LDS (n_big_fronts must be 0)");
-      covariances_prepare();
-      for (double &v : ts_ms_) v = 0;
-      if (nq == 0) return;
-      HIPCHK(hipEventRecord(ts_ev_[0], stream_));
-      launch_linearize(0.0, 0, 1);
-      launch_factor();
-      HIPCHK(hipEventRecord(ts_ev_[1], stream_));
-      bool first = true;
-      covariances_run(0, nq, na, nb, off, out, first);
+    static constexpr const char *who = "rr_pgo_covariances";
+    require_f64_unsharded_lds_factor(who);
+    if constexpr (f64_) {
+      covariances_prepare(who);
+      tree_query(who, "pair", nq, na, nb, off, ts_ms_, false, [&](int q0, int q1, const TsPlan &pl) {
+        ts_fill(ts_query_, pl.query);
+        ts_grow(ts_out_, (size_t)(off[q1] - off[q0]));
+      }, [&](int q0, int q1) {
+        CovArgs<T> c;
+        c.meta = ts_meta_.p;
+        c.query = ts_query_.p;
+        c.czrow = ts_czrow_.p;
+        c.Z = ts_z_.p;
+        c.out = ts_out_.p;
+        c.S = sym_.S;
+        hipLaunchKernelGGL((k_cov_pairs<T>), dim3((unsigned)(q1 - q0)), dim3(COV_THREADS), 0, stream_, c);
+        check_launch("k_cov_pairs");
+        return std::array<TsDest, 1>{{{out + off[q0], (size_t)(off[q1] - off[q0])}}};
+      });
     }
   }
   void covariances_times(double *ms) const override { for (int k = 0; k < 3; k++) ms[k] = ts_ms_[k]; }
 
-  // ---- Mahalanobis gate of candidate edges (include/rr_pgo.h, rr_pgo_gate_edges; treesolve.hip.h, k_gate_pairs)
-  // candidates [c0, c1): the plan of their nodes' columns is the covariance plan of the pairs (from, to)
-  void gate_run(int c0, int c1, const int32_t *from, const int32_t *to, const int64_t *soff, std::vector<GateCand> &cand,
-                double *d2, double *chi2, double *innov, bool &first) {
-    if constexpr (std::is_same<T, double>::value && std::is_same<S, double>::value) {
-      TsPlan pl;
-      covariances_plan(c0, c1, from, to, soff, pl);
-      const size_t ws = (size_t)(pl.zrows + pl.urows) * TS_MC * sizeof(T);
-      if (ws > TS_WS_BYTES) {
-        if (c1 - c0 <= 1) throw ApiError(RR_PGO_ENOMEM, "rr_pgo_gate_edges: one candidate needs " + std::to_string(ws) + " bytes of workspace");
-        const int mid = c0 + (c1 - c0) / 2;
-        gate_run(c0, mid, from, to, soff, cand, d2, chi2, innov, first);
-        gate_run(mid, c1, from, to, soff, cand, d2, chi2, innov, first);
-        return;
-      }
-      const int n = c1 - c0;
-      const int64_t n_s = soff[c1] - soff[c0];
-      auto front_of = [&](int v) { return ts_col_sn_[sym_.node_pcol[v]]; };
-      for (int c = c0; c < c1; c++) {
-        GateCand &gc = cand[c];
-        const CovQuery &cq = pl.query[c - c0];
-        gc.lca = cq.lca;
-        gc.fa = front_of(from[c]);
-        gc.fb = front_of(to[c]);
-        gc.chunk_a = cq.chunk_a;
-        gc.chunk_b = cq.chunk_b;
-        std::memcpy(gc.ca, cq.ca, sizeof(gc.ca));
-        std::memcpy(gc.cb, cq.cb, sizeof(gc.cb));
-        gc.ooff = cq.ooff;
-      }
-      ts_stage(pl);
-      ts_grow(gate_cand_, (size_t)n);
-      HIPCHK(hipMemcpyAsync(gate_cand_.p, cand.data() + c0, (size_t)n * sizeof(GateCand), hipMemcpyHostToDevice, stream_));
-      const size_t n_out = 2 * (size_t)n + (innov ? (size_t)n_s : 0);
-      ts_grow(ts_out_, n_out);
-      if (!first) HIPCHK(hipEventRecord(gate_ev_[1], stream_));
-      ts_forward(pl);
-      HIPCHK(hipEventRecord(gate_ev_[2], stream_));
-      GateArgs<T> a;
-      a.meta = ts_meta_.p;
-      a.cand = gate_cand_.p;
-      a.czrow = ts_czrow_.p;
-      a.Z = ts_z_.p;
-      a.pose = pose_.p;
-      a.d2 = ts_out_.p;
-      a.chi2 = ts_out_.p + n;
-      a.sout = innov ? ts_out_.p + 2 * (size_t)n : nullptr;
-      a.S = sym_.S;
-      if (is3d_) hipLaunchKernelGGL((k_gate_pairs<T, 6>), dim3((unsigned)n), dim3(COV_THREADS), 0, stream_, a);
-      else hipLaunchKernelGGL((k_gate_pairs<T, 3>), dim3((unsigned)n), dim3(COV_THREADS), 0, stream_, a);
-      check_launch("k_gate_pairs");
-      std::vector<double> host(n_out);
-      HIPCHK(hipMemcpyAsync(host.data(), ts_out_.p, n_out * sizeof(double), hipMemcpyDeviceToHost, stream_));
-      HIPCHK(hipEventRecord(gate_ev_[3], stream_));
-      HIPCHK(hipStreamSynchronize(stream_));
-      if (first) check_device_error();   // a non-positive pivot of H: nothing has been written
-      for (int k = first ? 0 : 1; k < 3; k++) {
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, gate_ev_[k], gate_ev_[k + 1]));
-        gate_ms_[k] += ms;
-      }
-      first = false;
-      std::memcpy(d2 + c0, host.data(), (size_t)n * sizeof(double));
-      if (chi2) std::memcpy(chi2 + c0, host.data() + n, (size_t)n * sizeof(double));
-      if (innov && n_s > 0) std::memcpy(innov + soff[c0], host.data() + 2 * (size_t)n, (size_t)n_s * sizeof(double));
-    }
-  }
-
+  // ---- Mahalanobis gate of candidate edges (include/rr_pgo.h, rr_pgo_gate_edges; treesolve.hip.h, k_gate_pairs): the plan
+  // of the candidates' nodes is the covariance plan of the pairs (from, to)
   void gate_edges(int n, const int32_t *from, const int32_t *to, const int64_t *soff, std::vector<GateCand> &cand, double *d2,
                   double *chi2, double *innov) override {
-    if (sharded_ || world_ > 1) throw ApiError(RR_PGO_EUNSUPPORTED, "rr_pgo_gate_edges: sharded handle (a rank holds a part of the factor only)");
-    if constexpr (!(std::is_same<T, double>::value && std::is_same<S, double>::value)) {
-      throw ApiError(RR_PGO_EUNSUPPORTED, "rr_pgo_gate_edges: F32 / MIXED handle (a single-precision factor of a matrix of condition ~1e10 has no meaningful inverse): create the handle with RR_PGO_F64");
-    } else {
-      if (sym_.n_big > 0) throw ApiError(RR_PGO_EUNSUPPORTED, "rr_pgo_gate_edges: " + std::to_string(sym_.n_big) + " fronts beyond LDS (n_big_fronts must be 0)");
-      try {
-        covariances_prepare();
-      } catch (const ApiError &e) {   // the same limits, under this entry point's name
-        std::string msg = e.what();
-        const std::string other = "rr_pgo_covariances";
-        const size_t at = msg.find(other);
-        if (at != std::string::npos) msg.replace(at, other.size(), "rr_pgo_gate_edges");
-        throw ApiError(e.code, msg);
-      }
-      for (EventHolder &e : gate_ev_) e.create(hipEventDefault);
-      for (double &v : gate_ms_) v = 0;
-      if (n == 0) return;
-      HIPCHK(hipEventRecord(gate_ev_[0], stream_));
-      launch_linearize(0.0, 0, 1);
-      launch_factor();
-      HIPCHK(hipEventRecord(gate_ev_[1], stream_));
-      bool first = true;
-      gate_run(0, n, from, to, soff, cand, d2, chi2, innov, first);
+    static constexpr const char *who = "rr_pgo_gate_edges";
+    require_f64_unsharded_lds_factor(who);
+    if constexpr (f64_) {
+      covariances_prepare(who);
+      auto n_innov = [&](int c0, int c1) { return innov ? (size_t)(soff[c1] - soff[c0]) : 0; };
+      tree_query(who, "candidate", n, from, to, soff, gate_ms_, true, [&](int c0, int c1, const TsPlan &pl) {
+        const size_t nc = (size_t)(c1 - c0);
+        for (int c = c0; c < c1; c++) {
+          cand[c].cq = pl.query[c - c0];
+          cand[c].fa = front_of(from[c]);
+          cand[c].fb = front_of(to[c]);
+        }
+        ts_grow(gate_cand_, nc);
+        HIPCHK(hipMemcpyAsync(gate_cand_.p, cand.data() + c0, nc * sizeof(GateCand), hipMemcpyHostToDevice, stream_));
+        ts_grow(ts_out_, 2 * nc + n_innov(c0, c1));
+      }, [&](int c0, int c1) {
+        const size_t nc = (size_t)(c1 - c0);
+        GateArgs<T> a;
+        a.meta = ts_meta_.p;
+        a.cand = gate_cand_.p;
+        a.czrow = ts_czrow_.p;
+        a.Z = ts_z_.p;
+        a.pose = pose_.p;
+        a.d2 = ts_out_.p;
+        a.chi2 = ts_out_.p + nc;
+        a.sout = innov ? ts_out_.p + 2 * nc : nullptr;
+        a.S = sym_.S;
+        if (is3d_) hipLaunchKernelGGL((k_gate_pairs<T, 6>), dim3((unsigned)nc), dim3(COV_THREADS), 0, stream_, a);
+        else hipLaunchKernelGGL((k_gate_pairs<T, 3>), dim3((unsigned)nc), dim3(COV_THREADS), 0, stream_, a);
+        check_launch("k_gate_pairs");
+        return std::array<TsDest, 3>{{{d2 + c0, nc}, {chi2 ? chi2 + c0 : nullptr, nc}, {innov ? innov + soff[c0] : nullptr, n_innov(c0, c1)}}};
+      });
     }
   }
   void gate_times(double *ms) const override { for (int k = 0; k < 3; k++) ms[k] = gate_ms_[k]; }
@@ -3762,31 +3728,34 @@ int rr_pgo_solve_form(const rr_pgo *h, int32_t *kform, double *k_bytes, double *
   return guarded([&] { h->engine->solve_form(kform, k_bytes, k_flops); });
 }
 
-int rr_pgo_marginals(rr_pgo *h, int32_t n_query, const int32_t *node_a, const int32_t *node_b, double *out,
-                     int64_t *out_offset, int64_t *n_vals) {
-  if (!h || n_query < 0 || (!node_a && node_b)) { g_last_error = "bad argument"; return RR_PGO_EINVAL; }
+// rr_pgo_marginals / rr_pgo_covariances behind their own argument rules: the offsets of the blocks, the node-range check, the
+// size query (out == NULL) and the call; out_offset is written on success only
+static int pair_query(rr_pgo *h, const char *who, void (EngineBase::*call)(int, const int32_t *, const int32_t *, const int64_t *, double *),
+                      int32_t n_query, const int32_t *node_a, const int32_t *node_b, double *out, int64_t *out_offset, int64_t *n_vals) {
   const int N = h->g.n_nodes();
-  if (!node_a && n_query != N) {
-    g_last_error = "rr_pgo_marginals: node_a == NULL asks for every node: n_query must be rr_pgo_num_nodes";
-    return RR_PGO_EINVAL;
-  }
   std::vector<int64_t> off((size_t)n_query + 1, 0);
   for (int q = 0; q < n_query; q++) {
     const int va = node_a ? node_a[q] : q, vb = node_b ? node_b[q] : va;
     if (va < 0 || va >= N || vb < 0 || vb >= N) {
-      g_last_error = "rr_pgo_marginals: query " + std::to_string(q) + ": node index out of range";
+      g_last_error = std::string(who) + ": query " + std::to_string(q) + ": node index out of range";
       return RR_PGO_EINVAL;
     }
     off[q + 1] = off[q] + (int64_t)node_dim(h->g.node_kind[va]) * node_dim(h->g.node_kind[vb]);
   }
   if (n_vals) *n_vals = off[n_query];
-  if (!out) {   // size query
-    if (out_offset) std::copy(off.begin(), off.end(), out_offset);
-    return RR_PGO_OK;
-  }
-  const int rc = guarded([&] { h->engine->marginals(n_query, node_a, node_b, off.data(), out); });
+  const int rc = out ? guarded([&] { (h->engine.get()->*call)(n_query, node_a, node_b, off.data(), out); }) : RR_PGO_OK;
   if (rc == RR_PGO_OK && out_offset) std::copy(off.begin(), off.end(), out_offset);
   return rc;
+}
+
+int rr_pgo_marginals(rr_pgo *h, int32_t n_query, const int32_t *node_a, const int32_t *node_b, double *out,
+                     int64_t *out_offset, int64_t *n_vals) {
+  if (!h || n_query < 0 || (!node_a && node_b)) { g_last_error = "bad argument"; return RR_PGO_EINVAL; }
+  if (!node_a && n_query != h->g.n_nodes()) {
+    g_last_error = "rr_pgo_marginals: node_a == NULL asks for every node: n_query must be rr_pgo_num_nodes";
+    return RR_PGO_EINVAL;
+  }
+  return pair_query(h, "rr_pgo_marginals", &EngineBase::marginals, n_query, node_a, node_b, out, out_offset, n_vals);
 }
 
 int rr_pgo_marginals_times(const rr_pgo *h, double *ms) {
@@ -3797,24 +3766,7 @@ int rr_pgo_marginals_times(const rr_pgo *h, double *ms) {
 int rr_pgo_covariances(rr_pgo *h, int32_t n_query, const int32_t *node_a, const int32_t *node_b, double *out,
                        int64_t *out_offset, int64_t *n_vals) {
   if (!h || n_query < 0 || (n_query > 0 && (!node_a || !node_b))) { g_last_error = "rr_pgo_covariances: bad argument (node_a and node_b are both required)"; return RR_PGO_EINVAL; }
-  const int N = h->g.n_nodes();
-  std::vector<int64_t> off((size_t)n_query + 1, 0);
-  for (int q = 0; q < n_query; q++) {
-    const int va = node_a[q], vb = node_b[q];
-    if (va < 0 || va >= N || vb < 0 || vb >= N) {
-      g_last_error = "rr_pgo_covariances: query " + std::to_string(q) + ": node index out of range";
-      return RR_PGO_EINVAL;
-    }
-    off[q + 1] = off[q] + (int64_t)node_dim(h->g.node_kind[va]) * node_dim(h->g.node_kind[vb]);
-  }
-  if (n_vals) *n_vals = off[n_query];
-  if (!out) {   // size query
-    if (out_offset) std::copy(off.begin(), off.end(), out_offset);
-    return RR_PGO_OK;
-  }
-  const int rc = guarded([&] { h->engine->covariances(n_query, node_a, node_b, off.data(), out); });
-  if (rc == RR_PGO_OK && out_offset) std::copy(off.begin(), off.end(), out_offset);
-  return rc;
+  return pair_query(h, "rr_pgo_covariances", &EngineBase::covariances, n_query, node_a, node_b, out, out_offset, n_vals);
 }
 
 int rr_pgo_covariances_times(const rr_pgo *h, double *ms) {

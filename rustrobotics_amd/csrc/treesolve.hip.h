@@ -33,7 +33,7 @@ constexpr int TS_LD = TS_MC + 16;               // LDS row stride of the right-h
                                                 // (lanes l and l + 16) land on opposite halves of the 64 banks
 constexpr int TS_THREADS = 512;
 constexpr int COV_THREADS = 512;
-constexpr size_t TS_WS_BYTES = (size_t)512 << 20;   // bound of Z + U of one pass
+constexpr size_t TS_WS_BYTES = (size_t)512 << 20;   // bound of Z + U of one pass (RR_PGO_TS_WS_BYTES=<n>: a handle's own)
 static_assert(TS_MC == 32, "row / column of a packed unit entry and of a flat Z / U index are taken with >> 5 and & 31");
 
 struct TsMeta {
@@ -225,15 +225,13 @@ __global__ void __launch_bounds__(COV_THREADS) k_cov_pairs(CovArgs<T> a) {
 // The four blocks of Sigma_{ab,ab} are large against P (the two poses move together): G forms the difference row by row,
 // on the common path, BEFORE it is squared, and P is positive semi-definite by construction.
 struct GateCand {
-  int32_t lca, fa, fb;            // lowest common front (-1: different trees), the fronts of a and of b
-  int32_t chunk_a, chunk_b;
-  int32_t na, nb, kind;           // the two nodes; RR_PGO_EDGE_*
-  uint8_t ca[8], cb[8];           // as CovQuery
-  int64_t ooff;                   // offset of S (d_e x d_e, row-major) in sout
+  CovQuery cq;                    // of the pair (a, b); ooff: offset of S (d_e x d_e, row-major) in sout
+  int32_t fa, fb;                 // the fronts of a and of b
+  int32_t na, nb, kind, pad;      // the two nodes; RR_PGO_EDGE_*
   double meas[8];                 // 2-D: x, y, cos, sin | SE(3): t (3), -, q (4, normalised)
   double info[36], cov[36];       // Omega and Omega^-1, row stride D (3 or 6), zero padded
 };
-static_assert(sizeof(GateCand) == 696, "GateCand is one 696-byte record");
+static_assert(sizeof(GateCand) == 712, "GateCand is one 712-byte record");
 
 template <typename T> struct GateArgs {
   const TsMeta *meta;
@@ -339,11 +337,11 @@ __global__ void __launch_bounds__(COV_THREADS) k_gate_pairs(GateArgs<T> a) {
     Aj[k] = sA[j * D + k];
     Bi[k] = sB[i * D + k];   // (the columns of B past d_b are zero: pose-landmark)
     Bj[k] = sB[j * D + k];
-    cola[k] = q->ca[k];
-    colb[k] = q->cb[min(k, db - 1)];
+    cola[k] = q->cq.ca[k];
+    colb[k] = q->cq.cb[min(k, db - 1)];
   }
-  const int32_t *za_tab = a.czrow + (int64_t)q->chunk_a * a.S, *zb_tab = a.czrow + (int64_t)q->chunk_b * a.S;
-  const int lca = q->lca;
+  const int32_t *za_tab = a.czrow + (int64_t)q->cq.chunk_a * a.S, *zb_tab = a.czrow + (int64_t)q->cq.chunk_b * a.S;
+  const int lca = q->cq.lca;
   T acc = 0;
   acc = gate_walk<T, D, true, false>(a.meta, a.Z, za_tab, zb_tab, q->fa, lca, slice, NS, cola, colb, Ai, Aj, Bi, Bj, acc);
   acc = gate_walk<T, D, false, true>(a.meta, a.Z, za_tab, zb_tab, q->fb, lca, slice, NS, cola, colb, Ai, Aj, Bi, Bj, acc);
@@ -359,7 +357,7 @@ __global__ void __launch_bounds__(COV_THREADS) k_gate_pairs(GateArgs<T> a) {
     sS[j * D + i] = s;
   }
   __syncthreads();
-  if (a.sout && tid < de * de) a.sout[q->ooff + tid] = (double)sS[(tid / de) * D + tid % de];   // both halves from the lower triangle
+  if (a.sout && tid < de * de) a.sout[q->cq.ooff + tid] = (double)sS[(tid / de) * D + tid % de];   // both halves from the lower triangle
   __syncthreads();
   if (tid == 0) {
     T c2 = 0;   // e^T Omega e, the sum order of edge_chi2_2d / edge_chi2_3d

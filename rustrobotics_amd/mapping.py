@@ -293,11 +293,14 @@ class PoseGraph:
         sab = vals[off[2]:off[3]].reshape(da, db)
         return np.block([[saa, sab], [sab.T, sbb]])
 
+    def _times(self, fn):
+        ms = np.zeros(3)
+        _check(fn(self._h, _dp(ms)))
+        return tuple(float(v) for v in ms)
+
     def marginals_times(self):
         """HIP-event milliseconds of the last marginals call: (linearise + factor, selected inverse, gather)."""
-        ms = np.zeros(3)
-        _check(_lib.load().rr_pgo_marginals_times(self._h, _dp(ms)))
-        return tuple(float(v) for v in ms)
+        return self._times(_lib.load().rr_pgo_marginals_times)
 
     # -- covariances of arbitrary pairs (include/rr_pgo.h, rr_pgo_covariances) -----------
     def covariance_blocks(self, node_a, node_b):
@@ -342,9 +345,7 @@ class PoseGraph:
 
     def covariances_times(self):
         """HIP-event milliseconds of the last covariance call: (linearise + factor, tree solve, products + gather)."""
-        ms = np.zeros(3)
-        _check(_lib.load().rr_pgo_covariances_times(self._h, _dp(ms)))
-        return tuple(float(v) for v in ms)
+        return self._times(_lib.load().rr_pgo_covariances_times)
 
     # -- Mahalanobis gate of candidate loop closures (include/rr_pgo.h, rr_pgo_gate_edges) ----
     def gate_edges(self, edge_kind, edge_from, edge_to, edge_meas, edge_info, return_innovation=False):
@@ -384,9 +385,7 @@ class PoseGraph:
 
     def gate_times(self):
         """HIP-event milliseconds of the last gate_edges call: (linearise + factor, tree solve, gate kernel + copy)."""
-        ms = np.zeros(3)
-        _check(_lib.load().rr_pgo_gate_times(self._h, _dp(ms)))
-        return tuple(float(v) for v in ms)
+        return self._times(_lib.load().rr_pgo_gate_times)
 
     # -- PoseGraph::plot, :375-431 -------------------------------------------------------
     def plot_data(self):

@@ -5,6 +5,7 @@ max|B|) is at most max(1e-12, 100 x noise floor), the floor being the worst diff
 independent f64 computations of the same blocks at the same state; here the floor itself must also be at most 1e-6.
 Every comparison prints its worst figure, the floor and the tolerance before it asserts."""
 import ctypes as C
+import re
 
 import numpy as np
 import pytest
@@ -141,6 +142,52 @@ def test_a_query_of_many_chunks_and_its_pairs_one_at_a_time(api):
     for q in range(0, 400, 20):
         one, _ = g.covariance_blocks(a[q:q + 1], b[q:q + 1])
         assert np.array_equal(one.reshape(got[q].shape), got[q]), (q, a[q], b[q])
+
+
+def test_a_plan_cut_by_the_workspace_bound_gives_the_same_bits(api, monkeypatch):
+    """24 pairs of 48 distinct seeded nodes of intel: 144 columns, at least 5 chunks.  A handle whose workspace bound
+    (RR_PGO_TS_WS_BYTES) is the largest need of a single pair must cut the list: a pair alone puts both nodes in one chunk
+    and needs the union of their two root paths; the list needs the sum over its chunks of each chunk's union, which holds
+    those two paths and at least the root front of a third chunk.  The cut changes no bit."""
+    from rustrobotics_amd import _lib
+    from rustrobotics_amd.mapping import PoseGraphError
+    PoseGraph = api[0]
+
+    def handle(bound=None):
+        if bound is None:
+            return PoseGraph.new(g2o_path("intel"))
+        monkeypatch.setenv("RR_PGO_TS_WS_BYTES", str(bound))
+        g = PoseGraph.new(g2o_path("intel"))
+        monkeypatch.delenv("RR_PGO_TS_WS_BYTES")
+        return g
+
+    def refused(g, q):
+        """the bytes the refusal of pair q alone names"""
+        with pytest.raises(PoseGraphError) as ei:
+            g.covariance_blocks(a[q:q + 1], b[q:q + 1])
+        assert ei.value.code == _lib.ENOMEM, ei.value
+        msg = _lib.load().rr_pgo_last_error().decode()
+        m = re.fullmatch(r"rr_pgo_covariances: one pair needs (\d+) bytes of workspace", msg)
+        assert m, msg
+        return int(m.group(1))
+
+    A = handle()
+    nodes = np.random.default_rng(17).choice(A.num_nodes, 48, replace=False).astype(np.int32)
+    a, b = nodes[:24], nodes[24:]
+    vals_A, off = A.covariance_blocks(a, b)
+    assert off[-1] == 24 * 9
+    B = handle(1)
+    need = [refused(B, q) for q in range(24)]
+    print(f"intel, 24 pairs alone: workspace needs {min(need)} .. {max(need)} bytes")
+    C_ = handle(max(need))
+    vals_C, off_C = C_.covariance_blocks(a, b)
+    assert np.array_equal(off_C, off)
+    assert np.array_equal(vals_C, vals_A)
+    for q in range(24):
+        one, _ = C_.covariance_blocks(a[q:q + 1], b[q:q + 1])
+        assert np.array_equal(one, vals_A[off[q]:off[q + 1]]), (q, a[q], b[q])
+    D = handle(max(need) - 1)
+    assert refused(D, int(np.argmax(need))) == max(need)
 
 
 @pytest.mark.parametrize("env,value", [(None, None), ("RR_PGO_SOLVE_KFORM", "0"), ("RR_PGO_LDS_FLOW", "0")])

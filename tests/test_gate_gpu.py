@@ -5,6 +5,7 @@ A GPU value passes when its relative difference to the reference is at most max(
 the worst relative difference between the reference's two independent computations of the same quantity; the floor itself
 must be at most FLOOR_MAX = 1e-6.  Every comparison prints its worst figure, the floor and the tolerance before it asserts."""
 import ctypes as C
+import re
 
 import numpy as np
 import pytest
@@ -131,6 +132,57 @@ def test_bits_do_not_depend_on_the_rest_of_the_call(api, name):
     d2, chi2, S = g.gate_edges(*reverse(cand), return_innovation=True)
     assert np.array_equal(d2[::-1], c["d2"]) and np.array_equal(chi2[::-1], c["chi2"])
     assert all(np.array_equal(x, y) for x, y in zip(S[::-1], c["S"]))
+
+
+def test_a_plan_cut_by_the_workspace_bound_gives_the_same_bits(api, monkeypatch):
+    """24 candidates of intel with distinct end nodes: at least 72 columns, at least 3 chunks.  A handle whose workspace bound
+    (RR_PGO_TS_WS_BYTES) is the largest need of a single candidate must cut the list (the reasoning of the test of this
+    name in tests/test_covariances_gpu.py).  The cut changes no bit of d2, chi2 and S."""
+    from rustrobotics_amd import _lib
+    from rustrobotics_amd.mapping import PoseGraphError
+    PoseGraph = api[0]
+    full = case(api, "intel")["cand"]
+    idx, seen = [], set()
+    for c, to in enumerate(full[2]):
+        if int(to) not in seen and len(idx) < 24:
+            seen.add(int(to))
+            idx.append(c)
+    assert len(idx) == 24
+    cand = select(full, idx)
+
+    def handle(bound=None):
+        if bound is None:
+            return PoseGraph.new(g2o_path("intel"))
+        monkeypatch.setenv("RR_PGO_TS_WS_BYTES", str(bound))
+        g = PoseGraph.new(g2o_path("intel"))
+        monkeypatch.delenv("RR_PGO_TS_WS_BYTES")
+        return g
+
+    def refused(g, q):
+        """the bytes the refusal of candidate q alone names"""
+        with pytest.raises(PoseGraphError) as ei:
+            g.gate_edges(*select(cand, [q]), return_innovation=True)
+        assert ei.value.code == _lib.ENOMEM, ei.value
+        msg = _lib.load().rr_pgo_last_error().decode()
+        m = re.fullmatch(r"rr_pgo_gate_edges: one candidate needs (\d+) bytes of workspace", msg)
+        assert m, msg
+        return int(m.group(1))
+
+    def same(got, want):
+        return np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]) and len(got[2]) == len(want[2]) and \
+            all(np.array_equal(x, y) for x, y in zip(got[2], want[2]))
+
+    want = handle().gate_edges(*cand, return_innovation=True)
+    B = handle(1)
+    need = [refused(B, q) for q in range(24)]
+    print(f"intel, 24 candidates alone: workspace needs {min(need)} .. {max(need)} bytes")
+    C_ = handle(max(need))
+    assert same(C_.gate_edges(*cand, return_innovation=True), want)
+    for q in range(24):
+        one = C_.gate_edges(*select(cand, [q]), return_innovation=True)
+        assert same(one, (want[0][q:q + 1], want[1][q:q + 1], want[2][q:q + 1])), q
+    D = handle(max(need) - 1)
+    assert refused(D, int(np.argmax(need))) == max(need)
 
 
 @pytest.mark.parametrize("solver", ["GaussNewton", "LevenbergMarquardt"])
