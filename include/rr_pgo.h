@@ -29,6 +29,10 @@ extern "C" {
 
 #define RR_PGO_ABI_VERSION 4  /* see rr_pgo_abi_version() */
 
+/* caps of one set of rr_pgo_gate_joint */
+#define RR_PGO_GATE_JOINT_MAX_DIM  48   /* stacked error dimension of one set */
+#define RR_PGO_GATE_JOINT_MAX_CAND 16   /* candidates of one set */
+
 typedef struct rr_pgo rr_pgo; /* opaque: replaces `struct PoseGraph`, pose_graph_optimization.rs:155-163 */
 
 enum {
@@ -256,6 +260,38 @@ int rr_pgo_gate_edges(rr_pgo *h, int32_t n_cand,
                       double *d2_out, double *chi2_out, double *innov_out, int64_t *innov_offset);
 /* ms[3]: HIP-event times of the last rr_pgo_gate_edges call -- linearise + factor, tree solve, gate kernel + copy. */
 int rr_pgo_gate_times(const rr_pgo *h, double *ms);
+
+/* Joint compatibility of SETS of candidates: set s is the ordered list set_cand[set_ptr[s] .. set_ptr[s + 1]) of indices
+ * into the n_cand candidates (given as for rr_pgo_gate_edges); a candidate may appear in any number of sets, and twice in
+ * one (two independent measurements).  With e_s the stacked errors of the set (D_s = the sum of its d_e) and
+ * G_s = [G_c1 .. G_cm], G_c = Z_a A_c^T + Z_b B_c^T as for rr_pgo_gate_edges:
+ *   S_s = blockdiag(Omega_c^-1) + G_s^T G_s        the joint innovation covariance: the cross block of candidates c and d is
+ *                                                  G_c^T G_d, summed over the pivot rows their root paths share
+ *   d2_out[s] = e_s^T S_s^-1 e_s                   compare with a chi-square quantile of D_s degrees of freedom
+ *   prefix_d2_out[set_ptr[s] + k] (may be NULL)    with S_s = L L^T, y = L^-1 e_s: the sum of y^2 over the rows of the set's
+ *                                                  first k + 1 candidates = the joint distance of the set cut after candidate
+ *                                                  k (the increment a branch-and-bound search asks for at each depth); the
+ *                                                  last one of a set is d2_out[s], same bits
+ *   innov_out (may be NULL): S_s, D_s x D_s row-major, sets packed; innov_offset (may be NULL): [n_sets + 1] offsets.
+ * S_s is symmetric bit for bit; the bits of its block (c, d) depend on the two candidates alone -- not on the rest of the
+ * set, on its order or on the other sets -- and a prefix equals d2_out of the truncated set bit for bit.  A one-candidate
+ * set agrees with rr_pgo_gate_edges to rounding (the sums run in another order), not bit for bit.  A non-positive pivot of
+ * S_s (rounding only) gives NaN for the set's d2 and for its prefixes from that candidate on.
+ * One linearisation, one factorisation and one tree solve per call, then one synchronisation; the state, the
+ * Levenberg-Marquardt lambda, rr_pgo_optimize's results, captured graphs and the robust setting are untouched.
+ * RR_PGO_EINVAL, decided before anything is launched or written, the message names the candidate or the set: every case
+ * of rr_pgo_gate_edges, n_sets < 0, a null required pointer (with n_sets > 0: the candidate arrays, set_ptr, set_cand,
+ * d2_out), set_ptr[0] != 0 or set_ptr decreasing, an empty set, a set_cand out of range, more than
+ * RR_PGO_GATE_JOINT_MAX_CAND candidates in a set, D_s > RR_PGO_GATE_JOINT_MAX_DIM.  n_sets == 0: RR_PGO_OK, nothing is read.
+ * RR_PGO_ENOTSPD and RR_PGO_EUNSUPPORTED as for rr_pgo_gate_edges.  RR_PGO_ENOMEM: one set alone needs more workspace than
+ * the handle's bound (the message gives the bytes); longer lists are cut at set boundaries, which changes no bit. */
+int rr_pgo_gate_joint(rr_pgo *h, int32_t n_cand,
+                      const int32_t *edge_kind, const int32_t *edge_from, const int32_t *edge_to,
+                      const double *edge_meas, const double *edge_info,
+                      int32_t n_sets, const int32_t *set_ptr, const int32_t *set_cand,
+                      double *d2_out, double *prefix_d2_out, double *innov_out, int64_t *innov_offset);
+/* ms[3]: HIP-event times of the last rr_pgo_gate_joint call -- linearise + factor, tree solve, joint kernel + copy. */
+int rr_pgo_gate_joint_times(const rr_pgo *h, double *ms);
 
 /* ---- inspection of the assembled system (parity tests) ------------------- */
 

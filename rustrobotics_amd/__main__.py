@@ -20,6 +20,11 @@
       one line per candidate: ids, Mahalanobis distance d2, e^T Omega e, accept / reject at the 0.95 chi-square quantile
       (rr_pgo_gate_edges)
 
+  --gate-joint FILE  (example mode): candidate lines as for --gate, plus lines `SET i j k ...` that name candidates by
+      their 0-based order in the file; after the optimisation one line per set: members, D_s, joint Mahalanobis distance
+      d2, the 0.95 chi-square quantile of D_s degrees of freedom, accept / reject, the prefix distances
+      (rr_pgo_gate_joint)
+
   python -m rustrobotics_amd <file.g2o> --bench [--repeats 20]
       = benches/graph_slam.rs:9-10   PoseGraph::new("dataset/g2o/intel.g2o", GaussNewton)?.optimize(10, false, false)
         timed end to end like criterion does: parsing, symbolic analysis, device setup and the ten
@@ -93,9 +98,10 @@ def print_joint(g, ids):
 GATE_TAGS = {"EDGE_SE2": 0, "EDGE_SE2_XY": 1, "EDGE_SE3:QUAT": 2}
 
 
-def parse_gate_file(path, index):
+def parse_gate_file(path, index, sets=None, flag="--gate"):
     """Candidate edges of a --gate file as (kind, from, to, meas, info, ids) in rr_pgo_graph_desc packing; `index` maps a
-    g2o vertex id to the node's index.  Needs no device.  An unknown tag or id is a SystemExit that names the line."""
+    g2o vertex id to the node's index.  Needs no device.  An unknown tag or id is a SystemExit that names the line.
+    sets: a list that receives (line number, [candidate, ...]) of every `SET i j k ...` line (--gate-joint)."""
     from .mapping import GATE_INFO_LEN, GATE_MEAS_LEN
     kind, a, b, meas, info, ids = [], [], [], [], [], []
     with open(path) as f:
@@ -103,20 +109,29 @@ def parse_gate_file(path, index):
             tok = line.split()
             if not tok or tok[0].startswith("#"):
                 continue
+            if sets is not None and tok[0] == "SET":
+                try:
+                    members = [int(t) for t in tok[1:]]
+                except ValueError:
+                    members = []
+                if not members:
+                    raise SystemExit(f"{flag}: {path}:{no}: expected candidate numbers after SET")
+                sets.append((no, members))
+                continue
             if tok[0] not in GATE_TAGS:
-                raise SystemExit(f"--gate: {path}:{no}: unknown tag {tok[0]!r} (EDGE_SE2, EDGE_SE2_XY or EDGE_SE3:QUAT)")
+                raise SystemExit(f"{flag}: {path}:{no}: unknown tag {tok[0]!r} (EDGE_SE2, EDGE_SE2_XY or EDGE_SE3:QUAT)")
             k = GATE_TAGS[tok[0]]
             nm, ni = GATE_MEAS_LEN[k], GATE_INFO_LEN[k]
             try:
                 i, j = int(tok[1]), int(tok[2])
                 vals = [float(t) for t in tok[3:]]
             except (ValueError, IndexError):
-                raise SystemExit(f"--gate: {path}:{no}: expected two vertex ids and {nm + ni} numbers after {tok[0]}")
+                raise SystemExit(f"{flag}: {path}:{no}: expected two vertex ids and {nm + ni} numbers after {tok[0]}")
             if len(vals) != nm + ni:
-                raise SystemExit(f"--gate: {path}:{no}: expected {nm + ni} values after the ids, got {len(vals)}")
+                raise SystemExit(f"{flag}: {path}:{no}: expected {nm + ni} values after the ids, got {len(vals)}")
             for v in (i, j):
                 if v not in index:
-                    raise SystemExit(f"--gate: {path}:{no}: no vertex with id {v} in the graph")
+                    raise SystemExit(f"{flag}: {path}:{no}: no vertex with id {v} in the graph")
             kind.append(k)
             a.append(index[i])
             b.append(index[j])
@@ -124,6 +139,27 @@ def parse_gate_file(path, index):
             info.extend(vals[nm:])
             ids.append((i, j))
     return kind, a, b, meas, info, ids
+
+
+def parse_gate_joint_file(path, index):
+    """A --gate-joint file: (kind, from, to, meas, info, ids, sets).  Candidate lines as in a --gate file; a line
+    `SET i j k ...` names candidates by their 0-based order in the file (before or after the line).  Needs no device.
+    No SET line, a member out of range, a set beyond the caps of rr_pgo_gate_joint: a SystemExit that names the line."""
+    from . import _lib
+    from .mapping import GATE_EDGE_DIM
+    raw = []
+    kind, a, b, meas, info, ids = parse_gate_file(path, index, raw, "--gate-joint")
+    if not raw:
+        raise SystemExit(f"--gate-joint: {path}: no SET line")
+    for no, members in raw:
+        for c in members:
+            if not 0 <= c < len(kind):
+                raise SystemExit(f"--gate-joint: {path}:{no}: no candidate {c} in the file ({len(kind)} candidates)")
+        dim = sum(GATE_EDGE_DIM[kind[c]] for c in members)
+        if len(members) > _lib.GATE_JOINT_MAX_CAND or dim > _lib.GATE_JOINT_MAX_DIM:
+            raise SystemExit(f"--gate-joint: {path}:{no}: a set holds at most {_lib.GATE_JOINT_MAX_CAND} candidates and "
+                             f"{_lib.GATE_JOINT_MAX_DIM} error scalars, this one {len(members)} and {dim}")
+    return kind, a, b, meas, info, ids, [members for _, members in raw]
 
 
 def print_gate(g, path):
@@ -144,6 +180,25 @@ def print_gate(g, path):
         print(f"{i} {j} d2 {d2[c]:.9g} chi2 {chi2[c]:.9g} threshold {thr[c]:g} {'accept' if d2[c] <= thr[c] else 'reject'}")
 
 
+def print_gate_joint(g, path):
+    import ctypes as C
+
+    import numpy as np
+    from . import _lib
+    from .mapping import gate_joint_dims, gate_joint_thresholds
+    d = _lib.GraphDesc()
+    _lib.load().rr_pgo_get_graph(g._h, C.byref(d))
+    n = d.n_nodes
+    file_ids = np.ctypeslib.as_array(d.node_id, (n,)) if (n and d.node_id) else np.arange(n)
+    kind, a, b, meas, info, _, sets = parse_gate_joint_file(path, {int(v): k for k, v in enumerate(file_ids)})
+    d2, prefix = g.gate_joint(kind, a, b, meas, info, sets, return_prefix=True)
+    dims, thr = gate_joint_dims(kind, sets), gate_joint_thresholds(kind, sets)
+    print(f"joint gate of {len(sets)} sets over {len(kind)} candidate edges from {path} (accept: d2 <= the 0.95 chi-square quantile):")
+    for s, members in enumerate(sets):
+        print(f"SET {' '.join(str(c) for c in members)} D {dims[s]} d2 {d2[s]:.9g} threshold {thr[s]:g} "
+              f"{'accept' if d2[s] <= thr[s] else 'reject'} prefixes {' '.join(f'{v:.9g}' for v in prefix[s])}")
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m rustrobotics_amd", description=__doc__,
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -162,6 +217,8 @@ def main(argv=None):
                     help="after the optimisation print the joint covariance of these g2o vertex ids (any nodes)")
     ap.add_argument("--gate", metavar="FILE", default=None,
                     help="after the optimisation gate the candidate EDGE_* lines of FILE: d2, e^T Omega e, accept / reject")
+    ap.add_argument("--gate-joint", metavar="FILE", default=None,
+                    help="after the optimisation gate the SET lines of FILE jointly: D_s, d2, threshold, accept / reject, prefixes")
     a = ap.parse_args(argv)
     solver = PoseGraphSolver[a.solver]
 
@@ -182,6 +239,8 @@ def main(argv=None):
             print_joint(g, a.joint)
         if a.gate:
             print_gate(g, a.gate)
+        if a.gate_joint:
+            print_gate_joint(g, a.gate_joint)
         return 0
     iters = 10 if a.iterations is None else a.iterations
     new().optimize(iters, False, False)   # warm-up: library load, HIP context

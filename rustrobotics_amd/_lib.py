@@ -19,6 +19,7 @@ F64, F32, MIXED = 0, 1, 2
 ROBUST_NONE, ROBUST_HUBER, ROBUST_CAUCHY = 0, 1, 2   # RR_PGO_ROBUST_* (rr_pgo_set_robust_kernel)
 ROBUST_KERNELS = {None: ROBUST_NONE, "none": ROBUST_NONE, "huber": ROBUST_HUBER, "cauchy": ROBUST_CAUCHY}
 PRECISIONS = {"f64": F64, "f32": F32, "mixed": MIXED}
+GATE_JOINT_MAX_DIM, GATE_JOINT_MAX_CAND = 48, 16   # RR_PGO_GATE_JOINT_MAX_DIM / _MAX_CAND
 NUM_KCLASS = 11
 KCLASS_NAMES = ("linearize", "factor", "solve", "update", "reduce", "big_assembly", "big_panel", "big_update",
                 "mid_factor", "big_solve", "big_flow")
@@ -33,7 +34,7 @@ EXPORTS = (
     "rr_pgo_exchange_buffer", "rr_pgo_set_exchange_buffer", "rr_pgo_stage", "rr_pgo_stage_scalars", "rr_pgo_stream",
     "rr_pgo_node_owner", "rr_pgo_trim", "rr_pgo_set_robust_kernel", "rr_pgo_edge_errors", "rr_pgo_solve_form",
     "rr_pgo_marginals", "rr_pgo_marginals_times", "rr_pgo_covariances", "rr_pgo_covariances_times",
-    "rr_pgo_gate_edges", "rr_pgo_gate_times",
+    "rr_pgo_gate_edges", "rr_pgo_gate_times", "rr_pgo_gate_joint", "rr_pgo_gate_joint_times",
 )
 
 
@@ -139,6 +140,8 @@ def load():
     L.rr_pgo_covariances_times.argtypes = [vp, dp]
     L.rr_pgo_gate_edges.argtypes = [vp, C.c_int32, ip, ip, ip, dp, dp, dp, dp, dp, C.POINTER(C.c_int64)]
     L.rr_pgo_gate_times.argtypes = [vp, dp]
+    L.rr_pgo_gate_joint.argtypes = [vp, C.c_int32, ip, ip, ip, dp, dp, C.c_int32, ip, ip, dp, dp, dp, C.POINTER(C.c_int64)]
+    L.rr_pgo_gate_joint_times.argtypes = [vp, dp]
     if L.rr_pgo_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH} speaks ABI version {L.rr_pgo_abi_version()}, this mirror {ABI_VERSION}: rebuild the library")
     _lib = L

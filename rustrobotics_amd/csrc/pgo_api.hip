@@ -273,6 +273,12 @@ struct EngineBase {
   virtual void gate_edges(int n, const int32_t *from, const int32_t *to, const int64_t *soff, std::vector<GateCand> &cand,
                           double *d2, double *chi2, double *innov) = 0;
   virtual void gate_times(double *ms) const = 0;
+  // rr_pgo_gate_joint (arguments checked; set s is the records [set_ptr[s], set_ptr[s + 1]) of from / to / cand, the sets
+  // expanded one after the other; dim: D_s; ioff: [n_sets + 1] offsets of the sets' S in innov; prefix and innov may be null) /
+  // rr_pgo_gate_joint_times
+  virtual void gate_joint(int n_sets, const int32_t *set_ptr, const int32_t *from, const int32_t *to, const int32_t *dim,
+                          const int64_t *ioff, std::vector<GateCand> &cand, double *d2, double *prefix, double *innov) = 0;
+  virtual void gate_joint_times(double *ms) const = 0;
   int n_launches_per_iter = 0;
 };
 
@@ -430,7 +436,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   DevBuf<T> kvals_;
   bool kform_ = false;
   double kform_bytes_ = 0, kform_flops_ = 0;   // one factorisation's K steps: panel rows read + X written, 2 per multiply-add
-  // queries over the factor (rr_pgo_marginals, rr_pgo_covariances, rr_pgo_gate_edges): the tree tables and the events are made
+  // queries over the factor (rr_pgo_marginals, rr_pgo_covariances, rr_pgo_gate_edges, rr_pgo_gate_joint): the tree tables and the events are made
   // by the first such call
   static constexpr bool f64_ = std::is_same<T, double>::value && std::is_same<S, double>::value;
   std::vector<int32_t> front_depth_, col_front_;   // depth of a front (a root: 0); permuted scalar column -> front
@@ -459,6 +465,11 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   // the gate of candidate edges (rr_pgo_gate_edges): the covariance plan and workspace above, plus its own records
   DevBuf<GateCand> gate_cand_;
   double gate_ms_[3] = {0, 0, 0};    // the last call: linearise + factor, tree solve, gate kernel + copy
+  // joint compatibility of sets of candidates (rr_pgo_gate_joint): gate_cand_ holds the sets' records one after the other;
+  // per set its record, the pivot columns of its fronts and the Z rows of its candidates' nodes there
+  DevBuf<JointSet> joint_set_;
+  DevBuf<int32_t> joint_fnc_, joint_fz_;
+  double joint_ms_[3] = {0, 0, 0};   // the last call: linearise + factor, tree solve, joint kernel + copy
   static constexpr int kGemvSlices = 16;   // row slices of the multi-workgroup L21^T x product
   DevBuf<double> chi_partial_, norm_partial_, hist_;
   DevBuf<int> counter_, err_, blocks_done_;
@@ -2646,7 +2657,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   }
 
 
-  // ---- queries over the factor: what rr_pgo_marginals, rr_pgo_covariances and rr_pgo_gate_edges share
+  // ---- queries over the factor: what rr_pgo_marginals, rr_pgo_covariances, rr_pgo_gate_edges and rr_pgo_gate_joint share
   void require_f64_unsharded_lds_factor(const char *who) const {
     const std::string w = who;
     if (sharded_ || world_ > 1) throw ApiError(RR_PGO_EUNSUPPORTED, w + ": sharded handle (a rank holds a part of the factor only)");
@@ -2808,7 +2819,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   }
   void marginals_times(double *ms) const override { for (int k = 0; k < 3; k++) ms[k] = sel_ms_[k]; }
 
-  // ---- the multi-column tree solve (treesolve.hip.h) under rr_pgo_covariances and rr_pgo_gate_edges
+  // ---- the multi-column tree solve (treesolve.hip.h) under rr_pgo_covariances, rr_pgo_gate_edges and rr_pgo_gate_joint
   struct TsPlan {
     std::vector<TsTask> tasks;                 // by level, deepest first
     std::vector<int32_t> child, unit, czrow, level_ptr;
@@ -3001,29 +3012,33 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   // the pairs' kernel into ts_out_ and returns the TsDest list of what it writes.  A plan beyond the workspace bound is cut
   // in halves by index, and the parts run one after the other over the same factor.  ms: the call's three intervals (every
   // upload lies in the second); time_copy: the third ends behind the copy to the host.
+  // cuts (optional): a table of n_parts + 1 ascending cut points, cuts[0] = 0 and cuts[n_parts] = n -- the list is then cut
+  // at these points only, in halves by the index of the part (`what` names a part); stage and launch still get pair indices.
   template <typename Stage, typename Launch>
   void tree_query(const char *who, const char *what, int n, const int32_t *a, const int32_t *b, const int64_t *off, double *ms,
-                  bool time_copy, Stage &&stage, Launch &&launch) {
+                  bool time_copy, Stage &&stage, Launch &&launch, const int32_t *cuts = nullptr, int n_parts = 0) {
     for (int k = 0; k < 3; k++) ms[k] = 0;
     if (n == 0) return;
+    auto first_of = [&](int u) { return cuts ? (int)cuts[u] : u; };   // the first pair of part u (no table: a part is a pair)
     HIPCHK(hipEventRecord(query_ev_[0], stream_));
     launch_linearize(0.0, 0, 1);
     launch_factor();
     HIPCHK(hipEventRecord(query_ev_[1], stream_));
     bool first = true;   // the factorisation of this call has not been waited for yet
-    std::vector<std::pair<int, int>> todo{{0, n}};   // ranges still to run, the next one last
+    std::vector<std::pair<int, int>> todo{{0, cuts ? n_parts : n}};   // ranges of parts still to run, the next one last
     std::vector<double> host;
     while (!todo.empty()) {
-      const int q0 = todo.back().first, q1 = todo.back().second;
+      const int u0 = todo.back().first, u1 = todo.back().second;
+      const int q0 = first_of(u0), q1 = first_of(u1);
       todo.pop_back();
       TsPlan pl;
       covariances_plan(q0, q1, a, b, off, pl);
       const size_t ws = (size_t)(pl.zrows + pl.urows) * TS_MC * sizeof(T);
       if (ws > ts_ws_bytes_) {
-        if (q1 - q0 <= 1) throw ApiError(RR_PGO_ENOMEM, std::string(who) + ": one " + what + " needs " + std::to_string(ws) + " bytes of workspace");
-        const int mid = q0 + (q1 - q0) / 2;
-        todo.emplace_back(mid, q1);
-        todo.emplace_back(q0, mid);
+        if (u1 - u0 <= 1) throw ApiError(RR_PGO_ENOMEM, std::string(who) + ": one " + what + " needs " + std::to_string(ws) + " bytes of workspace");
+        const int mid = u0 + (u1 - u0) / 2;
+        todo.emplace_back(mid, u1);
+        todo.emplace_back(u0, mid);
         continue;
       }
       ts_stage(pl);
@@ -3114,6 +3129,98 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     }
   }
   void gate_times(double *ms) const override { for (int k = 0; k < 3; k++) ms[k] = gate_ms_[k]; }
+
+  // ---- joint compatibility of sets of candidate edges (include/rr_pgo.h, rr_pgo_gate_joint; treesolve.hip.h, k_gate_joint):
+  // the plan is the covariance plan of the sets' pairs (from, to), one after the other, cut at set boundaries only
+  void gate_joint(int n_sets, const int32_t *set_ptr, const int32_t *from, const int32_t *to, const int32_t *dim,
+                  const int64_t *ioff, std::vector<GateCand> &cand, double *d2, double *prefix, double *innov) override {
+    static constexpr const char *who = "rr_pgo_gate_joint";
+    require_f64_unsharded_lds_factor(who);
+    if constexpr (f64_) {
+      covariances_prepare(who);
+      const Symbolic &sym = sym_;
+      const int n = n_sets > 0 ? set_ptr[n_sets] : 0;
+      const std::vector<int64_t> no_off((size_t)n + 1, 0);   // (a pair's record carries no output offset here)
+      std::vector<JointSet> sets;
+      std::vector<int32_t> fnc, fz, fronts, slot((size_t)sym.S, -1);   // slot: front -> its place among the set's fronts
+      auto set_of = [&](int q) { return (int)(std::lower_bound(set_ptr, set_ptr + n_sets + 1, q) - set_ptr); };   // (no set is empty)
+      auto n_innov = [&](int s0, int s1) { return innov ? (size_t)(ioff[s1] - ioff[s0]) : 0; };
+      tree_query(who, "set", n, from, to, no_off.data(), joint_ms_, true, [&](int q0, int q1, const TsPlan &pl) {
+        const int s0 = set_of(q0), s1 = set_of(q1);
+        sets.clear();
+        fnc.clear();
+        fz.clear();
+        for (int s = s0; s < s1; s++) {
+          const int c0 = set_ptr[s], m = set_ptr[s + 1] - c0;
+          // the union of the root paths of the set's nodes, ascending front index (children precede parents)
+          fronts.clear();
+          for (int k = c0; k < c0 + m; k++) {
+            cand[k].cq = pl.query[k - q0];
+            cand[k].fa = front_of(from[k]);
+            cand[k].fb = front_of(to[k]);
+            for (int f0 : {cand[k].fa, cand[k].fb})
+              for (int f = f0; f >= 0 && slot[f] < 0; f = sym.sn_parent[f]) {
+                slot[f] = 0;
+                fronts.push_back(f);
+              }
+          }
+          std::sort(fronts.begin(), fronts.end());
+          const int nf = (int)fronts.size();
+          JointSet js{};
+          js.cand0 = c0 - q0;
+          js.m = m;
+          js.dim = dim[s];
+          js.n_front = nf;
+          js.fptr = (int64_t)fnc.size();
+          js.zptr = (int64_t)fz.size();
+          js.soff = innov ? ioff[s] - ioff[s0] : 0;
+          for (int i = 0; i < nf; i++) {
+            slot[fronts[i]] = i;
+            fnc.push_back(sym.sn_ncols[fronts[i]]);
+          }
+          // per (front, candidate): the first Z row of `from` and of `to` there, -1 where the front is not on the node's path
+          fz.resize(fz.size() + (size_t)nf * m * 2, -1);
+          int32_t *z = fz.data() + js.zptr;
+          for (int k = c0; k < c0 + m; k++) {
+            const int chunk[2] = {cand[k].cq.chunk_a, cand[k].cq.chunk_b}, f0[2] = {cand[k].fa, cand[k].fb};
+            for (int side = 0; side < 2; side++)
+              for (int f = f0[side]; f >= 0; f = sym.sn_parent[f]) {
+                const int32_t zr = pl.czrow[(size_t)chunk[side] * sym.S + f];
+                if (zr < 0) throw ApiError(RR_PGO_ENODEVICE, std::string(who) + ": internal: a front of a node's path is not active in its chunk");
+                z[((size_t)slot[f] * m + (k - c0)) * 2 + side] = zr;
+              }
+          }
+          for (int f : fronts) slot[f] = -1;
+          sets.push_back(js);
+        }
+        ts_fill(joint_set_, sets);
+        ts_fill(joint_fnc_, fnc);
+        ts_fill(joint_fz_, fz);
+        const size_t nc = (size_t)(q1 - q0);
+        ts_grow(gate_cand_, nc);
+        HIPCHK(hipMemcpyAsync(gate_cand_.p, cand.data() + q0, nc * sizeof(GateCand), hipMemcpyHostToDevice, stream_));
+        ts_grow(ts_out_, (size_t)(s1 - s0) + nc + n_innov(s0, s1));
+      }, [&](int q0, int q1) {
+        const int s0 = set_of(q0), s1 = set_of(q1);
+        const size_t ns = (size_t)(s1 - s0), nc = (size_t)(q1 - q0);
+        JointArgs<T> a;
+        a.set = joint_set_.p;
+        a.cand = gate_cand_.p;
+        a.fnc = joint_fnc_.p;
+        a.fz = joint_fz_.p;
+        a.Z = ts_z_.p;
+        a.pose = pose_.p;
+        a.d2 = ts_out_.p;
+        a.prefix = ts_out_.p + ns;
+        a.sout = innov ? ts_out_.p + ns + nc : nullptr;
+        if (is3d_) hipLaunchKernelGGL((k_gate_joint<T, 6>), dim3((unsigned)ns), dim3(COV_THREADS), 0, stream_, a);
+        else hipLaunchKernelGGL((k_gate_joint<T, 3>), dim3((unsigned)ns), dim3(COV_THREADS), 0, stream_, a);
+        check_launch("k_gate_joint");
+        return std::array<TsDest, 3>{{{d2 + s0, ns}, {prefix ? prefix + q0 : nullptr, nc}, {innov ? innov + ioff[s0] : nullptr, n_innov(s0, s1)}}};
+      }, set_ptr, n_sets);
+    }
+  }
+  void gate_joint_times(double *ms) const override { for (int k = 0; k < 3; k++) ms[k] = joint_ms_[k]; }
 
   void debug_withhold(int mode) override {
     HIPCHK(hipStreamSynchronize(stream_));
@@ -3791,21 +3898,18 @@ static bool small_cholesky(double *w, int d, int ld) {
   return true;
 }
 
-int rr_pgo_gate_edges(rr_pgo *h, int32_t n_cand, const int32_t *edge_kind, const int32_t *edge_from, const int32_t *edge_to,
-                      const double *edge_meas, const double *edge_info, double *d2_out, double *chi2_out, double *innov_out,
-                      int64_t *innov_offset) {
-  if (!h || n_cand < 0) { g_last_error = "rr_pgo_gate_edges: bad argument (n_cand < 0 or no handle)"; return RR_PGO_EINVAL; }
-  if (n_cand > 0 && (!edge_kind || !edge_from || !edge_to || !edge_meas || !edge_info || !d2_out)) {
-    g_last_error = "rr_pgo_gate_edges: null argument (edge_kind, edge_from, edge_to, edge_meas, edge_info and d2_out are required)";
-    return RR_PGO_EINVAL;
-  }
+// What rr_pgo_gate_edges and rr_pgo_gate_joint share: every check of the candidates (the message names the candidate) and
+// their records -- kind, nodes, measurement, Omega and Omega^-1 -- with soff, the [n_cand + 1] offsets of d_e x d_e blocks
+static int gate_candidates(const char *api, const rr_pgo *h, int32_t n_cand, const int32_t *edge_kind, const int32_t *edge_from,
+                           const int32_t *edge_to, const double *edge_meas, const double *edge_info, std::vector<GateCand> &cand,
+                           std::vector<int64_t> &soff) {
   const HostGraph &g = h->g;
   const int N = g.n_nodes(), D = g.has_se3 ? 6 : 3;
-  std::vector<GateCand> cand((size_t)n_cand);
-  std::vector<int64_t> soff((size_t)n_cand + 1, 0);
+  cand.assign((size_t)n_cand, GateCand{});
+  soff.assign((size_t)n_cand + 1, 0);
   int64_t mo = 0, io = 0;
   for (int c = 0; c < n_cand; c++) {
-    const std::string who = "rr_pgo_gate_edges: candidate " + std::to_string(c) + ": ";
+    const std::string who = std::string(api) + ": candidate " + std::to_string(c) + ": ";
     auto bad = [&](const std::string &what) { g_last_error = who + what; return RR_PGO_EINVAL; };
     const int kind = edge_kind[c], a = edge_from[c], b = edge_to[c];
     if (kind != EDGE_SE2 && kind != EDGE_SE2_XY && kind != EDGE_SE3) return bad("unknown edge kind " + std::to_string(kind));
@@ -3860,6 +3964,20 @@ int rr_pgo_gate_edges(rr_pgo *h, int32_t n_cand, const int32_t *edge_kind, const
       }
     soff[c + 1] = soff[c] + de * de;
   }
+  return RR_PGO_OK;
+}
+
+int rr_pgo_gate_edges(rr_pgo *h, int32_t n_cand, const int32_t *edge_kind, const int32_t *edge_from, const int32_t *edge_to,
+                      const double *edge_meas, const double *edge_info, double *d2_out, double *chi2_out, double *innov_out,
+                      int64_t *innov_offset) {
+  if (!h || n_cand < 0) { g_last_error = "rr_pgo_gate_edges: bad argument (n_cand < 0 or no handle)"; return RR_PGO_EINVAL; }
+  if (n_cand > 0 && (!edge_kind || !edge_from || !edge_to || !edge_meas || !edge_info || !d2_out)) {
+    g_last_error = "rr_pgo_gate_edges: null argument (edge_kind, edge_from, edge_to, edge_meas, edge_info and d2_out are required)";
+    return RR_PGO_EINVAL;
+  }
+  std::vector<GateCand> cand;
+  std::vector<int64_t> soff;
+  if (const int rc = gate_candidates("rr_pgo_gate_edges", h, n_cand, edge_kind, edge_from, edge_to, edge_meas, edge_info, cand, soff)) return rc;
   const int rc = guarded([&] { h->engine->gate_edges(n_cand, edge_from, edge_to, soff.data(), cand, d2_out, chi2_out, innov_out); });
   if (rc == RR_PGO_OK && innov_offset) std::copy(soff.begin(), soff.end(), innov_offset);
   return rc;
@@ -3868,6 +3986,59 @@ int rr_pgo_gate_edges(rr_pgo *h, int32_t n_cand, const int32_t *edge_kind, const
 int rr_pgo_gate_times(const rr_pgo *h, double *ms) {
   if (!h || !ms) { g_last_error = "null argument"; return RR_PGO_EINVAL; }
   return guarded([&] { h->engine->gate_times(ms); });
+}
+
+static_assert(RR_PGO_GATE_JOINT_MAX_DIM == GJ_MAX_DIM && RR_PGO_GATE_JOINT_MAX_CAND == GJ_MAX_CAND, "the caps of k_gate_joint");
+
+int rr_pgo_gate_joint(rr_pgo *h, int32_t n_cand, const int32_t *edge_kind, const int32_t *edge_from, const int32_t *edge_to,
+                      const double *edge_meas, const double *edge_info, int32_t n_sets, const int32_t *set_ptr,
+                      const int32_t *set_cand, double *d2_out, double *prefix_d2_out, double *innov_out, int64_t *innov_offset) {
+  static constexpr const char *api = "rr_pgo_gate_joint";
+  auto bad = [&](const std::string &what) { g_last_error = std::string(api) + ": " + what; return RR_PGO_EINVAL; };
+  if (!h || n_cand < 0 || n_sets < 0) return bad("bad argument (n_cand < 0, n_sets < 0 or no handle)");
+  std::vector<GateCand> cand, flat;
+  std::vector<int64_t> soff, ioff((size_t)n_sets + 1, 0);
+  std::vector<int32_t> from, to, dim((size_t)n_sets, 0);
+  if (n_sets > 0) {
+    if ((n_cand > 0 && (!edge_kind || !edge_from || !edge_to || !edge_meas || !edge_info)) || !set_ptr || !set_cand || !d2_out)
+      return bad("null argument (edge_kind, edge_from, edge_to, edge_meas, edge_info, set_ptr, set_cand and d2_out are required)");
+    if (const int rc = gate_candidates(api, h, n_cand, edge_kind, edge_from, edge_to, edge_meas, edge_info, cand, soff)) return rc;
+    if (set_ptr[0] != 0) return bad("set_ptr[0] must be 0");
+    for (int s = 0; s < n_sets; s++) {
+      const std::string set = "set " + std::to_string(s) + ": ";
+      const int64_t m = (int64_t)set_ptr[s + 1] - set_ptr[s];
+      if (m < 0) return bad(set + "set_ptr decreases");
+      if (m == 0) return bad(set + "empty set");
+      if (m > RR_PGO_GATE_JOINT_MAX_CAND)
+        return bad(set + std::to_string(m) + " candidates (at most RR_PGO_GATE_JOINT_MAX_CAND = " + std::to_string(RR_PGO_GATE_JOINT_MAX_CAND) + ")");
+      for (int k = set_ptr[s]; k < set_ptr[s + 1]; k++) {
+        const int c = set_cand[k];
+        if (c < 0 || c >= n_cand) return bad(set + "candidate index " + std::to_string(c) + " out of range");
+        dim[s] += cand[c].kind == EDGE_SE2 ? 3 : cand[c].kind == EDGE_SE2_XY ? 2 : 6;
+      }
+      if (dim[s] > RR_PGO_GATE_JOINT_MAX_DIM)
+        return bad(set + "stacked error dimension " + std::to_string(dim[s]) + " (at most RR_PGO_GATE_JOINT_MAX_DIM = " + std::to_string(RR_PGO_GATE_JOINT_MAX_DIM) + ")");
+      ioff[s + 1] = ioff[s] + (int64_t)dim[s] * dim[s];
+    }
+    // the sets' records one after the other: the pairs (from, to) of the plan
+    const size_t n = (size_t)set_ptr[n_sets];
+    flat.reserve(n);
+    from.reserve(n);
+    to.reserve(n);
+    for (size_t k = 0; k < n; k++) {
+      flat.push_back(cand[set_cand[k]]);
+      from.push_back(flat.back().na);
+      to.push_back(flat.back().nb);
+    }
+  }
+  const int rc = guarded([&] { h->engine->gate_joint(n_sets, set_ptr, from.data(), to.data(), dim.data(), ioff.data(), flat, d2_out, prefix_d2_out, innov_out); });
+  if (rc == RR_PGO_OK && innov_offset) std::copy(ioff.begin(), ioff.end(), innov_offset);
+  return rc;
+}
+
+int rr_pgo_gate_joint_times(const rr_pgo *h, double *ms) {
+  if (!h || !ms) { g_last_error = "null argument"; return RR_PGO_EINVAL; }
+  return guarded([&] { h->engine->gate_joint_times(ms); });
 }
 
 int rr_pgo_iterate_async(rr_pgo *h, int32_t iters) {

@@ -7,7 +7,8 @@
 //
 //   k_tree_fwd    one workgroup per (chunk of TS_MC columns, active front), one launch per level of the tree, deepest first
 //   k_cov_pairs   one workgroup per query: Sigma_ab = sum over the common path's pivot rows of Z_a[row]^T Z_b[row]
-//   k_gate_pairs  one workgroup per candidate edge: its Mahalanobis distance from the same Z (the end of this file)
+//   k_gate_pairs  one workgroup per candidate edge: its Mahalanobis distance from the same Z
+//   k_gate_joint  one workgroup per set of candidate edges: their joint distance from the same Z (the end of this file)
 //
 // Columns.  The distinct queried nodes are ordered by (front, pivot column) -- fronts are numbered in elimination order, so
 // neighbours share paths -- and packed, whole nodes at a time, into chunks of TS_MC = 32 columns (unused columns stay zero).
@@ -388,6 +389,251 @@ __global__ void __launch_bounds__(COV_THREADS) k_gate_pairs(GateArgs<T> a) {
       d2 = fma(y, y, d2);
     }
     a.d2[blockIdx.x] = ok ? (double)d2 : __builtin_nan("");
+  }
+}
+
+// ---- joint compatibility of sets of candidate edges (rr_pgo_gate_joint)
+//
+// For a set of candidates c1 .. cm with stacked error e (D_s scalars) and G = [G_c1 .. G_cm], G_c = Z_a A_c^T + Z_b B_c^T:
+//   S = blockdiag(Omega_c^-1) + G^T G,   S = L L^T,   y = L^-1 e,   d2 = y^T y,
+//   prefix(k) = the sum of y^2 over the rows of the first k + 1 candidates = d2 of the set cut after candidate k.
+// G has one row per pivot row of the fronts on the union of the root paths of the set's nodes.  The host lists those fronts
+// in ascending front index and gives, per (front, candidate), the first Z row of `from` and of `to` there (-1: the front
+// is not on that node's path, and the node's part of G_c is exactly zero).
+//
+// Determinism.  Row r of a front belongs to wave r % 8 whatever the set; a wave adds fma(G_r[i], G_r[j], acc) over its rows
+// in the host's front order, and a candidate absent from a front contributes fma(0, x, acc) = acc.  So the bits of block
+// (c, d) of S depend on the two candidates alone, not on the rest of the set, on its order or on the plan.  The Cholesky
+// factorisation is left-looking, every dot product in ascending k: column c and y[c] depend on the leading (c + 1) x (c + 1)
+// part of S and e alone, which makes the prefixes the distances of the truncated sets bit for bit.
+constexpr int GJ_MAX_DIM = 48;                  // RR_PGO_GATE_JOINT_MAX_DIM
+constexpr int GJ_MAX_CAND = 16;                 // RR_PGO_GATE_JOINT_MAX_CAND
+constexpr int GJ_TILE = 6;                      // a lane accumulates a GJ_TILE x GJ_TILE tile of S: 8 x 8 tiles cover 48 x 48
+constexpr int GJ_RB = 4;                        // rows of G a wave forms per step (their loads are in flight together)
+constexpr int GJ_LD = GJ_MAX_DIM + 1;           // LDS row stride of S: lanes i and i + 1 of a column read 34 banks apart
+static_assert(GJ_TILE * 8 == GJ_MAX_DIM, "lane (ti, tj) = (lane >> 3, lane & 7) owns tile (ti, tj)");
+
+struct JointSet {
+  int32_t cand0, m;               // the set's records: JointArgs::cand[cand0 .. cand0 + m)
+  int32_t dim, n_front;           // D_s; fronts on the union of the root paths
+  int64_t fptr;                   // into JointArgs::fnc: pivot columns of the set's fronts, ascending front index
+  int64_t zptr;                   // into JointArgs::fz: [(front * m + candidate) * 2 + {0: from, 1: to}] first Z row, -1: absent
+  int64_t soff;                   // offset of S (D_s x D_s, row-major) in sout
+};
+static_assert(sizeof(JointSet) == 40, "JointSet is one 40-byte record");
+
+template <typename T> struct JointArgs {
+  const JointSet *set;
+  const GateCand *cand;           // cq.ca / cq.cb: the columns of the two nodes in their chunks
+  const int32_t *fnc, *fz;
+  const T *Z;
+  const typename VecT<T>::V4 *pose;
+  double *d2, *prefix, *sout;     // prefix: one per record of cand; sout null: S is not asked for
+};
+
+// LDS writes of a wave made visible to its other lanes (the wave runs in lockstep: no instruction but the waits)
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// One workgroup per set; D = 3 (a 2-D graph) or 6 (SE3).  Lanes c < m of wave 0 (and, SE3, of wave 1 for B) linearise the
+// candidates.  Lane k < D_s of every wave forms G_r[k] for GJ_RB of the wave's rows into the wave's LDS vector, then lane
+// (ti, tj), tj <= ti, adds the rows' outer products into its tile.  The eight waves' tiles are added in wave order, one turn
+// each, into S in LDS; wave 0 factors S, lane = row, with e as row D_s of the same recurrence (that row of L is y).
+template <typename T, int D>
+__global__ void __launch_bounds__(COV_THREADS) k_gate_joint(JointArgs<T> a) {
+  constexpr int NS = COV_THREADS / 64, MD = GJ_MAX_DIM, LD = GJ_LD, TL = GJ_TILE, RB = GJ_RB, MC = GJ_MAX_CAND;
+  using V4 = typename VecT<T>::V4;
+  __shared__ T sA[MC * D * D], sB[MC * D * D], se[MC * D], sS[(MD + 1) * LD], gw[NS * RB * MD];
+  __shared__ int32_t s_c[MD], s_i[MD], s_o[MC + 1];   // stacked scalar -> candidate, error row; candidate -> first scalar
+  const JointSet js = a.set[blockIdx.x];
+  const GateCand *cq = a.cand + js.cand0;
+  const int tid = threadIdx.x, lane = tid & 63, wave = wave_index();
+  const int m = js.m, Ds = js.dim;
+  // ---- linearise; wave 2 lays the stacked vector out meanwhile
+  if (lane < m && wave < (D == 3 ? 1 : 2)) {
+    const GateCand *q = cq + lane;
+    if constexpr (D == 3) {
+      const V4 z = {(T)q->meas[0], (T)q->meas[1], (T)q->meas[2], (T)q->meas[3]};
+      T e[3], A[3][3], B[3][3];
+      edge_linearize_2d<T>(q->kind, a.pose[q->na], a.pose[q->nb], z, e, A, B);
+#pragma unroll
+      for (int i = 0; i < 3; i++) {
+        se[lane * 3 + i] = e[i];
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+          sA[lane * 9 + i * 3 + j] = A[i][j];
+          sB[lane * 9 + i * 3 + j] = B[i][j];
+        }
+      }
+    } else {
+      const V4 it = a.pose[2 * q->na], iq = a.pose[2 * q->na + 1], jt = a.pose[2 * q->nb], jq = a.pose[2 * q->nb + 1];
+      const T ti[3] = {it.x, it.y, it.z}, qi[4] = {iq.x, iq.y, iq.z, iq.w};
+      const T tj[3] = {jt.x, jt.y, jt.z}, qj[4] = {jq.x, jq.y, jq.z, jq.w};
+      const T tz[3] = {(T)q->meas[0], (T)q->meas[1], (T)q->meas[2]};
+      const T qz[4] = {(T)q->meas[4], (T)q->meas[5], (T)q->meas[6], (T)q->meas[7]};
+      T e[6], J[6][6];
+      edge_linearize_3d<T>(wave, ti, qi, tj, qj, tz, qz, e, J);
+      T *dst = (wave ? sB : sA) + lane * 36;
+#pragma unroll
+      for (int i = 0; i < 6; i++) {
+        if (wave == 0) se[lane * 6 + i] = e[i];
+#pragma unroll
+        for (int j = 0; j < 6; j++) dst[i * 6 + j] = J[i][j];
+      }
+    }
+  }
+  if (tid == 128) {
+    int o = 0;
+    for (int c = 0; c < m; c++) {
+      const int de = cq[c].kind == 1 ? 2 : D;
+      s_o[c] = o;
+      for (int i = 0; i < de && o < MD; i++, o++) {   // (the host has checked D_s <= MD)
+        s_c[o] = c;
+        s_i[o] = i;
+      }
+    }
+    s_o[m] = o;
+  }
+  __syncthreads();
+  // ---- lane k < D_s: row i of A_c and B_c, the columns of c's nodes (the columns of B past d_b are zero: pose-landmark)
+  const bool live = lane < Ds;
+  const int c = live ? s_c[lane] : 0;
+  T Ai[D], Bi[D];
+  int cola[D], colb[D];
+  {
+    const int i = live ? s_i[lane] : 0, db = cq[c].kind == 1 ? 2 : D;
+#pragma unroll
+    for (int k = 0; k < D; k++) {
+      Ai[k] = live ? sA[c * D * D + i * D + k] : (T)0;
+      Bi[k] = live ? sB[c * D * D + i * D + k] : (T)0;
+      cola[k] = cq[c].cq.ca[k];
+      colb[k] = cq[c].cq.cb[min(k, db - 1)];
+    }
+  }
+  const int ti = lane >> 3, tj = lane & 7;
+  const bool tile = tj <= ti && TL * ti < Ds;
+  T acc[TL][TL];
+#pragma unroll
+  for (int x = 0; x < TL; x++)
+#pragma unroll
+    for (int y = 0; y < TL; y++) acc[x][y] = 0;
+  T *gmine = gw + wave * RB * MD;
+  const int32_t *fnc = a.fnc + js.fptr, *fz = a.fz + js.zptr;
+  for (int fi = 0; fi < js.n_front; fi++) {
+    const int nc = __builtin_amdgcn_readfirstlane(fnc[fi]);
+    int za = -1, zb = -1;
+    if (live) {
+      const int32_t *p = fz + ((int64_t)fi * m + c) * 2;
+      za = p[0];
+      zb = p[1];
+    }
+    for (int r0 = wave; r0 < nc; r0 += NS * RB) {
+      T g[RB];
+#pragma unroll
+      for (int q = 0; q < RB; q++) {
+        const int r = r0 + NS * q;
+        T v = 0;
+        if (r < nc) {
+          if (za >= 0) {
+            const T *p = a.Z + (int64_t)(za + r) * TS_MC;
+#pragma unroll
+            for (int k = 0; k < D; k++) v = fma(p[cola[k]], Ai[k], v);
+          }
+          if (zb >= 0) {
+            const T *p = a.Z + (int64_t)(zb + r) * TS_MC;
+#pragma unroll
+            for (int k = 0; k < D; k++) v = fma(p[colb[k]], Bi[k], v);
+          }
+        }
+        g[q] = v;
+      }
+      if (lane < MD) {
+#pragma unroll
+        for (int q = 0; q < RB; q++) gmine[q * MD + lane] = g[q];
+      }
+      wave_lds_sync();
+#pragma unroll
+      for (int q = 0; q < RB; q++)
+        if (r0 + NS * q < nc && tile) {
+          T gi[TL], gj[TL];
+#pragma unroll
+          for (int x = 0; x < TL; x++) {
+            gi[x] = gmine[q * MD + TL * ti + x];
+            gj[x] = gmine[q * MD + TL * tj + x];
+          }
+#pragma unroll
+          for (int x = 0; x < TL; x++)
+#pragma unroll
+            for (int y = 0; y < TL; y++) acc[x][y] = fma(gi[x], gj[y], acc[x][y]);
+        }
+      wave_lds_sync();   // the vector is rewritten by the next step
+    }
+  }
+  // ---- the eight waves' tiles in wave order
+  for (int w = 0; w < NS; w++) {
+    if (wave == w && tile) {
+#pragma unroll
+      for (int x = 0; x < TL; x++)
+#pragma unroll
+        for (int y = 0; y < TL; y++) {
+          T *d = sS + (TL * ti + x) * LD + TL * tj + y;
+          *d = w == 0 ? acc[x][y] : *d + acc[x][y];
+        }
+    }
+    __syncthreads();
+  }
+  // ---- Omega^-1 on the diagonal blocks; both halves of S from the lower triangle; e is row D_s
+  for (int t = tid; t < Ds * Ds; t += COV_THREADS) {
+    const int i = t / Ds, j = t - i * Ds;
+    if (j <= i && s_c[i] == s_c[j]) sS[i * LD + j] += (T)cq[s_c[i]].cov[s_i[i] * D + s_i[j]];
+  }
+  __syncthreads();
+  for (int t = tid; t < Ds * Ds; t += COV_THREADS) {
+    const int i = t / Ds, j = t - i * Ds;
+    if (j > i) sS[i * LD + j] = sS[j * LD + i];
+  }
+  if (tid < Ds) sS[Ds * LD + tid] = se[s_c[tid] * D + s_i[tid]];
+  __syncthreads();
+  if (a.sout)
+    for (int t = tid; t < Ds * Ds; t += COV_THREADS) {
+      const int i = t / Ds, j = t - i * Ds;
+      a.sout[js.soff + t] = (double)sS[i * LD + j];
+    }
+  __syncthreads();
+  // ---- S = L L^T in place, column by column, lane = row; row D_s of L is y = L^-1 e
+  if (wave == 0) {
+    const int i = lane;
+    int fail = Ds;   // the first column with a non-positive pivot (Omega is checked on the host: rounding only)
+    for (int col = 0; col < Ds; col++) {
+      T v = 0;
+      if (i >= col && i <= Ds) {
+        v = sS[i * LD + col];
+        for (int k = 0; k < col; k++) v = fma(-sS[i * LD + k], sS[col * LD + k], v);
+      }
+      const T d = __shfl(v, col);
+      if (!(d > (T)0)) {
+        fail = col;
+        break;
+      }
+      const T l = sqrt(d), inv = (T)1 / l;
+      if (i == col) sS[i * LD + col] = l;
+      else if (i > col && i <= Ds) sS[i * LD + col] = v * inv;
+      wave_lds_sync();
+    }
+    if (lane == 0) {
+      T d2 = 0;
+      for (int cc = 0, k = 0; cc < m; cc++) {
+        for (; k < s_o[cc + 1]; k++) {
+          const T y = sS[Ds * LD + k];
+          d2 = fma(y, y, d2);
+        }
+        a.prefix[js.cand0 + cc] = s_o[cc + 1] <= fail ? (double)d2 : __builtin_nan("");
+      }
+      a.d2[blockIdx.x] = fail == Ds ? (double)d2 : __builtin_nan("");
+    }
   }
 }
 

@@ -37,6 +37,12 @@ class PoseGraphError(RuntimeError):
 # dimension, measurement length and packed information length of an edge by kind (RR_PGO_EDGE_SE2, _SE2_XY, _SE3)
 CHI2_95_2, CHI2_95_3, CHI2_95_6 = 5.991, 7.815, 12.592
 GATE_DEFAULT_THRESHOLD = {0: CHI2_95_3, 1: CHI2_95_2, 2: CHI2_95_6}
+# ... and with 1 .. 48 degrees of freedom (CHI2_95[d]; the default of PoseGraph.gate_joint_accept: d = D_s)
+CHI2_95 = (None,
+           3.841, 5.991, 7.815, 9.488, 11.070, 12.592, 14.067, 15.507, 16.919, 18.307, 19.675, 21.026,
+           22.362, 23.685, 24.996, 26.296, 27.587, 28.869, 30.144, 31.410, 32.671, 33.924, 35.172, 36.415,
+           37.652, 38.885, 40.113, 41.337, 42.557, 43.773, 44.985, 46.194, 47.400, 48.602, 49.802, 50.998,
+           52.192, 53.384, 54.572, 55.758, 56.942, 58.124, 59.304, 60.481, 61.656, 62.830, 64.001, 65.171)
 GATE_EDGE_DIM = (3, 2, 6)
 GATE_MEAS_LEN = (3, 2, 7)
 GATE_INFO_LEN = (6, 3, 21)
@@ -50,6 +56,20 @@ def gate_thresholds(edge_kind, threshold=None):
     if hasattr(threshold, "keys"):
         return np.array([float(threshold[int(k)]) for k in kind])
     return np.full(kind.shape, float(threshold))
+
+
+def gate_joint_dims(edge_kind, sets):
+    """D_s of every set: the sum of its candidates' error dimensions"""
+    kind = np.asarray(edge_kind, np.int64)
+    return np.array([int(sum(GATE_EDGE_DIM[int(kind[c])] for c in s)) for s in sets], np.int64)
+
+
+def gate_joint_thresholds(edge_kind, sets, threshold=None):
+    """per-set threshold of PoseGraph.gate_joint_accept: a scalar, or None (the 0.95 quantile of D_s degrees of freedom)"""
+    dims = gate_joint_dims(edge_kind, sets)
+    if threshold is None:
+        return np.array([CHI2_95[int(d)] for d in dims], np.float64)
+    return np.full(dims.shape, float(threshold))
 
 
 def _check(rc):
@@ -386,6 +406,53 @@ class PoseGraph:
     def gate_times(self):
         """HIP-event milliseconds of the last gate_edges call: (linearise + factor, tree solve, gate kernel + copy)."""
         return self._times(_lib.load().rr_pgo_gate_times)
+
+    # -- joint compatibility of sets of candidates (include/rr_pgo.h, rr_pgo_gate_joint) ------
+    def gate_joint(self, edge_kind, edge_from, edge_to, edge_meas, edge_info, sets, return_prefix=False,
+                   return_innovation=False):
+        """rr_pgo_gate_joint: d2 of every set of `sets` -- ordered lists of indices into the candidates, which are given as
+        for gate_edges.  d2[s] = e_s^T S_s^-1 e_s with the stacked errors e_s and the joint innovation covariance S_s.
+        return_prefix adds the list of per-set arrays of prefix distances (entry k: the set cut after its candidate k),
+        return_innovation the list of the D_s x D_s matrices S_s; the result is d2 alone or a tuple in that order."""
+        L = _lib.load()
+        kind = np.ascontiguousarray(edge_kind, np.int32)
+        a = np.ascontiguousarray(edge_from, np.int32)
+        b = np.ascontiguousarray(edge_to, np.int32)
+        meas = np.ascontiguousarray(edge_meas, np.float64).ravel()
+        info = np.ascontiguousarray(edge_info, np.float64).ravel()
+        if kind.ndim != 1 or a.shape != kind.shape or b.shape != kind.shape:
+            raise ValueError("edge_kind, edge_from and edge_to need the same length")
+        if np.all(np.isin(kind, (0, 1, 2))):   # (an unknown kind is the library's to refuse)
+            if len(meas) != int(np.sum(np.take(GATE_MEAS_LEN, kind))) or len(info) != int(np.sum(np.take(GATE_INFO_LEN, kind))):
+                raise ValueError("edge_meas / edge_info do not have the length the edge kinds ask for")
+        sets = [np.asarray(s, np.int32).ravel() for s in sets]
+        ns = len(sets)
+        ptr = np.zeros(ns + 1, np.int32)
+        ptr[1:] = np.cumsum([len(s) for s in sets])
+        flat = np.ascontiguousarray(np.concatenate(sets) if ns else np.zeros(0), np.int32)
+        d2, prefix = np.zeros(ns), np.zeros(max(len(flat), 1))
+        off = np.zeros(ns + 1, np.int64)
+        vals = np.zeros(_lib.GATE_JOINT_MAX_DIM ** 2 * max(ns, 1)) if return_innovation else None
+        _check(L.rr_pgo_gate_joint(self._h, len(kind), _ip(kind), _ip(a), _ip(b), _dp(meas), _dp(info), ns, _ip(ptr), _ip(flat),
+                                   _dp(d2), _dp(prefix) if return_prefix else None, None if vals is None else _dp(vals),
+                                   off.ctypes.data_as(C.POINTER(C.c_int64))))
+        out = [d2]
+        if return_prefix:
+            out.append([prefix[ptr[s]:ptr[s + 1]].copy() for s in range(ns)])
+        if return_innovation:
+            dims = [int(round(np.sqrt(off[s + 1] - off[s]))) for s in range(ns)]
+            out.append([vals[off[s]:off[s + 1]].reshape(dims[s], dims[s]).copy() for s in range(ns)])
+        return d2 if len(out) == 1 else tuple(out)
+
+    def gate_joint_accept(self, edge_kind, edge_from, edge_to, edge_meas, edge_info, sets, threshold=None):
+        """Boolean per set, d2 <= threshold (True: the candidates of the set are jointly compatible).  threshold: a scalar,
+        or None: the 0.95 chi-square quantile of D_s degrees of freedom (CHI2_95)."""
+        d2 = self.gate_joint(edge_kind, edge_from, edge_to, edge_meas, edge_info, sets)
+        return d2 <= gate_joint_thresholds(edge_kind, sets, threshold)
+
+    def gate_joint_times(self):
+        """HIP-event milliseconds of the last gate_joint call: (linearise + factor, tree solve, joint kernel + copy)."""
+        return self._times(_lib.load().rr_pgo_gate_joint_times)
 
     # -- PoseGraph::plot, :375-431 -------------------------------------------------------
     def plot_data(self):
