@@ -580,7 +580,8 @@ __device__ __forceinline__ void flow_panel_wave(const FlowArgs<T> &fa, const Flo
 // (hardware NaNs are 0x7fc00000 / propagated payloads of the operands); every store of a W block writes all of its
 // 1024 entries, each entry goes from the mark to its value in one store, so a block without a mark is complete.
 template <typename T>
-__global__ void __launch_bounds__(256) k_flow_reset(unsigned *words, int64_t n, int flag_wgs, T *winv, const int64_t *wfill, T *xnew) {
+__global__ void __launch_bounds__(256) k_flow_reset(unsigned *words, int64_t n, int flag_wgs, T *winv, const int64_t *wfill, T *xnew, const int *err) {
+  if (opt_stopped(err)) return;   // rr_pgo_optimize: enqueued behind the iteration that met the stop rule (the launches that use the flags return too)
   if ((int)blockIdx.x < flag_wgs) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)flag_wgs * 256) words[i] = 0u;
   } else {

@@ -103,8 +103,9 @@ enum : int { DEVERR_NOT_SPD = 1, DEVERR_FLOW_TIMEOUT = 2 };
 // Levenberg-Marquardt accept / reject (:275-282) and the failure of a factorisation (:271) are decided here, by the
 // kernel that finishes an iteration, which also publishes the iteration's (chi2, |dx|) in a ring the host polls
 // (pinned, host-coherent memory).  The STOP WORD is the int behind the sticky error flag (err[1]): once it is set,
-// every later launch of the same call returns at its first instruction (the compute kernels) or leaves the state alone
-// (k_update), so an iteration that was enqueued before the host saw the stop costs a handful of empty launches.
+// every later launch of the same call but the linearisation returns at its first instruction, having read that ONE word
+// -- no ticket, flag, counter, partial, pose or ring slot -- so an iteration that was enqueued before the host saw the
+// stop costs a handful of empty launches that touch nothing (DESIGN.md 4a lists them).
 struct OptCtrl {
   double lambda;        // :254; x 2 on reject, / 2 on accept
   double last_error;    // :255, :284
@@ -123,8 +124,10 @@ enum : int { OPT_STOP = 1,      // the stop rule fired in this item: it is the l
              OPT_SKIPPED = 2,   // the item found the stop word set: only its chi2 (of the final state) means anything
              OPT_ERR_SHIFT = 8  // flags >> 8 = the device error flag (DEVERR_*) when the item's factorisation failed
 };
-__device__ __forceinline__ void opt_publish(OptCtrl *c, OptSlot *ring, double chi2, double norm, int flags) {
-  const unsigned long long n = c->seq + 1;
+// `seq`: OptCtrl::seq as the launch found it (the publisher of the previous item, an earlier launch, wrote it: it is loaded
+// at the start of the launch, not behind the launch's own reduction)
+__device__ __forceinline__ void opt_publish(OptCtrl *c, OptSlot *ring, double chi2, double norm, int flags, unsigned long long seq) {
+  const unsigned long long n = seq + 1;
   OptSlot *s = ring + (n - 1) % OPT_RING;
   s->chi2 = chi2;
   s->norm = norm;
@@ -300,19 +303,44 @@ struct FinArgs {
   OptSlot *ring_host;          // ... and the host-visible ring the iteration is published in
   int *err;                    // the engine's error block: [0] sticky error flag, [1] stop word
 };
+// What the last workgroup of an update launch needs and the launch itself does not produce: EVERY workgroup requests it at
+// its start, ahead of its node work (only the one that turns out to be last uses it), so that behind the block ticket one
+// dependent trip is left -- the other workgroups' |dx|^2 partials.  Who wrote each value:
+//   chi_partial[]             the linearisation of this iteration, an earlier launch
+//   *counter                  the last workgroup of the previous update launch (or the host's memset), earlier on the stream
+//   err[0]                    the factorisation / back substitution of this iteration, earlier launches (k_update raises no error)
+//   ctrl->tolerance           the first launch of the call;  ctrl->seq: the publisher of the previous item, an earlier launch
+// The stop word err[1] is not among them: a launch that finds it set has returned at its first instruction.
+struct FinPre {
+  double c;                    // this thread's share of chi_partial[]: indices t, t + THREADS, ... in that order
+  int early;                   // 0: the partials are too many to be read by every workgroup; the last one reads them late
+  int counter, e;
+  double tolerance;
+  unsigned long long seq;
+};
+enum : int { FIN_EARLY_PER_THREAD = 4 };   // (a lattice of 100 000 nodes has thousands of partials: there only the last workgroup reads them)
+template <int THREADS> __device__ __forceinline__ FinPre finalize_preload(const FinArgs &f) {
+  FinPre p{};
+  if (!f.enabled) return p;
+  p.early = f.n_chi <= FIN_EARLY_PER_THREAD * THREADS;
+  if (p.early)
+    for (int i = threadIdx.x; i < f.n_chi; i += THREADS) p.c += f.chi_partial[i];
+  p.counter = *f.counter;
+  if (f.ctrl) { p.e = f.err[0]; p.tolerance = f.ctrl->tolerance; p.seq = f.ctrl->seq; }
+  return p;
+}
 // Gauss-Newton inside rr_pgo_optimize (one thread): ct = chi2 of the state BEFORE this step (errors[i], :286), sqrt(nt) = |dx|
 // (:273); the stop rule, and the end of the call after a failed factorisation
-__device__ __forceinline__ void finalize_publish(const FinArgs &f, double ct, double nt) {
+__device__ __forceinline__ void finalize_publish(const FinArgs &f, const FinPre &p, double ct, double nt) {
   if (!f.ctrl) return;
-  const int e = f.err[0];
-  if (f.err[1]) return;   // enqueued behind the iteration that met the stop rule: this item's linearisation has published chi2 of the final state
+  const int e = p.e;
   const double nrm = sqrt(nt);
-  const bool stop = e != 0 || nrm < f.ctrl->tolerance;   // :298-300; a failed factorisation ends the call (:271)
+  const bool stop = e != 0 || nrm < p.tolerance;   // :298-300; a failed factorisation ends the call (:271)
   if (stop) f.err[1] = 1;
-  opt_publish(f.ctrl, f.ring_host, ct, nrm, (stop && !e ? OPT_STOP : 0) | (e << OPT_ERR_SHIFT));
+  opt_publish(f.ctrl, f.ring_host, ct, nrm, (stop && !e ? OPT_STOP : 0) | (e << OPT_ERR_SHIFT), p.seq);
 }
 template <int THREADS>
-__device__ __forceinline__ void finalize_in_last_block(const FinArgs &f, const double *norm_partial, int n_norm, double *red) {
+__device__ __forceinline__ void finalize_in_last_block(const FinArgs &f, const FinPre &p, const double *norm_partial, int n_norm, double *red) {
   __shared__ int is_last;
   if (threadIdx.x == 0) {
     __threadfence();                                  // this block's partial is out before it is counted
@@ -321,18 +349,19 @@ __device__ __forceinline__ void finalize_in_last_block(const FinArgs &f, const d
   __syncthreads();
   if (!is_last) return;
   __threadfence();                                    // the other blocks' partials are visible
-  double c = 0.0, n = 0.0;
-  for (int i = threadIdx.x; i < f.n_chi; i += THREADS) c += f.chi_partial[i];
+  double c = p.c, n = 0.0;
+  if (!p.early)
+    for (int i = threadIdx.x; i < f.n_chi; i += THREADS) c += f.chi_partial[i];
   for (int i = threadIdx.x; i < n_norm; i += THREADS) n += norm_partial[i];
   const double ct = block_sum<double, THREADS>(c, red);
   const double nt = block_sum<double, THREADS>(n, red);
   if (threadIdx.x == 0) {
-    const int slot = *f.counter % f.ring;
+    const int slot = p.counter % f.ring;
     if (f.n_chi > 0) f.hist[2 * slot] = ct;
     f.hist[2 * slot + 1] = sqrt(nt);
-    if (f.advance) *f.counter = *f.counter + 1;
+    if (f.advance) *f.counter = p.counter + 1;
     *f.blocks_done = 0;
-    finalize_publish(f, ct, nt);
+    finalize_publish(f, p, ct, nt);
   }
 }
 
@@ -350,7 +379,11 @@ struct OptItemArgs {
   int *err;
 };
 __global__ void __launch_bounds__(256) k_opt_item(OptItemArgs a) {
+  // enqueued behind the item that met the stop rule: that item's first linearisation has published chi2 of the final state
+  // (opt_publish_chi2_in_last_block) and cleared `reject` for the undo launch behind this one
+  if (a.err[1]) return;
   __shared__ double red[4];
+  const unsigned long long seq = a.ctrl->seq;   // (the publisher of the previous item wrote it)
   double c = 0.0, n = 0.0;
   for (int i = threadIdx.x; i < a.n_chi; i += 256) c += a.chi_partial[i];
   for (int i = threadIdx.x; i < a.n_norm; i += 256) n += a.norm_partial[i];
@@ -359,16 +392,15 @@ __global__ void __launch_bounds__(256) k_opt_item(OptItemArgs a) {
   if (threadIdx.x != 0) return;
   OptCtrl *k = a.ctrl;
   k->reject = 0;
-  if (a.err[1]) { opt_publish(k, a.ring, ct, 0.0, OPT_SKIPPED); return; }
   if (a.mode == 0) {
     k->last_error = ct;
-    opt_publish(k, a.ring, ct, 0.0, 0);
+    opt_publish(k, a.ring, ct, 0.0, 0, seq);
     return;
   }
   const int e = a.err[0];
   if (e) {   // the step was not applied (k_update saw the flag): no decision to take, the call ends
     a.err[1] = 1;
-    opt_publish(k, a.ring, ct, 0.0, e << OPT_ERR_SHIFT);
+    opt_publish(k, a.ring, ct, 0.0, e << OPT_ERR_SHIFT, seq);
     return;
   }
   const double nrm = sqrt(nt);
@@ -377,13 +409,24 @@ __global__ void __launch_bounds__(256) k_opt_item(OptItemArgs a) {
   k->last_error = ct;                                              // :284
   const bool stop = nrm < k->tolerance;
   if (stop) a.err[1] = 1;
-  opt_publish(k, a.ring, ct, nrm, stop ? OPT_STOP : 0);
+  opt_publish(k, a.ring, ct, nrm, stop ? OPT_STOP : 0, seq);
 }
 
+// What a linearisation inside rr_pgo_optimize decides its publication on, requested at the START of the launch (both were
+// loaded behind the node work, at the end of every workgroup):
+//   the stop word err[1]   set by the last workgroup of the previous item's final launch, earlier on the stream
+//   ctrl->seq              written by that same publisher
+// The call's first launch resets both itself (opt_reset_in_first_thread): it is never stopped and its item is the first.
+struct LinPre { bool stopped; unsigned long long seq; };
+template <typename A> __device__ __forceinline__ LinPre opt_publish_preload(const A &a) {
+  LinPre p{false, 0ull};
+  if (a.publish && !a.reset_ctrl) { p.stopped = a.err[1] != 0; p.seq = a.ctrl->seq; }
+  return p;
+}
 // (the sum in k_finalize_slot's order: 256 threads, stride 256, block_sum)
-template <typename A> __device__ __forceinline__ void opt_publish_chi2_in_last_block(const A &a, double *red) {
+template <typename A> __device__ __forceinline__ void opt_publish_chi2_in_last_block(const A &a, const LinPre &p, double *red) {
   if (!a.publish) return;
-  const bool stopped = !a.reset_ctrl && a.err[1] != 0;   // (the call's first launch resets the word: never stopped)
+  const bool stopped = p.stopped;
   if (a.publish == 1 && !stopped) return;
   __shared__ int is_last;
   if (threadIdx.x == 0) {
@@ -399,7 +442,8 @@ template <typename A> __device__ __forceinline__ void opt_publish_chi2_in_last_b
   if (threadIdx.x == 0) {
     *a.blocks_done = 0;
     if (!stopped) a.ctrl->last_error = ct;
-    opt_publish(a.ctrl, a.ring_host, ct, 0.0, stopped ? OPT_SKIPPED : 0);
+    else a.ctrl->reject = 0;   // Levenberg-Marquardt: the undo launch of this (skipped) item must not repeat the previous item's undo
+    opt_publish(a.ctrl, a.ring_host, ct, 0.0, stopped ? OPT_SKIPPED : 0, p.seq);
   }
 }
 
@@ -419,6 +463,7 @@ __global__ void __launch_bounds__(LIN_THREADS) k_linearize(LinArgs<TO, T> a) {
   for (int i = gid; i < a.n_zero_words; i += gridDim.x * LIN_THREADS) a.zero_words[i] = 0u;
   for (int i = gid; i < a.n_fill_words; i += gridDim.x * LIN_THREADS) a.fill_words[i] = X_PENDING_WORD;
   opt_reset_in_first_thread(a);
+  const LinPre lin_pre = opt_publish_preload(a);
   const T lambda = a.lambda_from_ctrl ? (T)a.ctrl->lambda : a.lambda;
   const int slot = gid / LIN_GROUP, sub = gid % LIN_GROUP;
   const int node = slot < a.n_nodes ? (a.node_list ? a.node_list[slot] : slot) : -1;
@@ -534,7 +579,7 @@ __global__ void __launch_bounds__(LIN_THREADS) k_linearize(LinArgs<TO, T> a) {
   }
   double tot = block_sum<double, LIN_THREADS>(chi, red);
   if (threadIdx.x == 0) a.chi2_partial[blockIdx.x] = tot;
-  opt_publish_chi2_in_last_block(a, red);
+  opt_publish_chi2_in_last_block(a, lin_pre, red);
 }
 
 // ---- the EDGE-PARALLEL form of the same linearisation (the north star's wording; RR_PGO_EDGE_LINEARIZE=1) ----
@@ -942,6 +987,7 @@ __global__ void __launch_bounds__(LIN_THREADS) k_linearize_se3(LinArgs3<TO, T> a
   for (int i = gid; i < a.n_zero_words; i += gridDim.x * LIN_THREADS) a.zero_words[i] = 0u;
   for (int i = gid; i < a.n_fill_words; i += gridDim.x * LIN_THREADS) a.fill_words[i] = X_PENDING_WORD;
   opt_reset_in_first_thread(a);
+  const LinPre lin_pre = opt_publish_preload(a);
   const T lambda = a.lambda_from_ctrl ? (T)a.ctrl->lambda : a.lambda;
   const int slot = gid / LIN_GROUP, sub = gid % LIN_GROUP;
   const int node = slot < a.n_nodes ? (a.node_list ? a.node_list[slot] : slot) : -1;
@@ -1072,7 +1118,7 @@ __global__ void __launch_bounds__(LIN_THREADS) k_linearize_se3(LinArgs3<TO, T> a
   }
   double tot = block_sum<double, LIN_THREADS>(chi, red);
   if (threadIdx.x == 0) a.chi2_partial[blockIdx.x] = tot;
-  opt_publish_chi2_in_last_block(a, red);
+  opt_publish_chi2_in_last_block(a, lin_pre, red);
 }
 
 // rr_pgo_edge_errors: one thread per edge, s = e^T W e and the robust weight w(s) at the current state, in f64 (file order).
@@ -1150,8 +1196,10 @@ __global__ void __launch_bounds__(UPD_THREADS) k_update_se3(UpdArgs3<TO, T> a) {
   const int slot = blockIdx.x * UPD_THREADS + threadIdx.x;
   const int node = slot < a.n_nodes ? (a.node_list ? a.node_list[slot] : slot) : -1;
   double nrm = 0.0;
+  if (opt_stopped(a.err)) return;   // as k_update
   if (a.gate && *a.gate == 0) return;
-  const bool failed = a.err && (a.err[0] != 0 || a.err[1] != 0);   // as k_update
+  const FinPre fin_pre = finalize_preload<UPD_THREADS>(a.fin);
+  const bool failed = a.err && a.err[0] != 0;   // as k_update
   if (node >= 0 && !failed) {
     T d[6];
     const TO *src = a.dx_ref_in ? a.dx_ref_in + a.node_offset[node] : a.x + a.node_pcol[node];
@@ -1189,7 +1237,7 @@ __global__ void __launch_bounds__(UPD_THREADS) k_update_se3(UpdArgs3<TO, T> a) {
   if (a.export_only) return;
   double tot = block_sum<double, UPD_THREADS>(nrm, red);
   if (threadIdx.x == 0) a.norm_partial[blockIdx.x] = tot;
-  if (a.fin.enabled) finalize_in_last_block<UPD_THREADS>(a.fin, a.norm_partial, (int)gridDim.x, red);
+  if (a.fin.enabled) finalize_in_last_block<UPD_THREADS>(a.fin, fin_pre, a.norm_partial, (int)gridDim.x, red);
 }
 
 // ------------------------------------------------------------ multifrontal
@@ -4044,9 +4092,11 @@ template <typename T, typename TC> struct GaugeArgs {
   T *v;                      // 3 * nc scratch: the three fields on the root's pivot columns
   TC ox, oy;                 // origin of the rotation field (centroid of S at set-up: conditioning only)
   T mu_t, mu_r;
+  const int *err;            // the engine's error block: [1] is rr_pgo_optimize's stop word
 };
 
 template <typename T, typename TC> __global__ void __launch_bounds__(256) k_gauge_vectors(GaugeArgs<T, TC> a) {
+  if (opt_stopped(a.err)) return;   // rr_pgo_optimize: enqueued behind the iteration that met the stop rule
   const int j = blockIdx.x * 256 + threadIdx.x;
   if (j >= a.nc) return;
   const int ent = a.col_node[j], node = ent >> 2, comp = ent & 3;
@@ -4058,6 +4108,7 @@ template <typename T, typename TC> __global__ void __launch_bounds__(256) k_gaug
 
 // F(i, j) += mu_t (tx_i tx_j + ty_i ty_j) + mu_r rot_i rot_j on the lower triangle of the root's pivot block
 template <typename T, typename TC> __global__ void __launch_bounds__(256) k_big_gauge(GaugeArgs<T, TC> a) {
+  if (opt_stopped(a.err)) return;   // rr_pgo_optimize: enqueued behind the iteration that met the stop rule
   const int j = blockIdx.x;
   const T *v0 = a.v, *v1 = a.v + a.nc, *v2 = a.v + 2 * a.nc;
   const T a0 = a.mu_t * v0[j], a1 = a.mu_t * v1[j], a2 = a.mu_r * v2[j];
@@ -4135,14 +4186,17 @@ __global__ void __launch_bounds__(UPD_THREADS) k_update(UpdArgs<TO, T> a) {
   const int slot = blockIdx.x * UPD_THREADS + threadIdx.x;
   const int node = slot < a.n_nodes ? (a.node_list ? a.node_list[slot] : slot) : -1;
   double nrm = 0.0;
+  // rr_pgo_optimize: enqueued behind the iteration that met the stop rule (:298-300) -- the state, the partials, the slot
+  // counter and the ring stay as that iteration left them
+  if (opt_stopped(a.err)) return;
   if (a.gate && *a.gate == 0) return;
-  // a failed factorisation, or a launch enqueued behind the iteration that met the stop rule (:298-300): the state stays
-  const bool failed = a.err && (a.err[0] != 0 || a.err[1] != 0);
+  const FinPre fin_pre = finalize_preload<UPD_THREADS>(a.fin);   // requested ahead of the node work
+  const bool failed = a.err && a.err[0] != 0;   // a failed factorisation: the state stays
   if (node >= 0 && !failed) nrm = update_node(a, node);
   if (a.export_only) return;
   double tot = block_sum<double, UPD_THREADS>(nrm, red);
   if (threadIdx.x == 0) a.norm_partial[blockIdx.x] = tot;
-  if (a.fin.enabled) finalize_in_last_block<UPD_THREADS>(a.fin, a.norm_partial, (int)gridDim.x, red);
+  if (a.fin.enabled) finalize_in_last_block<UPD_THREADS>(a.fin, fin_pre, a.norm_partial, (int)gridDim.x, red);
 }
 
 }  // namespace rrpgo

@@ -56,13 +56,15 @@ __global__ void __launch_bounds__(THREADS) k_factor_flow(FactorArgs<T> a, const 
   __shared__ T dinv[W16_SCR];   // inverse of the current 16 x 16 diagonal block + an identity (diag16_factor_invert_full)
   __shared__ int ticket_slot[2];
   T *smem = reinterpret_cast<T *>(smem_raw);
-  const bool stopped = opt_stopped(a.err);   // rr_pgo_optimize: enqueued behind the iteration that met the stop rule (the load is
-                                             // back before the first ticket is: nothing waits for it)
+  // rr_pgo_optimize: enqueued behind the iteration that met the stop rule -- no ticket is drawn: the stop word is the one
+  // word such a launch reads (the identity below is written while the load is on its way)
+  const bool stopped = opt_stopped(a.err);
   init_w16_identity<T>(dinv, threadIdx.x, THREADS);
+  if (stopped) return;
   if (THREADS > 256 && wave_index() == 0) __builtin_amdgcn_s_setprio(RRPGO_CHAIN_PRIO);
   for (int round = 0;; round++) {
     const int tk = lds_flow_ticket(ticket, &ticket_slot[round & 1]);
-    if (tk >= n_tasks || stopped) break;
+    if (tk >= n_tasks) break;
     const LdsFlowTask tr = tasks[tk];
     int snext = tr.sn;
     SnMeta mnext = tr.m;
@@ -112,10 +114,10 @@ __global__ void __launch_bounds__(THREADS) k_solve_flow(FactorArgs<T> a, const L
   extern __shared__ __align__(16) unsigned char smem_raw[];
   __shared__ int ticket_slot[2];
   T *smem = reinterpret_cast<T *>(smem_raw);
-  const bool stopped = opt_stopped(a.err);   // as k_factor_flow
+  if (opt_stopped(a.err)) return;   // as k_factor_flow
   for (int round = 0;; round++) {
     const int tk = lds_flow_ticket(ticket, &ticket_slot[round & 1]);
-    if (tk >= n_tasks || stopped) break;
+    if (tk >= n_tasks) break;
     const LdsFlowTask tr = tasks[tk];
     if (tr.kind == 1) {
       big_gemv_unit<T, true>(a, tr.m, part, N, tr.slices, tr.bx, tr.by, smem);

@@ -1482,6 +1482,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     ga.v = gauge_v_.p;
     ga.ox = (S)gauge_ox_; ga.oy = (S)gauge_oy_;
     ga.mu_t = (T)gauge_mu_t_; ga.mu_r = (T)gauge_mu_r_;
+    ga.err = err_.p;
     hipLaunchKernelGGL((k_gauge_vectors<T, S>), dim3((ga.nc + 255) / 256), dim3(256), 0, stream_, ga);
     hipLaunchKernelGGL((k_big_gauge<T, S>), dim3(ga.nc), dim3(256), 0, stream_, ga);
     check_launch("k_big_gauge");
@@ -1767,7 +1768,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
         if (flow_levels_[si]) { if (e1 == 0) e0 = flow_levels_[si]->wfill_begin; e1 = flow_levels_[si]->wfill_end; }
       const int flag_wgs = (int)std::min<int64_t>(((int64_t)flow_flags_.n + 255) / 256, 256);
       hipLaunchKernelGGL(k_flow_reset<T>, dim3((unsigned)(flag_wgs + std::max(e1 - e0, 0))), dim3(256), 0, stream_, flow_flags_.p, (int64_t)flow_flags_.n, flag_wgs,
-                         winv_.p, flow_wfill_.p + 2 * e0, xnew_.p);
+                         winv_.p, flow_wfill_.p + 2 * e0, xnew_.p, (const int *)err_.p);
       check_launch("k_flow_reset");
     }
     if (lds_flow_ && from == 0 && to > 0) {
@@ -2284,7 +2285,10 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
       check_launch("k_opt_item");
       return;
     }
+    // (as Gauss-Newton's: behind the stop this linearisation publishes the skipped item, every launch behind it returns at its stop word)
+    opt_publish_ = 1;
     launch_linearize(0.0, 1, 1);   // lambda: OptCtrl::lambda
+    opt_publish_ = 0;
     launch_factor();
     launch_solve();
     launch_update(nullptr, 1.0, true);
@@ -2330,8 +2334,9 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
       }
     } scope{this};
     opt_active_ = true; opt_first_ = true; opt_lambda_dev_ = lm; opt_lambda0_ = 0.01;   // :254
-    // TWO whole items in the queue: the device never waits for the host, and the item behind the stop is a handful of empty
-    // launches behind its linearisation (which publishes the final chi2)
+    // TWO whole items in the queue: the device never waits for the host.  The item behind the stop is its linearisation (which
+    // publishes the final chi2: the call returns on that) and a handful of launches that read the stop word and nothing else
+    //  -- they are still on the stream when the call returns, and whatever is enqueued next runs behind them
     long enq = 0, seen = 0;   // items enqueued / consumed
     int ne = 0, dev_err = 0;
     bool stop_seen = false;

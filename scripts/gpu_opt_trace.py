@@ -1,5 +1,9 @@
 """Diagnostic: a few optimize(10) calls from the initial state (the shape bench.py's headline times), for
 `rocprofv3 --kernel-trace`; with an argument `analyse <csv>` prints the timeline of the last call.
+The timeline of a call: per iteration k_linearize, k_factor_flow, k_solve_flow, k_update back to back; behind the iteration
+that meets the stop rule one more k_linearize (its last workgroup publishes the final chi2, a few us longer than a working
+one) and three launches that return at the stop word (4 - 5 us each, the launch itself); the restart (k_copy_words16) and
+the next call's first k_linearize follow on the same stream.
 usage: gpu_opt_trace.py <dataset> <calls>   |   gpu_opt_trace.py analyse <kernel_trace.csv>"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
