@@ -135,7 +135,7 @@ int32_t rr_pgo_anchor_node(const rr_pgo *h);/* from-node of the first pose-pose 
 
 /* host copy of the parsed graph in rr_pgo_graph_desc packing (so a caller or a
  * test can hand the identical graph to another implementation).  Pointers stay
- * valid until rr_pgo_destroy. */
+ * valid until rr_pgo_destroy or the next rr_pgo_extend. */
 int rr_pgo_get_graph(const rr_pgo *h, rr_pgo_graph_desc *out);
 
 /* ---- the hot path -------------------------------------------------------- */
@@ -292,6 +292,47 @@ int rr_pgo_gate_joint(rr_pgo *h, int32_t n_cand,
                       double *d2_out, double *prefix_d2_out, double *innov_out, int64_t *innov_offset);
 /* ms[3]: HIP-event times of the last rr_pgo_gate_joint call -- linearise + factor, tree solve, joint kernel + copy. */
 int rr_pgo_gate_joint_times(const rr_pgo *h, double *ms);
+
+/* ---- growing a live handle (build-defined; the reference builds a new PoseGraph) --------
+ * Append n_new_nodes nodes and n_new_edges edges, in rr_pgo_graph_desc packing.  New nodes get the indices
+ * N .. N + n_new_nodes - 1 (N = rr_pgo_num_nodes before the call), new edges come after the existing ones; old node indices,
+ * old dx offsets, old edge indices and the anchor rule (from-node of the first pose-pose edge in edge order) stay as they are
+ * -- a graph that had no pose-pose edge takes its anchor from the first new one.  New edges may name any node below
+ * N + n_new_nodes.  node_id == NULL: id = index; an id that repeats an existing or another new id is RR_PGO_EINVAL.
+ * After the call the handle is the handle rr_pgo_create would return for the grown graph, with the handle's options and under
+ * the environment as it is AT THE CALL (the RR_PGO_* switches are read again): same symbolic analysis, launches,
+ * rr_pgo_get_stats and rr_pgo_get_graph -- except that its device state equals the old device state BIT FOR BIT for every old
+ * node (the poses are copied device to device into the new state buffer: no read-back, no atan2), while new nodes hold
+ * node_state, converted exactly as rr_pgo_set_state converts it.  rr_pgo_get_graph keeps showing the old nodes' initial
+ * values, as before the call.
+ * node_state == NULL with n_new_nodes > 0: the new nodes are initialised on the device.  The host plans steps from structure
+ * alone: the ready set starts as the old nodes; the new edges are scanned in order, again and again, until a scan adds no
+ * step; an edge with exactly one ready endpoint whose other endpoint is a new node not yet ready is a step when it determines
+ * that node -- to = from (+) z for every kind (SE2: X_to = X_from Z; SE2_XY: l = t + R z; SE3: X_to = X_from Z), from = to (+) z^-1
+ * for pose-pose edges only -- and makes it ready.  A new node no step reaches is RR_PGO_EINVAL (the message names it), decided
+ * before anything changes.  One kernel (k_guess_nodes) executes the steps in the state's arithmetic type, dependent steps in
+ * list order, (cos, sin) and quaternions renormalised; the guessed values of the new nodes are copied into the host graph
+ * (rr_pgo_get_graph shows them, the analysis sees what a fresh handle on that graph would).
+ * Carried over: the solver option; the robust kernel's kind and delta; its edge mask, extended with 1 for every new edge (a
+ * fresh closure is robustified; a NULL mask stays NULL).  NOT carried: captured graphs, the tree and selected-inverse tables of
+ * the queries, rr_pgo_set_state's memo of the previous state, the Levenberg-Marquardt lambda and the *_times of earlier calls;
+ * rr_pgo_stream may return another stream.  Pointers from an earlier rr_pgo_get_graph become invalid.
+ * Atomic: the new graph, analysis and engine are built completely and then swapped in; the old stream is synchronised before
+ * the old engine goes.  Any failure -- RR_PGO_EINVAL below, RR_PGO_ENOMEM, a HIP error (RR_PGO_ENODEVICE) -- leaves the handle
+ * as it was, usable, with the same bits.
+ * RR_PGO_EINVAL, decided before anything is launched, the message names the node or edge: negative counts, a null required
+ * pointer (node_id may be NULL, node_state may be NULL as above), everything rr_pgo_create rejects for the grown graph (bad
+ * kinds, a kind that does not fit its endpoints, a self loop, an unknown vertex, mixed 2-D / 3-D), duplicate ids, an
+ * unreachable node in guess mode.  n_new_nodes == 0 && n_new_edges == 0: RR_PGO_OK, nothing changes.
+ * RR_PGO_EUNSUPPORTED: sharded handles (the message says why).  RR_PGO_F32 / RR_PGO_MIXED handles and graphs with fronts beyond
+ * LDS are supported: the rebuild is rr_pgo_create's constructor. */
+int rr_pgo_extend(rr_pgo *h,
+                  int32_t n_new_nodes, const int32_t *node_kind, const uint32_t *node_id, const double *node_state,
+                  int32_t n_new_edges, const int32_t *edge_kind, const int32_t *edge_from, const int32_t *edge_to,
+                  const double *edge_meas, const double *edge_info);
+/* ms[3] of the last rr_pgo_extend call: symbolic analysis and engine construction (host wall clock), state carry + initial
+ * guess (HIP events). */
+int rr_pgo_extend_times(const rr_pgo *h, double *ms);
 
 /* ---- inspection of the assembled system (parity tests) ------------------- */
 

@@ -18,7 +18,13 @@
   --gate FILE  (example mode): after the optimisation, gate the candidate edges of FILE -- EDGE_SE2 / EDGE_SE2_XY /
       EDGE_SE3:QUAT lines in the loader's field order, between vertex ids of the loaded graph, not part of it -- and print
       one line per candidate: ids, Mahalanobis distance d2, e^T Omega e, accept / reject at the 0.95 chi-square quantile
-      (rr_pgo_gate_edges)
+      (rr_pgo_gate_edges).  With --accept the accepted candidates are then added to the live handle (rr_pgo_extend), the
+      optimisation runs again, and chi2 before and after is printed
+
+  --extend FILE  (example mode): after the optimisation, append the VERTEX_* / EDGE_* lines of FILE (the loader's tags and
+      field order; new vertices need ids the graph does not have, edges may join old and new vertices) to the live handle
+      (rr_pgo_extend), optimise again and print chi2 before and after.  With --guess the file's vertex values are ignored
+      and the new vertices are initialised on the device along the new edges
 
   --gate-joint FILE  (example mode): candidate lines as for --gate, plus lines `SET i j k ...` that name candidates by
       their 0-based order in the file; after the optimisation one line per set: members, D_s, joint Mahalanobis distance
@@ -141,6 +147,111 @@ def parse_gate_file(path, index, sets=None, flag="--gate"):
     return kind, a, b, meas, info, ids
 
 
+VERTEX_TAGS = {"VERTEX_SE2": 0, "VERTEX_XY": 1, "VERTEX_SE3:QUAT": 2}
+
+
+def parse_extend_file(path, index, n_nodes=None, flag="--extend"):
+    """An --extend file as (node_kind, node_id, node_state, edge_kind, from, to, meas, info) in rr_pgo_graph_desc packing.
+    `index` maps the g2o vertex ids of the live graph to node indices (n_nodes: their number, default len(index)); the
+    file's vertices get the indices behind them, in file order, and its edges may name old and new vertices, before or
+    after the vertex line.  Needs no device.  An unknown tag, a repeated id, a short line or an unknown vertex is a
+    SystemExit that names the line."""
+    from .mapping import GATE_INFO_LEN, GATE_MEAS_LEN
+    n_old = len(index) if n_nodes is None else n_nodes
+    index = dict(index)
+    nkind, nid, nstate, edges = [], [], [], []
+    with open(path) as f:
+        for no, line in enumerate(f, 1):
+            tok = line.split()
+            if not tok or tok[0].startswith("#"):
+                continue
+            if tok[0] in VERTEX_TAGS:
+                k = VERTEX_TAGS[tok[0]]
+                nv = GATE_MEAS_LEN[k]
+                try:
+                    i = int(tok[1])
+                    vals = [float(t) for t in tok[2:]]
+                except (ValueError, IndexError):
+                    raise SystemExit(f"{flag}: {path}:{no}: expected a vertex id and {nv} numbers after {tok[0]}")
+                if len(vals) != nv:
+                    raise SystemExit(f"{flag}: {path}:{no}: expected {nv} values after the id, got {len(vals)}")
+                if i < 0 or i in index:
+                    raise SystemExit(f"{flag}: {path}:{no}: vertex id {i} is negative or already in use")
+                index[i] = n_old + len(nkind)
+                nkind.append(k)
+                nid.append(i)
+                nstate.extend(vals)
+                continue
+            if tok[0] not in GATE_TAGS:
+                raise SystemExit(f"{flag}: {path}:{no}: unknown tag {tok[0]!r} (VERTEX_SE2, VERTEX_XY, VERTEX_SE3:QUAT, "
+                                 "EDGE_SE2, EDGE_SE2_XY or EDGE_SE3:QUAT)")
+            k = GATE_TAGS[tok[0]]
+            nm, ni = GATE_MEAS_LEN[k], GATE_INFO_LEN[k]
+            try:
+                i, j = int(tok[1]), int(tok[2])
+                vals = [float(t) for t in tok[3:]]
+            except (ValueError, IndexError):
+                raise SystemExit(f"{flag}: {path}:{no}: expected two vertex ids and {nm + ni} numbers after {tok[0]}")
+            if len(vals) != nm + ni:
+                raise SystemExit(f"{flag}: {path}:{no}: expected {nm + ni} values after the ids, got {len(vals)}")
+            edges.append((no, k, i, j, vals))
+    kind, a, b, meas, info = [], [], [], [], []
+    for no, k, i, j, vals in edges:   # (an edge may come before the vertex line it names)
+        for v in (i, j):
+            if v not in index:
+                raise SystemExit(f"{flag}: {path}:{no}: no vertex with id {v} in the graph or in the file")
+        kind.append(k)
+        a.append(index[i])
+        b.append(index[j])
+        meas.extend(vals[:GATE_MEAS_LEN[k]])
+        info.extend(vals[GATE_MEAS_LEN[k]:])
+    return nkind, nid, nstate, kind, a, b, meas, info
+
+
+def _node_index(g):
+    import ctypes as C
+
+    import numpy as np
+    from . import _lib
+    d = _lib.GraphDesc()
+    _lib.load().rr_pgo_get_graph(g._h, C.byref(d))
+    n = d.n_nodes
+    file_ids = np.ctypeslib.as_array(d.node_id, (n,)) if (n and d.node_id) else np.arange(n)
+    return {int(v): k for k, v in enumerate(file_ids)}
+
+
+def _reoptimize(g, what, iterations):
+    before = g.global_error()
+    errors = g.optimize(iterations)
+    print(f"{what}: {g.num_nodes} nodes, {g.num_edges} edges; chi2 before {before:.9g}, after {errors[-1]:.9g} "
+          f"({len(errors) - 1} iterations)")
+
+
+def accept_gated(g, path, iterations):
+    """--gate FILE --accept: the candidates the gate accepts join the live handle, then the optimisation runs again."""
+    import numpy as np
+    from .mapping import GATE_INFO_LEN, GATE_MEAS_LEN, gate_thresholds
+    kind, a, b, meas, info, ids = parse_gate_file(path, _node_index(g))
+    d2, _ = g.gate_edges(kind, a, b, meas, info)
+    keep = [c for c in range(len(kind)) if d2[c] <= gate_thresholds(kind)[c]]
+    if not keep:
+        print("--accept: no candidate passed the gate, the graph is unchanged")
+        return
+    mo = np.concatenate([[0], np.cumsum(np.take(GATE_MEAS_LEN, kind))]).astype(int)
+    io = np.concatenate([[0], np.cumsum(np.take(GATE_INFO_LEN, kind))]).astype(int)
+    g.extend([kind[c] for c in keep], [a[c] for c in keep], [b[c] for c in keep],
+             np.concatenate([meas[mo[c]:mo[c + 1]] for c in keep]), np.concatenate([info[io[c]:io[c + 1]] for c in keep]))
+    _reoptimize(g, f"--accept: {len(keep)} of {len(kind)} candidates added ({' '.join(f'{ids[c][0]}-{ids[c][1]}' for c in keep)})", iterations)
+
+
+def extend_from_file(g, path, guess, iterations):
+    nkind, nid, nstate, kind, a, b, meas, info = parse_extend_file(path, _node_index(g), g.num_nodes)
+    g.extend(kind, a, b, meas, info, node_kind=nkind if nkind else None,
+             node_state=None if (guess or not nkind) else nstate, node_id=nid if nkind else None)
+    how = " (initial values guessed on the device)" if guess and nkind else ""
+    _reoptimize(g, f"--extend: {len(nkind)} vertices{how} and {len(kind)} edges of {path} added", iterations)
+
+
 def parse_gate_joint_file(path, index):
     """A --gate-joint file: (kind, from, to, meas, info, ids, sets).  Candidate lines as in a --gate file; a line
     `SET i j k ...` names candidates by their 0-based order in the file (before or after the line).  Needs no device.
@@ -217,9 +328,19 @@ def main(argv=None):
                     help="after the optimisation print the joint covariance of these g2o vertex ids (any nodes)")
     ap.add_argument("--gate", metavar="FILE", default=None,
                     help="after the optimisation gate the candidate EDGE_* lines of FILE: d2, e^T Omega e, accept / reject")
+    ap.add_argument("--accept", action="store_true",
+                    help="with --gate: add the accepted candidates to the live handle, optimise again, print chi2 before and after")
+    ap.add_argument("--extend", metavar="FILE", default=None,
+                    help="after the optimisation append the VERTEX_* / EDGE_* lines of FILE to the live handle and optimise again")
+    ap.add_argument("--guess", action="store_true",
+                    help="with --extend: ignore the file's vertex values, initialise the new vertices on the device")
     ap.add_argument("--gate-joint", metavar="FILE", default=None,
                     help="after the optimisation gate the SET lines of FILE jointly: D_s, d2, threshold, accept / reject, prefixes")
     a = ap.parse_args(argv)
+    if a.accept and not a.gate:
+        ap.error("--accept needs --gate FILE")
+    if a.guess and not a.extend:
+        ap.error("--guess needs --extend FILE")
     solver = PoseGraphSolver[a.solver]
 
     def new():
@@ -241,6 +362,10 @@ def main(argv=None):
             print_gate(g, a.gate)
         if a.gate_joint:
             print_gate_joint(g, a.gate_joint)
+        if a.gate and a.accept:
+            accept_gated(g, a.gate, 50 if a.iterations is None else a.iterations)
+        if a.extend:
+            extend_from_file(g, a.extend, a.guess, 50 if a.iterations is None else a.iterations)
         return 0
     iters = 10 if a.iterations is None else a.iterations
     new().optimize(iters, False, False)   # warm-up: library load, HIP context

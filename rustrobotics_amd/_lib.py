@@ -35,6 +35,7 @@ EXPORTS = (
     "rr_pgo_node_owner", "rr_pgo_trim", "rr_pgo_set_robust_kernel", "rr_pgo_edge_errors", "rr_pgo_solve_form",
     "rr_pgo_marginals", "rr_pgo_marginals_times", "rr_pgo_covariances", "rr_pgo_covariances_times",
     "rr_pgo_gate_edges", "rr_pgo_gate_times", "rr_pgo_gate_joint", "rr_pgo_gate_joint_times",
+    "rr_pgo_extend", "rr_pgo_extend_times",
 )
 
 
@@ -142,6 +143,8 @@ def load():
     L.rr_pgo_gate_times.argtypes = [vp, dp]
     L.rr_pgo_gate_joint.argtypes = [vp, C.c_int32, ip, ip, ip, dp, dp, C.c_int32, ip, ip, dp, dp, dp, C.POINTER(C.c_int64)]
     L.rr_pgo_gate_joint_times.argtypes = [vp, dp]
+    L.rr_pgo_extend.argtypes = [vp, C.c_int32, ip, C.POINTER(C.c_uint32), dp, C.c_int32, ip, ip, ip, dp, dp]
+    L.rr_pgo_extend_times.argtypes = [vp, dp]
     if L.rr_pgo_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH} speaks ABI version {L.rr_pgo_abi_version()}, this mirror {ABI_VERSION}: rebuild the library")
     _lib = L

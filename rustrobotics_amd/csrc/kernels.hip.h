@@ -1173,6 +1173,65 @@ template <typename TC> __global__ void __launch_bounds__(256) k_edge_errors(Edge
   if (a.w_out) a.w_out[k] = (double)wt;
 }
 
+// rr_pgo_extend without node_state: initial values of appended nodes, composed on the device from a pose that is already
+// known and an edge's measurement.  A step gives node `dst` from node `src`:
+//   GUESS_SE2      X_dst = X_src Z           GUESS_SE2_INV   X_dst = X_src Z^-1
+//   GUESS_XY       l_dst = t_src + R_src z
+//   GUESS_SE3      X_dst = X_src Z           GUESS_SE3_INV   X_dst = X_src Z^-1
+// Every step has at most one earlier step it depends on (the one that produced its source), so the steps form trees; the
+// host lays them out tree by tree, list order kept within a tree, and ONE THREAD walks one tree: no hand-off between
+// threads, no atomics, the same bits under every schedule.  (cos, sin) and quaternions are renormalised, in TC.
+enum { GUESS_SE2 = 0, GUESS_SE2_INV = 1, GUESS_XY = 2, GUESS_SE3 = 3, GUESS_SE3_INV = 4 };
+template <typename TC> struct GuessStep {
+  int32_t src, dst, op, pad;
+  typename VecT<TC>::V4 m0, m1;   // SE(2): (x, y, cos, sin), -- ; landmark: (x, y, 0, 0), -- ; SE(3): (t, 0), unit q
+};
+template <typename TC>
+__global__ void __launch_bounds__(64) k_guess_nodes(typename VecT<TC>::V4 *pose, int n_pose_nodes, int is3d, const GuessStep<TC> *steps,
+                                                    const int32_t *tree_ptr, int n_trees) {
+  using V4 = typename VecT<TC>::V4;
+  const int tree = blockIdx.x * 64 + threadIdx.x;
+  if (tree >= n_trees) return;
+  for (int k = tree_ptr[tree]; k < tree_ptr[tree + 1]; k++) {
+    const GuessStep<TC> st = steps[k];
+    if ((unsigned)st.src >= (unsigned)n_pose_nodes || (unsigned)st.dst >= (unsigned)n_pose_nodes) continue;   // (the host checked: never taken)
+    if (!is3d) {
+      const V4 p = pose[st.src], z = st.m0;
+      if (st.op == GUESS_XY) {
+        pose[st.dst] = V4{p.x + (p.z * z.x - p.w * z.y), p.y + (p.w * z.x + p.z * z.y), (TC)0, (TC)0};
+      } else if (st.op == GUESS_SE2) {
+        TC c = p.z * z.z - p.w * z.w, s = p.w * z.z + p.z * z.w;
+        const TC n = sqrt(c * c + s * s);
+        c /= n; s /= n;
+        pose[st.dst] = V4{p.x + (p.z * z.x - p.w * z.y), p.y + (p.w * z.x + p.z * z.y), c, s};
+      } else {   // X_src Z^-1: R = R_src R_z^T, t = t_src - R z_t
+        TC c = p.z * z.z + p.w * z.w, s = p.w * z.z - p.z * z.w;
+        const TC n = sqrt(c * c + s * s);
+        c /= n; s /= n;
+        pose[st.dst] = V4{p.x - (c * z.x - s * z.y), p.y - (s * z.x + c * z.y), c, s};
+      }
+    } else {
+      const V4 pt = pose[2 * st.src], pq = pose[2 * st.src + 1];
+      const TC t[3] = {pt.x, pt.y, pt.z}, q[4] = {pq.x, pq.y, pq.z, pq.w};
+      const TC zt[3] = {st.m0.x, st.m0.y, st.m0.z};
+      const TC sg = st.op == GUESS_SE3_INV ? (TC)-1 : (TC)1;
+      const TC zq[4] = {sg * st.m1.x, sg * st.m1.y, sg * st.m1.z, st.m1.w};   // the conjugate for Z^-1
+      TC r[4], d[3];
+      q_mul<TC>(q, zq, r);
+      const TC n = sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2] + r[3] * r[3]);
+      r[0] /= n; r[1] /= n; r[2] /= n; r[3] /= n;
+      if (st.op == GUESS_SE3_INV) {   // t = t_src - R_dst z_t
+        q_rot<TC>(r, zt, d);
+        d[0] = -d[0]; d[1] = -d[1]; d[2] = -d[2];
+      } else {
+        q_rot<TC>(q, zt, d);
+      }
+      pose[2 * st.dst] = V4{t[0] + d[0], t[1] + d[1], t[2] + d[2], (TC)0};
+      pose[2 * st.dst + 1] = V4{r[0], r[1], r[2], r[3]};
+    }
+  }
+}
+
 template <typename T, typename TC = T> struct UpdArgs3 {
   int n_nodes;
   typename VecT<TC>::V4 *pose;

@@ -21,6 +21,7 @@
 #include <stdexcept>
 #include <string>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 #include "../../include/rr_pgo.h"
@@ -236,6 +237,9 @@ static double now_ms() {
   return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
 }
 
+// one step of rr_pgo_extend's initial guess as the host plans it: node dst from node src and a measurement (graph packing)
+struct HostGuessStep { int32_t src, dst, op; double m[7]; };
+
 struct EngineBase {
   virtual ~EngineBase() = default;
   virtual void chi2(double *out) = 0;
@@ -279,6 +283,17 @@ struct EngineBase {
   virtual void gate_joint(int n_sets, const int32_t *set_ptr, const int32_t *from, const int32_t *to, const int32_t *dim,
                           const int64_t *ioff, std::vector<GateCand> &cand, double *d2, double *prefix, double *innov) = 0;
   virtual void gate_joint_times(double *ms) const = 0;
+  // rr_pgo_extend (arguments checked).  The state buffer is in node order, so a grown graph's buffer starts with the old one.
+  virtual const void *pose_dev() const = 0;
+  virtual size_t pose_node_bytes() const = 0;   // bytes of one node in the state buffer
+  // initial values of the nodes n_old .. n_total - 1: the old state and the steps' results in a staging buffer of this engine
+  // (guess_dev), made on its stream; new_state_out: the new nodes in rr_pgo_get_state's packing; *ms: HIP-event time
+  virtual void guess_nodes(const std::vector<HostGuessStep> &steps, const std::vector<int32_t> &tree_ptr, int n_old, int n_total,
+                           bool is3d, const int32_t *new_kind, double *new_state_out, double *ms) = 0;
+  virtual const void *guess_dev() const = 0;
+  // the first n_nodes nodes of the state from src (device memory of the same arithmetic type), on this engine's stream; waits
+  virtual void adopt_state(const void *src, size_t n_nodes, double *ms) = 0;
+  virtual void robust_setting(int *kind, double *delta, bool *masked, std::vector<int32_t> &mask) const = 0;
   int n_launches_per_iter = 0;
 };
 
@@ -505,6 +520,8 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   int robust_kind_ = ROBUST_NONE;
   double robust_delta_ = 1.0;
   DevBuf<uint8_t> robust_mask_;
+  std::vector<uint8_t> robust_mask_host_;
+  DevBuf<V4> guess_stage_;           // rr_pgo_extend's initial guess: the old state and the new nodes behind it (made by that call)
   int host_counter_ = 0;             // mirrors the device slot counter
 
  public:
@@ -2431,6 +2448,96 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     restore_saved_state();
   }
 
+  // ---- rr_pgo_extend
+  const void *pose_dev() const override { return pose_.p; }
+  size_t pose_node_bytes() const override { return (is3d_ ? 2 : 1) * sizeof(V4); }
+  const void *guess_dev() const override { return guess_stage_.p; }
+  void copy_words16(const void *src, void *dst, size_t bytes) {
+    const int64_t n16 = (int64_t)(bytes / 16);
+    if (n16 == 0) return;
+    hipLaunchKernelGGL(k_copy_words16, dim3((unsigned)std::min<int64_t>((n16 + 255) / 256, 1024)), dim3(256), 0, stream_,
+                       reinterpret_cast<const uint4 *>(src), reinterpret_cast<uint4 *>(dst), n16);
+    check_launch("k_copy_words16");
+  }
+  void guess_nodes(const std::vector<HostGuessStep> &steps, const std::vector<int32_t> &tree_ptr, int n_old, int n_total, bool is3d,
+                   const int32_t *new_kind, double *out, double *ms) override {
+    const size_t per = is3d ? 2 : 1;
+    if (n_old > 0 && is3d != is3d_) throw ApiError(RR_PGO_EINVAL, "internal: 2-D / 3-D form of the guess");
+    std::vector<GuessStep<S>> ds(steps.size());
+    for (size_t k = 0; k < steps.size(); k++) {
+      const HostGuessStep &h = steps[k];
+      if (h.src < 0 || h.src >= n_total || h.dst < n_old || h.dst >= n_total) throw ApiError(RR_PGO_EINVAL, "internal: guess step out of range");
+      GuessStep<S> &d = ds[k];
+      d.src = h.src; d.dst = h.dst; d.op = h.op; d.pad = 0;
+      // (measurements converted as the constructor converts an edge's)
+      if (h.op == GUESS_SE3 || h.op == GUESS_SE3_INV) {
+        const double n = std::sqrt(h.m[3] * h.m[3] + h.m[4] * h.m[4] + h.m[5] * h.m[5] + h.m[6] * h.m[6]);
+        d.m0 = V4{(S)h.m[0], (S)h.m[1], (S)h.m[2], (S)0};
+        d.m1 = V4{(S)(h.m[3] / n), (S)(h.m[4] / n), (S)(h.m[5] / n), (S)(h.m[6] / n)};
+      } else if (h.op == GUESS_XY) {
+        d.m0 = V4{(S)h.m[0], (S)h.m[1], (S)0, (S)0};
+        d.m1 = V4{(S)0, (S)0, (S)0, (S)0};
+      } else {
+        d.m0 = V4{(S)h.m[0], (S)h.m[1], (S)std::cos(h.m[2]), (S)std::sin(h.m[2])};
+        d.m1 = V4{(S)0, (S)0, (S)0, (S)0};
+      }
+    }
+    const int n_trees = (int)tree_ptr.size() - 1;
+    DevBuf<GuessStep<S>> dsteps;   // (no arena outside the constructor: buffers of their own, freed on return)
+    DevBuf<int32_t> dtree;
+    guess_stage_.alloc(per * (size_t)n_total);
+    HIPCHK(hipMemsetAsync(guess_stage_.p, 0, guess_stage_.n * sizeof(V4), stream_));
+    dsteps.alloc(ds.size());
+    dtree.alloc(tree_ptr.size());
+    EventHolder ev0, ev1;
+    ev0.create(hipEventDefault);
+    ev1.create(hipEventDefault);
+    HIPCHK(hipMemcpyAsync(dsteps.p, ds.data(), ds.size() * sizeof(GuessStep<S>), hipMemcpyHostToDevice, stream_));
+    HIPCHK(hipMemcpyAsync(dtree.p, tree_ptr.data(), tree_ptr.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
+    HIPCHK(hipEventRecord(ev0, stream_));
+    copy_words16(pose_.p, guess_stage_.p, per * (size_t)n_old * sizeof(V4));
+    hipLaunchKernelGGL((k_guess_nodes<S>), dim3((unsigned)((n_trees + 63) / 64)), dim3(64), 0, stream_, guess_stage_.p, n_total, is3d ? 1 : 0,
+                       dsteps.p, dtree.p, n_trees);
+    check_launch("k_guess_nodes");
+    HIPCHK(hipEventRecord(ev1, stream_));
+    std::vector<V4> pose(per * (size_t)(n_total - n_old));
+    HIPCHK(hipMemcpyAsync(pose.data(), guess_stage_.p + per * (size_t)n_old, pose.size() * sizeof(V4), hipMemcpyDeviceToHost, stream_));
+    HIPCHK(hipStreamSynchronize(stream_));
+    float t = 0;
+    HIPCHK(hipEventElapsedTime(&t, ev0, ev1));
+    *ms = t;
+    for (int i = 0; i < n_total - n_old; i++) {   // as get_state
+      if (is3d) {
+        const V4 &tt = pose[2 * i], &q = pose[2 * i + 1];
+        *out++ = (double)tt.x; *out++ = (double)tt.y; *out++ = (double)tt.z;
+        *out++ = (double)q.x; *out++ = (double)q.y; *out++ = (double)q.z; *out++ = (double)q.w;
+        continue;
+      }
+      *out++ = (double)pose[i].x;
+      *out++ = (double)pose[i].y;
+      if (new_kind[i] == NODE_SE2) *out++ = std::atan2((double)pose[i].w, (double)pose[i].z);
+    }
+  }
+  void adopt_state(const void *src, size_t n_nodes, double *ms) override {
+    if (n_nodes > (size_t)g_.n_nodes()) throw ApiError(RR_PGO_EINVAL, "internal: more nodes adopted than the graph has");
+    EventHolder ev0, ev1;
+    ev0.create(hipEventDefault);
+    ev1.create(hipEventDefault);
+    HIPCHK(hipEventRecord(ev0, stream_));
+    copy_words16(src, pose_.p, n_nodes * pose_node_bytes());
+    HIPCHK(hipEventRecord(ev1, stream_));
+    HIPCHK(hipStreamSynchronize(stream_));
+    float t = 0;
+    HIPCHK(hipEventElapsedTime(&t, ev0, ev1));
+    *ms = t;
+  }
+  void robust_setting(int *kind, double *delta, bool *masked, std::vector<int32_t> &mask) const override {
+    *kind = robust_kind_;
+    *delta = robust_delta_;
+    *masked = !robust_mask_host_.empty();
+    mask.assign(robust_mask_host_.begin(), robust_mask_host_.end());
+  }
+
   void assemble(double lambda, int lm, std::vector<double> &hv, std::vector<double> &b) override {
     refuse_rank_partial("rr_pgo_assemble");
     launch_linearize(lambda, lm, 1, true);   // always the reference's system (anchor prior), whatever the factor's gauge
@@ -2621,6 +2728,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     }
     HIPCHK(hipStreamSynchronize(stream_));   // launches already enqueued read the old mask
     robust_mask_.upload(m);                  // (empty: freed, every edge)
+    robust_mask_host_ = m;                   // (rr_pgo_extend carries the setting to the grown graph's engine)
     robust_kind_ = kind;
     robust_delta_ = kind != ROBUST_NONE ? delta : 1.0;
     // the captured graphs hold the old kernel and its arguments
@@ -3331,7 +3439,8 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
 using namespace rrpgo;
 
 struct rr_pgo {
-  HostGraph g;
+  // behind a pointer: the engine keeps a reference to the graph, and rr_pgo_extend swaps graph, analysis and engine together
+  std::unique_ptr<HostGraph> g = std::make_unique<HostGraph>();
   std::shared_ptr<const Symbolic> symp;   // shared with the analysis cache (structurally identical graphs analysed once)
   const Symbolic &sym_ref() const { return *symp; }
   rr_pgo_options opt;
@@ -3339,6 +3448,7 @@ struct rr_pgo {
   rr_pgo_stats stats;
   std::vector<int32_t> blk_rows, blk_cols;   // assemble() block list
   std::vector<int64_t> blk_offs;
+  double extend_ms[3] = {0, 0, 0};   // the last rr_pgo_extend: analysis, engine (host wall clock), state carry + guess (HIP events)
 };
 
 struct rr_pgo_synth {
@@ -3449,13 +3559,13 @@ void analyze_handle(std::unique_ptr<rr_pgo> &h, const rr_pgo_options *opt_in, do
   // fp32 6.05 ms per step with 48, 6.09 with 40, 6.12 with 56, 6.21 with 64; fp64 -- half the LDS budget per front --
   // 9.78 with 32, 10.41 with 48 or 64)
   const int big_leaf = opt.precision == RR_PGO_F64 ? 32 : 48;
-  so.nd_leaf = h->g.n_nodes() <= 6000 ? (1 << 30) : big_leaf;
-  so.split_separators = h->g.n_nodes() > 6000;   // wide top fronts: see symbolic.cpp, supernode pass
+  so.nd_leaf = h->g->n_nodes() <= 6000 ? (1 << 30) : big_leaf;
+  so.split_separators = h->g->n_nodes() > 6000;   // wide top fronts: see symbolic.cpp, supernode pass
   if (opt.world_size > 1) {   // sharding needs the nested-dissection top levels
     so.n_parts = opt.world_size;
     so.my_part = opt.rank;
     so.nd_leaf = big_leaf;
-    so.pin_node = h->g.anchor_node;   // every rank needs the anchor's entries of the solution (gauge transfer)
+    so.pin_node = h->g->anchor_node;   // every rank needs the anchor's entries of the solution (gauge transfer)
   }
   // tuning knobs of the symbolic phase
   // graphs whose fronts all fit LDS: ONE dataflow launch for the factorisation, one for the back substitution (lds_flow.hip.h);
@@ -3466,7 +3576,7 @@ void analyze_handle(std::unique_ptr<rr_pgo> &h, const rr_pgo_options *opt_in, do
   if (std::getenv("RR_PGO_NO_GEO")) so.geo_nd = false;
   // small graphs (trajectories with loop closures): the multilevel bisection finds narrower separators (intel: 97 -> 60 nodes along the heaviest root path) than the
   // level sets / coordinate cuts (symbolic.cpp, MultilevelBisection); the lattice's straight cuts are already the best there are
-  so.ml_nd = h->g.n_nodes() <= 6000;
+  so.ml_nd = h->g->n_nodes() <= 6000;
   if (const char *e = std::getenv("RR_PGO_ML_ND")) so.ml_nd = std::atoi(e) != 0;
   if (const char *e = std::getenv("RR_PGO_LDS_PIECES")) so.max_lds_pieces = std::max(1, std::atoi(e));
   // RR_PGO_JOIN_SEPARATORS=1: a region's last separator always chained into its parent separator's supernode; =0: never (small graphs:
@@ -3478,7 +3588,7 @@ void analyze_handle(std::unique_ptr<rr_pgo> &h, const rr_pgo_options *opt_in, do
   // the widest front the chain pass may merge into its parent (when the cost model says the parent finishes earlier): 80 pivot
   // columns for 2D graphs, 48 for 6 x 6 blocks -- re-measured on the r05 / r06 trees (profiles/r06_chain_cap_sweep.txt: intel + 3.1 %,
   // M3500 - 0.3 %, dlr + 0.0 % at 80; the SE(3) graphs lose 0.4 - 2 % beyond 48, where the model's error grows with the front)
-  if (!h->g.has_se3) so.merge_chain_nc = 80;
+  if (!h->g->has_se3) so.merge_chain_nc = 80;
   if (const char *e = std::getenv("RR_PGO_MERGE_CHAIN")) { so.merge_chain_nc = std::atoi(e); if (const char *c = std::strchr(e, ',')) so.merge_chain_gain_us = std::atof(c + 1); }
   if (const char *e = std::getenv("RR_PGO_AMALG_NP")) so.amalg_np = std::atoi(e);
   double t0 = now_ms();
@@ -3487,13 +3597,13 @@ void analyze_handle(std::unique_ptr<rr_pgo> &h, const rr_pgo_options *opt_in, do
   // and the switches above -- not of the measurements.  A caller that builds the same graph again (the reference's own bench is a
   // loop of PoseGraph::new(file) + optimize(10), benches/graph_slam.rs:9-10; UMFPACK users keep the symbolic object for the same
   // reason) gets the tables of the first analysis.  RR_PGO_ANALYSIS_CACHE=0: every handle is analysed afresh.
-  const uint64_t cache_key = analysis_cache_key(h->g, opt);
+  const uint64_t cache_key = analysis_cache_key(*h->g, opt);
   if (cache_key != 0)
-    if (std::shared_ptr<const Symbolic> hit = analysis_cache_find(cache_key, h->g, opt)) h->symp = hit;
+    if (std::shared_ptr<const Symbolic> hit = analysis_cache_find(cache_key, *h->g, opt)) h->symp = hit;
   Symbolic fresh;
   if (h->symp) {
   } else
-  if (h->g.n_nodes() <= 6000 && opt.world_size <= 1 && !opt.sharded && !(std::getenv("RR_PGO_ND_LEAF") && std::getenv("RR_PGO_AMALG_NP"))) {
+  if (h->g->n_nodes() <= 6000 && opt.world_size <= 1 && !opt.sharded && !(std::getenv("RR_PGO_ND_LEAF") && std::getenv("RR_PGO_AMALG_NP"))) {
     // Small graphs are bound by the critical path through the supernode tree, not by flops: a few
     // nested-dissection cuts above minimum-degree leaves shorten that path on the larger ones (M3500, dlr,
     // sphere2500: +20..26 % measured) and lengthen it on intel; merging mid-sized fronts (relaxed amalgamation up to 72
@@ -3510,17 +3620,17 @@ void analyze_handle(std::unique_ptr<rr_pgo> &h, const rr_pgo_options *opt_in, do
     for (int li = 0; li < 6; li++) {
       int leaf = so.ml_nd ? kLeafMultilevel[li] : kLeafLevelSets[li];
       if (std::getenv("RR_PGO_ND_LEAF")) { if (leaf != (1 << 30)) continue; leaf = so.nd_leaf; }
-      else if (leaf != (1 << 30) && ((!so.ml_nd && h->g.n_nodes() < 2400) || leaf >= h->g.n_nodes())) continue;   // (a leaf size >= the graph is no cut at all)
+      else if (leaf != (1 << 30) && ((!so.ml_nd && h->g->n_nodes() < 2400) || leaf >= h->g->n_nodes())) continue;   // (a leaf size >= the graph is no cut at all)
       // (with the multilevel bisection the undissected tree lost on every graph of 1000+ nodes by 30 - 60 % of the estimate, and its
       // minimum-degree pass over the whole graph is the slowest of the candidate analyses: 5.8 ms on dlr)
-      if (so.ml_nd && leaf == (1 << 30) && h->g.n_nodes() >= 1000 && !std::getenv("RR_PGO_ND_LEAF")) continue;
+      if (so.ml_nd && leaf == (1 << 30) && h->g->n_nodes() >= 1000 && !std::getenv("RR_PGO_ND_LEAF")) continue;
       cl.push_back({leaf, np_fixed ? so.amalg_np : 16, so.split_separators});   // the narrow rule first: it wins wherever every front lives in LDS
     }
     const size_t n_depths = cl.size();
     // the deepest dissections once more with mid-sized fronts merged up to 32 columns (intel, r05: the model's and the measured best)
     if (so.ml_nd && !np_fixed && !std::getenv("RR_PGO_ND_LEAF"))
       for (int leaf : {70, 50})
-        if (leaf < h->g.n_nodes()) cl.push_back({leaf, 32, so.split_separators});
+        if (leaf < h->g->n_nodes()) cl.push_back({leaf, 32, so.split_separators});
     // ... and the deeper dissections with a region's last separator NOT chained into its parent separator's supernode (the rule of the
     // large graphs, symbolic.cpp step 4): the sibling separator then runs beside it instead of before it.  Measured (r05, same kernels):
     // sphere2500 1539 -> 1697 it/s, torus3D 1066 -> 1191, dlr 7369 -> 7852, intel 7382 -> 6962 -- and the estimates say so beforehand
@@ -3528,7 +3638,7 @@ void analyze_handle(std::unique_ptr<rr_pgo> &h, const rr_pgo_options *opt_in, do
     const bool split_free = so.ml_nd && !join_env && !std::getenv("RR_PGO_ND_LEAF");
     if (split_free)
       for (int leaf : {100, 70, 50})
-        if (leaf < h->g.n_nodes()) cl.push_back({leaf, np_fixed ? so.amalg_np : 16, true});
+        if (leaf < h->g->n_nodes()) cl.push_back({leaf, np_fixed ? so.amalg_np : 16, true});
     Symbolic best;
     double best_crit = -1.0;
     int best_leaf = 0;
@@ -3542,7 +3652,7 @@ void analyze_handle(std::unique_ptr<rr_pgo> &h, const rr_pgo_options *opt_in, do
       for (const Cand &c : cl) o.nd_leaf = std::min(o.nd_leaf, c.leaf);
       o.nd_record = &splits;
       const double td = now_ms();
-      err = dissect_only(h->g, o);
+      err = dissect_only(*h->g, o);
       shared_splits = err.empty();
       if (std::getenv("RR_PGO_ANALYZE_TIMES")) std::fprintf(stderr, "analyze: shared dissection down to %d nodes: %.3f ms (%zu splits)\n", o.nd_leaf, now_ms() - td, splits.map.size());
     }
@@ -3556,7 +3666,7 @@ void analyze_handle(std::unique_ptr<rr_pgo> &h, const rr_pgo_options *opt_in, do
         o.amalg_np = list[c].np;
         o.split_separators = list[c].split;
         if (shared_splits) o.nd_replay = &splits;
-        try { errs[c] = analyze(h->g, o, cands[c]); } catch (const std::exception &e) { errs[c] = e.what(); }
+        try { errs[c] = analyze(*h->g, o, cands[c]); } catch (const std::exception &e) { errs[c] = e.what(); }
       });
       for (size_t c = 0; c < list.size(); c++) {
         if (!errs[c].empty()) { err = errs[c]; return; }
@@ -3584,14 +3694,14 @@ void analyze_handle(std::unique_ptr<rr_pgo> &h, const rr_pgo_options *opt_in, do
     (void)best_leaf;
     if (err.empty()) fresh = std::move(best);
   } else {
-    err = analyze(h->g, so, fresh);
+    err = analyze(*h->g, so, fresh);
     if (err.empty() && std::getenv("RR_PGO_ANALYZE_TIMES"))
       std::fprintf(stderr, "analyze: estimated critical path %.1f us (%d big fronts, %d supernodes)\n", fresh.est_critical_us, fresh.n_big, fresh.S);
   }
   if (!err.empty()) throw ApiError(RR_PGO_EINVAL, err);
   if (!h->symp) {
     h->symp = std::make_shared<const Symbolic>(std::move(fresh));
-    if (cache_key != 0) analysis_cache_store(cache_key, h->g, opt, h->symp);
+    if (cache_key != 0) analysis_cache_store(cache_key, *h->g, opt, h->symp);
   }
   double t1 = now_ms();
   rr_pgo_stats &s = h->stats;
@@ -3599,7 +3709,7 @@ void analyze_handle(std::unique_ptr<rr_pgo> &h, const rr_pgo_options *opt_in, do
   const Symbolic &y = h->sym_ref();
   const double sz = opt.precision == RR_PGO_F64 ? 8.0 : 4.0;
   int64_t diag_elems = 0, off_elems = 0;
-  for (int i = 0; i < y.N; i++) { int d = node_dim(h->g.node_kind[i]); diag_elems += d * d; }
+  for (int i = 0; i < y.N; i++) { int d = node_dim(h->g->node_kind[i]); diag_elems += d * d; }
   off_elems = y.n_hvals - diag_elems;
   s.nnz_h_blocks = y.N + y.n_offblocks;
   s.nnz_l_scalars = y.l_elems;
@@ -3619,8 +3729,8 @@ void analyze_handle(std::unique_ptr<rr_pgo> &h, const rr_pgo_options *opt_in, do
   // its whole M x M square in place (stored_factor_bytes; 2.2 x the nonzeros on the 1M-edge lattice)
   const double dim = y.dim;
   double edge_stream = 0;
-  for (int k = 0; k < h->g.n_edges(); k++)
-    edge_stream += 8.0 + sz * (edge_meas_len(h->g.edge_kind[k]) + edge_info_len(h->g.edge_kind[k]));
+  for (int k = 0; k < h->g->n_edges(); k++)
+    edge_stream += 8.0 + sz * (edge_meas_len(h->g->edge_kind[k]) + edge_info_len(h->g->edge_kind[k]));
   s.bytes_linearize = edge_stream + dim * sz /*poses*/ + (diag_elems + off_elems) * sz + dim * sz;
   s.bytes_chi2 = 0;  // fused into the linearisation pass
   s.bytes_factor = (diag_elems + off_elems) * sz + (double)y.nnz_l_entries * sz;
@@ -3629,8 +3739,14 @@ void analyze_handle(std::unique_ptr<rr_pgo> &h, const rr_pgo_options *opt_in, do
   s.stored_factor_bytes = (double)y.l_elems * sz;
 }
 
+void build_engine(std::unique_ptr<rr_pgo> &h);
 void build_handle(std::unique_ptr<rr_pgo> &h, const rr_pgo_options *opt_in, double parse_ms) {
   analyze_handle(h, opt_in, parse_ms);
+  build_engine(h);
+}
+
+// device part of PoseGraph::new: the engine of an analysed handle, the statistics that need it
+void build_engine(std::unique_ptr<rr_pgo> &h) {
   const rr_pgo_options opt = h->opt;
   // device
   int ndev = 0;
@@ -3642,9 +3758,9 @@ void build_handle(std::unique_ptr<rr_pgo> &h, const rr_pgo_options *opt_in, doub
   }
   const int wr = opt.world_size > 1 ? opt.rank : 0, ww = opt.world_size > 1 ? opt.world_size : 1;
   const bool shd = opt.sharded != 0;
-  if (opt.precision == RR_PGO_F64) h->engine = std::make_unique<Engine<double>>(h->g, h->sym_ref(), wr, ww, shd);
-  else if (opt.precision == RR_PGO_F32) h->engine = std::make_unique<Engine<float>>(h->g, h->sym_ref(), wr, ww, shd);
-  else h->engine = std::make_unique<Engine<float, double>>(h->g, h->sym_ref(), wr, ww, shd);
+  if (opt.precision == RR_PGO_F64) h->engine = std::make_unique<Engine<double>>(*h->g, h->sym_ref(), wr, ww, shd);
+  else if (opt.precision == RR_PGO_F32) h->engine = std::make_unique<Engine<float>>(*h->g, h->sym_ref(), wr, ww, shd);
+  else h->engine = std::make_unique<Engine<float, double>>(*h->g, h->sym_ref(), wr, ww, shd);
   // stats
   rr_pgo_stats &s = h->stats;
   const Symbolic &y = h->sym_ref();
@@ -3674,9 +3790,183 @@ void build_handle(std::unique_ptr<rr_pgo> &h, const rr_pgo_options *opt_in, doub
   s.big_flow_flops = bflow;
 }
 
+
+// ---- rr_pgo_extend: the steps of the initial guess, from structure alone (include/rr_pgo.h).  The ready set starts as the old
+// nodes; the new edges are scanned in order until a scan adds nothing.  Returns the first new node no step reaches, -1 if none.
+static int plan_guess_steps(const HostGraph &g, int n_old, int e_old, std::vector<HostGuessStep> &steps, std::vector<int32_t> &tree_ptr) {
+  const int N = g.n_nodes(), E = g.n_edges();
+  std::vector<char> ready((size_t)N, 0);
+  std::vector<int32_t> tree_of((size_t)N, -1), step_tree;
+  for (int i = 0; i < n_old; i++) ready[i] = 1;
+  int n_trees = 0;
+  for (bool added = true; added;) {
+    added = false;
+    for (int k = e_old; k < E; k++) {
+      const int f = g.edge_from[k], t = g.edge_to[k], ek = g.edge_kind[k];
+      int src, dst, op;
+      if (ready[f] && !ready[t] && t >= n_old) {
+        src = f; dst = t;
+        op = ek == EDGE_SE2 ? GUESS_SE2 : ek == EDGE_SE2_XY ? GUESS_XY : GUESS_SE3;
+      } else if (ready[t] && !ready[f] && f >= n_old && ek != EDGE_SE2_XY) {   // (a landmark does not determine the pose that saw it)
+        src = t; dst = f;
+        op = ek == EDGE_SE2 ? GUESS_SE2_INV : GUESS_SE3_INV;
+      } else {
+        continue;
+      }
+      HostGuessStep st{};
+      st.src = src; st.dst = dst; st.op = op;
+      const double *m = &g.edge_meas[g.edge_meas_off[k]];
+      for (int q = 0; q < edge_meas_len(ek); q++) st.m[q] = m[q];
+      steps.push_back(st);
+      tree_of[dst] = src < n_old ? n_trees++ : tree_of[src];
+      step_tree.push_back(tree_of[dst]);
+      ready[dst] = 1;
+      added = true;
+    }
+  }
+  for (int i = n_old; i < N; i++)
+    if (!ready[i]) return i;
+  // tree by tree, list order kept within a tree: one thread of k_guess_nodes walks one tree
+  std::vector<int32_t> idx(steps.size());
+  for (size_t i = 0; i < idx.size(); i++) idx[i] = (int32_t)i;
+  std::stable_sort(idx.begin(), idx.end(), [&](int32_t a, int32_t b) { return step_tree[a] < step_tree[b]; });
+  std::vector<HostGuessStep> sorted(steps.size());
+  tree_ptr.assign((size_t)n_trees + 1, 0);
+  for (size_t i = 0; i < idx.size(); i++) { sorted[i] = steps[idx[i]]; tree_ptr[step_tree[idx[i]] + 1]++; }
+  for (int t = 0; t < n_trees; t++) tree_ptr[t + 1] += tree_ptr[t];
+  steps.swap(sorted);
+  return -1;
+}
+
+static void extend_handle(rr_pgo *h, int32_t n_new_nodes, const int32_t *node_kind, const uint32_t *node_id, const double *node_state,
+                          int32_t n_new_edges, const int32_t *edge_kind, const int32_t *edge_from, const int32_t *edge_to,
+                          const double *edge_meas, const double *edge_info) {
+  const HostGraph &og = *h->g;
+  const int n_old = og.n_nodes(), e_old = og.n_edges(), n_total = n_old + n_new_nodes;
+  if (n_new_nodes > 0 && !node_kind) throw ApiError(RR_PGO_EINVAL, "rr_pgo_extend: null node_kind");
+  if (n_new_edges > 0 && (!edge_kind || !edge_from || !edge_to || !edge_meas || !edge_info)) throw ApiError(RR_PGO_EINVAL, "rr_pgo_extend: null edge arrays");
+  const bool guess = n_new_nodes > 0 && !node_state;
+  // ---- the grown graph, checked completely before anything is launched
+  auto nh = std::make_unique<rr_pgo>();
+  HostGraph &g = *nh->g;
+  g.node_kind = og.node_kind;
+  g.node_id = og.node_id;
+  g.node_state = og.node_state;
+  g.edge_kind = og.edge_kind;
+  g.edge_from = og.edge_from;
+  g.edge_to = og.edge_to;
+  g.edge_meas = og.edge_meas;
+  g.edge_info = og.edge_info;
+  std::unordered_map<uint32_t, int> ids;
+  ids.reserve((size_t)n_total * 2);
+  for (int i = 0; i < n_old; i++) ids.emplace(og.node_id[i], i);
+  const size_t state_old = g.node_state.size();
+  for (int i = 0; i < n_new_nodes; i++) {
+    const int node = n_old + i;
+    if (node_kind[i] < NODE_SE2 || node_kind[i] > NODE_SE3)
+      throw ApiError(RR_PGO_EINVAL, "rr_pgo_extend: new node " + std::to_string(i) + " (node " + std::to_string(node) + "): bad node kind " + std::to_string(node_kind[i]));
+    const uint32_t id = node_id ? node_id[i] : (uint32_t)node;
+    const auto ins = ids.emplace(id, node);
+    if (!ins.second)
+      throw ApiError(RR_PGO_EINVAL, "rr_pgo_extend: new node " + std::to_string(i) + " (node " + std::to_string(node) + "): id " + std::to_string(id) + " is the id of node " + std::to_string(ins.first->second));
+    g.node_kind.push_back(node_kind[i]);
+    g.node_id.push_back(id);
+    const int len = node_state_len(node_kind[i]);
+    for (int q = 0; q < len; q++) g.node_state.push_back(node_state ? *node_state++ : (q == 6 ? 1.0 : 0.0));   // (guess mode: filled in below)
+  }
+  for (int k = 0; k < n_new_edges; k++) {
+    const std::string who = "rr_pgo_extend: new edge " + std::to_string(k) + " (edge " + std::to_string(e_old + k) + ")";
+    const int ek = edge_kind[k], a = edge_from[k], b = edge_to[k];
+    if (ek < EDGE_SE2 || ek > EDGE_SE3) throw ApiError(RR_PGO_EINVAL, who + ": bad edge kind " + std::to_string(ek));
+    if (a < 0 || a >= n_total || b < 0 || b >= n_total) throw ApiError(RR_PGO_EINVAL, who + " references an unknown vertex");
+    if (a == b) throw ApiError(RR_PGO_EINVAL, who + " is a self loop");
+    const int ka = g.node_kind[a], kb = g.node_kind[b];
+    const bool ok = (ek == EDGE_SE2 && ka == NODE_SE2 && kb == NODE_SE2) || (ek == EDGE_SE2_XY && ka == NODE_SE2 && kb == NODE_XY) ||
+                    (ek == EDGE_SE3 && ka == NODE_SE3 && kb == NODE_SE3);
+    if (!ok) throw ApiError(RR_PGO_EINVAL, who + ": endpoint kinds do not match the edge kind");
+    g.edge_kind.push_back(ek);
+    g.edge_from.push_back(a);
+    g.edge_to.push_back(b);
+    g.edge_meas.insert(g.edge_meas.end(), edge_meas, edge_meas + edge_meas_len(ek));
+    g.edge_info.insert(g.edge_info.end(), edge_info, edge_info + edge_info_len(ek));
+    edge_meas += edge_meas_len(ek);
+    edge_info += edge_info_len(ek);
+  }
+  const std::string err = g.finalize();   // (what is left: mixed 2-D / 3-D)
+  if (!err.empty()) throw ApiError(RR_PGO_EINVAL, "rr_pgo_extend: " + err);
+  std::vector<HostGuessStep> steps;
+  std::vector<int32_t> tree_ptr;
+  if (guess) {
+    const int lost = plan_guess_steps(g, n_old, e_old, steps, tree_ptr);
+    if (lost >= 0)
+      throw ApiError(RR_PGO_EINVAL, "rr_pgo_extend: new node " + std::to_string(lost - n_old) + " (node " + std::to_string(lost) +
+                                        ") has no initial value: no chain of new edges determines it from a node of the graph");
+  }
+  // ---- from here on the device.  The old stream is drained: its last launches wrote the state that is carried.
+  HIPCHK(hipStreamSynchronize(h->engine->stream()));
+  double ms_dev = 0, t = 0;
+  if (guess) {
+    // (before the analysis, which reads the positions: on the OLD engine's stream, into a staging buffer of the grown state)
+    h->engine->guess_nodes(steps, tree_ptr, n_old, n_total, g.has_se3, g.node_kind.data() + n_old, g.node_state.data() + state_old, &t);
+    ms_dev += t;
+  }
+  const double t0 = now_ms();
+  analyze_handle(nh, &h->opt, 0.0);
+  const double t1 = now_ms();
+  build_engine(nh);
+  const double t2 = now_ms();
+  if (guess) nh->engine->adopt_state(h->engine->guess_dev(), (size_t)n_total, &t);
+  else nh->engine->adopt_state(h->engine->pose_dev(), (size_t)n_old, &t);
+  ms_dev += t;
+  int rk = ROBUST_NONE;
+  double rdelta = 1.0;
+  bool masked = false;
+  std::vector<int32_t> mask;
+  h->engine->robust_setting(&rk, &rdelta, &masked, mask);
+  if (rk != ROBUST_NONE) {
+    if (masked) mask.resize((size_t)g.n_edges(), 1);   // a fresh closure is robustified
+    nh->engine->set_robust(rk, rdelta, masked ? mask.data() : nullptr);
+  }
+  // ---- the swap: nothing below can fail.  The old engine (its stream drained above, the copy out of its buffers waited for)
+  // goes with nh.
+  std::swap(h->g, nh->g);
+  std::swap(h->symp, nh->symp);
+  std::swap(h->engine, nh->engine);
+  h->stats = nh->stats;
+  h->blk_rows.swap(nh->blk_rows);
+  h->blk_cols.swap(nh->blk_cols);
+  h->blk_offs.swap(nh->blk_offs);
+  h->extend_ms[0] = t1 - t0;
+  h->extend_ms[1] = t2 - t1;
+  h->extend_ms[2] = ms_dev;
+}
+
 }  // namespace
 
 extern "C" {
+
+int rr_pgo_extend(rr_pgo *h, int32_t n_new_nodes, const int32_t *node_kind, const uint32_t *node_id, const double *node_state,
+                  int32_t n_new_edges, const int32_t *edge_kind, const int32_t *edge_from, const int32_t *edge_to,
+                  const double *edge_meas, const double *edge_info) {
+  if (!h) { g_last_error = "null argument"; return RR_PGO_EINVAL; }
+  if (n_new_nodes < 0 || n_new_edges < 0) { g_last_error = "rr_pgo_extend: negative counts"; return RR_PGO_EINVAL; }
+  if (h->opt.world_size > 1 || h->opt.sharded) {
+    g_last_error = "rr_pgo_extend: sharded handle (every rank would have to grow and re-partition the same graph): create new handles on the grown graph";
+    return RR_PGO_EUNSUPPORTED;
+  }
+  if (n_new_nodes == 0 && n_new_edges == 0) return RR_PGO_OK;
+  if ((int64_t)h->g->n_nodes() + n_new_nodes > 0x7fffffffLL || (int64_t)h->g->n_edges() + n_new_edges > 0x7fffffffLL) {
+    g_last_error = "rr_pgo_extend: more than 2^31 - 1 nodes or edges";
+    return RR_PGO_EINVAL;
+  }
+  return guarded([&] { extend_handle(h, n_new_nodes, node_kind, node_id, node_state, n_new_edges, edge_kind, edge_from, edge_to, edge_meas, edge_info); });
+}
+
+int rr_pgo_extend_times(const rr_pgo *h, double *ms) {
+  if (!h || !ms) { g_last_error = "null argument"; return RR_PGO_EINVAL; }
+  for (int i = 0; i < 3; i++) ms[i] = h->extend_ms[i];
+  return RR_PGO_OK;
+}
 
 void rr_pgo_default_options(rr_pgo_options *opt) {
   std::memset(opt, 0, sizeof *opt);
@@ -3696,7 +3986,7 @@ int rr_pgo_load_g2o(const char *path, const rr_pgo_options *opt, rr_pgo **out) {
     auto h = std::make_unique<rr_pgo>();
     bool io = false;
     double t0 = now_ms();
-    std::string err = load_g2o(path, h->g, io);
+    std::string err = load_g2o(path, *h->g, io);
     if (!err.empty()) throw ApiError(io ? RR_PGO_EIO : RR_PGO_EPARSE, err);
     build_handle(h, opt, now_ms() - t0);
     *out = h.release();
@@ -3708,7 +3998,7 @@ int rr_pgo_create(const rr_pgo_graph_desc *d, const rr_pgo_options *opt, rr_pgo 
   *out = nullptr;
   return guarded([&] {
     auto h = std::make_unique<rr_pgo>();
-    HostGraph &g = h->g;
+    HostGraph &g = *h->g;
     if (d->n_nodes < 0 || d->n_edges < 0) throw ApiError(RR_PGO_EINVAL, "negative counts");
     if (d->n_nodes > 0 && (!d->node_kind || !d->node_state)) throw ApiError(RR_PGO_EINVAL, "null node arrays");
     if (d->n_edges > 0 && (!d->edge_kind || !d->edge_from || !d->edge_to || !d->edge_meas || !d->edge_info))
@@ -3742,15 +4032,15 @@ int rr_pgo_create(const rr_pgo_graph_desc *d, const rr_pgo_options *opt, rr_pgo 
 
 void rr_pgo_destroy(rr_pgo *h) { delete h; }
 
-int32_t rr_pgo_num_nodes(const rr_pgo *h) { return h ? h->g.n_nodes() : 0; }
-int32_t rr_pgo_num_edges(const rr_pgo *h) { return h ? h->g.n_edges() : 0; }
-int32_t rr_pgo_dim(const rr_pgo *h) { return h ? h->g.dim : 0; }
-int32_t rr_pgo_state_len(const rr_pgo *h) { return h ? (int32_t)h->g.node_state.size() : 0; }
-int32_t rr_pgo_anchor_node(const rr_pgo *h) { return h ? h->g.anchor_node : -1; }
+int32_t rr_pgo_num_nodes(const rr_pgo *h) { return h ? h->g->n_nodes() : 0; }
+int32_t rr_pgo_num_edges(const rr_pgo *h) { return h ? h->g->n_edges() : 0; }
+int32_t rr_pgo_dim(const rr_pgo *h) { return h ? h->g->dim : 0; }
+int32_t rr_pgo_state_len(const rr_pgo *h) { return h ? (int32_t)h->g->node_state.size() : 0; }
+int32_t rr_pgo_anchor_node(const rr_pgo *h) { return h ? h->g->anchor_node : -1; }
 
 int rr_pgo_get_graph(const rr_pgo *h, rr_pgo_graph_desc *out) {
   if (!h || !out) { g_last_error = "null argument"; return RR_PGO_EINVAL; }
-  fill_desc(h->g, out);
+  fill_desc(*h->g, out);
   return RR_PGO_OK;
 }
 
@@ -3844,7 +4134,7 @@ int rr_pgo_solve_form(const rr_pgo *h, int32_t *kform, double *k_bytes, double *
 // size query (out == NULL) and the call; out_offset is written on success only
 static int pair_query(rr_pgo *h, const char *who, void (EngineBase::*call)(int, const int32_t *, const int32_t *, const int64_t *, double *),
                       int32_t n_query, const int32_t *node_a, const int32_t *node_b, double *out, int64_t *out_offset, int64_t *n_vals) {
-  const int N = h->g.n_nodes();
+  const int N = h->g->n_nodes();
   std::vector<int64_t> off((size_t)n_query + 1, 0);
   for (int q = 0; q < n_query; q++) {
     const int va = node_a ? node_a[q] : q, vb = node_b ? node_b[q] : va;
@@ -3852,7 +4142,7 @@ static int pair_query(rr_pgo *h, const char *who, void (EngineBase::*call)(int, 
       g_last_error = std::string(who) + ": query " + std::to_string(q) + ": node index out of range";
       return RR_PGO_EINVAL;
     }
-    off[q + 1] = off[q] + (int64_t)node_dim(h->g.node_kind[va]) * node_dim(h->g.node_kind[vb]);
+    off[q + 1] = off[q] + (int64_t)node_dim(h->g->node_kind[va]) * node_dim(h->g->node_kind[vb]);
   }
   if (n_vals) *n_vals = off[n_query];
   const int rc = out ? guarded([&] { (h->engine.get()->*call)(n_query, node_a, node_b, off.data(), out); }) : RR_PGO_OK;
@@ -3863,7 +4153,7 @@ static int pair_query(rr_pgo *h, const char *who, void (EngineBase::*call)(int, 
 int rr_pgo_marginals(rr_pgo *h, int32_t n_query, const int32_t *node_a, const int32_t *node_b, double *out,
                      int64_t *out_offset, int64_t *n_vals) {
   if (!h || n_query < 0 || (!node_a && node_b)) { g_last_error = "bad argument"; return RR_PGO_EINVAL; }
-  if (!node_a && n_query != h->g.n_nodes()) {
+  if (!node_a && n_query != h->g->n_nodes()) {
     g_last_error = "rr_pgo_marginals: node_a == NULL asks for every node: n_query must be rr_pgo_num_nodes";
     return RR_PGO_EINVAL;
   }
@@ -3908,7 +4198,7 @@ static bool small_cholesky(double *w, int d, int ld) {
 static int gate_candidates(const char *api, const rr_pgo *h, int32_t n_cand, const int32_t *edge_kind, const int32_t *edge_from,
                            const int32_t *edge_to, const double *edge_meas, const double *edge_info, std::vector<GateCand> &cand,
                            std::vector<int64_t> &soff) {
-  const HostGraph &g = h->g;
+  const HostGraph &g = *h->g;
   const int N = g.n_nodes(), D = g.has_se3 ? 6 : 3;
   cand.assign((size_t)n_cand, GateCand{});
   soff.assign((size_t)n_cand + 1, 0);
@@ -4077,7 +4367,7 @@ int rr_pgo_analyze_g2o(const char *path, const rr_pgo_options *opt, rr_pgo_stats
     auto h = std::make_unique<rr_pgo>();
     const double t0 = now_ms();
     bool io_error = false;
-    const std::string err = load_g2o(path, h->g, io_error);
+    const std::string err = load_g2o(path, *h->g, io_error);
     if (!err.empty()) throw ApiError(io_error ? RR_PGO_EIO : RR_PGO_EPARSE, err);
     analyze_handle(h, opt, now_ms() - t0);
     *out = h->stats;
@@ -4226,7 +4516,7 @@ void *rr_pgo_stream(rr_pgo *h) { return h && h->engine ? (void *)h->engine->stre
 int rr_pgo_node_owner(const rr_pgo *h, int32_t *owner) {
   if (!h || !owner) { g_last_error = "null argument"; return RR_PGO_EINVAL; }
   const int ws = h->opt.world_size > 1 ? h->opt.world_size : 1;
-  for (int i = 0; i < h->g.n_nodes(); i++) owner[i] = ws > 1 ? h->sym_ref().node_part[i] : 0;
+  for (int i = 0; i < h->g->n_nodes(); i++) owner[i] = ws > 1 ? h->sym_ref().node_part[i] : 0;
   return RR_PGO_OK;
 }
 

@@ -454,6 +454,44 @@ class PoseGraph:
         """HIP-event milliseconds of the last gate_joint call: (linearise + factor, tree solve, joint kernel + copy)."""
         return self._times(_lib.load().rr_pgo_gate_joint_times)
 
+    # -- growing a live handle (include/rr_pgo.h, rr_pgo_extend) -------------------------------
+    def extend(self, edge_kind, edge_from, edge_to, edge_meas, edge_info, node_kind=None, node_state=None, node_id=None):
+        """rr_pgo_extend: append nodes (node_kind; None: none) and edges, in rr_pgo_graph_desc packing, to this handle.
+        The estimate of the old nodes stays on the device, bit for bit; new nodes take node_state, or -- node_state None --
+        an initial value composed on the device along the new edges.  Returns (first_new_node, first_new_edge)."""
+        L = _lib.load()
+        kind = np.ascontiguousarray(edge_kind, np.int32).ravel()
+        a = np.ascontiguousarray(edge_from, np.int32).ravel()
+        b = np.ascontiguousarray(edge_to, np.int32).ravel()
+        meas = np.ascontiguousarray(edge_meas, np.float64).ravel()
+        info = np.ascontiguousarray(edge_info, np.float64).ravel()
+        if a.shape != kind.shape or b.shape != kind.shape:
+            raise ValueError("edge_kind, edge_from and edge_to need the same length")
+        if np.all(np.isin(kind, (0, 1, 2))):   # (an unknown kind is the library's to refuse: the lengths are then not checked)
+            if len(meas) != int(np.sum(np.take(GATE_MEAS_LEN, kind))) or len(info) != int(np.sum(np.take(GATE_INFO_LEN, kind))):
+                raise ValueError("edge_meas / edge_info do not have the length the edge kinds ask for")
+        nk = np.zeros(0, np.int32) if node_kind is None else np.ascontiguousarray(node_kind, np.int32).ravel()
+        if node_kind is None and (node_state is not None or node_id is not None):
+            raise ValueError("node_state / node_id without node_kind")
+        st = ids = None
+        if node_state is not None:
+            st = np.ascontiguousarray(node_state, np.float64).ravel()
+            if np.all(np.isin(nk, (0, 1, 2))) and len(st) != int(np.sum(np.take(GATE_MEAS_LEN, nk))):
+                raise ValueError("node_state does not have the length the node kinds ask for")
+        if node_id is not None:
+            ids = np.ascontiguousarray(node_id, np.uint32).ravel()
+            if ids.shape != nk.shape:
+                raise ValueError("node_id needs one entry per new node")
+        first = (self.num_nodes, self.num_edges)
+        _check(L.rr_pgo_extend(self._h, len(nk), _ip(nk), None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_uint32)),
+                               None if st is None else _dp(st), len(kind), _ip(kind), _ip(a), _ip(b), _dp(meas), _dp(info)))
+        return first
+
+    def extend_times(self):
+        """Milliseconds of the last extend call: (symbolic analysis, engine construction -- host wall clock; state carry +
+        initial guess -- HIP events)."""
+        return self._times(_lib.load().rr_pgo_extend_times)
+
     # -- PoseGraph::plot, :375-431 -------------------------------------------------------
     def plot_data(self):
         """What the reference's figure shows: the poses (blue circles), the same poses joined in the order of their ids
