@@ -1,6 +1,7 @@
 // host_graph.h -- host-side pose graph, flattened (what the reference keeps as
 // Vec<Edge<f64>> + two FxHashMaps, pose_graph_optimization.rs:155-163).
 #pragma once
+#include <cmath>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -15,6 +16,36 @@ inline int node_state_len(int kind) { return kind == NODE_SE2 ? 3 : kind == NODE
 inline int edge_dim(int kind) { return kind == EDGE_SE2 ? 3 : kind == EDGE_SE2_XY ? 2 : 6; }
 inline int edge_meas_len(int kind) { return kind == EDGE_SE2 ? 3 : kind == EDGE_SE2_XY ? 2 : 7; }
 inline int edge_info_len(int kind) { return kind == EDGE_SE2 ? 6 : kind == EDGE_SE2_XY ? 3 : 21; }
+
+// The device form of a node's state and of an edge's measurement (the two numberings coincide), as two 4-vectors:
+//   SE2  x, y, cos, sin | -      XY  x, y, 0, 0 | -      SE3  t (3), 0 | q (4) / |q|
+// the quaternion normalised like UnitQuaternion::from_quaternion, the norm in double.  Every conversion in the library is
+// one of these two functions; the callers cast to the arithmetic type where they build the vectors.
+inline double quat_norm(const double *q) { return std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]); }
+// s: node_state_len(kind) scalars in HostGraph's packing; returns how many it read
+inline int pack_state(int kind, const double *s, double p[8]) {
+  p[0] = s[0]; p[1] = s[1];
+  p[2] = p[3] = p[4] = p[5] = p[6] = p[7] = 0.0;
+  if (kind == NODE_SE2) {
+    p[2] = std::cos(s[2]); p[3] = std::sin(s[2]);
+  } else if (kind == NODE_SE3) {
+    const double n = quat_norm(s + 3);
+    p[2] = s[2];
+    for (int t = 0; t < 4; t++) p[4 + t] = s[3 + t] / n;
+  }
+  return node_state_len(kind);
+}
+// the inverse (the angle of (cos, sin); the quaternion as it is); returns how many scalars it wrote
+inline int unpack_state(int kind, const double p[8], double *s) {
+  s[0] = p[0]; s[1] = p[1];
+  if (kind == NODE_SE2) {
+    s[2] = std::atan2(p[3], p[2]);
+  } else if (kind == NODE_SE3) {
+    s[2] = p[2];
+    for (int t = 0; t < 4; t++) s[3 + t] = p[4 + t];
+  }
+  return node_state_len(kind);
+}
 
 // Same packing as rr_pgo_graph_desc (include/rr_pgo.h).
 struct HostGraph {

@@ -241,6 +241,7 @@ static double now_ms() {
 struct HostGuessStep { int32_t src, dst, op; double m[7]; };
 
 struct EngineBase {
+  enum Query { Q_MARGINALS, Q_COVARIANCES, Q_GATE, Q_GATE_JOINT };   // the factor queries, in the order of their ABI functions
   virtual ~EngineBase() = default;
   virtual void chi2(double *out) = 0;
   virtual void linearize_solve(double lambda, int lm, double *dx_out) = 0;
@@ -268,21 +269,19 @@ struct EngineBase {
   virtual void edge_errors(double *s_out, double *w_out) = 0;                  // rr_pgo_edge_errors
   // rr_pgo_marginals (arguments checked; off: [nq + 1] offsets of the blocks in out) / rr_pgo_marginals_times
   virtual void marginals(int nq, const int32_t *na, const int32_t *nb, const int64_t *off, double *out) = 0;
-  virtual void marginals_times(double *ms) const = 0;
   // rr_pgo_covariances (arguments checked; off as for marginals) / rr_pgo_covariances_times
   virtual void covariances(int nq, const int32_t *na, const int32_t *nb, const int64_t *off, double *out) = 0;
-  virtual void covariances_times(double *ms) const = 0;
   // rr_pgo_gate_edges (arguments checked; cand: kind, nodes, measurement, Omega and Omega^-1 filled in; soff: [n + 1] offsets
   // of the innovation covariances in innov; chi2 and innov may be null) / rr_pgo_gate_times
   virtual void gate_edges(int n, const int32_t *from, const int32_t *to, const int64_t *soff, std::vector<GateCand> &cand,
                           double *d2, double *chi2, double *innov) = 0;
-  virtual void gate_times(double *ms) const = 0;
   // rr_pgo_gate_joint (arguments checked; set s is the records [set_ptr[s], set_ptr[s + 1]) of from / to / cand, the sets
   // expanded one after the other; dim: D_s; ioff: [n_sets + 1] offsets of the sets' S in innov; prefix and innov may be null) /
   // rr_pgo_gate_joint_times
   virtual void gate_joint(int n_sets, const int32_t *set_ptr, const int32_t *from, const int32_t *to, const int32_t *dim,
                           const int64_t *ioff, std::vector<GateCand> &cand, double *d2, double *prefix, double *innov) = 0;
-  virtual void gate_joint_times(double *ms) const = 0;
+  // the four rr_pgo_*_times: the three phases of the last call of query `which`, in ms
+  virtual void last_query_times(Query which, double *ms) const = 0;
   // rr_pgo_extend (arguments checked).  The state buffer is in node order, so a grown graph's buffer starts with the old one.
   virtual const void *pose_dev() const = 0;
   virtual size_t pose_node_bytes() const = 0;   // bytes of one node in the state buffer
@@ -334,6 +333,19 @@ __global__ void k_finalize_partial(const double *chi_partial, int n_chi, const d
 template <typename T, typename S = T> class Engine final : public EngineBase {
   using V4 = typename VecT<S>::V4;
   using V2 = typename VecT<S>::V2;
+  // pack_state / unpack_state (host_graph.h) in S: one V4, for SE(3) two; return the scalars read / written
+  static int pack_v4(int kind, const double *s, V4 *v) {
+    double p[8];
+    const int n = pack_state(kind, s, p);
+    v[0] = V4{(S)p[0], (S)p[1], (S)p[2], (S)p[3]};
+    if (kind == NODE_SE3) v[1] = V4{(S)p[4], (S)p[5], (S)p[6], (S)p[7]};
+    return n;
+  }
+  static int unpack_v4(int kind, const V4 *v, double *s) {
+    double p[8] = {(double)v[0].x, (double)v[0].y, (double)v[0].z, (double)v[0].w};
+    if (kind == NODE_SE3) { p[4] = (double)v[1].x; p[5] = (double)v[1].y; p[6] = (double)v[1].z; p[7] = (double)v[1].w; }
+    return unpack_state(kind, p, s);
+  }
   const HostGraph &g_;
   const Symbolic &sym_;
   DeviceArena arena_;   // declared before every DevBuf: destroyed after them
@@ -456,6 +468,9 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   static constexpr bool f64_ = std::is_same<T, double>::value && std::is_same<S, double>::value;
   std::vector<int32_t> front_depth_, col_front_;   // depth of a front (a root: 0); permuted scalar column -> front
   EventHolder query_ev_[4];
+  // the last call of each query (EngineBase::Query): linearise + factor | selected inverse or tree solve | the query's own
+  // kernel (gather; products + gather; gate kernel + copy; joint kernel + copy)
+  double query_ms_[4][3] = {};
   // marginal covariances (selinv.hip.h; rr_pgo_marginals): everything made on the first call
   DevBuf<T> svals_;                  // the selected inverse, a front's image laid out like its factor image (less the rhs row)
   DevBuf<SelMeta> sel_meta_;
@@ -464,7 +479,6 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   std::vector<int64_t> sel_soff_;
   size_t sel_lds_ = 0;
   bool sel_ready_ = false;
-  double sel_ms_[3] = {0, 0, 0};     // the last call: linearise + factor, selected inverse, gather
   // covariances of arbitrary pairs (treesolve.hip.h; rr_pgo_covariances): the per-front records are made on the first call,
   // in the arena; the plan of a call and its workspace live in buffers of their own that only grow
   DevBuf<TsMeta> ts_meta_;
@@ -476,15 +490,12 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   DevBuf<CovQuery> ts_query_;
   DevBuf<T> ts_z_, ts_u_;
   DevBuf<double> ts_out_;
-  double ts_ms_[3] = {0, 0, 0};      // the last call: linearise + factor, tree solve, products + gather
   // the gate of candidate edges (rr_pgo_gate_edges): the covariance plan and workspace above, plus its own records
   DevBuf<GateCand> gate_cand_;
-  double gate_ms_[3] = {0, 0, 0};    // the last call: linearise + factor, tree solve, gate kernel + copy
   // joint compatibility of sets of candidates (rr_pgo_gate_joint): gate_cand_ holds the sets' records one after the other;
   // per set its record, the pivot columns of its fronts and the Z rows of its candidates' nodes there
   DevBuf<JointSet> joint_set_;
   DevBuf<int32_t> joint_fnc_, joint_fz_;
-  double joint_ms_[3] = {0, 0, 0};   // the last call: linearise + factor, tree solve, joint kernel + copy
   static constexpr int kGemvSlices = 16;   // row slices of the multi-workgroup L21^T x product
   DevBuf<double> chi_partial_, norm_partial_, hist_;
   DevBuf<int> counter_, err_, blocks_done_;
@@ -558,53 +569,43 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     }
     e_idx_.upload(eidx);
     e_slot_.upload(eslot);
-    if (!is3d_) {
-      std::vector<V4> pose(N);
-      for (int i = 0; i < N; i++) {
-        const double *s = &g.node_state[g.node_state_off[i]];
-        if (g.node_kind[i] == NODE_SE2) pose[i] = V4{(S)s[0], (S)s[1], (S)std::cos(s[2]), (S)std::sin(s[2])};
-        else pose[i] = V4{(S)s[0], (S)s[1], (S)0, (S)0};
-      }
+    {   // states and measurements in their device form: one V4 per node and edge, SE(3) a pair (the host copies end with the block).
+      // The loops are split by dimension and the 2-D ones name their two kinds, so that each compiles to its own forms alone.
+      const size_t per = is3d_ ? 2 : 1;
+      std::vector<V4> pose(per * (size_t)N);
+      if (is3d_) for (int i = 0; i < N; i++) pack_v4(NODE_SE3, &g.node_state[g.node_state_off[i]], &pose[2 * (size_t)i]);
+      else for (int i = 0; i < N; i++) pack_v4(g.node_kind[i] == NODE_SE2 ? NODE_SE2 : NODE_XY, &g.node_state[g.node_state_off[i]], &pose[i]);
       pose_.upload(pose);
-      std::vector<V4> emeas(E), einfa(E);
-      std::vector<V2> einfb(E);
-      for (int k = 0; k < E; k++) {
-        const double *m = &g.edge_meas[g.edge_meas_off[k]];
-        const double *w = &g.edge_info[g.edge_info_off[k]];
-        if (g.edge_kind[k] == EDGE_SE2) {
-          emeas[k] = V4{(S)m[0], (S)m[1], (S)std::cos(m[2]), (S)std::sin(m[2])};
-          einfa[k] = V4{(S)w[0], (S)w[1], (S)w[2], (S)w[3]};
-          einfb[k] = V2{(S)w[4], (S)w[5]};
-        } else {
-          emeas[k] = V4{(S)m[0], (S)m[1], (S)0, (S)0};
-          einfa[k] = V4{(S)w[0], (S)w[1], (S)0, (S)w[2]};
-          einfb[k] = V2{(S)0, (S)0};
+      std::vector<V4> emeas(per * (size_t)E);
+      if (is3d_) for (int k = 0; k < E; k++) pack_v4(EDGE_SE3, &g.edge_meas[g.edge_meas_off[k]], &emeas[2 * (size_t)k]);
+      else for (int k = 0; k < E; k++) pack_v4(g.edge_kind[k] == EDGE_SE2 ? EDGE_SE2 : EDGE_SE2_XY, &g.edge_meas[g.edge_meas_off[k]], &emeas[k]);
+      e_meas_.upload(emeas);
+      if (!is3d_) {
+        std::vector<V4> einfa(E);
+        std::vector<V2> einfb(E);
+        for (int k = 0; k < E; k++) {
+          const double *w = &g.edge_info[g.edge_info_off[k]];
+          if (g.edge_kind[k] == EDGE_SE2) {
+            einfa[k] = V4{(S)w[0], (S)w[1], (S)w[2], (S)w[3]};
+            einfb[k] = V2{(S)w[4], (S)w[5]};
+          } else {
+            einfa[k] = V4{(S)w[0], (S)w[1], (S)0, (S)w[2]};
+            einfb[k] = V2{(S)0, (S)0};
+          }
         }
+        e_info_a_.upload(einfa);
+        e_info_b_.upload(einfb);
+        std::vector<EdgeRec<S>> erec(E);
+        for (int k = 0; k < E; k++) erec[k] = EdgeRec<S>{eidx[k].x, eidx[k].y, eslot[k], emeas[k], einfa[k], einfb[k]};
+        e_rec_.upload(erec);
+      } else {
+        std::vector<S> einfo(21 * (size_t)E);
+        for (int k = 0; k < E; k++) {
+          const double *w = &g.edge_info[g.edge_info_off[k]];
+          for (int t = 0; t < 21; t++) einfo[21 * (size_t)k + t] = (S)w[t];
+        }
+        e_info3_.upload(einfo);
       }
-      e_meas_.upload(emeas);
-      e_info_a_.upload(einfa);
-      e_info_b_.upload(einfb);
-      std::vector<EdgeRec<S>> erec(E);
-      for (int k = 0; k < E; k++) erec[k] = EdgeRec<S>{eidx[k].x, eidx[k].y, eslot[k], emeas[k], einfa[k], einfb[k]};
-      e_rec_.upload(erec);
-    } else {
-      // SE(3): (t, -), (q) pairs; quaternions normalised like UnitQuaternion::from_quaternion
-      auto pack7 = [](const double *s, V4 &a, V4 &b) {
-        const double n = std::sqrt(s[3] * s[3] + s[4] * s[4] + s[5] * s[5] + s[6] * s[6]);
-        a = V4{(S)s[0], (S)s[1], (S)s[2], (S)0};
-        b = V4{(S)(s[3] / n), (S)(s[4] / n), (S)(s[5] / n), (S)(s[6] / n)};
-      };
-      std::vector<V4> pose(2 * (size_t)N), emeas(2 * (size_t)E);
-      std::vector<S> einfo(21 * (size_t)E);
-      for (int i = 0; i < N; i++) pack7(&g.node_state[g.node_state_off[i]], pose[2 * i], pose[2 * i + 1]);
-      for (int k = 0; k < E; k++) {
-        pack7(&g.edge_meas[g.edge_meas_off[k]], emeas[2 * k], emeas[2 * k + 1]);
-        const double *w = &g.edge_info[g.edge_info_off[k]];
-        for (int t = 0; t < 21; t++) einfo[21 * (size_t)k + t] = (S)w[t];
-      }
-      pose_.upload(pose);
-      e_meas_.upload(emeas);
-      e_info3_.upload(einfo);
     }
     std::vector<int2> inc(sym.inc_list.size());
     if (E >= (1 << 27)) throw ApiError(RR_PGO_EUNSUPPORTED, "more than 2^27 edges");
@@ -2390,29 +2391,15 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     std::vector<V4> pose(pose_.n);
     HIPCHK(hipMemcpyAsync(pose.data(), pose_.p, pose.size() * sizeof(V4), hipMemcpyDeviceToHost, stream_));
     HIPCHK(hipStreamSynchronize(stream_));
-    for (int i = 0; i < N; i++) {
-      if (is3d_) {
-        const V4 &t = pose[2 * i], &q = pose[2 * i + 1];
-        *out++ = (double)t.x; *out++ = (double)t.y; *out++ = (double)t.z;
-        *out++ = (double)q.x; *out++ = (double)q.y; *out++ = (double)q.z; *out++ = (double)q.w;
-        continue;
-      }
-      *out++ = (double)pose[i].x;
-      *out++ = (double)pose[i].y;
-      if (g_.node_kind[i] == NODE_SE2) *out++ = std::atan2((double)pose[i].w, (double)pose[i].z);
-    }
+    const size_t per = is3d_ ? 2 : 1;
+    for (int i = 0; i < N; i++) out += unpack_v4(g_.node_kind[i], &pose[per * i], out);
   }
 
   // (the poses go through a pinned staging buffer into a device-side copy, from there into the state, and the call does not
   // wait for either copy; the state of the previous call is remembered, so setting the SAME state again -- restarting a run,
   // what the benchmark does between two optimize() calls -- costs the host a comparison and one small launch instead of the
   // conversion loop (a cosine and a sine per pose) and a host-to-device copy)
-  void restore_saved_state() {
-    const int64_t n16 = (int64_t)(pose_.n * sizeof(V4) / 16);
-    hipLaunchKernelGGL(k_copy_words16, dim3((unsigned)std::min<int64_t>((n16 + 255) / 256, 1024)), dim3(256), 0, stream_,
-                       reinterpret_cast<const uint4 *>(pose_saved_.p), reinterpret_cast<uint4 *>(pose_.p), n16);
-    check_launch("k_copy_words16");
-  }
+  void restore_saved_state() { copy_words16(pose_saved_.p, pose_.p, pose_.n * sizeof(V4)); }
   void set_state(const double *st) override {
     const int N = g_.n_nodes();
     const size_t n_in = g_.node_state.size();
@@ -2429,20 +2416,8 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     }
     state_in_.assign(st, st + n_in);
     V4 *pose = state_stage_.p;
-    for (int i = 0; i < N; i++) {
-      if (is3d_) {
-        const double n = std::sqrt(st[3] * st[3] + st[4] * st[4] + st[5] * st[5] + st[6] * st[6]);
-        pose[2 * i] = V4{(S)st[0], (S)st[1], (S)st[2], (S)0};
-        pose[2 * i + 1] = V4{(S)(st[3] / n), (S)(st[4] / n), (S)(st[5] / n), (S)(st[6] / n)};
-        st += 7;
-      } else if (g_.node_kind[i] == NODE_SE2) {
-        pose[i] = V4{(S)st[0], (S)st[1], (S)std::cos(st[2]), (S)std::sin(st[2])};
-        st += 3;
-      } else {
-        pose[i] = V4{(S)st[0], (S)st[1], (S)0, (S)0};
-        st += 2;
-      }
-    }
+    if (is3d_) for (int i = 0; i < N; i++) st += pack_v4(NODE_SE3, st, pose + 2 * (size_t)i);   // (split as in the constructor)
+    else for (int i = 0; i < N; i++) st += pack_v4(g_.node_kind[i] == NODE_SE2 ? NODE_SE2 : NODE_XY, st, pose + i);
     HIPCHK(hipMemcpyAsync(pose_saved_.p, pose, pose_.n * sizeof(V4), hipMemcpyHostToDevice, stream_));
     HIPCHK(hipEventRecord(state_stage_ev_, stream_));
     restore_saved_state();
@@ -2452,6 +2427,19 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   const void *pose_dev() const override { return pose_.p; }
   size_t pose_node_bytes() const override { return (is3d_ ? 2 : 1) * sizeof(V4); }
   const void *guess_dev() const override { return guess_stage_.p; }
+  // HIP-event time, in ms, of what `work` puts on the stream; waits for it
+  template <typename F> double timed_ms(F &&work) {
+    EventHolder ev0, ev1;
+    ev0.create(hipEventDefault);
+    ev1.create(hipEventDefault);
+    HIPCHK(hipEventRecord(ev0, stream_));
+    work();
+    HIPCHK(hipEventRecord(ev1, stream_));
+    HIPCHK(hipStreamSynchronize(stream_));
+    float t = 0;
+    HIPCHK(hipEventElapsedTime(&t, ev0, ev1));
+    return t;
+  }
   void copy_words16(const void *src, void *dst, size_t bytes) {
     const int64_t n16 = (int64_t)(bytes / 16);
     if (n16 == 0) return;
@@ -2469,18 +2457,10 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
       if (h.src < 0 || h.src >= n_total || h.dst < n_old || h.dst >= n_total) throw ApiError(RR_PGO_EINVAL, "internal: guess step out of range");
       GuessStep<S> &d = ds[k];
       d.src = h.src; d.dst = h.dst; d.op = h.op; d.pad = 0;
-      // (measurements converted as the constructor converts an edge's)
-      if (h.op == GUESS_SE3 || h.op == GUESS_SE3_INV) {
-        const double n = std::sqrt(h.m[3] * h.m[3] + h.m[4] * h.m[4] + h.m[5] * h.m[5] + h.m[6] * h.m[6]);
-        d.m0 = V4{(S)h.m[0], (S)h.m[1], (S)h.m[2], (S)0};
-        d.m1 = V4{(S)(h.m[3] / n), (S)(h.m[4] / n), (S)(h.m[5] / n), (S)(h.m[6] / n)};
-      } else if (h.op == GUESS_XY) {
-        d.m0 = V4{(S)h.m[0], (S)h.m[1], (S)0, (S)0};
-        d.m1 = V4{(S)0, (S)0, (S)0, (S)0};
-      } else {
-        d.m0 = V4{(S)h.m[0], (S)h.m[1], (S)std::cos(h.m[2]), (S)std::sin(h.m[2])};
-        d.m1 = V4{(S)0, (S)0, (S)0, (S)0};
-      }
+      V4 m[2] = {};
+      pack_v4(h.op == GUESS_XY ? EDGE_SE2_XY : h.op == GUESS_SE3 || h.op == GUESS_SE3_INV ? EDGE_SE3 : EDGE_SE2, h.m, m);
+      d.m0 = m[0];
+      d.m1 = m[1];
     }
     const int n_trees = (int)tree_ptr.size() - 1;
     DevBuf<GuessStep<S>> dsteps;   // (no arena outside the constructor: buffers of their own, freed on return)
@@ -2489,47 +2469,22 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     HIPCHK(hipMemsetAsync(guess_stage_.p, 0, guess_stage_.n * sizeof(V4), stream_));
     dsteps.alloc(ds.size());
     dtree.alloc(tree_ptr.size());
-    EventHolder ev0, ev1;
-    ev0.create(hipEventDefault);
-    ev1.create(hipEventDefault);
     HIPCHK(hipMemcpyAsync(dsteps.p, ds.data(), ds.size() * sizeof(GuessStep<S>), hipMemcpyHostToDevice, stream_));
     HIPCHK(hipMemcpyAsync(dtree.p, tree_ptr.data(), tree_ptr.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
-    HIPCHK(hipEventRecord(ev0, stream_));
-    copy_words16(pose_.p, guess_stage_.p, per * (size_t)n_old * sizeof(V4));
-    hipLaunchKernelGGL((k_guess_nodes<S>), dim3((unsigned)((n_trees + 63) / 64)), dim3(64), 0, stream_, guess_stage_.p, n_total, is3d ? 1 : 0,
-                       dsteps.p, dtree.p, n_trees);
-    check_launch("k_guess_nodes");
-    HIPCHK(hipEventRecord(ev1, stream_));
+    *ms = timed_ms([&] {
+      copy_words16(pose_.p, guess_stage_.p, per * (size_t)n_old * sizeof(V4));
+      hipLaunchKernelGGL((k_guess_nodes<S>), dim3((unsigned)((n_trees + 63) / 64)), dim3(64), 0, stream_, guess_stage_.p, n_total, is3d ? 1 : 0,
+                         dsteps.p, dtree.p, n_trees);
+      check_launch("k_guess_nodes");
+    });
     std::vector<V4> pose(per * (size_t)(n_total - n_old));
     HIPCHK(hipMemcpyAsync(pose.data(), guess_stage_.p + per * (size_t)n_old, pose.size() * sizeof(V4), hipMemcpyDeviceToHost, stream_));
     HIPCHK(hipStreamSynchronize(stream_));
-    float t = 0;
-    HIPCHK(hipEventElapsedTime(&t, ev0, ev1));
-    *ms = t;
-    for (int i = 0; i < n_total - n_old; i++) {   // as get_state
-      if (is3d) {
-        const V4 &tt = pose[2 * i], &q = pose[2 * i + 1];
-        *out++ = (double)tt.x; *out++ = (double)tt.y; *out++ = (double)tt.z;
-        *out++ = (double)q.x; *out++ = (double)q.y; *out++ = (double)q.z; *out++ = (double)q.w;
-        continue;
-      }
-      *out++ = (double)pose[i].x;
-      *out++ = (double)pose[i].y;
-      if (new_kind[i] == NODE_SE2) *out++ = std::atan2((double)pose[i].w, (double)pose[i].z);
-    }
+    for (int i = 0; i < n_total - n_old; i++) out += unpack_v4(new_kind[i], &pose[per * i], out);
   }
   void adopt_state(const void *src, size_t n_nodes, double *ms) override {
     if (n_nodes > (size_t)g_.n_nodes()) throw ApiError(RR_PGO_EINVAL, "internal: more nodes adopted than the graph has");
-    EventHolder ev0, ev1;
-    ev0.create(hipEventDefault);
-    ev1.create(hipEventDefault);
-    HIPCHK(hipEventRecord(ev0, stream_));
-    copy_words16(src, pose_.p, n_nodes * pose_node_bytes());
-    HIPCHK(hipEventRecord(ev1, stream_));
-    HIPCHK(hipStreamSynchronize(stream_));
-    float t = 0;
-    HIPCHK(hipEventElapsedTime(&t, ev0, ev1));
-    *ms = t;
+    *ms = timed_ms([&] { copy_words16(src, pose_.p, n_nodes * pose_node_bytes()); });
   }
   void robust_setting(int *kind, double *delta, bool *masked, std::vector<int32_t> &mask) const override {
     *kind = robust_kind_;
@@ -2926,11 +2881,11 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
       if (n_vals > 0) HIPCHK(hipMemcpyAsync(host.data(), d_out.p, host.size() * sizeof(double), hipMemcpyDeviceToHost, stream_));
       HIPCHK(hipStreamSynchronize(stream_));
       check_device_error();
-      query_times(sel_ms_, false);
+      query_times(query_ms_[Q_MARGINALS], false);
       if (n_vals > 0) std::memcpy(out, host.data(), host.size() * sizeof(double));
     }
   }
-  void marginals_times(double *ms) const override { for (int k = 0; k < 3; k++) ms[k] = sel_ms_[k]; }
+  void last_query_times(Query which, double *ms) const override { for (int k = 0; k < 3; k++) ms[k] = query_ms_[which][k]; }
 
   // ---- the multi-column tree solve (treesolve.hip.h) under rr_pgo_covariances, rr_pgo_gate_edges and rr_pgo_gate_joint
   struct TsPlan {
@@ -3184,7 +3139,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     require_f64_unsharded_lds_factor(who);
     if constexpr (f64_) {
       covariances_prepare(who);
-      tree_query(who, "pair", nq, na, nb, off, ts_ms_, false, [&](int q0, int q1, const TsPlan &pl) {
+      tree_query(who, "pair", nq, na, nb, off, query_ms_[Q_COVARIANCES], false, [&](int q0, int q1, const TsPlan &pl) {
         ts_fill(ts_query_, pl.query);
         ts_grow(ts_out_, (size_t)(off[q1] - off[q0]));
       }, [&](int q0, int q1) {
@@ -3201,7 +3156,6 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
       });
     }
   }
-  void covariances_times(double *ms) const override { for (int k = 0; k < 3; k++) ms[k] = ts_ms_[k]; }
 
   // ---- Mahalanobis gate of candidate edges (include/rr_pgo.h, rr_pgo_gate_edges; treesolve.hip.h, k_gate_pairs): the plan
   // of the candidates' nodes is the covariance plan of the pairs (from, to)
@@ -3212,7 +3166,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     if constexpr (f64_) {
       covariances_prepare(who);
       auto n_innov = [&](int c0, int c1) { return innov ? (size_t)(soff[c1] - soff[c0]) : 0; };
-      tree_query(who, "candidate", n, from, to, soff, gate_ms_, true, [&](int c0, int c1, const TsPlan &pl) {
+      tree_query(who, "candidate", n, from, to, soff, query_ms_[Q_GATE], true, [&](int c0, int c1, const TsPlan &pl) {
         const size_t nc = (size_t)(c1 - c0);
         for (int c = c0; c < c1; c++) {
           cand[c].cq = pl.query[c - c0];
@@ -3241,7 +3195,6 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
       });
     }
   }
-  void gate_times(double *ms) const override { for (int k = 0; k < 3; k++) ms[k] = gate_ms_[k]; }
 
   // ---- joint compatibility of sets of candidate edges (include/rr_pgo.h, rr_pgo_gate_joint; treesolve.hip.h, k_gate_joint):
   // the plan is the covariance plan of the sets' pairs (from, to), one after the other, cut at set boundaries only
@@ -3258,7 +3211,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
       std::vector<int32_t> fnc, fz, fronts, slot((size_t)sym.S, -1);   // slot: front -> its place among the set's fronts
       auto set_of = [&](int q) { return (int)(std::lower_bound(set_ptr, set_ptr + n_sets + 1, q) - set_ptr); };   // (no set is empty)
       auto n_innov = [&](int s0, int s1) { return innov ? (size_t)(ioff[s1] - ioff[s0]) : 0; };
-      tree_query(who, "set", n, from, to, no_off.data(), joint_ms_, true, [&](int q0, int q1, const TsPlan &pl) {
+      tree_query(who, "set", n, from, to, no_off.data(), query_ms_[Q_GATE_JOINT], true, [&](int q0, int q1, const TsPlan &pl) {
         const int s0 = set_of(q0), s1 = set_of(q1);
         sets.clear();
         fnc.clear();
@@ -3333,7 +3286,6 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
       }, set_ptr, n_sets);
     }
   }
-  void gate_joint_times(double *ms) const override { for (int k = 0; k < 3; k++) ms[k] = joint_ms_[k]; }
 
   void debug_withhold(int mode) override {
     HIPCHK(hipStreamSynchronize(stream_));
@@ -3541,10 +3493,10 @@ static void analysis_cache_store(uint64_t key, const HostGraph &g, const rr_pgo_
 }
 
 // host part of PoseGraph::new: options, symbolic analysis, the statistics that need no device
-void analyze_handle(std::unique_ptr<rr_pgo> &h, const rr_pgo_options *opt_in, double parse_ms) {
+void analyze_handle(rr_pgo &h, const rr_pgo_options *opt_in, double parse_ms) {
   rr_pgo_options opt;
   if (opt_in) opt = *opt_in; else rr_pgo_default_options(&opt);
-  h->opt = opt;
+  h.opt = opt;
   if (opt.precision != RR_PGO_F64 && opt.precision != RR_PGO_F32 && opt.precision != RR_PGO_MIXED)
     throw ApiError(RR_PGO_EINVAL, "bad precision");
   if (opt.world_size > 1) {
@@ -3559,13 +3511,13 @@ void analyze_handle(std::unique_ptr<rr_pgo> &h, const rr_pgo_options *opt_in, do
   // fp32 6.05 ms per step with 48, 6.09 with 40, 6.12 with 56, 6.21 with 64; fp64 -- half the LDS budget per front --
   // 9.78 with 32, 10.41 with 48 or 64)
   const int big_leaf = opt.precision == RR_PGO_F64 ? 32 : 48;
-  so.nd_leaf = h->g->n_nodes() <= 6000 ? (1 << 30) : big_leaf;
-  so.split_separators = h->g->n_nodes() > 6000;   // wide top fronts: see symbolic.cpp, supernode pass
+  so.nd_leaf = h.g->n_nodes() <= 6000 ? (1 << 30) : big_leaf;
+  so.split_separators = h.g->n_nodes() > 6000;   // wide top fronts: see symbolic.cpp, supernode pass
   if (opt.world_size > 1) {   // sharding needs the nested-dissection top levels
     so.n_parts = opt.world_size;
     so.my_part = opt.rank;
     so.nd_leaf = big_leaf;
-    so.pin_node = h->g->anchor_node;   // every rank needs the anchor's entries of the solution (gauge transfer)
+    so.pin_node = h.g->anchor_node;   // every rank needs the anchor's entries of the solution (gauge transfer)
   }
   // tuning knobs of the symbolic phase
   // graphs whose fronts all fit LDS: ONE dataflow launch for the factorisation, one for the back substitution (lds_flow.hip.h);
@@ -3576,7 +3528,7 @@ void analyze_handle(std::unique_ptr<rr_pgo> &h, const rr_pgo_options *opt_in, do
   if (std::getenv("RR_PGO_NO_GEO")) so.geo_nd = false;
   // small graphs (trajectories with loop closures): the multilevel bisection finds narrower separators (intel: 97 -> 60 nodes along the heaviest root path) than the
   // level sets / coordinate cuts (symbolic.cpp, MultilevelBisection); the lattice's straight cuts are already the best there are
-  so.ml_nd = h->g->n_nodes() <= 6000;
+  so.ml_nd = h.g->n_nodes() <= 6000;
   if (const char *e = std::getenv("RR_PGO_ML_ND")) so.ml_nd = std::atoi(e) != 0;
   if (const char *e = std::getenv("RR_PGO_LDS_PIECES")) so.max_lds_pieces = std::max(1, std::atoi(e));
   // RR_PGO_JOIN_SEPARATORS=1: a region's last separator always chained into its parent separator's supernode; =0: never (small graphs:
@@ -3588,7 +3540,7 @@ void analyze_handle(std::unique_ptr<rr_pgo> &h, const rr_pgo_options *opt_in, do
   // the widest front the chain pass may merge into its parent (when the cost model says the parent finishes earlier): 80 pivot
   // columns for 2D graphs, 48 for 6 x 6 blocks -- re-measured on the r05 / r06 trees (profiles/r06_chain_cap_sweep.txt: intel + 3.1 %,
   // M3500 - 0.3 %, dlr + 0.0 % at 80; the SE(3) graphs lose 0.4 - 2 % beyond 48, where the model's error grows with the front)
-  if (!h->g->has_se3) so.merge_chain_nc = 80;
+  if (!h.g->has_se3) so.merge_chain_nc = 80;
   if (const char *e = std::getenv("RR_PGO_MERGE_CHAIN")) { so.merge_chain_nc = std::atoi(e); if (const char *c = std::strchr(e, ',')) so.merge_chain_gain_us = std::atof(c + 1); }
   if (const char *e = std::getenv("RR_PGO_AMALG_NP")) so.amalg_np = std::atoi(e);
   double t0 = now_ms();
@@ -3597,13 +3549,13 @@ void analyze_handle(std::unique_ptr<rr_pgo> &h, const rr_pgo_options *opt_in, do
   // and the switches above -- not of the measurements.  A caller that builds the same graph again (the reference's own bench is a
   // loop of PoseGraph::new(file) + optimize(10), benches/graph_slam.rs:9-10; UMFPACK users keep the symbolic object for the same
   // reason) gets the tables of the first analysis.  RR_PGO_ANALYSIS_CACHE=0: every handle is analysed afresh.
-  const uint64_t cache_key = analysis_cache_key(*h->g, opt);
+  const uint64_t cache_key = analysis_cache_key(*h.g, opt);
   if (cache_key != 0)
-    if (std::shared_ptr<const Symbolic> hit = analysis_cache_find(cache_key, *h->g, opt)) h->symp = hit;
+    if (std::shared_ptr<const Symbolic> hit = analysis_cache_find(cache_key, *h.g, opt)) h.symp = hit;
   Symbolic fresh;
-  if (h->symp) {
+  if (h.symp) {
   } else
-  if (h->g->n_nodes() <= 6000 && opt.world_size <= 1 && !opt.sharded && !(std::getenv("RR_PGO_ND_LEAF") && std::getenv("RR_PGO_AMALG_NP"))) {
+  if (h.g->n_nodes() <= 6000 && opt.world_size <= 1 && !opt.sharded && !(std::getenv("RR_PGO_ND_LEAF") && std::getenv("RR_PGO_AMALG_NP"))) {
     // Small graphs are bound by the critical path through the supernode tree, not by flops: a few
     // nested-dissection cuts above minimum-degree leaves shorten that path on the larger ones (M3500, dlr,
     // sphere2500: +20..26 % measured) and lengthen it on intel; merging mid-sized fronts (relaxed amalgamation up to 72
@@ -3620,17 +3572,17 @@ void analyze_handle(std::unique_ptr<rr_pgo> &h, const rr_pgo_options *opt_in, do
     for (int li = 0; li < 6; li++) {
       int leaf = so.ml_nd ? kLeafMultilevel[li] : kLeafLevelSets[li];
       if (std::getenv("RR_PGO_ND_LEAF")) { if (leaf != (1 << 30)) continue; leaf = so.nd_leaf; }
-      else if (leaf != (1 << 30) && ((!so.ml_nd && h->g->n_nodes() < 2400) || leaf >= h->g->n_nodes())) continue;   // (a leaf size >= the graph is no cut at all)
+      else if (leaf != (1 << 30) && ((!so.ml_nd && h.g->n_nodes() < 2400) || leaf >= h.g->n_nodes())) continue;   // (a leaf size >= the graph is no cut at all)
       // (with the multilevel bisection the undissected tree lost on every graph of 1000+ nodes by 30 - 60 % of the estimate, and its
       // minimum-degree pass over the whole graph is the slowest of the candidate analyses: 5.8 ms on dlr)
-      if (so.ml_nd && leaf == (1 << 30) && h->g->n_nodes() >= 1000 && !std::getenv("RR_PGO_ND_LEAF")) continue;
+      if (so.ml_nd && leaf == (1 << 30) && h.g->n_nodes() >= 1000 && !std::getenv("RR_PGO_ND_LEAF")) continue;
       cl.push_back({leaf, np_fixed ? so.amalg_np : 16, so.split_separators});   // the narrow rule first: it wins wherever every front lives in LDS
     }
     const size_t n_depths = cl.size();
     // the deepest dissections once more with mid-sized fronts merged up to 32 columns (intel, r05: the model's and the measured best)
     if (so.ml_nd && !np_fixed && !std::getenv("RR_PGO_ND_LEAF"))
       for (int leaf : {70, 50})
-        if (leaf < h->g->n_nodes()) cl.push_back({leaf, 32, so.split_separators});
+        if (leaf < h.g->n_nodes()) cl.push_back({leaf, 32, so.split_separators});
     // ... and the deeper dissections with a region's last separator NOT chained into its parent separator's supernode (the rule of the
     // large graphs, symbolic.cpp step 4): the sibling separator then runs beside it instead of before it.  Measured (r05, same kernels):
     // sphere2500 1539 -> 1697 it/s, torus3D 1066 -> 1191, dlr 7369 -> 7852, intel 7382 -> 6962 -- and the estimates say so beforehand
@@ -3638,7 +3590,7 @@ void analyze_handle(std::unique_ptr<rr_pgo> &h, const rr_pgo_options *opt_in, do
     const bool split_free = so.ml_nd && !join_env && !std::getenv("RR_PGO_ND_LEAF");
     if (split_free)
       for (int leaf : {100, 70, 50})
-        if (leaf < h->g->n_nodes()) cl.push_back({leaf, np_fixed ? so.amalg_np : 16, true});
+        if (leaf < h.g->n_nodes()) cl.push_back({leaf, np_fixed ? so.amalg_np : 16, true});
     Symbolic best;
     double best_crit = -1.0;
     int best_leaf = 0;
@@ -3652,7 +3604,7 @@ void analyze_handle(std::unique_ptr<rr_pgo> &h, const rr_pgo_options *opt_in, do
       for (const Cand &c : cl) o.nd_leaf = std::min(o.nd_leaf, c.leaf);
       o.nd_record = &splits;
       const double td = now_ms();
-      err = dissect_only(*h->g, o);
+      err = dissect_only(*h.g, o);
       shared_splits = err.empty();
       if (std::getenv("RR_PGO_ANALYZE_TIMES")) std::fprintf(stderr, "analyze: shared dissection down to %d nodes: %.3f ms (%zu splits)\n", o.nd_leaf, now_ms() - td, splits.map.size());
     }
@@ -3666,7 +3618,7 @@ void analyze_handle(std::unique_ptr<rr_pgo> &h, const rr_pgo_options *opt_in, do
         o.amalg_np = list[c].np;
         o.split_separators = list[c].split;
         if (shared_splits) o.nd_replay = &splits;
-        try { errs[c] = analyze(*h->g, o, cands[c]); } catch (const std::exception &e) { errs[c] = e.what(); }
+        try { errs[c] = analyze(*h.g, o, cands[c]); } catch (const std::exception &e) { errs[c] = e.what(); }
       });
       for (size_t c = 0; c < list.size(); c++) {
         if (!errs[c].empty()) { err = errs[c]; return; }
@@ -3694,22 +3646,22 @@ void analyze_handle(std::unique_ptr<rr_pgo> &h, const rr_pgo_options *opt_in, do
     (void)best_leaf;
     if (err.empty()) fresh = std::move(best);
   } else {
-    err = analyze(*h->g, so, fresh);
+    err = analyze(*h.g, so, fresh);
     if (err.empty() && std::getenv("RR_PGO_ANALYZE_TIMES"))
       std::fprintf(stderr, "analyze: estimated critical path %.1f us (%d big fronts, %d supernodes)\n", fresh.est_critical_us, fresh.n_big, fresh.S);
   }
   if (!err.empty()) throw ApiError(RR_PGO_EINVAL, err);
-  if (!h->symp) {
-    h->symp = std::make_shared<const Symbolic>(std::move(fresh));
-    if (cache_key != 0) analysis_cache_store(cache_key, *h->g, opt, h->symp);
+  if (!h.symp) {
+    h.symp = std::make_shared<const Symbolic>(std::move(fresh));
+    if (cache_key != 0) analysis_cache_store(cache_key, *h.g, opt, h.symp);
   }
   double t1 = now_ms();
-  rr_pgo_stats &s = h->stats;
+  rr_pgo_stats &s = h.stats;
   std::memset(&s, 0, sizeof s);
-  const Symbolic &y = h->sym_ref();
+  const Symbolic &y = h.sym_ref();
   const double sz = opt.precision == RR_PGO_F64 ? 8.0 : 4.0;
   int64_t diag_elems = 0, off_elems = 0;
-  for (int i = 0; i < y.N; i++) { int d = node_dim(h->g->node_kind[i]); diag_elems += d * d; }
+  for (int i = 0; i < y.N; i++) { int d = node_dim(h.g->node_kind[i]); diag_elems += d * d; }
   off_elems = y.n_hvals - diag_elems;
   s.nnz_h_blocks = y.N + y.n_offblocks;
   s.nnz_l_scalars = y.l_elems;
@@ -3729,8 +3681,8 @@ void analyze_handle(std::unique_ptr<rr_pgo> &h, const rr_pgo_options *opt_in, do
   // its whole M x M square in place (stored_factor_bytes; 2.2 x the nonzeros on the 1M-edge lattice)
   const double dim = y.dim;
   double edge_stream = 0;
-  for (int k = 0; k < h->g->n_edges(); k++)
-    edge_stream += 8.0 + sz * (edge_meas_len(h->g->edge_kind[k]) + edge_info_len(h->g->edge_kind[k]));
+  for (int k = 0; k < h.g->n_edges(); k++)
+    edge_stream += 8.0 + sz * (edge_meas_len(h.g->edge_kind[k]) + edge_info_len(h.g->edge_kind[k]));
   s.bytes_linearize = edge_stream + dim * sz /*poses*/ + (diag_elems + off_elems) * sz + dim * sz;
   s.bytes_chi2 = 0;  // fused into the linearisation pass
   s.bytes_factor = (diag_elems + off_elems) * sz + (double)y.nnz_l_entries * sz;
@@ -3739,15 +3691,15 @@ void analyze_handle(std::unique_ptr<rr_pgo> &h, const rr_pgo_options *opt_in, do
   s.stored_factor_bytes = (double)y.l_elems * sz;
 }
 
-void build_engine(std::unique_ptr<rr_pgo> &h);
-void build_handle(std::unique_ptr<rr_pgo> &h, const rr_pgo_options *opt_in, double parse_ms) {
+void build_engine(rr_pgo &h);
+void build_handle(rr_pgo &h, const rr_pgo_options *opt_in, double parse_ms) {
   analyze_handle(h, opt_in, parse_ms);
   build_engine(h);
 }
 
 // device part of PoseGraph::new: the engine of an analysed handle, the statistics that need it
-void build_engine(std::unique_ptr<rr_pgo> &h) {
-  const rr_pgo_options opt = h->opt;
+void build_engine(rr_pgo &h) {
+  const rr_pgo_options opt = h.opt;
   // device
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
@@ -3758,21 +3710,21 @@ void build_engine(std::unique_ptr<rr_pgo> &h) {
   }
   const int wr = opt.world_size > 1 ? opt.rank : 0, ww = opt.world_size > 1 ? opt.world_size : 1;
   const bool shd = opt.sharded != 0;
-  if (opt.precision == RR_PGO_F64) h->engine = std::make_unique<Engine<double>>(*h->g, h->sym_ref(), wr, ww, shd);
-  else if (opt.precision == RR_PGO_F32) h->engine = std::make_unique<Engine<float>>(*h->g, h->sym_ref(), wr, ww, shd);
-  else h->engine = std::make_unique<Engine<float, double>>(*h->g, h->sym_ref(), wr, ww, shd);
+  if (opt.precision == RR_PGO_F64) h.engine = std::make_unique<Engine<double>>(*h.g, h.sym_ref(), wr, ww, shd);
+  else if (opt.precision == RR_PGO_F32) h.engine = std::make_unique<Engine<float>>(*h.g, h.sym_ref(), wr, ww, shd);
+  else h.engine = std::make_unique<Engine<float, double>>(*h.g, h.sym_ref(), wr, ww, shd);
   // stats
-  rr_pgo_stats &s = h->stats;
-  const Symbolic &y = h->sym_ref();
-  s.n_launches_per_iter = h->engine->n_launches_per_iter;
+  rr_pgo_stats &s = h.stats;
+  const Symbolic &y = h.sym_ref();
+  s.n_launches_per_iter = h.engine->n_launches_per_iter;
   // trailing updates of the huge fronts: a super-panel of w columns updates the lower triangle of the T rows to its
   // right, w * T (T + 1) / 2 multiply-adds -- counted for the launches of k_big_update and, separately, for the tiles
   // that run inside k_big_flow launches.  (The updates INSIDE a super-panel belong to the panel kernels / PANEL tasks
   // and are not counted here.)
   double buf = 0, bflow = 0;
   std::vector<char> in_flow(y.S, 0);
-  h->engine->mark_flow_fronts(in_flow);
-  const int sch_tile = h->engine->schur_tile();   // 0: no split (flow levels that keep their Schur tiles are marked 2 in in_flow)
+  h.engine->mark_flow_fronts(in_flow);
+  const int sch_tile = h.engine->schur_tile();   // 0: no split (flow levels that keep their Schur tiles are marked 2 in in_flow)
   auto schur_origin_fn = [&](int nc) { return (double)big_schur_origin(nc, sch_tile); };
   const std::function<double(int)> schur_origin_of = sch_tile ? std::function<double(int)>(schur_origin_fn) : std::function<double(int)>();
   for (int f = 0; f < y.S; f++)
@@ -3911,9 +3863,9 @@ static void extend_handle(rr_pgo *h, int32_t n_new_nodes, const int32_t *node_ki
     ms_dev += t;
   }
   const double t0 = now_ms();
-  analyze_handle(nh, &h->opt, 0.0);
+  analyze_handle(*nh, &h->opt, 0.0);
   const double t1 = now_ms();
-  build_engine(nh);
+  build_engine(*nh);
   const double t2 = now_ms();
   if (guess) nh->engine->adopt_state(h->engine->guess_dev(), (size_t)n_total, &t);
   else nh->engine->adopt_state(h->engine->pose_dev(), (size_t)n_old, &t);
@@ -3928,14 +3880,8 @@ static void extend_handle(rr_pgo *h, int32_t n_new_nodes, const int32_t *node_ki
     nh->engine->set_robust(rk, rdelta, masked ? mask.data() : nullptr);
   }
   // ---- the swap: nothing below can fail.  The old engine (its stream drained above, the copy out of its buffers waited for)
-  // goes with nh.
-  std::swap(h->g, nh->g);
-  std::swap(h->symp, nh->symp);
-  std::swap(h->engine, nh->engine);
-  h->stats = nh->stats;
-  h->blk_rows.swap(nh->blk_rows);
-  h->blk_cols.swap(nh->blk_cols);
-  h->blk_offs.swap(nh->blk_offs);
+  // goes with nh.  Every field changes sides (the engines refer to the pointees of g and symp, which do not move).
+  std::swap(*h, *nh);
   h->extend_ms[0] = t1 - t0;
   h->extend_ms[1] = t2 - t1;
   h->extend_ms[2] = ms_dev;
@@ -3988,7 +3934,7 @@ int rr_pgo_load_g2o(const char *path, const rr_pgo_options *opt, rr_pgo **out) {
     double t0 = now_ms();
     std::string err = load_g2o(path, *h->g, io);
     if (!err.empty()) throw ApiError(io ? RR_PGO_EIO : RR_PGO_EPARSE, err);
-    build_handle(h, opt, now_ms() - t0);
+    build_handle(*h, opt, now_ms() - t0);
     *out = h.release();
   });
 }
@@ -4025,7 +3971,7 @@ int rr_pgo_create(const rr_pgo_graph_desc *d, const rr_pgo_options *opt, rr_pgo 
     g.edge_info.assign(d->edge_info, d->edge_info + ni);
     std::string err = g.finalize();
     if (!err.empty()) throw ApiError(RR_PGO_EINVAL, err);
-    build_handle(h, opt, 0.0);
+    build_handle(*h, opt, 0.0);
     *out = h.release();
   });
 }
@@ -4162,7 +4108,7 @@ int rr_pgo_marginals(rr_pgo *h, int32_t n_query, const int32_t *node_a, const in
 
 int rr_pgo_marginals_times(const rr_pgo *h, double *ms) {
   if (!h || !ms) { g_last_error = "null argument"; return RR_PGO_EINVAL; }
-  return guarded([&] { h->engine->marginals_times(ms); });
+  return guarded([&] { h->engine->last_query_times(EngineBase::Q_MARGINALS, ms); });
 }
 
 int rr_pgo_covariances(rr_pgo *h, int32_t n_query, const int32_t *node_a, const int32_t *node_b, double *out,
@@ -4173,7 +4119,7 @@ int rr_pgo_covariances(rr_pgo *h, int32_t n_query, const int32_t *node_a, const 
 
 int rr_pgo_covariances_times(const rr_pgo *h, double *ms) {
   if (!h || !ms) { g_last_error = "null argument"; return RR_PGO_EINVAL; }
-  return guarded([&] { h->engine->covariances_times(ms); });
+  return guarded([&] { h->engine->last_query_times(EngineBase::Q_COVARIANCES, ms); });
 }
 
 // Cholesky of the d x d matrix in w (row stride ld), in place in the lower triangle; false: not positive definite
@@ -4214,7 +4160,7 @@ static int gate_candidates(const char *api, const rr_pgo *h, int32_t n_cand, con
     if (kind == EDGE_SE2 && (ka != NODE_SE2 || kb != NODE_SE2)) return bad("an SE2 edge needs two SE2 poses");
     if (kind == EDGE_SE2_XY && (ka != NODE_SE2 || kb != NODE_XY)) return bad("an SE2_XY edge goes from an SE2 pose to an XY landmark");
     if (kind == EDGE_SE3 && (ka != NODE_SE3 || kb != NODE_SE3)) return bad("an SE3 edge needs two SE3 poses");
-    const int nm = edge_meas_len(kind), ni = edge_info_len(kind), de = kind == EDGE_SE2 ? 3 : kind == EDGE_SE2_XY ? 2 : 6;
+    const int nm = edge_meas_len(kind), ni = edge_info_len(kind), de = edge_dim(kind);
     const double *m = edge_meas + mo, *w = edge_info + io;
     mo += nm;
     io += ni;
@@ -4225,16 +4171,8 @@ static int gate_candidates(const char *api, const rr_pgo *h, int32_t n_cand, con
     gc.kind = kind;
     gc.na = a;
     gc.nb = b;
-    if (kind == EDGE_SE2) {
-      gc.meas[0] = m[0]; gc.meas[1] = m[1]; gc.meas[2] = std::cos(m[2]); gc.meas[3] = std::sin(m[2]);
-    } else if (kind == EDGE_SE2_XY) {
-      gc.meas[0] = m[0]; gc.meas[1] = m[1];
-    } else {   // the quaternion normalised like UnitQuaternion::from_quaternion, as the handle's own measurements are
-      const double nq = std::sqrt(m[3] * m[3] + m[4] * m[4] + m[5] * m[5] + m[6] * m[6]);
-      if (!(nq > 0.0)) return bad("zero quaternion in the measurement");
-      gc.meas[0] = m[0]; gc.meas[1] = m[1]; gc.meas[2] = m[2];
-      for (int t = 0; t < 4; t++) gc.meas[4 + t] = m[3 + t] / nq;
-    }
+    if (kind == EDGE_SE3 && !(quat_norm(m + 3) > 0.0)) return bad("zero quaternion in the measurement");
+    pack_state(kind, m, gc.meas);
     // Omega from its packed upper triangle; Omega^-1 = L^-T L^-1 from its Cholesky factor
     double L[36] = {0}, Li[36] = {0};
     for (int i = 0, t = 0; i < de; i++)
@@ -4280,7 +4218,7 @@ int rr_pgo_gate_edges(rr_pgo *h, int32_t n_cand, const int32_t *edge_kind, const
 
 int rr_pgo_gate_times(const rr_pgo *h, double *ms) {
   if (!h || !ms) { g_last_error = "null argument"; return RR_PGO_EINVAL; }
-  return guarded([&] { h->engine->gate_times(ms); });
+  return guarded([&] { h->engine->last_query_times(EngineBase::Q_GATE, ms); });
 }
 
 static_assert(RR_PGO_GATE_JOINT_MAX_DIM == GJ_MAX_DIM && RR_PGO_GATE_JOINT_MAX_CAND == GJ_MAX_CAND, "the caps of k_gate_joint");
@@ -4309,7 +4247,7 @@ int rr_pgo_gate_joint(rr_pgo *h, int32_t n_cand, const int32_t *edge_kind, const
       for (int k = set_ptr[s]; k < set_ptr[s + 1]; k++) {
         const int c = set_cand[k];
         if (c < 0 || c >= n_cand) return bad(set + "candidate index " + std::to_string(c) + " out of range");
-        dim[s] += cand[c].kind == EDGE_SE2 ? 3 : cand[c].kind == EDGE_SE2_XY ? 2 : 6;
+        dim[s] += edge_dim(cand[c].kind);
       }
       if (dim[s] > RR_PGO_GATE_JOINT_MAX_DIM)
         return bad(set + "stacked error dimension " + std::to_string(dim[s]) + " (at most RR_PGO_GATE_JOINT_MAX_DIM = " + std::to_string(RR_PGO_GATE_JOINT_MAX_DIM) + ")");
@@ -4333,7 +4271,7 @@ int rr_pgo_gate_joint(rr_pgo *h, int32_t n_cand, const int32_t *edge_kind, const
 
 int rr_pgo_gate_joint_times(const rr_pgo *h, double *ms) {
   if (!h || !ms) { g_last_error = "null argument"; return RR_PGO_EINVAL; }
-  return guarded([&] { h->engine->gate_joint_times(ms); });
+  return guarded([&] { h->engine->last_query_times(EngineBase::Q_GATE_JOINT, ms); });
 }
 
 int rr_pgo_iterate_async(rr_pgo *h, int32_t iters) {
@@ -4369,7 +4307,7 @@ int rr_pgo_analyze_g2o(const char *path, const rr_pgo_options *opt, rr_pgo_stats
     bool io_error = false;
     const std::string err = load_g2o(path, *h->g, io_error);
     if (!err.empty()) throw ApiError(io_error ? RR_PGO_EIO : RR_PGO_EPARSE, err);
-    analyze_handle(h, opt, now_ms() - t0);
+    analyze_handle(*h, opt, now_ms() - t0);
     *out = h->stats;
   });
 }

@@ -244,6 +244,44 @@ template <typename T> struct GateArgs {
   int32_t S;
 };
 
+// A candidate's error e and Jacobians A, B (row-major D x D) at the current state, by the linearisation's own code.
+// role 0: e and A, and in 2-D also B; role 1: B of SE3 (a second lane shares the work; in 2-D it has none).
+template <typename T, int D>
+__device__ __forceinline__ void gate_linearize(const GateCand *q, const typename VecT<T>::V4 *pose, int role, T *se, T *sA, T *sB) {
+  using V4 = typename VecT<T>::V4;
+  if constexpr (D == 3) {
+    if (role == 0) {
+      const V4 z = {(T)q->meas[0], (T)q->meas[1], (T)q->meas[2], (T)q->meas[3]};
+      T e[3], A[3][3], B[3][3];
+      edge_linearize_2d<T>(q->kind, pose[q->na], pose[q->nb], z, e, A, B);
+#pragma unroll
+      for (int i = 0; i < 3; i++) {
+        se[i] = e[i];
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+          sA[i * 3 + j] = A[i][j];
+          sB[i * 3 + j] = B[i][j];
+        }
+      }
+    }
+  } else {
+    const V4 it = pose[2 * q->na], iq = pose[2 * q->na + 1], jt = pose[2 * q->nb], jq = pose[2 * q->nb + 1];
+    const T ti[3] = {it.x, it.y, it.z}, qi[4] = {iq.x, iq.y, iq.z, iq.w};
+    const T tj[3] = {jt.x, jt.y, jt.z}, qj[4] = {jq.x, jq.y, jq.z, jq.w};
+    const T tz[3] = {(T)q->meas[0], (T)q->meas[1], (T)q->meas[2]};
+    const T qz[4] = {(T)q->meas[4], (T)q->meas[5], (T)q->meas[6], (T)q->meas[7]};
+    T e[6], J[6][6];
+    edge_linearize_3d<T>(role, ti, qi, tj, qj, tz, qz, e, J);
+    T *dst = role ? sB : sA;
+#pragma unroll
+    for (int i = 0; i < 6; i++) {
+      if (role == 0) se[i] = e[i];
+#pragma unroll
+      for (int j = 0; j < 6; j++) dst[i * 6 + j] = J[i][j];
+    }
+  }
+}
+
 // the rows of the fronts from f up to (not including) `stop`, slice by slice: acc += G_r[i] G_r[j]
 template <typename T, int D, bool UA, bool UB>
 __device__ __forceinline__ T gate_walk(const TsMeta *meta, const T *Z, const int32_t *za_tab, const int32_t *zb_tab, int f, int stop,
@@ -285,45 +323,12 @@ __device__ __forceinline__ T gate_walk(const TsMeta *meta, const T *Z, const int
 template <typename T, int D>
 __global__ void __launch_bounds__(COV_THREADS) k_gate_pairs(GateArgs<T> a) {
   constexpr int NS = COV_THREADS / 64;
-  using V4 = typename VecT<T>::V4;
   __shared__ T part[NS * 32], sA[D * D], sB[D * D], se[D], sS[D * D];
   const GateCand *q = a.cand + blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63, slice = wave_index();
   const int kind = q->kind;
   const int de = kind == 1 ? 2 : D, db = kind == 1 ? 2 : D, ntri = de * (de + 1) / 2;
-  if (lane == 0 && slice < 2) {
-    if constexpr (D == 3) {
-      if (slice == 0) {
-        const V4 z = {(T)q->meas[0], (T)q->meas[1], (T)q->meas[2], (T)q->meas[3]};
-        T e[3], A[3][3], B[3][3];
-        edge_linearize_2d<T>(kind, a.pose[q->na], a.pose[q->nb], z, e, A, B);
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-          se[i] = e[i];
-#pragma unroll
-          for (int j = 0; j < 3; j++) {
-            sA[i * 3 + j] = A[i][j];
-            sB[i * 3 + j] = B[i][j];
-          }
-        }
-      }
-    } else {
-      const V4 it = a.pose[2 * q->na], iq = a.pose[2 * q->na + 1], jt = a.pose[2 * q->nb], jq = a.pose[2 * q->nb + 1];
-      const T ti[3] = {it.x, it.y, it.z}, qi[4] = {iq.x, iq.y, iq.z, iq.w};
-      const T tj[3] = {jt.x, jt.y, jt.z}, qj[4] = {jq.x, jq.y, jq.z, jq.w};
-      const T tz[3] = {(T)q->meas[0], (T)q->meas[1], (T)q->meas[2]};
-      const T qz[4] = {(T)q->meas[4], (T)q->meas[5], (T)q->meas[6], (T)q->meas[7]};
-      T e[6], J[6][6];
-      edge_linearize_3d<T>(slice, ti, qi, tj, qj, tz, qz, e, J);
-      T *dst = slice ? sB : sA;
-#pragma unroll
-      for (int i = 0; i < 6; i++) {
-        if (slice == 0) se[i] = e[i];
-#pragma unroll
-        for (int j = 0; j < 6; j++) dst[i * 6 + j] = J[i][j];
-      }
-    }
-  }
+  if (lane == 0 && slice < 2) gate_linearize<T, D>(q, a.pose, slice, se, sA, sB);
   __syncthreads();
   // ---- entry t = (i, j), j <= i, of the lower triangle; lanes past the triangle repeat its last entry
   const int t = min(lane, ntri - 1);
@@ -445,7 +450,6 @@ __device__ __forceinline__ void wave_lds_sync() {
 template <typename T, int D>
 __global__ void __launch_bounds__(COV_THREADS) k_gate_joint(JointArgs<T> a) {
   constexpr int NS = COV_THREADS / 64, MD = GJ_MAX_DIM, LD = GJ_LD, TL = GJ_TILE, RB = GJ_RB, MC = GJ_MAX_CAND;
-  using V4 = typename VecT<T>::V4;
   __shared__ T sA[MC * D * D], sB[MC * D * D], se[MC * D], sS[(MD + 1) * LD], gw[NS * RB * MD];
   __shared__ int32_t s_c[MD], s_i[MD], s_o[MC + 1];   // stacked scalar -> candidate, error row; candidate -> first scalar
   const JointSet js = a.set[blockIdx.x];
@@ -453,38 +457,8 @@ __global__ void __launch_bounds__(COV_THREADS) k_gate_joint(JointArgs<T> a) {
   const int tid = threadIdx.x, lane = tid & 63, wave = wave_index();
   const int m = js.m, Ds = js.dim;
   // ---- linearise; wave 2 lays the stacked vector out meanwhile
-  if (lane < m && wave < (D == 3 ? 1 : 2)) {
-    const GateCand *q = cq + lane;
-    if constexpr (D == 3) {
-      const V4 z = {(T)q->meas[0], (T)q->meas[1], (T)q->meas[2], (T)q->meas[3]};
-      T e[3], A[3][3], B[3][3];
-      edge_linearize_2d<T>(q->kind, a.pose[q->na], a.pose[q->nb], z, e, A, B);
-#pragma unroll
-      for (int i = 0; i < 3; i++) {
-        se[lane * 3 + i] = e[i];
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-          sA[lane * 9 + i * 3 + j] = A[i][j];
-          sB[lane * 9 + i * 3 + j] = B[i][j];
-        }
-      }
-    } else {
-      const V4 it = a.pose[2 * q->na], iq = a.pose[2 * q->na + 1], jt = a.pose[2 * q->nb], jq = a.pose[2 * q->nb + 1];
-      const T ti[3] = {it.x, it.y, it.z}, qi[4] = {iq.x, iq.y, iq.z, iq.w};
-      const T tj[3] = {jt.x, jt.y, jt.z}, qj[4] = {jq.x, jq.y, jq.z, jq.w};
-      const T tz[3] = {(T)q->meas[0], (T)q->meas[1], (T)q->meas[2]};
-      const T qz[4] = {(T)q->meas[4], (T)q->meas[5], (T)q->meas[6], (T)q->meas[7]};
-      T e[6], J[6][6];
-      edge_linearize_3d<T>(wave, ti, qi, tj, qj, tz, qz, e, J);
-      T *dst = (wave ? sB : sA) + lane * 36;
-#pragma unroll
-      for (int i = 0; i < 6; i++) {
-        if (wave == 0) se[lane * 6 + i] = e[i];
-#pragma unroll
-        for (int j = 0; j < 6; j++) dst[i * 6 + j] = J[i][j];
-      }
-    }
-  }
+  if (lane < m && wave < (D == 3 ? 1 : 2))
+    gate_linearize<T, D>(cq + lane, a.pose, wave, se + lane * D, sA + lane * D * D, sB + lane * D * D);
   if (tid == 128) {
     int o = 0;
     for (int c = 0; c < m; c++) {

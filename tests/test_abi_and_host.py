@@ -480,6 +480,18 @@ def test_replayed_dissections_are_the_computed_ones(tmp_path):
     assert out.returncode == 0 and "replayed == computed for every depth" in out.stdout, out.stdout + out.stderr
 
 
+def test_state_packing_is_exact_and_round_trips(tmp_path):
+    """host_graph.h, pack_state / unpack_state: the ONE definition of the device form of states and measurements (SE2 x, y, cos,
+    sin; XY x, y, 0, 0; SE3 t, 0 | q / |q|) against an independent restatement, compared with ==; unpack of pack returns the
+    position and the normalised quaternion exactly and atan2's own angle; both return node_state_len(kind)
+    (tests/native/pack_state_check.cpp)."""
+    exe = tmp_path / "pack_state_check"
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I", CSRC,
+                           os.path.join(ROOT, "tests", "native", "pack_state_check.cpp"), "-o", str(exe)])
+    out = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert out.returncode == 0 and "pack and unpack agree with the restated device form" in out.stdout, out.stdout + out.stderr
+
+
 def test_algorithmic_bytes_follow_survey_8d(lib):
     """SURVEY.md 8(d), worked totals for intel.g2o in fp64: linearise 0.90 MB, solve 0.43 + 3 x 1.24 + 0.17 = 4.3 MB with
     nnzblk(L) = 17 193 [probe], update 0.12 MB -- 5.4 MB per iteration with chi2 fused into the linearisation.  The
