@@ -1,12 +1,12 @@
 // kernels.hip.h -- gfx950 device code for the pose-graph Gauss-Newton path.
 //
-//   k_linearize      error + Jacobians + J^T W J / J^T W e + chi2     (reference :434-486,165-192,537-574)
+//   k_linearize      error + Jacobians + J^T W J / J^T W e + chi2     (reference :434-486,165-192,537-574); D = 3: SE(2), 6: SE(3)
 //   k_factor_tasks   multifrontal supernodal Cholesky, fronts in LDS  (replaces umfpack.factorize, :138)
 //   k_solve_tasks    back substitution down the supernode tree         (replaces umfpack.solve, :141)
-//   k_update         update_nodes + |dx|^2                             (reference :229-245,273)
+//   k_update         update_nodes + |dx|^2                             (reference :229-245,273); D as k_linearize
 //   k_finalize_slot  fixed-order reduction of the chi2 / |dx|^2 partials (pgo_api.hip)
 //   k_big_* / k_solve_mid / k_big_flow (flow.hip.h)  fronts beyond LDS (see "huge fronts" below)
-//   k_linearize_se3 / k_update_se3, k_pack_boundary / k_pack_shared / k_sum_shared   SE(3), sharding over ranks
+//   k_pack_boundary / k_pack_shared / k_sum_shared   sharding over ranks
 //
 // Wavefront = 64 lanes.  Cross-workgroup dependencies are kernel boundaries on one stream -- except inside the dataflow
 // launches (k_factor_flow / k_solve_flow, lds_flow.hip.h; k_big_flow / k_big_solve_flow, flow.hip.h), whose workgroups hand
@@ -154,19 +154,18 @@ template <typename TC> struct EdgeRec {
 static_assert(sizeof(EdgeRec<float>) == 64 && sizeof(EdgeRec<double>) == 128, "EdgeRec is four / eight sixteen-byte loads of one line");
 template <typename T, typename TC = T> struct LinArgs {
   int n_nodes;
-  const EdgeRec<TC> *e_rec;              // per edge: what the arrays below hold, as one record (k_linearize reads this)
-  const typename VecT<TC>::V4 *pose;     // x, y, cos, sin  (XY landmarks: x, y, -, -)
+  const typename VecT<TC>::V4 *pose;     // SE(2): x, y, cos, sin  (XY landmarks: x, y, -, -); SE(3): 2 per node, (tx,ty,tz,-), (qx,qy,qz,qw)
+  const EdgeRec<TC> *e_rec;              // SE(2): every edge as one record; SE(3) keeps the four arrays below
   const int2 *e_idx;                     // from, to
-  const typename VecT<TC>::V4 *e_meas;   // SE2: x, y, cos, sin | SE2_XY: x, y, 0, 0
-  const typename VecT<TC>::V4 *e_info_a; // i11 i12 i13 i22
-  const typename VecT<TC>::V2 *e_info_b; // i23 i33
+  const typename VecT<TC>::V4 *e_meas;   // 2 per edge, packed like a pose
+  const TC *e_info;                      // 21 per edge, row-major upper triangle
   const int64_t *e_slot;                 // (offset into hvals << 1) | transposed
   const int32_t *inc_ptr;
   const int2 *inc_list;                  // per incidence: (edge << 4 | offdiag << 3 | owns << 2 | kind << 1 | role, the OTHER endpoint's node) --
                                          // the far pose is requested together with the edge record, not after it (sharded runs: see Engine)
   const int32_t *node_list;              // sharded runs: the nodes this rank linearises (own + shared), else null;
                                          // n_nodes is then the length of the list
-  const uint8_t *node_dim;               // 3 (SE2) or 2 (XY)
+  const uint8_t *node_dim;               // SE(2): 3 (pose) or 2 (XY landmark); SE(3) does not read it
   const int32_t *node_offset;            // reference scalar offset
   const int64_t *diag_off;
   T *hvals;
@@ -203,6 +202,10 @@ template <typename A> __device__ __forceinline__ void opt_reset_in_first_thread(
     a.ctrl->reject = 0;
     a.err[1] = 0;
   }
+}
+// the node of a launch's slot-th thread group (sharded runs: through the rank's node list), -1 past the end
+template <typename A> __device__ __forceinline__ int listed_node(const A &a, int slot) {
+  return slot < a.n_nodes ? (a.node_list ? a.node_list[slot] : slot) : -1;
 }
 
 // ---------------------------------------------------------------- factor maths
@@ -254,6 +257,141 @@ template <typename T> __device__ __forceinline__ T edge_chi2_2d(const T W[3][3],
   const T we1 = W[1][0] * e[0] + W[1][1] * e[1] + W[1][2] * e[2];
   const T we2 = W[2][0] * e[0] + W[2][1] * e[1] + W[2][2] * e[2];
   return e[0] * we0 + e[1] * we1 + e[2] * we2;
+}
+
+// ---- SE(3)
+// NOT reference behaviour: the reference's SE(3) path is todo!() (pose_graph_optimization.rs:241,
+// 357,570; SURVEY F4).  Build-defined, g2o file convention, identical to the oracle's definition:
+//   E = Z^-1 * Xi^-1 * Xj ,  e = [ t_E ; sign(w_E) * vec(q_E) ]                (6 scalars)
+//   update  X <- X * (dt, Exp(dw)) :  t += R dt ,  q <- q (x) exp(dw)            (right increments)
+// Jacobians (cf. the structure hinted at :488-514: A = [-Ra, Ra*skew(t_b); 0, ..], B = [Re, 0; 0, ..]):
+//   B = [ R_E , 0 ; 0 , (s/2)(w_E I + [v_E]x) ]
+//   A = [ -Rz^T , Rz^T [t_C]x ; 0 , -(s/2) vec3x3( L(q_z^-1) R(q_C) ) ] ,  C = Xi^-1 Xj
+// e^T W e of one SE(3) edge
+template <typename T> __device__ __forceinline__ T edge_chi2_3d(const T W[6][6], const T e[6]) {
+  T c2 = 0;
+#pragma unroll
+  for (int i = 0; i < 6; i++) {
+    T we = 0;
+#pragma unroll
+    for (int r = 0; r < 6; r++) we += W[i][r] * e[r];
+    c2 += e[i] * we;
+  }
+  return c2;
+}
+
+template <typename T> __device__ __forceinline__ void q_mul(const T a[4], const T b[4], T r[4]) {
+  r[0] = a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1];
+  r[1] = a[3] * b[1] - a[0] * b[2] + a[1] * b[3] + a[2] * b[0];
+  r[2] = a[3] * b[2] + a[0] * b[1] - a[1] * b[0] + a[2] * b[3];
+  r[3] = a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2];
+}
+template <typename T> __device__ __forceinline__ void q_rot(const T q[4], const T v[3], T r[3]) {
+  const T cx = q[1] * v[2] - q[2] * v[1], cy = q[2] * v[0] - q[0] * v[2], cz = q[0] * v[1] - q[1] * v[0];
+  const T dx = q[1] * cz - q[2] * cy, dy = q[2] * cx - q[0] * cz, dz = q[0] * cy - q[1] * cx;
+  r[0] = v[0] + 2 * (q[3] * cx + dx);
+  r[1] = v[1] + 2 * (q[3] * cy + dy);
+  r[2] = v[2] + 2 * (q[3] * cz + dz);
+}
+template <typename T> __device__ __forceinline__ void q_to_rot(const T q[4], T R[3][3]) {
+  const T x = q[0], y = q[1], z = q[2], w = q[3];
+  R[0][0] = 1 - 2 * (y * y + z * z); R[0][1] = 2 * (x * y - z * w);     R[0][2] = 2 * (x * z + y * w);
+  R[1][0] = 2 * (x * y + z * w);     R[1][1] = 1 - 2 * (x * x + z * z); R[1][2] = 2 * (y * z - x * w);
+  R[2][0] = 2 * (x * z - y * w);     R[2][1] = 2 * (y * z + x * w);     R[2][2] = 1 - 2 * (x * x + y * y);
+}
+
+// error (6) and the requested Jacobian (role 0: A w.r.t. Xi, role 1: B w.r.t. Xj), 6 x 6 row-major
+template <typename T>
+__device__ void edge_linearize_3d(int role, const T ti[3], const T qi[4], const T tj[3], const T qj[4],
+                                  const T tz[3], const T qz[4], T e[6], T J[6][6]) {
+  const T qic[4] = {-qi[0], -qi[1], -qi[2], qi[3]};
+  const T qzc[4] = {-qz[0], -qz[1], -qz[2], qz[3]};
+  // C = Xi^-1 Xj
+  T d[3] = {tj[0] - ti[0], tj[1] - ti[1], tj[2] - ti[2]}, tC[3], qC[4];
+  q_rot(qic, d, tC);
+  q_mul(qic, qj, qC);
+  // E = Z^-1 C
+  T d2[3] = {tC[0] - tz[0], tC[1] - tz[1], tC[2] - tz[2]}, tE[3], qE[4];
+  q_rot(qzc, d2, tE);
+  q_mul(qzc, qC, qE);
+  const T sgn = qE[3] < 0 ? (T)-1 : (T)1;
+  e[0] = tE[0]; e[1] = tE[1]; e[2] = tE[2];
+  e[3] = sgn * qE[0]; e[4] = sgn * qE[1]; e[5] = sgn * qE[2];
+#pragma unroll
+  for (int r = 0; r < 6; r++)
+#pragma unroll
+    for (int c = 0; c < 6; c++) J[r][c] = 0;
+  if (role) {
+    T RE[3][3];
+    q_to_rot(qE, RE);
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+#pragma unroll
+      for (int c = 0; c < 3; c++) J[r][c] = RE[r][c];
+    const T h = (T)0.5 * sgn, w = qE[3], vx = qE[0], vy = qE[1], vz = qE[2];
+    J[3][3] = h * w;   J[3][4] = -h * vz; J[3][5] = h * vy;
+    J[4][3] = h * vz;  J[4][4] = h * w;   J[4][5] = -h * vx;
+    J[5][3] = -h * vy; J[5][4] = h * vx;  J[5][5] = h * w;
+  } else {
+    T RZt[3][3];
+    q_to_rot(qzc, RZt);   // rotation of Z^-1 = Rz^T
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+#pragma unroll
+      for (int c = 0; c < 3; c++) J[r][c] = -RZt[r][c];
+      // Rz^T [tC]x : column k = Rz^T (tC x e_k)... [tC]x u = tC x u
+      J[r][3] = RZt[r][1] * tC[2] - RZt[r][2] * tC[1];
+      J[r][4] = RZt[r][2] * tC[0] - RZt[r][0] * tC[2];
+      J[r][5] = RZt[r][0] * tC[1] - RZt[r][1] * tC[0];
+    }
+    // d vec(q_E)/d dw_i = -(1/2) vec( qz^-1 (x) (u,0) (x) qC ), column by column
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+      T u[4] = {k == 0 ? (T)1 : (T)0, k == 1 ? (T)1 : (T)0, k == 2 ? (T)1 : (T)0, (T)0}, t1[4], t2[4];
+      q_mul(qzc, u, t1);
+      q_mul(t1, qC, t2);
+      J[3][3 + k] = (T)-0.5 * sgn * t2[0];
+      J[4][3 + k] = (T)-0.5 * sgn * t2[1];
+      J[5][3 + k] = (T)-0.5 * sgn * t2[2];
+    }
+  }
+}
+
+// ---- operand loaders: the one definition of each unpacking
+template <typename T> __device__ __forceinline__ void info_2d(const EdgeRec<T> &rec, T (&W)[3][3]) {
+  const typename VecT<T>::V4 wa = rec.info_a;
+  const typename VecT<T>::V2 wb = rec.info_b;
+  W[0][0] = wa.x; W[0][1] = wa.y; W[0][2] = wa.z;
+  W[1][0] = wa.y; W[1][1] = wa.w; W[1][2] = wb.x;
+  W[2][0] = wa.z; W[2][1] = wb.x; W[2][2] = wb.y;
+}
+template <typename T> __device__ __forceinline__ void info_3d(const T *w, T (&W)[6][6]) {   // 21 entries, row-major upper triangle
+  int t = 0;
+#pragma unroll
+  for (int i = 0; i < 6; i++)
+#pragma unroll
+    for (int j = i; j < 6; j++) { W[i][j] = w[t]; W[j][i] = w[t]; t++; }
+}
+template <typename T>
+__device__ __forceinline__ void pose_3d(const typename VecT<T>::V4 &vt, const typename VecT<T>::V4 &vq, T (&t)[3], T (&q)[4]) {
+  t[0] = vt.x; t[1] = vt.y; t[2] = vt.z;
+  q[0] = vq.x; q[1] = vq.y; q[2] = vq.z; q[3] = vq.w;
+}
+template <int D, typename T> __device__ __forceinline__ T edge_chi2(const T (&W)[D][D], const T (&e)[D]) {
+  if constexpr (D == 3) return edge_chi2_2d<T>(W, e);
+  else return edge_chi2_3d<T>(W, e);
+}
+// sum over r of a[r] * b[r * sb], in the order each dimension has always summed it: the 2-D forms are written out and start
+// from the first product, the SE(3) loops start from zero (the two differ in the sign of a zero)
+template <int D, typename T> __device__ __forceinline__ T row_dot(const T *a, const T *b, int sb) {
+  if constexpr (D == 3) {
+    return a[0] * b[0] + a[1] * b[sb] + a[2] * b[2 * sb];
+  } else {
+    T s = 0;
+#pragma unroll
+    for (int r = 0; r < D; r++) s += a[r] * b[r * sb];
+    return s;
+  }
 }
 
 // Robust kernels (include/rr_pgo.h, rr_pgo_set_robust_kernel): rho(s) and the IRLS weight w = rho'(s) at s = e^T W e.
@@ -447,17 +585,19 @@ template <typename A> __device__ __forceinline__ void opt_publish_chi2_in_last_b
   }
 }
 
-// One group of LIN_GROUP lanes per node pulls the node's incident edges
-// (deterministic: no atomics, fixed summation order), builds the node's
-// diagonal block and right-hand side; the lane holding an edge in its `from`
-// role also writes the off-diagonal block and the edge's chi2 term.
+// The pull form, SE(2) (D = 3) and SE(3) (D = 6) in one frame.  One group of LIN_GROUP lanes per node pulls the node's
+// incident edges (deterministic: no atomics, fixed summation order), builds the node's diagonal block and right-hand
+// side; the lane holding an edge in its `from` role also writes the off-diagonal block and the edge's chi2 term.
+// Per dimension: loading the operands, the call of edge_linearize_2d / _3d, B for the off-diagonal block, and the
+// store layout of the blocks (an XY landmark's 2 x 2 / 3 x 2 blocks, the transposed slot).  Everything else exists once.
 // RK: the robust kernel (ROBUST_*).  Every incidence of a robustified edge computes s = e^T W e and scales W by w(s) before
 // J^T W is formed, so the diagonal block, the right-hand side and the off-diagonal block all carry the weight; both endpoints'
 // lanes compute e from the same operands, hence the same w.  The from-role lane adds rho(s) to chi2.
-template <typename TO, typename T, int RK = ROBUST_NONE>
+template <typename TO, typename T, int RK = ROBUST_NONE, int D = 3>
 __global__ void __launch_bounds__(LIN_THREADS) k_linearize(LinArgs<TO, T> a) {
   using V4 = typename VecT<T>::V4;
-  using V2 = typename VecT<T>::V2;
+  constexpr int NV = D / 3;             // V4s per node and per measurement
+  constexpr int NT = D * (D + 1) / 2;   // lower triangle of the diagonal block, row-major: (0,0),(1,0),(1,1),...
   __shared__ double red[LIN_THREADS / 64];
   const int gid = blockIdx.x * LIN_THREADS + threadIdx.x;
   for (int i = gid; i < a.n_zero_words; i += gridDim.x * LIN_THREADS) a.zero_words[i] = 0u;
@@ -466,14 +606,19 @@ __global__ void __launch_bounds__(LIN_THREADS) k_linearize(LinArgs<TO, T> a) {
   const LinPre lin_pre = opt_publish_preload(a);
   const T lambda = a.lambda_from_ctrl ? (T)a.ctrl->lambda : a.lambda;
   const int slot = gid / LIN_GROUP, sub = gid % LIN_GROUP;
-  const int node = slot < a.n_nodes ? (a.node_list ? a.node_list[slot] : slot) : -1;
+  const int node = listed_node(a, slot);
   double chi = 0.0;
-  T hd[6] = {0, 0, 0, 0, 0, 0};  // 00 10 11 20 21 22
-  T bv[3] = {0, 0, 0};
-  int nd = 0;
+  T hd[NT], bv[D];
+#pragma unroll
+  for (int t = 0; t < NT; t++) hd[t] = 0;
+#pragma unroll
+  for (int t = 0; t < D; t++) bv[t] = 0;
+  int nd = D;
   if (node >= 0) {
-    nd = a.node_dim[node];
-    const V4 self = a.pose[node];
+    if constexpr (D == 3) nd = a.node_dim[node];
+    V4 self[NV];
+#pragma unroll
+    for (int v = 0; v < NV; v++) self[v] = a.pose[NV * node + v];
     const int q1 = a.inc_ptr[node + 1];
     for (int q = a.inc_ptr[node] + sub; q < q1; q += LIN_GROUP) {
       const int2 inc = a.inc_list[q];
@@ -483,98 +628,139 @@ __global__ void __launch_bounds__(LIN_THREADS) k_linearize(LinArgs<TO, T> a) {
       // two shared nodes is written by every rank (bit 3)
       if (!(ent & 12)) continue;
       const bool owns = ent & 4;
-      const int k = ent >> 4, kind = (ent >> 1) & 1, role = ent & 1;
-      const EdgeRec<T> rec = a.e_rec[k];
-      const V4 other = a.pose[inc.y];
-      const V4 z = rec.meas;
-      const V4 wa = rec.info_a;
-      const V2 wb = rec.info_b;
-      T W[3][3] = {{wa.x, wa.y, wa.z}, {wa.y, wa.w, wb.x}, {wa.z, wb.x, wb.y}};
-      T e[3], A[3][3], B[3][3];
-      edge_linearize_2d<T>(kind, role ? other : self, role ? self : other, z, e, A, B);
+      const int k = ent >> 4, role = ent & 1;
+      // ---- per dimension: the operands, e and J = the Jacobian of this endpoint (A in the from role, B in the to role)
+      T W[D][D], e[D], J[D][D];
+      [[maybe_unused]] EdgeRec<T> rec;                                 // SE(2)
+      [[maybe_unused]] T B2[3][3];                                     // SE(2): B comes with A
+      [[maybe_unused]] T ts[3], qs[4], to[3], qo[4], tz[3], qz[4];     // SE(3): B is evaluated where it is needed
+      if constexpr (D == 3) {
+        rec = a.e_rec[k];
+        const V4 other = a.pose[inc.y];
+        info_2d<T>(rec, W);
+        T A[3][3];
+        edge_linearize_2d<T>((ent >> 1) & 1, role ? other : self[0], role ? self[0] : other, rec.meas, e, A, B2);
+#pragma unroll
+        for (int r = 0; r < 3; r++)
+#pragma unroll
+          for (int c = 0; c < 3; c++) J[r][c] = role ? B2[r][c] : A[r][c];
+      } else {
+        pose_3d<T>(self[0], self[1], ts, qs);
+        pose_3d<T>(a.pose[2 * inc.y], a.pose[2 * inc.y + 1], to, qo);
+        pose_3d<T>(a.e_meas[2 * k], a.e_meas[2 * k + 1], tz, qz);
+        info_3d<T>(a.e_info + (int64_t)k * 21, W);
+        if (role) edge_linearize_3d<T>(1, to, qo, ts, qs, tz, qz, e, J);
+        else edge_linearize_3d<T>(0, ts, qs, to, qo, tz, qz, e, J);
+      }
+      // ---- the frame
       T s_rob = 0;
       bool rob = false;
       if constexpr (RK != ROBUST_NONE) {
-        s_rob = edge_chi2_2d<T>(W, e);
+        s_rob = edge_chi2<D, T>(W, e);
         rob = !a.robust_mask || a.robust_mask[k];
         if (rob) {   // masked-off edges keep W as it is
           const T w = robust_weight<RK, T>(s_rob, a.robust_delta, a.robust_delta2);
 #pragma unroll
-          for (int i = 0; i < 3; i++)
+          for (int i = 0; i < D; i++)
 #pragma unroll
-            for (int j = 0; j < 3; j++) W[i][j] *= w;
+            for (int j = 0; j < D; j++) W[i][j] *= w;
         }
       }
-      // J = A (from role) or B (to role);  JW = J^T W
-      T JW[3][3];
+      T JW[D][D];   // J^T W
 #pragma unroll
-      for (int i = 0; i < 3; i++)
+      for (int i = 0; i < D; i++)
 #pragma unroll
-        for (int j = 0; j < 3; j++) {
+        for (int j = 0; j < D; j++) {
           T s = 0;
 #pragma unroll
-          for (int r = 0; r < 3; r++) s += (role ? B[r][i] : A[r][i]) * W[r][j];
+          for (int r = 0; r < D; r++) s += J[r][i] * W[r][j];
           JW[i][j] = s;
         }
       if (a.write_system && owns) {
         int t = 0;
 #pragma unroll
-        for (int i = 0; i < 3; i++)
+        for (int i = 0; i < D; i++)
 #pragma unroll
           for (int j = 0; j <= i; j++) {
             T s = 0;
 #pragma unroll
-            for (int r = 0; r < 3; r++) s += JW[i][r] * (role ? B[r][j] : A[r][j]);
+            for (int r = 0; r < D; r++) s += JW[i][r] * J[r][j];
             hd[t++] += s;
           }
 #pragma unroll
-        for (int i = 0; i < 3; i++) bv[i] += JW[i][0] * e[0] + JW[i][1] * e[1] + JW[i][2] * e[2];
+        for (int i = 0; i < D; i++) bv[i] += row_dot<D, T>(JW[i], e, 1);
       }
       if (role == 0) {
         // chi2 term e^T W e (:555,568), accumulated in f64; rho(e^T W e) under a robust kernel
         if constexpr (RK == ROBUST_NONE) {
-          if (owns) chi += (double)edge_chi2_2d<T>(W, e);   // every edge's term is owned by one rank
+          if (owns) chi += (double)edge_chi2<D, T>(W, e);   // every edge's term is owned by one rank
         } else {
           if (owns) chi += (double)(rob ? robust_rho<RK, T>(s_rob, a.robust_delta, a.robust_delta2) : s_rob);
         }
         if (a.write_system && (ent & 8)) {
-          // off-diagonal block H[from rows, to cols] = A^T W B
-          const int64_t so = rec.slot;
-          TO *dst = a.hvals + (so >> 1);
-          const bool tr = so & 1;
-          const int d2 = kind ? 2 : 3;
+          // ---- per dimension: the off-diagonal block H[from rows, to cols] = A^T W B and where it goes
+          if constexpr (D == 3) {
+            const int64_t so = rec.slot;
+            TO *dst = a.hvals + (so >> 1);
+            const bool tr = so & 1;
+            const int d2 = ((ent >> 1) & 1) ? 2 : 3;
 #pragma unroll
-          for (int i = 0; i < 3; i++)
+            for (int i = 0; i < 3; i++)
 #pragma unroll
-            for (int j = 0; j < 3; j++) {
-              if (j >= d2) continue;
-              T s = JW[i][0] * B[0][j] + JW[i][1] * B[1][j] + JW[i][2] * B[2][j];
-              dst[tr ? j * 3 + i : i * d2 + j] = (TO)s;
-            }
+              for (int j = 0; j < 3; j++) {
+                if (j >= d2) continue;
+                dst[tr ? j * 3 + i : i * d2 + j] = (TO)row_dot<3, T>(JW[i], &B2[0][j], 3);
+              }
+          } else {
+            T e2[6], Bm[6][6];
+            edge_linearize_3d<T>(1, ts, qs, to, qo, tz, qz, e2, Bm);
+            const int64_t so = a.e_slot[k];
+            TO *dst = a.hvals + (so >> 1);
+            const bool tr = so & 1;
+#pragma unroll
+            for (int i = 0; i < 6; i++)
+#pragma unroll
+              for (int j = 0; j < 6; j++) dst[tr ? j * 6 + i : i * 6 + j] = (TO)row_dot<6, T>(JW[i], &Bm[0][j], 6);
+          }
         }
       }
     }
   }
   if (a.write_system) {
 #pragma unroll
-    for (int t = 0; t < 6; t++) hd[t] = group_sum8(hd[t]);
+    for (int t = 0; t < NT; t++) hd[t] = group_sum8(hd[t]);
 #pragma unroll
-    for (int t = 0; t < 3; t++) bv[t] = group_sum8(bv[t]);
+    for (int t = 0; t < D; t++) bv[t] = group_sum8(bv[t]);
     if (node >= 0 && sub == 0) {
       T add = lambda;
       if (node == a.anchor) add += (T)10000000.0;
       if (a.adds_diag && !a.adds_diag[node]) add = 0;
+      // ---- per dimension: the diagonal block's layout
       TO *d = a.hvals + a.diag_off[node];
-      if (nd == 3) {
-        d[0] = (TO)(hd[0] + add); d[1] = (TO)hd[1];         d[2] = (TO)hd[3];
-        d[3] = (TO)hd[1];         d[4] = (TO)(hd[2] + add); d[5] = (TO)hd[4];
-        d[6] = (TO)hd[3];         d[7] = (TO)hd[4];         d[8] = (TO)(hd[5] + add);
+      if constexpr (D == 3) {
+        if (nd == 3) {
+          d[0] = (TO)(hd[0] + add); d[1] = (TO)hd[1];         d[2] = (TO)hd[3];
+          d[3] = (TO)hd[1];         d[4] = (TO)(hd[2] + add); d[5] = (TO)hd[4];
+          d[6] = (TO)hd[3];         d[7] = (TO)hd[4];         d[8] = (TO)(hd[5] + add);
+        } else {
+          d[0] = (TO)(hd[0] + add); d[1] = (TO)hd[1];
+          d[2] = (TO)hd[1];         d[3] = (TO)(hd[2] + add);
+        }
       } else {
-        d[0] = (TO)(hd[0] + add); d[1] = (TO)hd[1];
-        d[2] = (TO)hd[1];         d[3] = (TO)(hd[2] + add);
+        int t = 0;
+#pragma unroll
+        for (int i = 0; i < 6; i++)
+#pragma unroll
+          for (int j = 0; j <= i; j++) {
+            const T v = hd[t++] + (i == j ? add : (T)0);
+            d[i * 6 + j] = (TO)v;
+            d[j * 6 + i] = (TO)v;
+          }
       }
       TO *bo = a.b + a.node_offset[node];
-      for (int t = 0; t < nd; t++) bo[t] = (TO)(-bv[t]);
+#pragma unroll
+      for (int t = 0; t < D; t++)
+        if (t < nd) bo[t] = (TO)(-bv[t]);
     }
   }
   double tot = block_sum<double, LIN_THREADS>(chi, red);
@@ -618,25 +804,17 @@ __global__ void __launch_bounds__(256) k_lin_finish(LinArgs<TO, T> a) {
 template <typename TO, typename T>
 __global__ void __launch_bounds__(LIN_THREADS) k_linearize_edges(LinArgs<TO, T> a, int n_edges) {
   using V4 = typename VecT<T>::V4;
-  using V2 = typename VecT<T>::V2;
   __shared__ double red[LIN_THREADS / 64];
   const int k = blockIdx.x * LIN_THREADS + threadIdx.x;
   const int lane = threadIdx.x & 63;
   const bool live = k < n_edges;
-  const int kc = live ? k : n_edges - 1;
-  const int2 ft = a.e_idx[kc];
-  const int kind = a.node_dim[ft.y] == 2 ? 1 : 0;   // an XY landmark is always the `to` end (g2o.rs:98-115)
-  const V4 x1 = a.pose[ft.x], x2 = a.pose[ft.y];
-  const V4 z = a.e_meas[kc];
-  const V4 wa = a.e_info_a[kc];
-  const V2 wb = a.e_info_b[kc];
-  const T W[3][3] = {{wa.x, wa.y, wa.z}, {wa.y, wa.w, wb.x}, {wa.z, wb.x, wb.y}};
-  T e[3], A[3][3], B[3][3];
-  edge_linearize_2d<T>(kind, x1, x2, z, e, A, B);
-  const T we0 = W[0][0] * e[0] + W[0][1] * e[1] + W[0][2] * e[2];
-  const T we1 = W[1][0] * e[0] + W[1][1] * e[1] + W[1][2] * e[2];
-  const T we2 = W[2][0] * e[0] + W[2][1] * e[1] + W[2][2] * e[2];
-  double chi = live ? (double)(e[0] * we0 + e[1] * we1 + e[2] * we2) : 0.0;
+  const EdgeRec<T> rec = a.e_rec[live ? k : n_edges - 1];
+  const int kind = a.node_dim[rec.to] == 2 ? 1 : 0;   // an XY landmark is always the `to` end (g2o.rs:98-115)
+  const V4 x1 = a.pose[rec.from], x2 = a.pose[rec.to];
+  T W[3][3], e[3], A[3][3], B[3][3];
+  info_2d<T>(rec, W);
+  edge_linearize_2d<T>(kind, x1, x2, rec.meas, e, A, B);
+  double chi = live ? (double)edge_chi2_2d<T>(W, e) : 0.0;
   if (a.write_system) {
     T AW[3][3], BW[3][3];   // J^T W
 #pragma unroll
@@ -670,7 +848,7 @@ __global__ void __launch_bounds__(LIN_THREADS) k_linearize_edges(LinArgs<TO, T> 
     }
     if (live) {
       // off-diagonal block H[from rows, to cols] = A^T W B
-      const int64_t so = a.e_slot[k];
+      const int64_t so = rec.slot;
       TO *dst = a.hvals + (so >> 1);
       const bool tr = so & 1;
       const int d2 = kind ? 2 : 3;
@@ -684,7 +862,7 @@ __global__ void __launch_bounds__(LIN_THREADS) k_linearize_edges(LinArgs<TO, T> 
         }
     }
     // from-node terms: segmented inclusive scan over the wave (head flag = first lane of a run of equal `from`)
-    const int key = live ? ft.x : -1;
+    const int key = live ? rec.from : -1;
     const int kprev = __shfl_up(key, 1);
     bool head = lane == 0 || kprev != key;
 #pragma unroll
@@ -714,8 +892,8 @@ __global__ void __launch_bounds__(LIN_THREADS) k_linearize_edges(LinArgs<TO, T> 
         unsafeAtomicAdd(bo + 0, (TO)f[6]); unsafeAtomicAdd(bo + 1, (TO)f[7]);
       }
     };
-    if (tail) add_node(ft.x, fa);
-    if (live) add_node(ft.y, fb);
+    if (tail) add_node(rec.from, fa);
+    if (live) add_node(rec.to, fb);
   }
   const double tot = block_sum<double, LIN_THREADS>(chi, red);
   if (threadIdx.x == 0) a.chi2_partial[blockIdx.x] = tot;
@@ -738,7 +916,6 @@ template <typename T> __device__ __forceinline__ void lds_atomic_add(T *p, T v) 
 template <typename TO, typename T>
 __global__ void __launch_bounds__(256) k_linearize_wave_edges(LinArgs<TO, T> a, int n_edges) {
   using V4 = typename VecT<T>::V4;
-  using V2 = typename VecT<T>::V2;
   __shared__ int slot_node[WE_SLOTS];
   __shared__ T slot_acc[WE_SLOTS][9];     // 00 10 11 20 21 22 of J^T W J, then -J^T W e
   __shared__ T stage[4][40];              // per wave: A (9) | B (9) | W (9) | e (3) | W e (3)
@@ -759,10 +936,8 @@ __global__ void __launch_bounds__(256) k_linearize_wave_edges(LinArgs<TO, T> a, 
     const EdgeRec<T> rec = a.e_rec[k];
     const int kind = a.node_dim[rec.to] == 2 ? 1 : 0;
     const V4 x1 = a.pose[rec.from], x2 = a.pose[rec.to];
-    const V4 wa = rec.info_a;
-    const V2 wb = rec.info_b;
-    const T W[3][3] = {{wa.x, wa.y, wa.z}, {wa.y, wa.w, wb.x}, {wa.z, wb.x, wb.y}};
-    T e[3], A[3][3], B[3][3];
+    T W[3][3], e[3], A[3][3], B[3][3];
+    info_2d<T>(rec, W);
     edge_linearize_2d<T>(kind, x1, x2, rec.meas, e, A, B);
     // stage the operands (every lane holds the same values: lane q of the first 39 writes entry q)
     T mine = 0;
@@ -847,280 +1022,6 @@ __global__ void __launch_bounds__(256) k_linearize_wave_edges(LinArgs<TO, T> a, 
   if (threadIdx.x == 0) a.chi2_partial[blockIdx.x] = tot;
 }
 
-// ------------------------------------------------------------------ SE(3)
-// NOT reference behaviour: the reference's SE(3) path is todo!() (pose_graph_optimization.rs:241,
-// 357,570; SURVEY F4).  Build-defined, g2o file convention, identical to the oracle's definition:
-//   E = Z^-1 * Xi^-1 * Xj ,  e = [ t_E ; sign(w_E) * vec(q_E) ]                (6 scalars)
-//   update  X <- X * (dt, Exp(dw)) :  t += R dt ,  q <- q (x) exp(dw)            (right increments)
-// Jacobians (cf. the structure hinted at :488-514: A = [-Ra, Ra*skew(t_b); 0, ..], B = [Re, 0; 0, ..]):
-//   B = [ R_E , 0 ; 0 , (s/2)(w_E I + [v_E]x) ]
-//   A = [ -Rz^T , Rz^T [t_C]x ; 0 , -(s/2) vec3x3( L(q_z^-1) R(q_C) ) ] ,  C = Xi^-1 Xj
-template <typename T, typename TC = T> struct LinArgs3 {
-  int n_nodes;
-  const typename VecT<TC>::V4 *pose;    // 2 per node: (tx,ty,tz,-), (qx,qy,qz,qw)
-  const int2 *e_idx;
-  const typename VecT<TC>::V4 *e_meas;  // 2 per edge, same packing
-  const TC *e_info;                     // 21 per edge, row-major upper triangle
-  const int64_t *e_slot;
-  const int32_t *inc_ptr;
-  const int2 *inc_list;                 // as LinArgs::inc_list: (edge << 4 | offdiag << 3 | owns << 2 | role, the other endpoint's node)
-  const int32_t *node_list;             // sharded runs: the nodes this rank linearises, else null
-  const int32_t *node_offset;
-  const int64_t *diag_off;
-  T *hvals;
-  T *b;
-  double *chi2_partial;
-  int anchor;
-  TC lambda;
-  int write_system;
-  const uint8_t *adds_diag;             // sharded runs: per node, 1 = this rank adds prior / lambda
-  unsigned *zero_words;                 // as LinArgs::zero_words
-  int n_zero_words;
-  unsigned *fill_words;                 // as LinArgs::fill_words
-  int n_fill_words;
-  OptCtrl *ctrl;                        // as LinArgs::ctrl ...
-  int lambda_from_ctrl, reset_ctrl;
-  double reset_lambda, reset_tolerance;
-  int *err;
-  int publish;
-  OptSlot *ring_host;
-  int *blocks_done;
-  TC robust_delta, robust_delta2;       // as LinArgs
-  const uint8_t *robust_mask;
-};
-
-// e^T W e of one SE(3) edge
-template <typename T> __device__ __forceinline__ T edge_chi2_3d(const T W[6][6], const T e[6]) {
-  T c2 = 0;
-#pragma unroll
-  for (int i = 0; i < 6; i++) {
-    T we = 0;
-#pragma unroll
-    for (int r = 0; r < 6; r++) we += W[i][r] * e[r];
-    c2 += e[i] * we;
-  }
-  return c2;
-}
-
-template <typename T> __device__ __forceinline__ void q_mul(const T a[4], const T b[4], T r[4]) {
-  r[0] = a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1];
-  r[1] = a[3] * b[1] - a[0] * b[2] + a[1] * b[3] + a[2] * b[0];
-  r[2] = a[3] * b[2] + a[0] * b[1] - a[1] * b[0] + a[2] * b[3];
-  r[3] = a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2];
-}
-template <typename T> __device__ __forceinline__ void q_rot(const T q[4], const T v[3], T r[3]) {
-  const T cx = q[1] * v[2] - q[2] * v[1], cy = q[2] * v[0] - q[0] * v[2], cz = q[0] * v[1] - q[1] * v[0];
-  const T dx = q[1] * cz - q[2] * cy, dy = q[2] * cx - q[0] * cz, dz = q[0] * cy - q[1] * cx;
-  r[0] = v[0] + 2 * (q[3] * cx + dx);
-  r[1] = v[1] + 2 * (q[3] * cy + dy);
-  r[2] = v[2] + 2 * (q[3] * cz + dz);
-}
-template <typename T> __device__ __forceinline__ void q_to_rot(const T q[4], T R[3][3]) {
-  const T x = q[0], y = q[1], z = q[2], w = q[3];
-  R[0][0] = 1 - 2 * (y * y + z * z); R[0][1] = 2 * (x * y - z * w);     R[0][2] = 2 * (x * z + y * w);
-  R[1][0] = 2 * (x * y + z * w);     R[1][1] = 1 - 2 * (x * x + z * z); R[1][2] = 2 * (y * z - x * w);
-  R[2][0] = 2 * (x * z - y * w);     R[2][1] = 2 * (y * z + x * w);     R[2][2] = 1 - 2 * (x * x + y * y);
-}
-
-// error (6) and the requested Jacobian (role 0: A w.r.t. Xi, role 1: B w.r.t. Xj), 6 x 6 row-major
-template <typename T>
-__device__ void edge_linearize_3d(int role, const T ti[3], const T qi[4], const T tj[3], const T qj[4],
-                                  const T tz[3], const T qz[4], T e[6], T J[6][6]) {
-  const T qic[4] = {-qi[0], -qi[1], -qi[2], qi[3]};
-  const T qzc[4] = {-qz[0], -qz[1], -qz[2], qz[3]};
-  // C = Xi^-1 Xj
-  T d[3] = {tj[0] - ti[0], tj[1] - ti[1], tj[2] - ti[2]}, tC[3], qC[4];
-  q_rot(qic, d, tC);
-  q_mul(qic, qj, qC);
-  // E = Z^-1 C
-  T d2[3] = {tC[0] - tz[0], tC[1] - tz[1], tC[2] - tz[2]}, tE[3], qE[4];
-  q_rot(qzc, d2, tE);
-  q_mul(qzc, qC, qE);
-  const T sgn = qE[3] < 0 ? (T)-1 : (T)1;
-  e[0] = tE[0]; e[1] = tE[1]; e[2] = tE[2];
-  e[3] = sgn * qE[0]; e[4] = sgn * qE[1]; e[5] = sgn * qE[2];
-#pragma unroll
-  for (int r = 0; r < 6; r++)
-#pragma unroll
-    for (int c = 0; c < 6; c++) J[r][c] = 0;
-  if (role) {
-    T RE[3][3];
-    q_to_rot(qE, RE);
-#pragma unroll
-    for (int r = 0; r < 3; r++)
-#pragma unroll
-      for (int c = 0; c < 3; c++) J[r][c] = RE[r][c];
-    const T h = (T)0.5 * sgn, w = qE[3], vx = qE[0], vy = qE[1], vz = qE[2];
-    J[3][3] = h * w;   J[3][4] = -h * vz; J[3][5] = h * vy;
-    J[4][3] = h * vz;  J[4][4] = h * w;   J[4][5] = -h * vx;
-    J[5][3] = -h * vy; J[5][4] = h * vx;  J[5][5] = h * w;
-  } else {
-    T RZt[3][3];
-    q_to_rot(qzc, RZt);   // rotation of Z^-1 = Rz^T
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-#pragma unroll
-      for (int c = 0; c < 3; c++) J[r][c] = -RZt[r][c];
-      // Rz^T [tC]x : column k = Rz^T (tC x e_k)... [tC]x u = tC x u
-      J[r][3] = RZt[r][1] * tC[2] - RZt[r][2] * tC[1];
-      J[r][4] = RZt[r][2] * tC[0] - RZt[r][0] * tC[2];
-      J[r][5] = RZt[r][0] * tC[1] - RZt[r][1] * tC[0];
-    }
-    // d vec(q_E)/d dw_i = -(1/2) vec( qz^-1 (x) (u,0) (x) qC ), column by column
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-      T u[4] = {k == 0 ? (T)1 : (T)0, k == 1 ? (T)1 : (T)0, k == 2 ? (T)1 : (T)0, (T)0}, t1[4], t2[4];
-      q_mul(qzc, u, t1);
-      q_mul(t1, qC, t2);
-      J[3][3 + k] = (T)-0.5 * sgn * t2[0];
-      J[4][3 + k] = (T)-0.5 * sgn * t2[1];
-      J[5][3 + k] = (T)-0.5 * sgn * t2[2];
-    }
-  }
-}
-
-template <typename TO, typename T, int RK = ROBUST_NONE>   // RK: as k_linearize
-__global__ void __launch_bounds__(LIN_THREADS) k_linearize_se3(LinArgs3<TO, T> a) {
-  using V4 = typename VecT<T>::V4;
-  __shared__ double red[LIN_THREADS / 64];
-  const int gid = blockIdx.x * LIN_THREADS + threadIdx.x;
-  for (int i = gid; i < a.n_zero_words; i += gridDim.x * LIN_THREADS) a.zero_words[i] = 0u;
-  for (int i = gid; i < a.n_fill_words; i += gridDim.x * LIN_THREADS) a.fill_words[i] = X_PENDING_WORD;
-  opt_reset_in_first_thread(a);
-  const LinPre lin_pre = opt_publish_preload(a);
-  const T lambda = a.lambda_from_ctrl ? (T)a.ctrl->lambda : a.lambda;
-  const int slot = gid / LIN_GROUP, sub = gid % LIN_GROUP;
-  const int node = slot < a.n_nodes ? (a.node_list ? a.node_list[slot] : slot) : -1;
-  double chi = 0.0;
-  T hd[21], bv[6];   // lower triangle of the 6 x 6 diagonal block, row-major: (0,0),(1,0),(1,1),...
-#pragma unroll
-  for (int t = 0; t < 21; t++) hd[t] = 0;
-#pragma unroll
-  for (int t = 0; t < 6; t++) bv[t] = 0;
-  if (node >= 0) {
-    const V4 st = a.pose[2 * node], sq = a.pose[2 * node + 1];
-    const T ts[3] = {st.x, st.y, st.z}, qs[4] = {sq.x, sq.y, sq.z, sq.w};
-    const int q1 = a.inc_ptr[node + 1];
-    for (int q = a.inc_ptr[node] + sub; q < q1; q += LIN_GROUP) {
-      const int2 inc = a.inc_list[q];
-      const int ent = inc.x;
-      if (!(ent & 12)) continue;   // sharded runs: see k_linearize
-      const bool owns = ent & 4;
-      const int k = ent >> 4, role = ent & 1;
-      const int other = inc.y;
-      const V4 ot = a.pose[2 * other], oq = a.pose[2 * other + 1];
-      const T to[3] = {ot.x, ot.y, ot.z}, qo[4] = {oq.x, oq.y, oq.z, oq.w};
-      const V4 zt = a.e_meas[2 * k], zq = a.e_meas[2 * k + 1];
-      const T tz[3] = {zt.x, zt.y, zt.z}, qz[4] = {zq.x, zq.y, zq.z, zq.w};
-      T W[6][6];
-      {
-        const T *w = a.e_info + (int64_t)k * 21;
-        int t = 0;
-#pragma unroll
-        for (int i = 0; i < 6; i++)
-#pragma unroll
-          for (int j = i; j < 6; j++) { W[i][j] = w[t]; W[j][i] = w[t]; t++; }
-      }
-      T e[6], J[6][6];
-      if (role) edge_linearize_3d<T>(1, to, qo, ts, qs, tz, qz, e, J);
-      else edge_linearize_3d<T>(0, ts, qs, to, qo, tz, qz, e, J);
-      T s_rob = 0;
-      bool rob = false;
-      if constexpr (RK != ROBUST_NONE) {
-        s_rob = edge_chi2_3d<T>(W, e);
-        rob = !a.robust_mask || a.robust_mask[k];
-        if (rob) {
-          const T w = robust_weight<RK, T>(s_rob, a.robust_delta, a.robust_delta2);
-#pragma unroll
-          for (int i = 0; i < 6; i++)
-#pragma unroll
-            for (int j = 0; j < 6; j++) W[i][j] *= w;
-        }
-      }
-      T JW[6][6];   // J^T W
-#pragma unroll
-      for (int i = 0; i < 6; i++)
-#pragma unroll
-        for (int j = 0; j < 6; j++) {
-          T sacc = 0;
-#pragma unroll
-          for (int r = 0; r < 6; r++) sacc += J[r][i] * W[r][j];
-          JW[i][j] = sacc;
-        }
-      if (a.write_system && owns) {
-        int t = 0;
-#pragma unroll
-        for (int i = 0; i < 6; i++)
-#pragma unroll
-          for (int j = 0; j <= i; j++) {
-            T sacc = 0;
-#pragma unroll
-            for (int r = 0; r < 6; r++) sacc += JW[i][r] * J[r][j];
-            hd[t++] += sacc;
-          }
-#pragma unroll
-        for (int i = 0; i < 6; i++) {
-          T sacc = 0;
-#pragma unroll
-          for (int r = 0; r < 6; r++) sacc += JW[i][r] * e[r];
-          bv[i] += sacc;
-        }
-      }
-      if (role == 0) {
-        if constexpr (RK == ROBUST_NONE) {
-          if (owns) chi += (double)edge_chi2_3d<T>(W, e);
-        } else {
-          if (owns) chi += (double)(rob ? robust_rho<RK, T>(s_rob, a.robust_delta, a.robust_delta2) : s_rob);
-        }
-        if (a.write_system && (ent & 8)) {
-          // off-diagonal block H[from rows, to cols] = A^T W B: B of the same edge
-          T e2[6], Bm[6][6];
-          edge_linearize_3d<T>(1, ts, qs, to, qo, tz, qz, e2, Bm);
-          const int64_t so = a.e_slot[k];
-          TO *dst = a.hvals + (so >> 1);
-          const bool tr = so & 1;
-#pragma unroll
-          for (int i = 0; i < 6; i++)
-#pragma unroll
-            for (int j = 0; j < 6; j++) {
-              T sacc = 0;
-#pragma unroll
-              for (int r = 0; r < 6; r++) sacc += JW[i][r] * Bm[r][j];
-              dst[tr ? j * 6 + i : i * 6 + j] = (TO)sacc;
-            }
-        }
-      }
-    }
-  }
-  if (a.write_system) {
-#pragma unroll
-    for (int t = 0; t < 21; t++) hd[t] = group_sum8(hd[t]);
-#pragma unroll
-    for (int t = 0; t < 6; t++) bv[t] = group_sum8(bv[t]);
-    if (node >= 0 && sub == 0) {
-      T add = lambda;
-      if (node == a.anchor) add += (T)10000000.0;
-      if (a.adds_diag && !a.adds_diag[node]) add = 0;
-      TO *d = a.hvals + a.diag_off[node];
-      int t = 0;
-#pragma unroll
-      for (int i = 0; i < 6; i++)
-#pragma unroll
-        for (int j = 0; j <= i; j++) {
-          const T v = hd[t++] + (i == j ? add : (T)0);
-          d[i * 6 + j] = (TO)v;
-          d[j * 6 + i] = (TO)v;
-        }
-      TO *bo = a.b + a.node_offset[node];
-#pragma unroll
-      for (int i = 0; i < 6; i++) bo[i] = (TO)(-bv[i]);
-    }
-  }
-  double tot = block_sum<double, LIN_THREADS>(chi, red);
-  if (threadIdx.x == 0) a.chi2_partial[blockIdx.x] = tot;
-  opt_publish_chi2_in_last_block(a, lin_pre, red);
-}
-
 // rr_pgo_edge_errors: one thread per edge, s = e^T W e and the robust weight w(s) at the current state, in f64 (file order).
 // The same error code as the linearisation kernels (edge_linearize_2d / edge_linearize_3d), in TC.
 template <typename TC> struct EdgeErrArgs {
@@ -1136,25 +1037,26 @@ template <typename TC> struct EdgeErrArgs {
   double *s_out, *w_out;
 };
 template <typename TC> __global__ void __launch_bounds__(256) k_edge_errors(EdgeErrArgs<TC> a) {
-  using V4 = typename VecT<TC>::V4;
   const int k = blockIdx.x * 256 + threadIdx.x;
   if (k >= a.n_edges) return;
   TC s;
   if (!a.is3d) {
     const EdgeRec<TC> rec = a.e_rec[k];
-    const V4 wa = rec.info_a;
-    const typename VecT<TC>::V2 wb = rec.info_b;
-    const TC W[3][3] = {{wa.x, wa.y, wa.z}, {wa.y, wa.w, wb.x}, {wa.z, wb.x, wb.y}};
-    TC e[3], A[3][3], B[3][3];
+    TC W[3][3], e[3], A[3][3], B[3][3];
+    info_2d<TC>(rec, W);
     edge_linearize_2d<TC>(a.node_dim[rec.to] == 2 ? 1 : 0, a.pose[rec.from], a.pose[rec.to], rec.meas, e, A, B);
     s = edge_chi2_2d<TC>(W, e);
   } else {
     const int2 ft = a.e_idx[k];
+    using V4 = typename VecT<TC>::V4;
     const V4 it = a.pose[2 * ft.x], iq = a.pose[2 * ft.x + 1], jt = a.pose[2 * ft.y], jq = a.pose[2 * ft.y + 1];
     const V4 zt = a.e_meas[2 * k], zq = a.e_meas[2 * k + 1];
-    const TC ti[3] = {it.x, it.y, it.z}, qi[4] = {iq.x, iq.y, iq.z, iq.w};
-    const TC tj[3] = {jt.x, jt.y, jt.z}, qj[4] = {jq.x, jq.y, jq.z, jq.w};
-    const TC tz[3] = {zt.x, zt.y, zt.z}, qz[4] = {zq.x, zq.y, zq.z, zq.w};
+    TC ti[3], qi[4], tj[3], qj[4], tz[3], qz[4];
+    pose_3d<TC>(it, iq, ti, qi);
+    pose_3d<TC>(jt, jq, tj, qj);
+    pose_3d<TC>(zt, zq, tz, qz);
+    // info_3d, written out: through the loader (in any of eight forms tried) the fp32 instantiation's packed multiply-adds
+    // pair up differently and s changes in its last bit on sphere2500 and parking-garage (profiles/EXPERIMENTS.md, r17)
     TC W[6][6];
     const TC *w = a.e_info + (int64_t)k * 21;
     int t = 0;
@@ -1230,73 +1132,6 @@ __global__ void __launch_bounds__(64) k_guess_nodes(typename VecT<TC>::V4 *pose,
       pose[2 * st.dst + 1] = V4{r[0], r[1], r[2], r[3]};
     }
   }
-}
-
-template <typename T, typename TC = T> struct UpdArgs3 {
-  int n_nodes;
-  typename VecT<TC>::V4 *pose;
-  const int32_t *node_pcol, *node_offset;
-  const T *x, *dx_ref_in;
-  T *dx_ref_out;
-  TC sign;
-  double *norm_partial;
-  int export_only;     // 1: only write dx_ref_out
-  const int *err;      // sticky device error flag: a failed factorisation must not touch the state
-  const int32_t *node_list;    // sharded runs: the nodes this rank updates (own + shared), n_nodes = its length
-  const uint8_t *norm_counts;  // sharded runs: per node, 1 = this rank adds the node's |dx|^2 (every node counted once)
-  const int *gate;             // as UpdArgs::gate
-  FinArgs fin;
-};
-
-// X <- X * (dt, Exp(dw)):  t += R dt ;  q <- normalise( q (x) exp(dw) )
-template <typename TO, typename T>
-__global__ void __launch_bounds__(UPD_THREADS) k_update_se3(UpdArgs3<TO, T> a) {
-  __shared__ double red[UPD_THREADS / 64];
-  const int slot = blockIdx.x * UPD_THREADS + threadIdx.x;
-  const int node = slot < a.n_nodes ? (a.node_list ? a.node_list[slot] : slot) : -1;
-  double nrm = 0.0;
-  if (opt_stopped(a.err)) return;   // as k_update
-  if (a.gate && *a.gate == 0) return;
-  const FinPre fin_pre = finalize_preload<UPD_THREADS>(a.fin);
-  const bool failed = a.err && a.err[0] != 0;   // as k_update
-  if (node >= 0 && !failed) {
-    T d[6];
-    const TO *src = a.dx_ref_in ? a.dx_ref_in + a.node_offset[node] : a.x + a.node_pcol[node];
-#pragma unroll
-    for (int t = 0; t < 6; t++) d[t] = (T)src[t];
-    if (a.dx_ref_out) {
-      TO *dst = a.dx_ref_out + a.node_offset[node];
-#pragma unroll
-      for (int t = 0; t < 6; t++) dst[t] = src[t];
-    }
-    if (a.export_only) return;
-#pragma unroll
-    for (int t = 0; t < 6; t++) { nrm += (double)d[t] * (double)d[t]; d[t] *= a.sign; }
-    if (a.norm_counts && !a.norm_counts[node]) nrm = 0.0;
-    auto pt = a.pose[2 * node], pq = a.pose[2 * node + 1];
-    const T q[4] = {pq.x, pq.y, pq.z, pq.w};
-    T rt[3];
-    q_rot(q, d, rt);
-    pt.x += rt[0]; pt.y += rt[1]; pt.z += rt[2];
-    const T th = sqrt(d[3] * d[3] + d[4] * d[4] + d[5] * d[5]);
-    T dq[4];
-    if (th < (T)1e-12) {
-      dq[0] = (T)0.5 * d[3]; dq[1] = (T)0.5 * d[4]; dq[2] = (T)0.5 * d[5]; dq[3] = 1;
-    } else {
-      const T sc = sin((T)0.5 * th) / th;
-      dq[0] = sc * d[3]; dq[1] = sc * d[4]; dq[2] = sc * d[5]; dq[3] = cos((T)0.5 * th);
-    }
-    T qn[4];
-    q_mul(q, dq, qn);
-    const T inv = (T)1 / sqrt(qn[0] * qn[0] + qn[1] * qn[1] + qn[2] * qn[2] + qn[3] * qn[3]);
-    pq.x = qn[0] * inv; pq.y = qn[1] * inv; pq.z = qn[2] * inv; pq.w = qn[3] * inv;
-    a.pose[2 * node] = pt;
-    a.pose[2 * node + 1] = pq;
-  }
-  if (a.export_only) return;
-  double tot = block_sum<double, UPD_THREADS>(nrm, red);
-  if (threadIdx.x == 0) a.norm_partial[blockIdx.x] = tot;
-  if (a.fin.enabled) finalize_in_last_block<UPD_THREADS>(a.fin, fin_pre, a.norm_partial, (int)gridDim.x, red);
 }
 
 // ------------------------------------------------------------ multifrontal
@@ -4180,14 +4015,14 @@ template <typename T, typename TC> __global__ void __launch_bounds__(256) k_big_
 template <typename T, typename TC = T> struct UpdArgs {
   int n_nodes;
   typename VecT<TC>::V4 *pose;
-  const uint8_t *node_dim;
+  const uint8_t *node_dim;   // SE(2): 3 (pose) or 2 (XY landmark); SE(3): null
   const int32_t *node_pcol, *node_offset;
   const T *x;          // permuted solution (used when dx_ref_in == nullptr)
   const T *dx_ref_in;  // reference-order step supplied by the caller (rr_pgo_update)
   T *dx_ref_out;       // reference-order copy of the applied step (may be null)
   TC sign;
   double *norm_partial;
-  int gauge_anchor;    // >= 0: x is a solution in the root-separator gauge; transfer it to the anchor gauge first
+  int gauge_anchor;    // SE(2), >= 0 (SE(3): -1): x is a solution in the root-separator gauge; transfer it to the anchor gauge first
   int export_only;     // 1: only write dx_ref_out (rr_pgo_linearize_solve), the state stays as it is
   const int *err;      // sticky device error flag: a failed factorisation must not touch the state
   const int32_t *node_list;    // sharded runs: the nodes this rank updates (own + shared), n_nodes = its length
@@ -4239,11 +4074,51 @@ __device__ __forceinline__ double update_node(const UpdArgs<TO, T> &a, int node)
   return nrm;
 }
 
+// SE(3): X <- X * (dt, Exp(dw)):  t += R dt ;  q <- normalise( q (x) exp(dw) ); returns the node's |dx|^2 term
 template <typename TO, typename T>
+__device__ __forceinline__ double update_node_se3(const UpdArgs<TO, T> &a, int node) {
+  double nrm = 0.0;
+  T d[6];
+  const TO *src = a.dx_ref_in ? a.dx_ref_in + a.node_offset[node] : a.x + a.node_pcol[node];
+#pragma unroll
+  for (int t = 0; t < 6; t++) d[t] = (T)src[t];
+  if (a.dx_ref_out) {
+    TO *dst = a.dx_ref_out + a.node_offset[node];
+#pragma unroll
+    for (int t = 0; t < 6; t++) dst[t] = src[t];
+  }
+  if (a.export_only) return nrm;
+#pragma unroll
+  for (int t = 0; t < 6; t++) { nrm += (double)d[t] * (double)d[t]; d[t] *= a.sign; }
+  if (a.norm_counts && !a.norm_counts[node]) nrm = 0.0;
+  auto pt = a.pose[2 * node], pq = a.pose[2 * node + 1];
+  T t0[3], q[4];
+  pose_3d<T>(pt, pq, t0, q);
+  T rt[3];
+  q_rot(q, d, rt);
+  pt.x += rt[0]; pt.y += rt[1]; pt.z += rt[2];
+  const T th = sqrt(d[3] * d[3] + d[4] * d[4] + d[5] * d[5]);
+  T dq[4];
+  if (th < (T)1e-12) {
+    dq[0] = (T)0.5 * d[3]; dq[1] = (T)0.5 * d[4]; dq[2] = (T)0.5 * d[5]; dq[3] = 1;
+  } else {
+    const T sc = sin((T)0.5 * th) / th;
+    dq[0] = sc * d[3]; dq[1] = sc * d[4]; dq[2] = sc * d[5]; dq[3] = cos((T)0.5 * th);
+  }
+  T qn[4];
+  q_mul(q, dq, qn);
+  const T inv = (T)1 / sqrt(qn[0] * qn[0] + qn[1] * qn[1] + qn[2] * qn[2] + qn[3] * qn[3]);
+  pq.x = qn[0] * inv; pq.y = qn[1] * inv; pq.z = qn[2] * inv; pq.w = qn[3] * inv;
+  a.pose[2 * node] = pt;
+  a.pose[2 * node + 1] = pq;
+  return nrm;
+}
+
+// The update's frame, SE(2) (D = 3) and SE(3) (D = 6): only the node's own update is per dimension.
+template <typename TO, typename T, int D = 3>
 __global__ void __launch_bounds__(UPD_THREADS) k_update(UpdArgs<TO, T> a) {
   __shared__ double red[UPD_THREADS / 64];
-  const int slot = blockIdx.x * UPD_THREADS + threadIdx.x;
-  const int node = slot < a.n_nodes ? (a.node_list ? a.node_list[slot] : slot) : -1;
+  const int node = listed_node(a, blockIdx.x * UPD_THREADS + threadIdx.x);
   double nrm = 0.0;
   // rr_pgo_optimize: enqueued behind the iteration that met the stop rule (:298-300) -- the state, the partials, the slot
   // counter and the ring stay as that iteration left them
@@ -4251,7 +4126,10 @@ __global__ void __launch_bounds__(UPD_THREADS) k_update(UpdArgs<TO, T> a) {
   if (a.gate && *a.gate == 0) return;
   const FinPre fin_pre = finalize_preload<UPD_THREADS>(a.fin);   // requested ahead of the node work
   const bool failed = a.err && a.err[0] != 0;   // a failed factorisation: the state stays
-  if (node >= 0 && !failed) nrm = update_node(a, node);
+  if (node >= 0 && !failed) {
+    if constexpr (D == 3) nrm = update_node(a, node);
+    else nrm = update_node_se3(a, node);
+  }
   if (a.export_only) return;
   double tot = block_sum<double, UPD_THREADS>(nrm, red);
   if (threadIdx.x == 0) a.norm_partial[blockIdx.x] = tot;

@@ -352,11 +352,12 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   PooledStream stream_;
   hipGraphExec_t gn_exec_ = nullptr;
   // graph data
-  DevBuf<V4> pose_, e_meas_, e_info_a_;
-  DevBuf<V2> e_info_b_;
-  DevBuf<int2> e_idx_;
-  DevBuf<EdgeRec<S>> e_rec_;   // SE(2): every edge's from / to / slot / measurement / information as one record (k_linearize)
-  DevBuf<int64_t> e_slot_, diag_off_;
+  DevBuf<V4> pose_;
+  DevBuf<EdgeRec<S>> e_rec_;   // SE(2): every edge's from / to / slot / measurement / information as one record
+  DevBuf<int2> e_idx_;         // SE(3): from, to;
+  DevBuf<V4> e_meas_;          //        the measurement, a pair per edge;
+  DevBuf<int64_t> e_slot_;     //        (offset into hvals << 1) | transposed
+  DevBuf<int64_t> diag_off_;
   DevBuf<int32_t> inc_ptr_, node_offset_, node_pcol_;
   DevBuf<int2> inc_list_;
   DevBuf<uint8_t> node_dim_;
@@ -561,49 +562,49 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     std::vector<uint8_t> ndim(N);
     for (int i = 0; i < N; i++) ndim[i] = (uint8_t)node_dim(g.node_kind[i]);
     node_dim_.upload(ndim);
-    std::vector<int2> eidx(E);
-    std::vector<int64_t> eslot(E);
-    for (int k = 0; k < E; k++) {
-      eidx[k] = int2{g.edge_from[k], g.edge_to[k]};
-      eslot[k] = (sym.blk_off[sym.edge_slot[k]] << 1) | (sym.edge_transposed[k] ? 1 : 0);
-    }
-    e_idx_.upload(eidx);
-    e_slot_.upload(eslot);
-    {   // states and measurements in their device form: one V4 per node and edge, SE(3) a pair (the host copies end with the block).
+    auto edge_slot = [&](int k) { return (int64_t)((sym.blk_off[sym.edge_slot[k]] << 1) | (sym.edge_transposed[k] ? 1 : 0)); };
+    {   // states and edges in their device form (the host copies end with the block): one V4 per node, SE(3) a pair; an SE(2)
+      // edge is one record, an SE(3) edge an entry of four arrays.
       // The loops are split by dimension and the 2-D ones name their two kinds, so that each compiles to its own forms alone.
       const size_t per = is3d_ ? 2 : 1;
       std::vector<V4> pose(per * (size_t)N);
       if (is3d_) for (int i = 0; i < N; i++) pack_v4(NODE_SE3, &g.node_state[g.node_state_off[i]], &pose[2 * (size_t)i]);
       else for (int i = 0; i < N; i++) pack_v4(g.node_kind[i] == NODE_SE2 ? NODE_SE2 : NODE_XY, &g.node_state[g.node_state_off[i]], &pose[i]);
       pose_.upload(pose);
-      std::vector<V4> emeas(per * (size_t)E);
-      if (is3d_) for (int k = 0; k < E; k++) pack_v4(EDGE_SE3, &g.edge_meas[g.edge_meas_off[k]], &emeas[2 * (size_t)k]);
-      else for (int k = 0; k < E; k++) pack_v4(g.edge_kind[k] == EDGE_SE2 ? EDGE_SE2 : EDGE_SE2_XY, &g.edge_meas[g.edge_meas_off[k]], &emeas[k]);
-      e_meas_.upload(emeas);
       if (!is3d_) {
-        std::vector<V4> einfa(E);
-        std::vector<V2> einfb(E);
+        std::vector<EdgeRec<S>> erec(E);
         for (int k = 0; k < E; k++) {
+          EdgeRec<S> &r = erec[k];
+          r.from = g.edge_from[k];
+          r.to = g.edge_to[k];
+          r.slot = edge_slot(k);
           const double *w = &g.edge_info[g.edge_info_off[k]];
           if (g.edge_kind[k] == EDGE_SE2) {
-            einfa[k] = V4{(S)w[0], (S)w[1], (S)w[2], (S)w[3]};
-            einfb[k] = V2{(S)w[4], (S)w[5]};
+            pack_v4(EDGE_SE2, &g.edge_meas[g.edge_meas_off[k]], &r.meas);
+            r.info_a = V4{(S)w[0], (S)w[1], (S)w[2], (S)w[3]};
+            r.info_b = V2{(S)w[4], (S)w[5]};
           } else {
-            einfa[k] = V4{(S)w[0], (S)w[1], (S)0, (S)w[2]};
-            einfb[k] = V2{(S)0, (S)0};
+            pack_v4(EDGE_SE2_XY, &g.edge_meas[g.edge_meas_off[k]], &r.meas);
+            r.info_a = V4{(S)w[0], (S)w[1], (S)0, (S)w[2]};
+            r.info_b = V2{(S)0, (S)0};
           }
         }
-        e_info_a_.upload(einfa);
-        e_info_b_.upload(einfb);
-        std::vector<EdgeRec<S>> erec(E);
-        for (int k = 0; k < E; k++) erec[k] = EdgeRec<S>{eidx[k].x, eidx[k].y, eslot[k], emeas[k], einfa[k], einfb[k]};
         e_rec_.upload(erec);
       } else {
+        std::vector<int2> eidx(E);
+        std::vector<int64_t> eslot(E);
+        std::vector<V4> emeas(2 * (size_t)E);
         std::vector<S> einfo(21 * (size_t)E);
         for (int k = 0; k < E; k++) {
+          eidx[k] = int2{g.edge_from[k], g.edge_to[k]};
+          eslot[k] = edge_slot(k);
+          pack_v4(EDGE_SE3, &g.edge_meas[g.edge_meas_off[k]], &emeas[2 * (size_t)k]);
           const double *w = &g.edge_info[g.edge_info_off[k]];
           for (int t = 0; t < 21; t++) einfo[21 * (size_t)k + t] = (S)w[t];
         }
+        e_idx_.upload(eidx);
+        e_slot_.upload(eslot);
+        e_meas_.upload(emeas);
         e_info3_.upload(einfo);
       }
     }
@@ -1605,12 +1606,11 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     a.e_rec = e_rec_.p;
     a.e_idx = e_idx_.p;
     a.e_meas = e_meas_.p;
-    a.e_info_a = e_info_a_.p;
-    a.e_info_b = e_info_b_.p;
+    a.e_info = e_info3_.p;
     a.e_slot = e_slot_.p;
     a.inc_ptr = inc_ptr_.p;
     a.inc_list = inc_list_.p;
-    a.node_dim = node_dim_.p;
+    a.node_dim = is3d_ ? nullptr : node_dim_.p;
     a.node_offset = node_offset_.p;
     a.diag_off = diag_off_.p;
     a.hvals = hvals_.p;
@@ -1628,14 +1628,14 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     robust_fields(a);
     return a;
   }
-  template <typename A> void robust_fields(A &a) const {
+  void robust_fields(LinArgs<T, S> &a) const {
     a.robust_delta = (S)robust_delta_;
     a.robust_delta2 = (S)(robust_delta_ * robust_delta_);
     a.robust_mask = robust_mask_.n ? robust_mask_.p : nullptr;
   }
   // what a linearisation inside a pipelined rr_pgo_optimize call carries: the reset of the loop state (first launch of
   // the call), lambda from the device (Levenberg-Marquardt)
-  template <typename A> void opt_lin_fields(A &a, int lm) {
+  void opt_lin_fields(LinArgs<T, S> &a, int lm) {
     a.ctrl = opt_active_ ? opt_ctrl_.p : nullptr;
     a.err = err_.p;
     a.lambda_from_ctrl = (opt_active_ && opt_lambda_dev_ && lm) ? 1 : 0;
@@ -1732,48 +1732,18 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
       if (edge_lin_wave_) hipLaunchKernelGGL((k_linearize_wave_edges<T, S>), dim3(n_lin_blocks_), dim3(256), 0, stream_, la, g_.n_edges());
       else hipLaunchKernelGGL((k_linearize_edges<T, S>), dim3(n_lin_blocks_), dim3(LIN_THREADS), 0, stream_, la, g_.n_edges());
       if (write_system) hipLaunchKernelGGL((k_lin_finish<T, S>), dim3(nb), dim3(256), 0, stream_, la);
-    } else if (!is3d_) {
-      if (robust_kind_ == ROBUST_HUBER)
-        hipLaunchKernelGGL((k_linearize<T, S, ROBUST_HUBER>), dim3(n_lin_blocks_), dim3(LIN_THREADS), 0, stream_,
-                           lin_args(lambda, lm, write_system, reference_prior));
-      else if (robust_kind_ == ROBUST_CAUCHY)
-        hipLaunchKernelGGL((k_linearize<T, S, ROBUST_CAUCHY>), dim3(n_lin_blocks_), dim3(LIN_THREADS), 0, stream_,
-                           lin_args(lambda, lm, write_system, reference_prior));
-      else
-        hipLaunchKernelGGL((k_linearize<T, S>), dim3(n_lin_blocks_), dim3(LIN_THREADS), 0, stream_,
-                           lin_args(lambda, lm, write_system, reference_prior));
     } else {
-      LinArgs3<T, S> a;
-      a.n_nodes = n_list_;
-      a.node_list = node_list_.p;
-      a.pose = pose_.p;
-      a.e_idx = e_idx_.p;
-      a.e_meas = e_meas_.p;
-      a.e_info = e_info3_.p;
-      a.e_slot = e_slot_.p;
-      a.inc_ptr = inc_ptr_.p;
-      a.inc_list = inc_list_.p;
-      a.node_offset = node_offset_.p;
-      a.diag_off = diag_off_.p;
-      a.hvals = hvals_.p;
-      a.b = b_.p;
-      a.chi2_partial = chi_partial_.p;
-      a.anchor = g_.anchor_node;
-      a.lambda = lm ? (S)lambda : (S)0;
-      a.write_system = write_system;
-      a.adds_diag = norm_counts_.p;
-      a.zero_words = lds_flow_ ? dep_flags_.p : nullptr;
-      a.n_zero_words = lds_flow_ ? 2 * sym_.S + 64 : 0;
-      a.fill_words = lds_flow_ ? reinterpret_cast<unsigned *>(x_ptr_) : nullptr;
-      a.n_fill_words = lds_flow_ ? (int)((size_t)g_.dim * sizeof(T) / 4) : 0;
-      opt_lin_fields(a, lm);
-      robust_fields(a);
-      if (robust_kind_ == ROBUST_HUBER) hipLaunchKernelGGL((k_linearize_se3<T, S, ROBUST_HUBER>), dim3(n_lin_blocks_), dim3(LIN_THREADS), 0, stream_, a);
-      else if (robust_kind_ == ROBUST_CAUCHY) hipLaunchKernelGGL((k_linearize_se3<T, S, ROBUST_CAUCHY>), dim3(n_lin_blocks_), dim3(LIN_THREADS), 0, stream_, a);
-      else hipLaunchKernelGGL((k_linearize_se3<T, S>), dim3(n_lin_blocks_), dim3(LIN_THREADS), 0, stream_, a);
+      const LinArgs<T, S> la = lin_args(lambda, lm, write_system, reference_prior);
+      if (robust_kind_ == ROBUST_HUBER) launch_pull<ROBUST_HUBER>(la);
+      else if (robust_kind_ == ROBUST_CAUCHY) launch_pull<ROBUST_CAUCHY>(la);
+      else launch_pull<ROBUST_NONE>(la);
     }
     check_launch("k_linearize");
     pend(RR_PGO_K_LINEARIZE);
+  }
+  template <int RK> void launch_pull(const LinArgs<T, S> &la) {   // the pull form of either dimension under robust kernel RK
+    if (is3d_) hipLaunchKernelGGL((k_linearize<T, S, RK, 6>), dim3(n_lin_blocks_), dim3(LIN_THREADS), 0, stream_, la);
+    else hipLaunchKernelGGL((k_linearize<T, S, RK, 3>), dim3(n_lin_blocks_), dim3(LIN_THREADS), 0, stream_, la);
   }
 
   void launch_factor() { launch_factor_range(0, sym_.steps.size()); }
@@ -2051,45 +2021,26 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
       if (opt_active_) { fin.ctrl = opt_ctrl_.p; fin.ring_host = opt_ring_; fin.err = err_.p; }
     }
     pbegin();
-    if (!is3d_) {
-      UpdArgs<T, S> u;
-      u.n_nodes = n_list_;
-      u.node_list = node_list_.p;
-      u.norm_counts = norm_counts_.p;
-      u.pose = pose_.p;
-      u.node_dim = node_dim_.p;
-      u.node_pcol = node_pcol_.p;
-      u.node_offset = node_offset_.p;
-      u.x = x_ptr_;
-      u.dx_ref_in = dx_ref_in;
-      u.dx_ref_out = write_ref ? dx_ref_.p : nullptr;
-      u.sign = (S)sign;
-      u.norm_partial = norm_partial_.p;
-      u.gauge_anchor = (!dx_ref_in && gauge_now_) ? g_.anchor_node : -1;
-      u.export_only = export_only ? 1 : 0;
-      u.err = dx_ref_in ? nullptr : err_.p;
-      u.gate = gate;
-      u.fin = fin;
-      hipLaunchKernelGGL((k_update<T, S>), dim3(n_upd_blocks_), dim3(UPD_THREADS), 0, stream_, u);
-    } else {
-      UpdArgs3<T, S> u;
-      u.n_nodes = n_list_;
-      u.node_list = node_list_.p;
-      u.norm_counts = norm_counts_.p;
-      u.pose = pose_.p;
-      u.node_pcol = node_pcol_.p;
-      u.node_offset = node_offset_.p;
-      u.x = x_ptr_;
-      u.dx_ref_in = dx_ref_in;
-      u.dx_ref_out = write_ref ? dx_ref_.p : nullptr;
-      u.sign = (S)sign;
-      u.norm_partial = norm_partial_.p;
-      u.export_only = export_only ? 1 : 0;
-      u.err = dx_ref_in ? nullptr : err_.p;
-      u.gate = gate;
-      u.fin = fin;
-      hipLaunchKernelGGL((k_update_se3<T, S>), dim3(n_upd_blocks_), dim3(UPD_THREADS), 0, stream_, u);
-    }
+    UpdArgs<T, S> u;
+    u.n_nodes = n_list_;
+    u.node_list = node_list_.p;
+    u.norm_counts = norm_counts_.p;
+    u.pose = pose_.p;
+    u.node_dim = is3d_ ? nullptr : node_dim_.p;
+    u.node_pcol = node_pcol_.p;
+    u.node_offset = node_offset_.p;
+    u.x = x_ptr_;
+    u.dx_ref_in = dx_ref_in;
+    u.dx_ref_out = write_ref ? dx_ref_.p : nullptr;
+    u.sign = (S)sign;
+    u.norm_partial = norm_partial_.p;
+    u.gauge_anchor = (!is3d_ && !dx_ref_in && gauge_now_) ? g_.anchor_node : -1;
+    u.export_only = export_only ? 1 : 0;
+    u.err = dx_ref_in ? nullptr : err_.p;
+    u.gate = gate;
+    u.fin = fin;
+    if (is3d_) hipLaunchKernelGGL((k_update<T, S, 6>), dim3(n_upd_blocks_), dim3(UPD_THREADS), 0, stream_, u);
+    else hipLaunchKernelGGL((k_update<T, S, 3>), dim3(n_upd_blocks_), dim3(UPD_THREADS), 0, stream_, u);
     check_launch("k_update");
     pend(RR_PGO_K_UPDATE);
   }

@@ -265,9 +265,9 @@ __device__ __forceinline__ void gate_linearize(const GateCand *q, const typename
       }
     }
   } else {
-    const V4 it = pose[2 * q->na], iq = pose[2 * q->na + 1], jt = pose[2 * q->nb], jq = pose[2 * q->nb + 1];
-    const T ti[3] = {it.x, it.y, it.z}, qi[4] = {iq.x, iq.y, iq.z, iq.w};
-    const T tj[3] = {jt.x, jt.y, jt.z}, qj[4] = {jq.x, jq.y, jq.z, jq.w};
+    T ti[3], qi[4], tj[3], qj[4];
+    pose_3d<T>(pose[2 * q->na], pose[2 * q->na + 1], ti, qi);
+    pose_3d<T>(pose[2 * q->nb], pose[2 * q->nb + 1], tj, qj);
     const T tz[3] = {(T)q->meas[0], (T)q->meas[1], (T)q->meas[2]};
     const T qz[4] = {(T)q->meas[4], (T)q->meas[5], (T)q->meas[6], (T)q->meas[7]};
     T e[6], J[6][6];

@@ -1310,7 +1310,7 @@ def test_se3_beyond_sphere2500(api, oracle):
 
 
 def test_se3_factor_matches_the_50_digit_fixture(api):
-    """k_linearize_se3 against tests/golden/se3_jacobians.json (error and both Jacobians of the SE(3) factor from
+    """k_linearize (SE(3): D = 6) against tests/golden/se3_jacobians.json (error and both Jacobians of the SE(3) factor from
     50-digit central differences, scripts/gen_se3_golden.py -- independent of the oracle and of the kernels): on the
     one-edge graph of every case rr_pgo_assemble must return H_ii = A^T W A + 1e7 I (the edge's from-node is the
     anchor), H_ij = A^T W B, H_jj = B^T W B and b = -[A^T W e ; B^T W e], with a random SPD information matrix."""
