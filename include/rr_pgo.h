@@ -193,12 +193,47 @@ enum { RR_PGO_ROBUST_NONE = 0, RR_PGO_ROBUST_HUBER = 1, RR_PGO_ROBUST_CAUCHY = 2
 /* edge_mask: [n_edges], nonzero = robustified; NULL = every edge.  Copied.  EINVAL: unknown kind, delta not finite or <= 0
  * (NONE ignores delta), mask length implied by n_edges. */
 int rr_pgo_set_robust_kernel(rr_pgo *h, int32_t kind, double delta, const int32_t *edge_mask);
-/* s_e = e^T Omega e and w_e at the current state, file order; weight_out may be NULL.  EUNSUPPORTED on sharded handles. */
+/* s_e = e^T Omega e and w_e at the current state, file order; weight_out may be NULL.  EUNSUPPORTED on sharded handles.
+ * Edges only: the priors of rr_pgo_set_priors have rr_pgo_prior_errors. */
 int rr_pgo_edge_errors(rr_pgo *h, double *chi2_out, double *weight_out);
+
+/* ---- absolute priors on poses and landmarks (build-defined; the reference has only the anchor term) ----
+ * A prior on node i is the edge of the node's own kind from a FIXED identity pose to node i: an SE2 pose takes an
+ * RR_PGO_EDGE_SE2 term, an XY landmark an RR_PGO_EDGE_SE2_XY term, an SE3 pose an RR_PGO_EDGE_SE3 term, with measurement z
+ * and information Omega packed exactly as an edge's are (3 | 2 | 7 and 6 | 3 | 21 values).  So e = Log(Z^-1 X_i) for poses,
+ * e = l - z for landmarks, B = de/d(node) as the linearisation computes it for such an edge at the current state, and
+ *   H_ii += w B^T Omega B,   b_i gets w B^T Omega e before the negation,   chi2 += rho(e^T Omega e)
+ * with w and rho of the handle's robust kernel when the prior is flagged robust and a kernel is set, else w = 1, rho(s) = s.
+ * Arithmetic in the linearisation's type (f64 in the f64 and mixed modes, f32 in the f32 mode); chi2 sums in f64.  The
+ * Levenberg-Marquardt lambda and the anchor term are never weighted.  The sparsity pattern of H does not change.
+ * rr_pgo_set_priors REPLACES the handle's whole prior list; the arrays are copied.  node: [n_priors] node indices, a node
+ * may carry any number of priors (they add); meas, info: packed in prior order by the node's kind; robust: [n_priors],
+ * nonzero = robustified, NULL = none.  n_priors == 0 clears the list: the handle then behaves, bit for bit, as a handle that
+ * never had priors, and keep_anchor is forced back to 1.
+ * keep_anchor != 0: the 1e7 term on rr_pgo_anchor_node stays; the system is the reference's plus the priors.
+ * keep_anchor == 0: the anchor term is dropped from every later linearisation and the priors alone must fix the gauge.
+ * That is the CALLER'S responsibility: a system the priors leave singular (no pose prior in a connected component, say)
+ * ends as RR_PGO_ENOTSPD or as an ill-conditioned solve, not as an error of this call.
+ * The list holds from the next linearisation on, for every entry point that linearises: rr_pgo_chi2,
+ * rr_pgo_linearize_solve, rr_pgo_optimize, rr_pgo_iterate_async, rr_pgo_assemble, rr_pgo_profile, and the four factor
+ * queries below.  The state, the Levenberg-Marquardt lambda and the robust setting are untouched; captured graphs are
+ * dropped, as by rr_pgo_set_robust_kernel.  On RR_PGO_F32 / RR_PGO_MIXED handles whose Gauss-Newton steps use the gauge
+ * transfer (a big root front), that transfer is off while the list is non-empty: the system is then the one described here.
+ * RR_PGO_EINVAL, decided before anything changes, the message names the prior: n_priors < 0, a null required pointer, a
+ * node out of range, a non-finite value, Omega not positive definite, an SE3 measurement whose quaternion has zero norm.
+ * RR_PGO_EUNSUPPORTED (the message says which): sharded handles; handles created under RR_PGO_EDGE_LINEARIZE=1 or =2 (the
+ * measured-alternative linearisation forms are not taught the priors). */
+int rr_pgo_set_priors(rr_pgo *h, int32_t n_priors, const int32_t *node, const double *meas, const double *info,
+                      const int32_t *robust /* may be NULL: none */, int32_t keep_anchor);
+int32_t rr_pgo_num_priors(const rr_pgo *h);
+/* s_p = e^T Omega e and w_p of every prior at the current state, in the order of the rr_pgo_set_priors call; weight_out may
+ * be NULL.  The counterpart of rr_pgo_edge_errors, which stays edges-only.  EUNSUPPORTED as for rr_pgo_set_priors. */
+int rr_pgo_prior_errors(rr_pgo *h, double *s_out, double *weight_out /* may be NULL */);
 
 /* ---- marginal covariances (build-defined; the reference has none) ----------
  * Blocks of Sigma = H^-1 at the current state (H as rr_pgo_linearize_solve(h, 0, 0) builds it: anchor prior 1e7 included,
- * lambda = 0, robust weights included while a kernel is set).
+ * lambda = 0, robust weights included while a kernel is set; with a prior list, rr_pgo_set_priors, H is the one with the
+ * priors, and without the anchor term under keep_anchor == 0).
  * Query q asks for block (node_a[q], node_b[q]): d_a x d_b, row-major, tangent coordinates in the order
  * rr_pgo_linearize_solve's dx uses for the node.  node_b == NULL: diagonal blocks of node_a.
  * node_a == NULL too: n_query must be rr_pgo_num_nodes, all diagonal blocks in node order.
@@ -216,7 +251,8 @@ int rr_pgo_marginals(rr_pgo *h, int32_t n_query, const int32_t *node_a, const in
 int rr_pgo_marginals_times(const rr_pgo *h, double *ms);
 
 /* Covariance blocks of ARBITRARY node pairs: block q is Sigma(node_a[q], node_b[q]), d_a x d_b row-major, for any two
- * valid nodes -- joined by an edge or far apart in the elimination tree (a == b: the node's diagonal block).  Same H, same
+ * valid nodes -- joined by an edge or far apart in the elimination tree (a == b: the node's diagonal block).  Same H (the
+ * one with the priors of rr_pgo_set_priors when the handle has any), same
  * coordinates, same out / out_offset / n_vals conventions as rr_pgo_marginals (out == NULL: size query; out_offset may
  * be NULL), with these differences: node_a and node_b are both required; every pair is answered; a node may appear in
  * any number of queries.
@@ -240,6 +276,7 @@ int rr_pgo_covariances_times(const rr_pgo *h, double *ms);
  * order) -- that is NOT part of the graph:
  *   e, A = de/d(from), B = de/d(to)   what the linearisation computes for such an edge at the current state (dx's coordinates)
  *   S = Omega^-1 + [A B] Sigma_{ab,ab} [A B]^T     the innovation covariance; Sigma = H^-1, H as for rr_pgo_covariances
+ *                                                  (with the priors of rr_pgo_set_priors when the handle has any)
  *   d2_out[c] = e^T S^-1 e                         compare with a chi-square quantile of d_e = 3 / 2 / 6 degrees of freedom
  *   chi2_out[c] = e^T Omega e                      the term the edge would add to rr_pgo_chi2 (may be NULL)
  *   innov_out (may be NULL): S per candidate, d_e x d_e row-major, packed; innov_offset (may be NULL): [n_cand + 1] offsets.
@@ -264,7 +301,8 @@ int rr_pgo_gate_times(const rr_pgo *h, double *ms);
 /* Joint compatibility of SETS of candidates: set s is the ordered list set_cand[set_ptr[s] .. set_ptr[s + 1]) of indices
  * into the n_cand candidates (given as for rr_pgo_gate_edges); a candidate may appear in any number of sets, and twice in
  * one (two independent measurements).  With e_s the stacked errors of the set (D_s = the sum of its d_e) and
- * G_s = [G_c1 .. G_cm], G_c = Z_a A_c^T + Z_b B_c^T as for rr_pgo_gate_edges:
+ * G_s = [G_c1 .. G_cm], G_c = Z_a A_c^T + Z_b B_c^T as for rr_pgo_gate_edges (the same H: with the priors of
+ * rr_pgo_set_priors when the handle has any):
  *   S_s = blockdiag(Omega_c^-1) + G_s^T G_s        the joint innovation covariance: the cross block of candidates c and d is
  *                                                  G_c^T G_d, summed over the pivot rows their root paths share
  *   d2_out[s] = e_s^T S_s^-1 e_s                   compare with a chi-square quantile of D_s degrees of freedom
@@ -314,7 +352,8 @@ int rr_pgo_gate_joint_times(const rr_pgo *h, double *ms);
  * list order, (cos, sin) and quaternions renormalised; the guessed values of the new nodes are copied into the host graph
  * (rr_pgo_get_graph shows them, the analysis sees what a fresh handle on that graph would).
  * Carried over: the solver option; the robust kernel's kind and delta; its edge mask, extended with 1 for every new edge (a
- * fresh closure is robustified; a NULL mask stays NULL).  NOT carried: captured graphs, the tree and selected-inverse tables of
+ * fresh closure is robustified; a NULL mask stays NULL); the prior list of rr_pgo_set_priors with its robust flags and
+ * keep_anchor (node indices do not change).  NOT carried: captured graphs, the tree and selected-inverse tables of
  * the queries, rr_pgo_set_state's memo of the previous state, the Levenberg-Marquardt lambda and the *_times of earlier calls;
  * rr_pgo_stream may return another stream.  Pointers from an earlier rr_pgo_get_graph become invalid.
  * Atomic: the new graph, analysis and engine are built completely and then swapped in; the old stream is synchronised before

@@ -9,6 +9,12 @@
   --robust huber:DELTA | cauchy:DELTA  (both modes): a robust kernel on every edge (include/rr_pgo.h); the errors printed
       are then the robust cost
 
+  --priors FILE  (both modes): absolute priors (rr_pgo_set_priors), one per line: NODE_ID (the g2o vertex id), then the
+      measurement and the upper triangle of the information matrix in g2o's order for the node's kind (SE2 pose: x y theta
+      and 6 values; XY landmark: x y and 3; SE3 pose: x y z qx qy qz qw and 21); `#` starts a comment.  A vertex may be
+      named any number of times.  With --free-anchor the 1e7 term on the anchor node is dropped and the priors alone fix
+      the gauge.  Both apply before --robust and the optimisation; the report prints the priors' share of the final cost
+
   --marginals FILE  (example mode): after the optimisation, one line per node -- id, d, the upper triangle of its d x d
       covariance block (rr_pgo_marginals; f64 handles whose fronts all live in LDS)
 
@@ -145,6 +151,50 @@ def parse_gate_file(path, index, sets=None, flag="--gate"):
             info.extend(vals[nm:])
             ids.append((i, j))
     return kind, a, b, meas, info, ids
+
+
+def parse_priors_file(path, index, node_kind):
+    """A --priors file as (node, meas, info) in the packing of rr_pgo_set_priors.  `index` maps a g2o vertex id to the
+    node's index, node_kind[index] is the node's kind.  Needs no device.  A short line, a bad number or an unknown vertex
+    is a SystemExit that names the line."""
+    from .mapping import GATE_INFO_LEN, GATE_MEAS_LEN
+    node, meas, info = [], [], []
+    with open(path) as f:
+        for no, line in enumerate(f, 1):
+            tok = line.split("#", 1)[0].split()
+            if not tok:
+                continue
+            try:
+                i = int(tok[0])
+                vals = [float(t) for t in tok[1:]]
+            except ValueError:
+                raise SystemExit(f"--priors: {path}:{no}: expected a vertex id and numbers")
+            if i not in index:
+                raise SystemExit(f"--priors: {path}:{no}: no vertex with id {i} in the graph")
+            k = int(node_kind[index[i]])
+            nm, ni = GATE_MEAS_LEN[k], GATE_INFO_LEN[k]
+            if len(vals) != nm + ni:
+                raise SystemExit(f"--priors: {path}:{no}: expected {nm + ni} values after the id "
+                                 f"({nm} of the measurement, {ni} of the information), got {len(vals)}")
+            node.append(index[i])
+            meas.extend(vals[:nm])
+            info.extend(vals[nm:])
+    return node, meas, info
+
+
+def apply_priors_file(g, path, free_anchor):
+    node, meas, info = parse_priors_file(path, _node_index(g), g.graph_arrays()[0])
+    g.set_priors(node, meas, info, keep_anchor=not free_anchor)
+    return len(node)
+
+
+def print_prior_share(g):
+    import numpy as np
+    s, _ = g.prior_errors()
+    total = g.global_error()
+    # the cost of a prior is rho(s): s itself unless the prior is flagged robust (the CLI flags none)
+    share = float(np.sum(s))
+    print(f"priors: {len(s)} priors carry {share:.9g} of the final cost {total:.9g} ({100.0 * share / total if total else 0.0:.3g} %)")
 
 
 VERTEX_TAGS = {"VERTEX_SE2": 0, "VERTEX_XY": 1, "VERTEX_SE3:QUAT": 2}
@@ -322,6 +372,10 @@ def main(argv=None):
     ap.add_argument("--repeats", type=int, default=20)
     ap.add_argument("--robust", type=_robust_arg, default=None, metavar="KIND:DELTA",
                     help="robust kernel on every edge: huber:DELTA or cauchy:DELTA")
+    ap.add_argument("--priors", metavar="FILE", default=None,
+                    help="absolute priors, one per line: NODE_ID, measurement, upper triangle of the information")
+    ap.add_argument("--free-anchor", action="store_true",
+                    help="with --priors: drop the 1e7 term on the anchor node, the priors alone fix the gauge")
     ap.add_argument("--marginals", metavar="FILE", default=None,
                     help="after the optimisation write every node's covariance block: id, d, upper triangle")
     ap.add_argument("--joint", type=_ids_arg, metavar="ID,ID,...", default=None,
@@ -341,10 +395,14 @@ def main(argv=None):
         ap.error("--accept needs --gate FILE")
     if a.guess and not a.extend:
         ap.error("--guess needs --extend FILE")
+    if a.free_anchor and not a.priors:
+        ap.error("--free-anchor needs --priors FILE")
     solver = PoseGraphSolver[a.solver]
 
     def new():
         g = PoseGraph.new(a.file, solver, precision=a.precision)
+        if a.priors:
+            apply_priors_file(g, a.priors, a.free_anchor)
         if a.robust:
             g.set_robust_kernel(*a.robust)
         return g
@@ -353,7 +411,11 @@ def main(argv=None):
         if a.robust:
             print(f"robust kernel {a.robust[0]}, delta {a.robust[1]:g}")
         g = new()
+        if a.priors:
+            print(f"{g.num_priors} priors from {a.priors}" + (", anchor term dropped" if a.free_anchor else ""))
         g.optimize(50 if a.iterations is None else a.iterations, True, a.plot)
+        if a.priors:
+            print_prior_share(g)
         if a.marginals:
             write_marginals(g, a.marginals)
         if a.joint:

@@ -35,7 +35,7 @@ EXPORTS = (
     "rr_pgo_node_owner", "rr_pgo_trim", "rr_pgo_set_robust_kernel", "rr_pgo_edge_errors", "rr_pgo_solve_form",
     "rr_pgo_marginals", "rr_pgo_marginals_times", "rr_pgo_covariances", "rr_pgo_covariances_times",
     "rr_pgo_gate_edges", "rr_pgo_gate_times", "rr_pgo_gate_joint", "rr_pgo_gate_joint_times",
-    "rr_pgo_extend", "rr_pgo_extend_times",
+    "rr_pgo_extend", "rr_pgo_extend_times", "rr_pgo_set_priors", "rr_pgo_num_priors", "rr_pgo_prior_errors",
 )
 
 
@@ -145,6 +145,10 @@ def load():
     L.rr_pgo_gate_joint_times.argtypes = [vp, dp]
     L.rr_pgo_extend.argtypes = [vp, C.c_int32, ip, C.POINTER(C.c_uint32), dp, C.c_int32, ip, ip, ip, dp, dp]
     L.rr_pgo_extend_times.argtypes = [vp, dp]
+    L.rr_pgo_set_priors.argtypes = [vp, C.c_int32, ip, dp, dp, ip, C.c_int32]
+    L.rr_pgo_num_priors.argtypes = [vp]
+    L.rr_pgo_num_priors.restype = C.c_int32
+    L.rr_pgo_prior_errors.argtypes = [vp, dp, dp]
     if L.rr_pgo_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH} speaks ABI version {L.rr_pgo_abi_version()}, this mirror {ABI_VERSION}: rebuild the library")
     _lib = L

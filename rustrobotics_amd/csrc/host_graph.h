@@ -16,6 +16,8 @@ inline int node_state_len(int kind) { return kind == NODE_SE2 ? 3 : kind == NODE
 inline int edge_dim(int kind) { return kind == EDGE_SE2 ? 3 : kind == EDGE_SE2_XY ? 2 : 6; }
 inline int edge_meas_len(int kind) { return kind == EDGE_SE2 ? 3 : kind == EDGE_SE2_XY ? 2 : 7; }
 inline int edge_info_len(int kind) { return kind == EDGE_SE2 ? 6 : kind == EDGE_SE2_XY ? 3 : 21; }
+// a prior on a node is the edge of the node's own kind from a fixed identity pose (rr_pgo_set_priors)
+inline int prior_edge_kind(int node_kind) { return node_kind == NODE_SE2 ? EDGE_SE2 : node_kind == NODE_XY ? EDGE_SE2_XY : EDGE_SE3; }
 
 // The device form of a node's state and of an edge's measurement (the two numberings coincide), as two 4-vectors:
 //   SE2  x, y, cos, sin | -      XY  x, y, 0, 0 | -      SE3  t (3), 0 | q (4) / |q|

@@ -192,6 +192,12 @@ template <typename T, typename TC = T> struct LinArgs {
   int *blocks_done;                      // zero between launches
   TC robust_delta, robust_delta2;        // robust kernel (k_linearize's RK): delta and delta^2
   const uint8_t *robust_mask;            // per edge: 1 = robustified; null = every edge
+  // priors (rr_pgo_set_priors; read by k_linearize's PR instantiations only): CSR by node, records in CSR order
+  const int32_t *prior_ptr;              // [n_nodes + 1]
+  const EdgeRec<TC> *prior_rec;          // SE(2): `to` = the node, meas and information packed as an edge of the node's kind
+  const typename VecT<TC>::V4 *prior_meas;   // SE(3): 2 per prior, packed like a pose
+  const TC *prior_info;                  // SE(3): 21 per prior, row-major upper triangle
+  const uint8_t *prior_robust;           // per prior: 1 = robustified while a kernel is set
 };
 template <typename A> __device__ __forceinline__ void opt_reset_in_first_thread(const A &a) {
   if (a.reset_ctrl && blockIdx.x == 0 && threadIdx.x == 0) {
@@ -394,6 +400,20 @@ template <int D, typename T> __device__ __forceinline__ T row_dot(const T *a, co
   }
 }
 
+// A prior on a node (include/rr_pgo.h, rr_pgo_set_priors) is the edge of the node's kind from a FIXED identity pose to the
+// node: e and B = de/d(node) are what the edge functions return with a constant identity as the `from` operand.
+template <typename T>
+__device__ __forceinline__ void prior_linearize_2d(int kind, const typename VecT<T>::V4 &x, const typename VecT<T>::V4 &z, T e[3], T B[3][3]) {
+  const typename VecT<T>::V4 ident{(T)0, (T)0, (T)1, (T)0};
+  T A[3][3];
+  edge_linearize_2d<T>(kind, ident, x, z, e, A, B);
+}
+template <typename T>
+__device__ __forceinline__ void prior_linearize_3d(const T tx[3], const T qx[4], const T tz[3], const T qz[4], T e[6], T B[6][6]) {
+  const T t0[3] = {(T)0, (T)0, (T)0}, q0[4] = {(T)0, (T)0, (T)0, (T)1};
+  edge_linearize_3d<T>(1, t0, q0, tx, qx, tz, qz, e, B);
+}
+
 // Robust kernels (include/rr_pgo.h, rr_pgo_set_robust_kernel): rho(s) and the IRLS weight w = rho'(s) at s = e^T W e.
 // A template argument of the linearisation kernels: the NONE instantiation is the plain least-squares code.
 enum : int { ROBUST_NONE = 0, ROBUST_HUBER = 1, ROBUST_CAUCHY = 2 };
@@ -593,7 +613,12 @@ template <typename A> __device__ __forceinline__ void opt_publish_chi2_in_last_b
 // RK: the robust kernel (ROBUST_*).  Every incidence of a robustified edge computes s = e^T W e and scales W by w(s) before
 // J^T W is formed, so the diagonal block, the right-hand side and the off-diagonal block all carry the weight; both endpoints'
 // lanes compute e from the same operands, hence the same w.  The from-role lane adds rho(s) to chi2.
-template <typename TO, typename T, int RK = ROBUST_NONE, int D = 3>
+// PR: the handle has priors (rr_pgo_set_priors).  false is the kernel without them, the one every handle without priors
+// launches.  true adds a second strided loop over the node's priors behind the incidence loop: a prior is the edge of the
+// node's kind from a fixed identity pose, evaluated through the frame of an edge's `to` role (robust scaling of W, J^T W,
+// diagonal block, right-hand side); the lane that evaluates it adds its chi2 term.  The priors of a node are summed in
+// their fixed CSR order by the same lanes and the same group_sum8: no atomics, the same bits in every run.
+template <typename TO, typename T, int RK = ROBUST_NONE, int D = 3, bool PR = false>
 __global__ void __launch_bounds__(LIN_THREADS) k_linearize(LinArgs<TO, T> a) {
   using V4 = typename VecT<T>::V4;
   constexpr int NV = D / 3;             // V4s per node and per measurement
@@ -723,6 +748,64 @@ __global__ void __launch_bounds__(LIN_THREADS) k_linearize(LinArgs<TO, T> a) {
               for (int j = 0; j < 6; j++) dst[tr ? j * 6 + i : i * 6 + j] = (TO)row_dot<6, T>(JW[i], &Bm[0][j], 6);
           }
         }
+      }
+    }
+    if constexpr (PR) {
+      const int p1 = a.prior_ptr[node + 1];
+      for (int p = a.prior_ptr[node] + sub; p < p1; p += LIN_GROUP) {
+        T W[D][D], e[D], J[D][D];
+        // ---- per dimension: the operands, e and J = B of the edge identity -> node
+        if constexpr (D == 3) {
+          const EdgeRec<T> rec = a.prior_rec[p];
+          info_2d<T>(rec, W);
+          prior_linearize_2d<T>(nd == 2 ? 1 : 0, self[0], rec.meas, e, J);
+        } else {
+          T ts[3], qs[4], tz[3], qz[4];
+          pose_3d<T>(self[0], self[1], ts, qs);
+          pose_3d<T>(a.prior_meas[2 * p], a.prior_meas[2 * p + 1], tz, qz);
+          info_3d<T>(a.prior_info + (int64_t)p * 21, W);
+          prior_linearize_3d<T>(ts, qs, tz, qz, e, J);
+        }
+        // ---- the frame, as for an edge in its `to` role
+        T s_rob = 0;
+        bool rob = false;
+        if constexpr (RK != ROBUST_NONE) {
+          s_rob = edge_chi2<D, T>(W, e);
+          rob = a.prior_robust[p] != 0;
+          if (rob) {
+            const T w = robust_weight<RK, T>(s_rob, a.robust_delta, a.robust_delta2);
+#pragma unroll
+            for (int i = 0; i < D; i++)
+#pragma unroll
+              for (int j = 0; j < D; j++) W[i][j] *= w;
+          }
+        }
+        if (a.write_system) {
+          T JW[D][D];   // J^T W
+#pragma unroll
+          for (int i = 0; i < D; i++)
+#pragma unroll
+            for (int j = 0; j < D; j++) {
+              T s = 0;
+#pragma unroll
+              for (int r = 0; r < D; r++) s += J[r][i] * W[r][j];
+              JW[i][j] = s;
+            }
+          int t = 0;
+#pragma unroll
+          for (int i = 0; i < D; i++)
+#pragma unroll
+            for (int j = 0; j <= i; j++) {
+              T s = 0;
+#pragma unroll
+              for (int r = 0; r < D; r++) s += JW[i][r] * J[r][j];
+              hd[t++] += s;
+            }
+#pragma unroll
+          for (int i = 0; i < D; i++) bv[i] += row_dot<D, T>(JW[i], e, 1);
+        }
+        if constexpr (RK == ROBUST_NONE) chi += (double)edge_chi2<D, T>(W, e);
+        else chi += (double)(rob ? robust_rho<RK, T>(s_rob, a.robust_delta, a.robust_delta2) : s_rob);
       }
     }
   }
@@ -1073,6 +1156,48 @@ template <typename TC> __global__ void __launch_bounds__(256) k_edge_errors(Edge
   }
   a.s_out[k] = (double)s;
   if (a.w_out) a.w_out[k] = (double)wt;
+}
+
+// rr_pgo_prior_errors: one thread per prior (CSR order; the host puts them back in the call's order), s = e^T Omega e and the
+// robust weight of flagged priors at the current state, in f64.  The error code of k_linearize's prior loop, in TC.
+template <typename TC> struct PriorErrArgs {
+  int n_priors, is3d, kind;              // kind: ROBUST_*
+  const int32_t *node;                   // per prior
+  const EdgeRec<TC> *rec;                // SE(2)
+  const typename VecT<TC>::V4 *pose;     // SE(2): 1 per node; SE(3): 2 per node
+  const typename VecT<TC>::V4 *meas;     // SE(3): 2 per prior
+  const TC *info;                        // SE(3): 21 per prior
+  const uint8_t *node_dim;               // SE(2): 3 (pose) or 2 (landmark)
+  TC delta, delta2;
+  const uint8_t *robust;                 // per prior
+  double *s_out, *w_out;
+};
+template <typename TC> __global__ void __launch_bounds__(256) k_prior_errors(PriorErrArgs<TC> a) {
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= a.n_priors) return;
+  const int node = a.node[p];
+  TC s;
+  if (!a.is3d) {
+    const EdgeRec<TC> rec = a.rec[p];
+    TC W[3][3], e[3], B[3][3];
+    info_2d<TC>(rec, W);
+    prior_linearize_2d<TC>(a.node_dim[node] == 2 ? 1 : 0, a.pose[node], rec.meas, e, B);
+    s = edge_chi2_2d<TC>(W, e);
+  } else {
+    TC tx[3], qx[4], tz[3], qz[4], W[6][6], e[6], B[6][6];
+    pose_3d<TC>(a.pose[2 * node], a.pose[2 * node + 1], tx, qx);
+    pose_3d<TC>(a.meas[2 * p], a.meas[2 * p + 1], tz, qz);
+    info_3d<TC>(a.info + (int64_t)p * 21, W);
+    prior_linearize_3d<TC>(tx, qx, tz, qz, e, B);
+    s = edge_chi2_3d<TC>(W, e);
+  }
+  TC wt = 1;
+  if (a.robust[p]) {
+    if (a.kind == ROBUST_HUBER) wt = robust_weight<ROBUST_HUBER, TC>(s, a.delta, a.delta2);
+    else if (a.kind == ROBUST_CAUCHY) wt = robust_weight<ROBUST_CAUCHY, TC>(s, a.delta, a.delta2);
+  }
+  a.s_out[p] = (double)s;
+  a.w_out[p] = (double)wt;
 }
 
 // rr_pgo_extend without node_state: initial values of appended nodes, composed on the device from a pose that is already

@@ -240,6 +240,15 @@ static double now_ms() {
 // one step of rr_pgo_extend's initial guess as the host plans it: node dst from node src and a measurement (graph packing)
 struct HostGuessStep { int32_t src, dst, op; double m[7]; };
 
+// the prior list of a handle (rr_pgo_set_priors) as the caller gave it, checked: rr_pgo_extend carries it to the grown handle
+struct PriorSet {
+  std::vector<int32_t> node;
+  std::vector<double> meas, info;   // packed in prior order by the node's kind, as edge measurements and information are
+  std::vector<uint8_t> robust;      // per prior
+  int keep_anchor = 1;
+  int n() const { return (int)node.size(); }
+};
+
 struct EngineBase {
   enum Query { Q_MARGINALS, Q_COVARIANCES, Q_GATE, Q_GATE_JOINT };   // the factor queries, in the order of their ABI functions
   virtual ~EngineBase() = default;
@@ -267,6 +276,10 @@ struct EngineBase {
   virtual void debug_withhold(int mode) = 0;   // failure injection for the dataflow launches (rr_pgo_debug_withhold)
   virtual void set_robust(int kind, double delta, const int32_t *mask) = 0;   // rr_pgo_set_robust_kernel (arguments checked)
   virtual void edge_errors(double *s_out, double *w_out) = 0;                  // rr_pgo_edge_errors
+  virtual void refuse_priors(const char *who) const = 0;                       // EUNSUPPORTED where priors cannot be held
+  virtual void set_priors(const PriorSet &ps) = 0;                             // rr_pgo_set_priors (arguments checked)
+  virtual const PriorSet &priors() const = 0;
+  virtual void prior_errors(double *s_out, double *w_out) = 0;                 // rr_pgo_prior_errors
   // rr_pgo_marginals (arguments checked; off: [nq + 1] offsets of the blocks in out) / rr_pgo_marginals_times
   virtual void marginals(int nq, const int32_t *na, const int32_t *nb, const int64_t *off, double *out) = 0;
   // rr_pgo_covariances (arguments checked; off as for marginals) / rr_pgo_covariances_times
@@ -533,6 +546,15 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   double robust_delta_ = 1.0;
   DevBuf<uint8_t> robust_mask_;
   std::vector<uint8_t> robust_mask_host_;
+  // priors (rr_pgo_set_priors): the caller's list, and its device form -- CSR by node, records in CSR order (a node's priors
+  // in the call's order).  The buffers live in the arena and only grow (DevBuf::n is their capacity).
+  PriorSet priors_;
+  std::vector<int32_t> prior_order_;   // CSR position -> index in the call
+  DevBuf<int32_t> prior_ptr_, prior_node_;
+  DevBuf<EdgeRec<S>> prior_rec_;       // SE(2)
+  DevBuf<V4> prior_meas_;              // SE(3)
+  DevBuf<S> prior_info3_;              // SE(3)
+  DevBuf<uint8_t> prior_robust_;
   DevBuf<V4> guess_stage_;           // rr_pgo_extend's initial guess: the old state and the new nodes behind it (made by that call)
   int host_counter_ = 0;             // mirrors the device slot counter
 
@@ -1598,7 +1620,8 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
 
   LinArgs<T, S> lin_args(double lambda, int lm, int write_system, bool reference_prior = false) {
     // Gauss-Newton with a single-precision factor: no anchor prior, the root front carries the gauge term
-    if (write_system) gauge_now_ = gauge_ok_ && !lm && !reference_prior;
+    // (not with priors: the gauge term assumes that H without the anchor term is singular along the SE(2) gauge)
+    if (write_system) gauge_now_ = gauge_ok_ && !lm && !reference_prior && priors_.n() == 0;
     LinArgs<T, S> a;
     a.n_nodes = n_list_;
     a.node_list = node_list_.p;
@@ -1616,7 +1639,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     a.hvals = hvals_.p;
     a.b = b_.p;
     a.chi2_partial = chi_partial_.p;
-    a.anchor = (write_system && gauge_now_) ? -1 : g_.anchor_node;
+    a.anchor = ((write_system && gauge_now_) || !priors_.keep_anchor) ? -1 : g_.anchor_node;
     a.lambda = lm ? (S)lambda : (S)0;
     a.write_system = write_system;
     a.adds_diag = norm_counts_.p;
@@ -1626,12 +1649,20 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     a.n_fill_words = lds_flow_ ? (int)((size_t)g_.dim * sizeof(T) / 4) : 0;
     opt_lin_fields(a, lm);
     robust_fields(a);
+    prior_fields(a);
     return a;
   }
   void robust_fields(LinArgs<T, S> &a) const {
     a.robust_delta = (S)robust_delta_;
     a.robust_delta2 = (S)(robust_delta_ * robust_delta_);
     a.robust_mask = robust_mask_.n ? robust_mask_.p : nullptr;
+  }
+  void prior_fields(LinArgs<T, S> &a) const {   // (read by the PR instantiations alone: launch_pull)
+    a.prior_ptr = prior_ptr_.p;
+    a.prior_rec = prior_rec_.p;
+    a.prior_meas = prior_meas_.p;
+    a.prior_info = prior_info3_.p;
+    a.prior_robust = prior_robust_.p;
   }
   // what a linearisation inside a pipelined rr_pgo_optimize call carries: the reset of the loop state (first launch of
   // the call), lambda from the device (Levenberg-Marquardt)
@@ -1742,6 +1773,11 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     pend(RR_PGO_K_LINEARIZE);
   }
   template <int RK> void launch_pull(const LinArgs<T, S> &la) {   // the pull form of either dimension under robust kernel RK
+    if (priors_.n() > 0) {   // (a handle without priors launches the kernels it always did)
+      if (is3d_) hipLaunchKernelGGL((k_linearize<T, S, RK, 6, true>), dim3(n_lin_blocks_), dim3(LIN_THREADS), 0, stream_, la);
+      else hipLaunchKernelGGL((k_linearize<T, S, RK, 3, true>), dim3(n_lin_blocks_), dim3(LIN_THREADS), 0, stream_, la);
+      return;
+    }
     if (is3d_) hipLaunchKernelGGL((k_linearize<T, S, RK, 6>), dim3(n_lin_blocks_), dim3(LIN_THREADS), 0, stream_, la);
     else hipLaunchKernelGGL((k_linearize<T, S, RK, 3>), dim3(n_lin_blocks_), dim3(LIN_THREADS), 0, stream_, la);
   }
@@ -2673,6 +2709,113 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     HIPCHK(hipStreamSynchronize(stream_));
     std::memcpy(s_out, host.data(), E * sizeof(double));
     if (w_out) std::memcpy(w_out, host.data() + E, E * sizeof(double));
+  }
+
+  // ---- priors (include/rr_pgo.h, rr_pgo_set_priors)
+  void refuse_priors(const char *who) const override {
+    const std::string w = who;
+    if (sharded_ || world_ > 1) throw ApiError(RR_PGO_EUNSUPPORTED, w + ": sharded handle (the ranks' node lists and diagonal ownership are not taught the priors)");
+    if (edge_lin_env_) throw ApiError(RR_PGO_EUNSUPPORTED, w + ": handle created under RR_PGO_EDGE_LINEARIZE (the edge-parallel linearisation forms are not taught the priors)");
+  }
+  template <typename U> void upload_grow(DevBuf<U> &buf, const std::vector<U> &v) {
+    if (v.size() > buf.n) {
+      ArenaScope scope(&arena_);
+      buf.alloc(v.size());
+    }
+    if (!v.empty()) HIPCHK(hipMemcpy(buf.p, v.data(), v.size() * sizeof(U), hipMemcpyHostToDevice));
+  }
+  void set_priors(const PriorSet &ps) override {
+    refuse_priors("rr_pgo_set_priors");
+    const int P = ps.n(), N = g_.n_nodes();
+    // CSR by node; a node's priors keep the call's order (they are summed in it)
+    std::vector<int32_t> ptr((size_t)N + 1, 0), order((size_t)P), pnode((size_t)P);
+    for (int p = 0; p < P; p++) ptr[(size_t)ps.node[p] + 1]++;
+    for (int i = 0; i < N; i++) ptr[(size_t)i + 1] += ptr[i];
+    std::vector<int64_t> moff((size_t)P + 1, 0), ioff((size_t)P + 1, 0);
+    for (int p = 0; p < P; p++) {
+      const int ek = prior_edge_kind(g_.node_kind[ps.node[p]]);
+      moff[(size_t)p + 1] = moff[p] + edge_meas_len(ek);
+      ioff[(size_t)p + 1] = ioff[p] + edge_info_len(ek);
+    }
+    {
+      std::vector<int32_t> fill(ptr.begin(), ptr.end() - 1);
+      for (int p = 0; p < P; p++) order[(size_t)fill[ps.node[p]]++] = p;
+    }
+    std::vector<EdgeRec<S>> rec(is3d_ ? 0 : (size_t)P);
+    std::vector<V4> meas(is3d_ ? 2 * (size_t)P : 0);
+    std::vector<S> info(is3d_ ? 21 * (size_t)P : 0);
+    std::vector<uint8_t> rob((size_t)P);
+    for (int c = 0; c < P; c++) {
+      const int p = order[c], node = ps.node[p];
+      const double *m = &ps.meas[(size_t)moff[p]], *w = &ps.info[(size_t)ioff[p]];
+      pnode[c] = node;
+      rob[c] = ps.robust[p];
+      if (is3d_) {
+        pack_v4(EDGE_SE3, m, &meas[2 * (size_t)c]);
+        for (int t = 0; t < 21; t++) info[21 * (size_t)c + t] = (S)w[t];
+        continue;
+      }
+      EdgeRec<S> &r = rec[c];   // (slot stays 0: a prior has no off-diagonal block)
+      r.from = -1;
+      r.to = node;
+      if (g_.node_kind[node] == NODE_SE2) {
+        pack_v4(EDGE_SE2, m, &r.meas);
+        r.info_a = V4{(S)w[0], (S)w[1], (S)w[2], (S)w[3]};
+        r.info_b = V2{(S)w[4], (S)w[5]};
+      } else {
+        pack_v4(EDGE_SE2_XY, m, &r.meas);
+        r.info_a = V4{(S)w[0], (S)w[1], (S)0, (S)w[2]};
+        r.info_b = V2{(S)0, (S)0};
+      }
+    }
+    HIPCHK(hipStreamSynchronize(stream_));   // launches already enqueued read the old list
+    if (P > 0) {
+      upload_grow(prior_ptr_, ptr);
+      upload_grow(prior_node_, pnode);
+      upload_grow(prior_rec_, rec);
+      upload_grow(prior_meas_, meas);
+      upload_grow(prior_info3_, info);
+      upload_grow(prior_robust_, rob);
+    }
+    priors_ = ps;
+    if (P == 0) priors_.keep_anchor = 1;
+    prior_order_.swap(order);
+    gauge_now_ = false;   // (set again by the next linearisation that writes a system)
+    // the captured graphs hold the old kernel and its arguments
+    if (gn_exec_) { (void)hipGraphExecDestroy(gn_exec_); gn_exec_ = nullptr; }
+    for (hipGraphExec_t &e : stage_exec_) if (e) { (void)hipGraphExecDestroy(e); e = nullptr; }
+  }
+  const PriorSet &priors() const override { return priors_; }
+  void prior_errors(double *s_out, double *w_out) override {
+    refuse_priors("rr_pgo_prior_errors");
+    const int P = priors_.n();
+    if (P == 0) return;
+    DevBuf<double> out;
+    out.alloc(2 * (size_t)P);
+    PriorErrArgs<S> a;
+    a.n_priors = P;
+    a.is3d = is3d_ ? 1 : 0;
+    a.kind = robust_kind_;
+    a.node = prior_node_.p;
+    a.rec = prior_rec_.p;
+    a.pose = pose_.p;
+    a.meas = prior_meas_.p;
+    a.info = prior_info3_.p;
+    a.node_dim = node_dim_.p;
+    a.delta = (S)robust_delta_;
+    a.delta2 = (S)(robust_delta_ * robust_delta_);
+    a.robust = prior_robust_.p;
+    a.s_out = out.p;
+    a.w_out = out.p + P;
+    hipLaunchKernelGGL((k_prior_errors<S>), dim3((P + 255) / 256), dim3(256), 0, stream_, a);
+    check_launch("k_prior_errors");
+    std::vector<double> host(2 * (size_t)P);
+    HIPCHK(hipMemcpyAsync(host.data(), out.p, host.size() * sizeof(double), hipMemcpyDeviceToHost, stream_));
+    HIPCHK(hipStreamSynchronize(stream_));
+    for (int c = 0; c < P; c++) {
+      s_out[prior_order_[c]] = host[c];
+      if (w_out) w_out[prior_order_[c]] = host[(size_t)P + c];
+    }
   }
 
 
@@ -3741,6 +3884,24 @@ static int plan_guess_steps(const HostGraph &g, int n_old, int e_old, std::vecto
   return -1;
 }
 
+// rr_pgo_set_priors behind its checks, and rr_pgo_extend's carry: the engine takes the list, the statistics its bytes
+// (the CSR pointers, and per prior the node, the robust flag, the measurement and the information: whole numbers, exact)
+static double prior_bytes(const rr_pgo &h, const PriorSet &ps) {
+  if (ps.n() == 0) return 0.0;
+  const double sz = h.opt.precision == RR_PGO_F32 ? 4.0 : 8.0;   // the linearisation's type
+  double bytes = 4.0 * (h.g->n_nodes() + 1);
+  for (int p = 0; p < ps.n(); p++) {
+    const int ek = prior_edge_kind(h.g->node_kind[ps.node[p]]);
+    bytes += 5.0 + sz * (edge_meas_len(ek) + edge_info_len(ek));
+  }
+  return bytes;
+}
+static void apply_priors(rr_pgo &h, const PriorSet &ps) {
+  const double before = prior_bytes(h, h.engine->priors());
+  h.engine->set_priors(ps);
+  h.stats.bytes_linearize += prior_bytes(h, h.engine->priors()) - before;
+}
+
 static void extend_handle(rr_pgo *h, int32_t n_new_nodes, const int32_t *node_kind, const uint32_t *node_id, const double *node_state,
                           int32_t n_new_edges, const int32_t *edge_kind, const int32_t *edge_from, const int32_t *edge_to,
                           const double *edge_meas, const double *edge_info) {
@@ -3830,6 +3991,7 @@ static void extend_handle(rr_pgo *h, int32_t n_new_nodes, const int32_t *node_ki
     if (masked) mask.resize((size_t)g.n_edges(), 1);   // a fresh closure is robustified
     nh->engine->set_robust(rk, rdelta, masked ? mask.data() : nullptr);
   }
+  if (h->engine->priors().n() > 0) apply_priors(*nh, h->engine->priors());   // node indices do not change
   // ---- the swap: nothing below can fail.  The old engine (its stream drained above, the copy out of its buffers waited for)
   // goes with nh.  Every field changes sides (the engines refer to the pointees of g and symp, which do not move).
   std::swap(*h, *nh);
@@ -4149,6 +4311,46 @@ static int gate_candidates(const char *api, const rr_pgo *h, int32_t n_cand, con
     soff[c + 1] = soff[c] + de * de;
   }
   return RR_PGO_OK;
+}
+
+int rr_pgo_set_priors(rr_pgo *h, int32_t n_priors, const int32_t *node, const double *meas, const double *info,
+                      const int32_t *robust, int32_t keep_anchor) {
+  if (!h) { g_last_error = "null argument"; return RR_PGO_EINVAL; }
+  if (n_priors < 0) { g_last_error = "rr_pgo_set_priors: n_priors < 0"; return RR_PGO_EINVAL; }
+  if (n_priors > 0 && (!node || !meas || !info)) { g_last_error = "rr_pgo_set_priors: null argument (node, meas and info are required)"; return RR_PGO_EINVAL; }
+  if (const int rc = guarded([&] { h->engine->refuse_priors("rr_pgo_set_priors"); })) return rc;
+  const HostGraph &g = *h->g;
+  PriorSet ps;
+  ps.keep_anchor = keep_anchor != 0 ? 1 : 0;
+  for (int p = 0; p < n_priors; p++) {
+    auto bad = [&](const std::string &what) { g_last_error = "rr_pgo_set_priors: prior " + std::to_string(p) + ": " + what; return RR_PGO_EINVAL; };
+    if (node[p] < 0 || node[p] >= g.n_nodes()) return bad("node index out of range");
+    const int ek = prior_edge_kind(g.node_kind[node[p]]), nm = edge_meas_len(ek), ni = edge_info_len(ek), de = edge_dim(ek);
+    for (int t = 0; t < nm; t++)
+      if (!std::isfinite(meas[t])) return bad("non-finite measurement");
+    if (ek == EDGE_SE3 && !(quat_norm(meas + 3) > 0.0)) return bad("zero quaternion in the measurement");
+    double L[36] = {0};
+    for (int i = 0, t = 0; i < de; i++)
+      for (int j = i; j < de; j++, t++) {
+        if (!std::isfinite(info[t])) return bad("non-finite information matrix");
+        L[j * 6 + i] = L[i * 6 + j] = info[t];
+      }
+    if (!small_cholesky(L, de, 6)) return bad("information matrix not positive definite");
+    ps.node.push_back(node[p]);
+    ps.meas.insert(ps.meas.end(), meas, meas + nm);
+    ps.info.insert(ps.info.end(), info, info + ni);
+    ps.robust.push_back(robust && robust[p] != 0 ? 1 : 0);
+    meas += nm;
+    info += ni;
+  }
+  return guarded([&] { apply_priors(*h, ps); });
+}
+
+int32_t rr_pgo_num_priors(const rr_pgo *h) { return h ? h->engine->priors().n() : 0; }
+
+int rr_pgo_prior_errors(rr_pgo *h, double *s_out, double *weight_out) {
+  if (!h || !s_out) { g_last_error = "null argument"; return RR_PGO_EINVAL; }
+  return guarded([&] { h->engine->prior_errors(s_out, weight_out); });
 }
 
 int rr_pgo_gate_edges(rr_pgo *h, int32_t n_cand, const int32_t *edge_kind, const int32_t *edge_from, const int32_t *edge_to,

@@ -276,6 +276,48 @@ class PoseGraph:
         _check(_lib.load().rr_pgo_edge_errors(self._h, _dp(s), _dp(w)))
         return s, w
 
+    # -- priors (include/rr_pgo.h, "absolute priors") --------------------------------------
+    def set_priors(self, node, meas, info, robust=None, keep_anchor=True):
+        """Replace the handle's prior list.  node: node index per prior; meas, info: flat, packed in prior order as an
+        edge of the node's kind is (SE2 pose 3 | 6, XY landmark 2 | 3, SE3 pose 7 | 21); robust: per prior, nonzero = under
+        the handle's robust kernel (None: none); keep_anchor False drops the 1e7 anchor term, the priors alone then fix
+        the gauge.  Takes effect from the next linearisation on; an empty list clears."""
+        node = np.ascontiguousarray(node, np.int32).reshape(-1)
+        meas = np.ascontiguousarray(meas, np.float64).reshape(-1)
+        info = np.ascontiguousarray(info, np.float64).reshape(-1)
+        flags = None
+        if robust is not None:
+            flags = np.ascontiguousarray(robust).astype(np.int32).reshape(-1)
+            if flags.shape != node.shape:
+                raise ValueError("robust needs one entry per prior")
+        # the library reads the packed arrays prior by prior, up to the first node it refuses: they must reach that far
+        d = _lib.GraphDesc()
+        _check(_lib.load().rr_pgo_get_graph(self._h, C.byref(d)))
+        nk = np.ctypeslib.as_array(d.node_kind, (d.n_nodes,)) if d.n_nodes else np.zeros(0, np.int32)
+        bad = np.flatnonzero((node < 0) | (node >= len(nk)))
+        kinds = nk[node[:int(bad[0])] if len(bad) else node]
+        need_m, need_i = int(np.sum(np.take(GATE_MEAS_LEN, kinds))), int(np.sum(np.take(GATE_INFO_LEN, kinds)))
+        if (len(meas) < need_m or len(info) < need_i) if len(bad) else (len(meas) != need_m or len(info) != need_i):
+            raise ValueError("meas / info do not have the length the priors' node kinds ask for")
+        _check(_lib.load().rr_pgo_set_priors(self._h, len(node), _ip(node), _dp(meas), _dp(info),
+                                             None if flags is None else _ip(flags), 1 if keep_anchor else 0))
+
+    def clear_priors(self):
+        """Back to a handle without priors (the anchor term is kept again)."""
+        _check(_lib.load().rr_pgo_set_priors(self._h, 0, None, None, None, None, 1))
+
+    @property
+    def num_priors(self):
+        return _lib.load().rr_pgo_num_priors(self._h)
+
+    def prior_errors(self):
+        """(s, w): e^T Omega e of every prior at the current state and its robust weight (1 unless flagged and a kernel is
+        set), in the order of the set_priors call."""
+        n = self.num_priors
+        s, w = np.zeros(n), np.zeros(n)
+        _check(_lib.load().rr_pgo_prior_errors(self._h, _dp(s), _dp(w)))
+        return s, w
+
     # -- marginal covariances (include/rr_pgo.h, "marginal covariances") -----------------
     def marginal_blocks(self, node_a=None, node_b=None):
         """rr_pgo_marginals as it is: (values, offsets) of the queried blocks of Sigma = H^-1 at the current state.
