@@ -1308,6 +1308,8 @@ template <typename T> struct FactorArgs {
   // dataflow launches of the LDS fronts (lds_flow.hip.h; null / 0 elsewhere)
   const int32_t *child_dep;    // per child_meta entry: index in dep_flags of the flag that says the child's update matrix is in memory,
                                // -1 = the child was factored earlier in the same task (by this workgroup)
+  const int32_t *child_due;    // per child_meta entry (every launch form): the 16-column block of the parent's panel at whose start the child's
+                               // update matrix is added, 0 = before the panel (panel_factor, LateAdd)
   const int32_t *parent_dep;   // per front, back substitution: index of the flag that says the parent's solution is in memory, -1 = none
                                // (a root, or the parent was solved earlier in the same task)
   unsigned *dep_flags;         // [0, S): factor flags, [S, 2 S): solve flags; zeroed before every factorisation
@@ -1793,10 +1795,22 @@ template <typename T> __device__ __forceinline__ void init_w16_identity(T *wscr,
 // the Schur complement of every block but the last is then applied here, block by block, by the waves that
 // idle while wave 0 factors the next diagonal block; the caller applies the last block (columns
 // 16 * ((nc - 1) / 16) .. nc) after the panel.
+// late: children whose update matrices touch no pivot column left of block k are added at the TOP of block k's iteration
+// (process_front; symbolic.cpp orders the pivot columns so that the late children come last): late.due() is the block of the
+// next such child (-1: none left), late(k) adds every child due at k between two workgroup barriers -- the look-ahead of block
+// k - 1 is finished before the first, the diagonal block of k and the owed rest update of k - 1 start after the second (the rest
+// update and the extend-add both add into the columns right of block k and into the update matrix).  No child due: nothing changes.
 struct NoUAddr { __device__ float *operator()(int, int) const { return nullptr; } };
-template <typename T, int THREADS, bool FAST = false, typename UAddr = NoUAddr>
+struct NoLateAdd { __device__ int due() const { return -1; } __device__ void operator()(int) const {} };
+template <typename F> struct LateAdd {
+  const int *next_due;
+  F add;
+  __device__ __forceinline__ int due() const { return *next_due; }
+  __device__ __forceinline__ void operator()(int k) const { add(k); }
+};
+template <typename T, int THREADS, bool FAST = false, typename UAddr = NoUAddr, typename Late = NoLateAdd>
 __device__ __forceinline__ void panel_factor(T *P, int M, int nc, int *err, T *wscr /* 16 * 17 (FAST: W16_SCR) scalars of LDS */, T *wout,
-                             unsigned long long *acc = nullptr, int nu = 0, UAddr uaddr = UAddr(), bool defer_u = false) {
+                             unsigned long long *acc = nullptr, int nu = 0, UAddr uaddr = UAddr(), bool defer_u = false, Late late = Late()) {
   using MM = Mfma16<T>;
   constexpr int NB = 16;
   constexpr int NW = THREADS / 64;
@@ -1832,6 +1846,9 @@ __device__ __forceinline__ void panel_factor(T *P, int M, int nc, int *err, T *w
   };
   for (int k0 = 0; k0 < nc; k0 += NB) {
     const int nb = min(NB, nc - k0);
+    if constexpr (!std::is_same<Late, NoLateAdd>::value) {
+      if (late.due() == (k0 >> 4)) late(k0 >> 4);
+    }
     RRPGO_ACC_BEGIN();
     constexpr bool fast = FAST;
     auto diag = [&] {
@@ -1914,6 +1931,20 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 // for right before ITS extend-add -- everything that does not depend on it (zeroing, H entries, rhs, the children before
 // it, its scatter map) is done by then; update matrices move with sc1 accesses; the front's flag is set as soon as its
 // update matrix is in memory, the panel is copied out after that.  The arithmetic is the same in both forms.
+// -DRRPGO_STAMPS -DRRPGO_STAMPS_CHILD (scripts/gpu_flow_children.py): the parent records, in the CHILD's row, when it began to
+// wait for the child (slot 7), when the wait was over (slot 8) and the block of its panel at which it added the child (slot 9,
+// a plain number) -- instead of the child's own phase sums of panel_factor, which this build does not take: two workgroups must
+// not write the same words (their CUs may sit behind different L2s).  Children of another task only.
+#ifdef RRPGO_STAMPS_CHILD
+#define RRPGO_CHILD_STAMPS(child, t_wait, block)                                  \
+  if (tid == 0 && a.stamps && (child) >= 0) {                                     \
+    a.stamps[(int64_t)(child) * 12 + 7] = (t_wait);                               \
+    a.stamps[(int64_t)(child) * 12 + 8] = wall_clock64();                         \
+    a.stamps[(int64_t)(child) * 12 + 9] = (unsigned long long)(block);            \
+  }
+#else
+#define RRPGO_CHILD_STAMPS(child, t_wait, block)
+#endif
 template <typename T, int THREADS, bool IN_PLACE, bool FLOW = false>
 __device__ void process_front(const FactorArgs<T> &a, int s, const SnMeta &m, T *P, T *U, int uld, T *dinv) {
   static_assert(!(FLOW && IN_PLACE), "the dataflow form is for fronts in LDS");
@@ -1942,9 +1973,13 @@ __device__ void process_front(const FactorArgs<T> &a, int s, const SnMeta &m, T 
   if (tid < nc) pb = a.b[a.perm[m.col0 + tid]];
   ChildMeta cnext{};
   int dnext = -1;   // FLOW: flag of the child cnext, -1 = nothing to wait for
+  // children are added mid-panel in the fp64 LDS form only: elsewhere the host hands out all-zero due blocks (pgo_api.hip checks)
+  constexpr bool LATE = !IN_PLACE && sizeof(T) == 8;
+  int duenext = -1; // block of the panel at which the child cnext is added (0: before the panel), -1 = no child left
   if (m.child_count > 0) {
     cnext = a.child_meta[m.child_begin];
     if (FLOW) dnext = a.child_dep[m.child_begin];
+    duenext = !LATE ? 0 : __builtin_amdgcn_readfirstlane(a.child_due[m.child_begin]);   // (uniform: a scalar register, not one per lane)
   }
   if (IN_PLACE) {
     for (int64_t t = tid; t < (int64_t)M * M; t += THREADS) P[t] = 0;  // whole front, ld M
@@ -1997,7 +2032,7 @@ __device__ void process_front(const FactorArgs<T> &a, int s, const SnMeta &m, T 
     prefetch_map(c);
     if (!FLOW || dep < 0) prefetch_val(c);
   };
-  if (m.child_count > 0) prefetch(cnext, dnext);   // under the barrier and the assembly stores
+  if (duenext == 0) prefetch(cnext, dnext);   // under the barrier and the assembly stores
   if (IN_PLACE) __syncthreads();
   else lds_barrier();
   RRPGO_STAMP(a, s, 1);
@@ -2019,12 +2054,16 @@ __device__ void process_front(const FactorArgs<T> &a, int s, const SnMeta &m, T 
   // ---- extend-add of the children's update matrices, fixed child order.  A packed child into an LDS
   // parent has one precomputed destination per element; the first EPRE elements per thread of child q+1
   // are requested while child q is being added (each child is otherwise a global round trip + a barrier).
-  for (int q = 0; q < m.child_count; q++) {
+  // The children due at block 0 here; the others (sorted by their block) from inside the panel (late_add below).
+  int q = 0;
+  for (; duenext == 0; q++) {
     const ChildMeta c = cnext;
     const int dep = dnext;
+    duenext = -1;
     if (q + 1 < m.child_count) {   // the next record in flight under this child
       cnext = a.child_meta[m.child_begin + q + 1];
       if (FLOW) dnext = a.child_dep[m.child_begin + q + 1];
+      duenext = !LATE ? 0 : __builtin_amdgcn_readfirstlane(a.child_due[m.child_begin + q + 1]);
     }
     const T *Uc = child_u(c);
     if (FLOW && dep >= 0) {   // every wave for itself; the barrier below joins them
@@ -2034,6 +2073,7 @@ __device__ void process_front(const FactorArgs<T> &a, int s, const SnMeta &m, T 
       dep_wait(a.dep_flags + dep, a.err, a.wait_ticks);
 #ifdef RRPGO_STAMPS
       if (tid == 0 && a.stamps) a.stamps[(int64_t)s * 12 + 10] += wall_clock64() - w0_;   // time spent waiting for children
+      RRPGO_CHILD_STAMPS(dep, w0_, 0);
 #endif
     }
     __syncthreads();
@@ -2046,7 +2086,7 @@ __device__ void process_front(const FactorArgs<T> &a, int s, const SnMeta &m, T 
 #pragma unroll
       for (int u = 0; u < EPRE; u++)
         if (ed[u] >= 0) P[ed[u]] += ev[u];
-      if (q + 1 < m.child_count) prefetch(cnext, dnext);
+      if (duenext == 0) prefetch(cnext, dnext);
       int t = tid + EPRE * THREADS;
       for (; t + 3 * THREADS < cnt; t += 4 * THREADS) {
         const int d0 = map[t], d1 = map[t + THREADS], d2 = map[t + 2 * THREADS], d3 = map[t + 3 * THREADS];
@@ -2061,7 +2101,7 @@ __device__ void process_front(const FactorArgs<T> &a, int s, const SnMeta &m, T 
         if (d0 >= 0) P[d0] += uc_ld(Uc, ub, t);
       }
     } else {
-      if (q + 1 < m.child_count) prefetch(cnext, dnext);
+      if (duenext == 0) prefetch(cnext, dnext);
       const int32_t *rel = a.rel + c.rel_ptr;
       const int ncu = c.ncu;
       for (int t = tid; t < ncu * ncu; t += THREADS) {
@@ -2089,12 +2129,66 @@ __device__ void process_front(const FactorArgs<T> &a, int s, const SnMeta &m, T 
   auto uaddr = [&](int i, int j) {   // 32-bit index arithmetic for the packed triangle in LDS
     return IN_PLACE ? U + ((int64_t)j * uld + i) : U + (j * nu - ((j * (j - 1)) >> 1) + (i - j));
   };
-  {
+  // The children due at a later block (arrival order, symbolic.cpp step 5: handles whose fronts all live in LDS, so packed
+  // children with a scatter map): every child due at block k, in list order, from the top of block k's iteration.  The wait
+  // (FLOW) is the wait of the loop above -- bounded, draining.  By construction no destination lies in a pivot column left of
+  // block k.  Only the child's index and the next due block are carried through the panel.
+  // INVARIANT (symbolic.cpp, where child_due is built): a due block > 0 exists only in a handle without a front beyond LDS, and
+  // there every child has a packed update matrix and a scatter map (scat_ptr >= 0) -- this loop has no rel-map form.
+  auto late_add = [&](int k) {
+    do {
+      const ChildMeta c = a.child_meta[m.child_begin + q];
+      [[maybe_unused]] int dep = -1;
+      if (FLOW) dep = a.child_dep[m.child_begin + q];
+      q++;
+      duenext = q < m.child_count ? __builtin_amdgcn_readfirstlane(a.child_due[m.child_begin + q]) : -1;
+      const T *Uc = child_u(c);
+      const int32_t *map = a.scat + c.scat_ptr;
+      const int cnt = c.ncu * (c.ncu + 1) / 2;
+      [[maybe_unused]] const Sc1Buf<T> ub(Uc, FLOW ? (uint32_t)cnt * (uint32_t)sizeof(T) : 0u);
+      if (FLOW && dep >= 0) {
 #ifdef RRPGO_STAMPS
+        const unsigned long long w0_ = wall_clock64();
+#endif
+        dep_wait(a.dep_flags + dep, a.err, a.wait_ticks);
+#ifdef RRPGO_STAMPS
+        if (tid == 0 && a.stamps) a.stamps[(int64_t)s * 12 + 10] += wall_clock64() - w0_;
+        RRPGO_CHILD_STAMPS(dep, w0_, k);
+#endif
+      }
+      __syncthreads();   // the look-ahead of block k - 1, or the child before, is done with the entries this child adds to
+      // (the panel's registers are live here: two loads in flight per thread, not the four of the loop before the panel)
+      // (opaque: with a plain thread index the compiler keeps `a.scat + 4 tid`, a launch invariant, in a register pair through
+      // every front of k_factor_flow -- the two registers the 1024-thread form does not have: 12 bytes of scratch without this)
+      // (What the register allocator does with it is the compiler's choice: after a change of toolchain, read the kernel's
+      // resource usage again -- profiles/EXPERIMENTS.md r19, "Registers", has the command and the figures.)
+      int t = threadIdx.x;
+      asm volatile("" : "+v"(t));
+#pragma nounroll
+      for (; t + THREADS < cnt; t += 2 * THREADS) {
+        const int d0 = map[t], d1 = map[t + THREADS];
+        const T v0 = uc_ld(Uc, ub, t), v1 = uc_ld(Uc, ub, t + THREADS);
+        if (d0 >= 0) P[d0] += v0;
+        if (d1 >= 0) P[d1] += v1;
+      }
+      if (t < cnt) {
+        const int d0 = map[t];
+        if (d0 >= 0) P[d0] += uc_ld(Uc, ub, t);
+      }
+    } while (duenext == k);
+    __syncthreads();
+  };
+  // the hook of the fp64 LDS form, nothing elsewhere: chosen at compile time, so that the other forms are built without it
+  const auto late = [&] {
+    if constexpr (LATE) return LateAdd<decltype(late_add)>{&duenext, late_add};
+    else return NoLateAdd();
+  }();
+  {
+#if defined(RRPGO_STAMPS) && !defined(RRPGO_STAMPS_CHILD)   // (slots 7 .. 9 of this row belong to the parent in that build)
   if (tid == 0 && a.stamps) { a.stamps[(int64_t)s * 12 + 7] = 0; a.stamps[(int64_t)s * 12 + 8] = 0; a.stamps[(int64_t)s * 12 + 9] = 0; }
-  panel_factor<T, THREADS, !IN_PLACE>(P, M, nc, a.err, dinv, a.winv + (int64_t)m.wblk * 256, a.stamps ? a.stamps + (int64_t)s * 12 : nullptr, nu, uaddr, defer_u);
+  panel_factor<T, THREADS, !IN_PLACE>(P, M, nc, a.err, dinv, a.winv + (int64_t)m.wblk * 256, a.stamps ? a.stamps + (int64_t)s * 12 : nullptr, nu, uaddr, defer_u, late);
 #else
-  panel_factor<T, THREADS, !IN_PLACE>(P, M, nc, a.err, dinv, a.winv + (int64_t)m.wblk * 256, nullptr, nu, uaddr, defer_u);
+  panel_factor<T, THREADS, !IN_PLACE>(P, M, nc, a.err, dinv, a.winv + (int64_t)m.wblk * 256, nullptr, nu, uaddr, defer_u, late);
 #endif
   }
   RRPGO_STAMP(a, s, 4);

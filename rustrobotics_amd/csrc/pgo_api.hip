@@ -446,6 +446,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   // k_factor_flow / k_solve_flow (lds_flow.hip.h): every front in LDS, the factorisation and the back substitution ONE launch each
   bool lds_flow_ = false;
   DevBuf<int32_t> child_dep_, parent_dep_;
+  DevBuf<int32_t> child_due_;   // per child_meta entry: the block of the parent's panel at which the child is added (Symbolic::child_due)
   std::vector<int32_t> host_child_dep_;
   DevBuf<unsigned> dep_flags_;      // [0, S) factor flags, [S, 2 S) solve flags, then the two tickets on lines of their own, then a word nobody sets
   DevBuf<LdsFlowTask> lds_ftasks_, lds_stasks_;
@@ -826,6 +827,10 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
         xnew_.zero();
       }
       child_meta_.upload(cm);
+      if (sizeof(T) != 8)   // the fp32 kernels add every child before the panel (kernels.hip.h, process_front)
+        for (int32_t d : sym.child_due)
+          if (d != 0) throw ApiError(RR_PGO_EUNSUPPORTED, "internal: a due block in a handle with an fp32 factor");
+      child_due_.upload(sym.child_due);
       if (const char *e = getenv("RR_PGO_FLOW_TIMEOUT_MS")) wait_ticks_ = (unsigned long long)std::max(1.0, std::atof(e) * 1e5);
       if (sym.lds_flow) {
         // dataflow launches of the LDS fronts: who waits for whom (a dependency inside one task needs no flag), and
@@ -1711,6 +1716,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     a.trace = nullptr;
 #endif
     a.child_dep = child_dep_.p;
+    a.child_due = child_due_.p;
     a.parent_dep = parent_dep_.p;
     a.dep_flags = dep_flags_.p;
     a.parent_dep_self = sym_.S;
@@ -3637,6 +3643,14 @@ void analyze_handle(rr_pgo &h, const rr_pgo_options *opt_in, double parse_ms) {
   if (!h.g->has_se3) so.merge_chain_nc = 80;
   if (const char *e = std::getenv("RR_PGO_MERGE_CHAIN")) { so.merge_chain_nc = std::atoi(e); if (const char *c = std::strchr(e, ',')) so.merge_chain_gain_us = std::atof(c + 1); }
   if (const char *e = std::getenv("RR_PGO_AMALG_NP")) so.amalg_np = std::atoi(e);
+  // Pivot nodes of every supernode in arrival order and children added mid-panel (symbolic.cpp, step 5), where every front lives
+  // in LDS and the factor is fp64.  RR_PGO_ARRIVAL_ORDER=0: the elimination order, every child before the panel (the order of
+  // r18 and before: the same bits).  An fp32 factor (f32, mixed) always keeps that order: far from the answer its iterates carry
+  // cond(H) x 2^-24 of rounding, which another pivot order moves like another summation order does (dlr, Levenberg-Marquardt: the K
+  // form and the chain form of the back substitution settle 7e-4 apart in the old order, 1.4e-3 in the new), and the fp32
+  // workloads that are measured have fronts beyond LDS
+  so.arrival_order = opt.precision == RR_PGO_F64;
+  if (const char *e = std::getenv("RR_PGO_ARRIVAL_ORDER")) so.arrival_order = so.arrival_order && std::atoi(e) != 0;
   double t0 = now_ms();
   std::string err;
   // The analysis is a function of the graph's structure (and, through the coordinate cuts, of the initial positions), the options

@@ -1346,6 +1346,50 @@ std::string analyze(const HostGraph &g, const SymbolicOptions &opt, Symbolic &sy
       if (any && !apply_moves(out_nodes)) return "internal: block balancing lost nodes";
     }
   }
+  // Pivot nodes in ARRIVAL order.  The partition is final and a front is dense, so the order of the pivots inside a supernode is
+  // free; a child's update matrix touches only the pivot columns in its own row set, and extend-add commutes with the Schur
+  // updates.  With the nodes of every supernode sorted by the model's finish time of the LATEST child that touches them (nodes no
+  // child touches first), a front factors the blocks its late children do not touch while they are still running: each child is
+  // added no later than the block of its first pivot column (child_due, below, which also caps it at the block of every child
+  // that finishes later; kernels.hip.h, panel_factor).  The finish times depend on
+  // ncols, nrows and child counts alone, which the order inside a supernode does not change.  Graphs whose fronts all live in
+  // LDS, one rank -- the condition of the finish-time order of the child lists.
+  bool arrival = opt.arrival_order && opt.n_parts <= 1;
+  if (arrival) {
+    std::vector<int32_t> ncs(S, 0), nrs(S, 0), kids(S, 0);
+    for (int f = 0; f < S && arrival; f++) {
+      for (int p = sym.sn_first_pos[f]; p < sym.sn_first_pos[f] + sym.sn_npos[f]; p++) ncs[f] += w[order[p]];
+      for (int x : rows[f]) nrs[f] += w[order[x]];
+      if (sym.sn_parent[f] >= 0) kids[sym.sn_parent[f]]++;
+      arrival = lds_elems(ncs[f], nrs[f]) <= lds_budget;
+    }
+    if (arrival) {
+      std::vector<double> fin(S, 0.0), key(N, 0.0);
+      std::vector<int32_t> norder(order);
+      bool moved = false;
+      for (int f = 0; f < S; f++) {   // children before parents: fin[f] holds the latest child's finish when f's turn comes
+        const int a = sym.sn_first_pos[f], b = a + sym.sn_npos[f];
+        if (kids[f] > 0) {
+          std::stable_sort(norder.begin() + a, norder.begin() + b, [&](int32_t u, int32_t v) { return key[pos_of[u]] < key[pos_of[v]]; });
+          for (int p = a; p < b && !moved; p++) moved = norder[p] != order[p];
+        }
+        fin[f] += front_cost_us(ncs[f], nrs[f], kids[f]);
+        const int pf = sym.sn_parent[f];
+        if (pf < 0) continue;
+        fin[pf] = std::max(fin[pf], fin[f]);
+        const int pb = sym.sn_first_pos[pf] + sym.sn_npos[pf];
+        for (int x : rows[f]) {   // ascending positions
+          if (x >= pb) break;
+          key[x] = std::max(key[x], fin[f]);
+        }
+      }
+      if (moved) {
+        order.swap(norder);
+        for (int p = 0; p < N; p++) pos_of[order[p]] = p;
+        symbolic_rows();
+      }
+    }
+  }
   sym.order = order;
   sym.pos_of = pos_of;
 
@@ -1556,6 +1600,33 @@ std::string analyze(const HostGraph &g, const SymbolicOptions &opt, Symbolic &sy
       std::stable_sort(sym.child_list.begin() + sym.child_ptr[f], sym.child_list.begin() + sym.child_ptr[f + 1],
                        [&](int32_t a, int32_t b) { return fin[a] < fin[b]; });
     }
+  }
+  // Arrival order: a child is due at the 16-column block of its parent that holds the child's first row (a pivot column of the
+  // parent, so the block exists): nothing of its update matrix lands left of that block ...
+  // INVARIANT the kernel relies on (process_front, late_add: it has no rel-map form and does not check): a due block > 0 exists
+  // only where n_big == 0, and there every child gets a packed update matrix and a scatter map below (scat_ptr >= 0 for every
+  // c with a parent when neither is big).  Whoever changes the conditions of scat_ptr changes this one with them.
+  // (`arrival` was decided before the reorder by lds_elems(nc, nr) <= lds_budget of every front, n_big in step 6 by the same
+  // comparison on the same nc, nr -- the reorder changes neither: the two agree.  Should they ever differ, the handle would be
+  // reordered with all-zero due blocks: correct, but not the bits of the elimination order.)
+  sym.child_due.assign(sym.child_list.size(), 0);
+  if (arrival && sym.n_big == 0) {
+    std::vector<int32_t> due(S, 0);
+    for (int c = 0; c < S; c++)
+      if (sym.sn_parent[c] >= 0) due[c] = (sym.sn_rows[sym.sn_rows_ptr[c]] - sym.sn_col0[sym.sn_parent[c]]) / 16;
+    // ... and no later than any child expected to finish after it: by the time the front waits for that one, this one is in, and
+    // adding it in the same stop of the panel saves the barrier pair of a stop of its own where nothing is left to wait for
+    // (the front is past its last arrival then: every further stop is on the critical path).  Earlier is always allowed.
+    // Measured on intel: 7.66 k iterations/s before, 7.78 k with every child at the block of its own first column, 7.94 k capped.
+    for (int f = 0; f < S; f++) {   // (the list is in finish-time order here)
+      int32_t cap = INT32_MAX;
+      for (int q = sym.child_ptr[f + 1] - 1; q >= sym.child_ptr[f]; q--) {
+        int32_t &d = due[sym.child_list[q]];
+        d = cap = std::min(cap, d);
+      }
+    }
+    // (non-decreasing along the list now: the order stays the finish-time order)
+    for (size_t q = 0; q < sym.child_list.size(); q++) sym.child_due[q] = due[sym.child_list[q]];
   }
   {
     // blocks are sorted by column position, so a supernode's blocks are contiguous

@@ -72,6 +72,10 @@ struct SymbolicOptions {
   int my_part = 0;          // with n_parts > 1: the rank whose schedule is emitted (own subtrees, then shared top)
   int pin_node = -1;        // with n_parts > 1: this node (the anchor) is made part of the top separator
   double task_us = 0.0;     // subtrees cheaper than this (model us) become one leaf task; 0 = pick by the cost model
+  bool arrival_order = true;   // graphs whose fronts all fit LDS (and n_parts == 1): a supernode's pivot nodes in the order in which the
+                               // children that touch them are expected to finish, every child added no later than the 16-column block of
+                               // its first pivot column and than any child that finishes after it (Symbolic::child_due); false: the
+                               // elimination order as it was, every child before the panel (the engine: fp64 factors only)
   bool lds_flow = false;    // graphs whose fronts all fit LDS (and n_parts == 1): ONE task list in ticket order for the dataflow
                             // launches k_factor_flow / k_solve_flow (lds_flow.hip.h) instead of one step per tree level
   int64_t panel_budget_elems = 0;  // must stay 0: fronts beyond LDS whose pivot panel fits this budget would form a step class of
@@ -145,7 +149,10 @@ struct Symbolic {
   std::vector<int64_t> scat_ptr;                  // per supernode (as a child), -1 = no map
   std::vector<int32_t> scat;
   std::vector<int32_t> child_ptr, child_list;
-  std::vector<int64_t> rel_ptr;      // per supernode (as a child): into rel, nrows+1 entries
+  std::vector<int32_t> child_due;    // per child_list entry: the 16-column block of the parent's panel before which the child's update matrix
+                                     // is added (at most the block of its first pivot column, and of every child that finishes later; 0 = before
+                                     // the panel, the only value without arrival_order); non-decreasing along a front's list
+  std::vector<int64_t> rel_ptr;     // per supernode (as a child): into rel, nrows+1 entries
   std::vector<int32_t> rel;          // local index in the parent's front (last entry = parent's rhs row)
   // ---- schedule
   std::vector<int32_t> task_ptr, task_sn;
