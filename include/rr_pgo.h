@@ -421,6 +421,17 @@ int rr_pgo_get_stats(const rr_pgo *h, rr_pgo_stats *out);
  * Not part of bytes_factor / bytes_solve, which count every datum of the factor once. */
 int rr_pgo_solve_form(const rr_pgo *h, int32_t *kform, double *k_bytes, double *k_flops);
 
+/* Iterations this handle's engine has put on its stream so far, by the form in which they were enqueued (out: 4 entries):
+ * out[0] plain launches outside rr_pgo_optimize's device-side loop (rr_pgo_iterate_async, the loop of rr_pgo_optimize with
+ *        one host round trip per iteration, rr_pgo_profile),
+ * out[1] replays of the captured hipGraph of one Gauss-Newton iteration,
+ * out[2] items of rr_pgo_optimize's device-side loop (an item is an iteration or the chi2 pass that ends a call),
+ * out[3] captures (instantiations) of that hipGraph.
+ * Host-side counters, incremented where the launches are enqueued: no device work, no synchronisation.  rr_pgo_extend
+ * builds a new engine for the grown graph, so the counters start again at 0 there; rr_pgo_set_robust_kernel and
+ * rr_pgo_set_priors drop the captured graph, so the next replay counts another capture. */
+int rr_pgo_launch_counts(const rr_pgo *h, int64_t *out);
+
 /* Host-only: parse + symbolic analysis of a g2o file, the rr_pgo_stats a handle on it would report (fields that depend
  * on the device -- n_launches_per_iter, big_update_flops, big_flow_flops -- are 0).  Needs no HIP device. */
 int rr_pgo_analyze_g2o(const char *path, const rr_pgo_options *opt, rr_pgo_stats *out);

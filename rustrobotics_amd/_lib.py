@@ -33,6 +33,7 @@ EXPORTS = (
     "rr_pgo_get_stats", "rr_pgo_analyze_g2o", "rr_pgo_abi_version", "rr_pgo_debug_withhold", "rr_pgo_profile", "rr_pgo_synth_grid", "rr_pgo_synth_free",
     "rr_pgo_exchange_buffer", "rr_pgo_set_exchange_buffer", "rr_pgo_stage", "rr_pgo_stage_scalars", "rr_pgo_stream",
     "rr_pgo_node_owner", "rr_pgo_trim", "rr_pgo_set_robust_kernel", "rr_pgo_edge_errors", "rr_pgo_solve_form",
+    "rr_pgo_launch_counts",
     "rr_pgo_marginals", "rr_pgo_marginals_times", "rr_pgo_covariances", "rr_pgo_covariances_times",
     "rr_pgo_gate_edges", "rr_pgo_gate_times", "rr_pgo_gate_joint", "rr_pgo_gate_joint_times",
     "rr_pgo_extend", "rr_pgo_extend_times", "rr_pgo_set_priors", "rr_pgo_num_priors", "rr_pgo_prior_errors",
@@ -118,6 +119,7 @@ def load():
     L.rr_pgo_sync.argtypes = [vp]
     L.rr_pgo_get_stats.argtypes = [vp, C.POINTER(Stats)]
     L.rr_pgo_solve_form.argtypes = [vp, ip, dp, dp]
+    L.rr_pgo_launch_counts.argtypes = [vp, C.POINTER(C.c_int64)]
     L.rr_pgo_profile.argtypes = [vp, C.c_int32, dp, C.POINTER(C.c_int64), C.c_int32]
     L.rr_pgo_synth_grid.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.c_uint64, C.c_uint64, C.POINTER(vp),
                                     C.POINTER(GraphDesc)]

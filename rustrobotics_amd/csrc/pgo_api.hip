@@ -307,6 +307,9 @@ struct EngineBase {
   virtual void adopt_state(const void *src, size_t n_nodes, double *ms) = 0;
   virtual void robust_setting(int *kind, double *delta, bool *masked, std::vector<int32_t> &mask) const = 0;
   int n_launches_per_iter = 0;
+  // rr_pgo_launch_counts: iterations put on the stream as plain launches / as replays of the captured hipGraph / as items of
+  // the device-side loop, and instantiations of that graph.  Host-side, counted where the launches are enqueued.
+  int64_t launch_counts[4] = {0, 0, 0, 0};
 };
 
 constexpr int HIST = 4096;  // ring of (chi2, |dx|) pairs written by k_finalize
@@ -1750,12 +1753,18 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     if (e != hipSuccess) throw ApiError(RR_PGO_ENODEVICE, std::string("kernel launch failed (") + what + "): " + hipGetErrorString(e));
   }
 
-  void launch_linearize(double lambda, int lm, int write_system, bool reference_prior = false) {
+  // a pipelined rr_pgo_optimize call may have left its stop word set: every path outside such a call starts here -- the plain
+  // launches in launch_linearize, the replays BEFORE ensure_gn_graph (a replay never passes through launch_linearize, and a
+  // captured graph must hold no memset node, whatever ran before its capture)
+  void clear_stop_word() {
     if (stop_dirty_ && !opt_active_) {
-      // a pipelined rr_pgo_optimize call may have left its stop word set: every path outside such a call starts here
       HIPCHK(hipMemsetAsync(err_.p + 1, 0, sizeof(int), stream_));
       stop_dirty_ = false;
     }
+  }
+
+  void launch_linearize(double lambda, int lm, int write_system, bool reference_prior = false) {
+    clear_stop_word();
     pbegin();
     if (!is3d_ && edge_lin_) {
       // the edge-parallel form (experiment knob RR_PGO_EDGE_LINEARIZE): clear + prior, one thread per edge, mirror
@@ -2118,6 +2127,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     const hipError_t ie = hipGraphInstantiate(&gn_exec_, graph, nullptr, nullptr, 0);
     (void)hipGraphDestroy(graph);
     if (ie != hipSuccess) { gn_exec_ = nullptr; throw ApiError(RR_PGO_ENODEVICE, std::string("hipGraphInstantiate: ") + hipGetErrorString(ie)); }
+    launch_counts[3]++;
   }
 
   // One host round trip per iteration: the two scalars and the device error flag come back in
@@ -2218,12 +2228,16 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
       // (optimize() reads two scalars back after every iteration, so the enqueueing is not hidden behind the device as it is
       // in iterate_async: dozens of launches stay one graph launch here.)  RR_PGO_FORCE_GRAPH=1: always the graph.
       const bool eager = (no_graph_ || n_launches_per_iter <= 8) && !gn_exec_ && !force_graph_;
-      if (!eager) ensure_gn_graph();
+      if (!eager) {
+        clear_stop_word();   // before the capture: the graph holds no memset, and its replays pass no launch_linearize
+        ensure_gn_graph();
+      }
       reset_counter();
       int done = 0;
       for (int i = 0; i < iters; i++) {
         if (eager) enqueue_gn_iteration();
         else HIPCHK(hipGraphLaunch(gn_exec_, stream_));
+        launch_counts[eager ? 0 : 1]++;
         double chi, nrm;
         read_slot(i, &chi, &nrm);
         errors[ne++] = chi;
@@ -2239,6 +2253,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
       errors[ne++] = last_error;
       for (int i = 0; i < iters; i++) {
         reset_counter();
+        launch_counts[0]++;
         launch_linearize(lambda, 1, 1);
         launch_factor();
         launch_solve();
@@ -2282,6 +2297,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     oi.chi_partial = chi_partial_.p; oi.norm_partial = norm_partial_.p; oi.n_chi = n_lin_blocks_; oi.n_norm = 0; oi.mode = 0;
     oi.ctrl = opt_ctrl_.p; oi.ring = opt_ring_; oi.err = err_.p;
     struct Pub { int &p; ~Pub() { p = 0; } } pub{opt_publish_};
+    launch_counts[2]++;
     if (!lm) {
       // an iteration: its linearisation publishes only when the stop word is set (then the rest of the item is empty
       // launches); the item behind the last iteration: chi2 only, published by the linearisation's last workgroup
@@ -2506,11 +2522,12 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     // (the 1M-edge lattice: ~0.2 ms of enqueueing against 4.4 ms of kernels).  Measured: intel + 2 %, sphere2500 + 0.8 %,
     // lattice + 0.7 %.  RR_PGO_FORCE_GRAPH=1: replays of the captured hipGraph (r01 - r03's form).
     if (no_graph_ || !force_graph_) {
-      for (int i = 0; i < iters; i++) enqueue_gn_iteration();
+      for (int i = 0; i < iters; i++) { enqueue_gn_iteration(); launch_counts[0]++; }
       return;
     }
+    clear_stop_word();   // before the capture: the graph holds no memset, and its replays pass no launch_linearize
     ensure_gn_graph();
-    for (int i = 0; i < iters; i++) HIPCHK(hipGraphLaunch(gn_exec_, stream_));
+    for (int i = 0; i < iters; i++) { HIPCHK(hipGraphLaunch(gn_exec_, stream_)); launch_counts[1]++; }
   }
 
   void sync() override {
@@ -3471,7 +3488,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     for (int k = 0; k < RR_PGO_NUM_KCLASS; k++) { prof_.ms[k] = 0; prof_.n[k] = 0; }
     prof_.on = true;
     try {
-      for (int i = 0; i < iters; i++) enqueue_gn_iteration();
+      for (int i = 0; i < iters; i++) { enqueue_gn_iteration(); launch_counts[0]++; }
       HIPCHK(hipStreamSynchronize(stream_));
     } catch (...) {
       prof_.on = false;
@@ -4201,6 +4218,12 @@ int rr_pgo_edge_errors(rr_pgo *h, double *chi2_out, double *weight_out) {
 int rr_pgo_solve_form(const rr_pgo *h, int32_t *kform, double *k_bytes, double *k_flops) {
   if (!h || !kform) { g_last_error = "null argument"; return RR_PGO_EINVAL; }
   return guarded([&] { h->engine->solve_form(kform, k_bytes, k_flops); });
+}
+
+int rr_pgo_launch_counts(const rr_pgo *h, int64_t *out) {
+  if (!h || !out) { g_last_error = "null argument"; return RR_PGO_EINVAL; }
+  for (int k = 0; k < 4; k++) out[k] = h->engine->launch_counts[k];
+  return RR_PGO_OK;
 }
 
 // rr_pgo_marginals / rr_pgo_covariances behind their own argument rules: the offsets of the blocks, the node-range check, the

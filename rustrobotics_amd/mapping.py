@@ -680,6 +680,11 @@ class PoseGraph:
         kform, kb, kf = C.c_int32(0), C.c_double(0), C.c_double(0)
         _check(_lib.load().rr_pgo_solve_form(self._h, C.byref(kform), C.byref(kb), C.byref(kf)))
         out.update(solve_kform=int(kform.value), kform_bytes=float(kb.value), kform_flops=float(kf.value))
+        # iterations enqueued so far, by launch form (rr_pgo_launch_counts): host-side counters of this handle's engine
+        counts = (C.c_int64 * 4)()
+        _check(_lib.load().rr_pgo_launch_counts(self._h, counts))
+        out.update(n_plain_iterations=int(counts[0]), n_graph_replays=int(counts[1]), n_loop_items=int(counts[2]),
+                   n_graph_captures=int(counts[3]))
         return out
 
     @staticmethod

@@ -63,6 +63,20 @@ def random_graph(rng, n_pose, n_lm, n_extra, se3=False):
     return nk, ns, np.array(ek, np.int32), np.array(ef, np.int32), np.array(et, np.int32), np.concatenate(em), np.concatenate(ei)
 
 
+def two_component_graph(info_sign=1.0):
+    """nodes 0-1 and 2-3 joined pairwise: the prior reaches only the first pair, the second is singular (exactly: the
+    arithmetic of these integers is exact, the failing pivot is 0.0); info_sign = -1 makes H negative definite instead"""
+    nk = np.zeros(4, np.int32)
+    ns = np.array([0, 0, 0, 1, 0, 0, 5, 5, 0, 6, 5, 0], float)
+    ek = np.zeros(2, np.int32)
+    ef, et = np.array([0, 2], np.int32), np.array([1, 3], np.int32)
+    # the second edge has a residual (a step would move its nodes); all headings are 0 and every entry a small dyadic
+    # rational, so H is formed exactly and the unanchored pair's last pivot is exactly 0 in the very first iteration
+    em = np.array([1, 0, 0, 1.5, 0.25, 0.0], float)
+    ei = info_sign * np.tile([1, 0, 0, 1, 0, 1], 2).astype(float)
+    return nk, ns, ek, ef, et, em, ei
+
+
 # ---- the pieces of such a graph, for generators of other shapes (tests/query_small_cases.py); random_graph keeps its own
 # copies: its seeded graphs are pinned by the order of its draws
 

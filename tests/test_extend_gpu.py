@@ -324,6 +324,10 @@ def test_replayed_graph_iterations_around_extend(api, monkeypatch):
     sa, sb = a.state(), b.state()
     assert np.array_equal(sa, sb) and not np.array_equal(sa, s)
     assert a.global_error() == b.global_error()
+    # replays of a graph captured on the grown graph's engine (rr_pgo_extend builds a new one: its counters start again)
+    sta, stb = a.stats(), b.stats()
+    assert (sta["n_graph_replays"], sta["n_graph_captures"], sta["n_plain_iterations"]) == (8, 1, 0)
+    assert (stb["n_graph_replays"], stb["n_graph_captures"], stb["n_plain_iterations"]) == (10, 1, 0)
 
 
 # ---- 8. refusal

@@ -219,6 +219,9 @@ def test_replayed_graph_iterations_after_the_gate_give_the_same_bits(api, monkey
     a.sync()
     b.sync()
     assert np.array_equal(a.state(), b.state())
+    for g in (a, b):   # every one of the ten iterations was a replay of the one captured graph
+        st = g.stats()
+        assert (st["n_graph_replays"], st["n_graph_captures"], st["n_plain_iterations"]) == (10, 1, 0)
 
 
 def test_cauchy_weights_are_part_of_the_inverted_matrix(api):

@@ -12,7 +12,7 @@ import pytest
 import scipy.sparse as sp
 
 from conftest import ROOT, g2o_path
-from random_graphs import random_graph as _random_graph
+from random_graphs import random_graph as _random_graph, two_component_graph as _two_component_graph
 
 pytestmark = pytest.mark.gpu
 
@@ -329,19 +329,6 @@ def test_not_positive_definite_is_reported(api):
     assert ei_.value.code == -5
 
 
-def _two_component_graph(info_sign=1.0):
-    """nodes 0-1 and 2-3 joined pairwise: the prior reaches only the first pair, the second is singular (exactly: the
-    arithmetic of these integers is exact, the failing pivot is 0.0); info_sign = -1 makes H negative definite instead"""
-    nk = np.zeros(4, np.int32)
-    ns = np.array([0, 0, 0, 1, 0, 0, 5, 5, 0, 6, 5, 0], float)
-    ek = np.zeros(2, np.int32)
-    ef, et = np.array([0, 2], np.int32), np.array([1, 3], np.int32)
-    # the second edge has a residual (a step would move its nodes); all headings are 0 and every entry a small dyadic
-    # rational, so H is formed exactly and the unanchored pair's last pivot is exactly 0 in the very first iteration
-    em = np.array([1, 0, 0, 1.5, 0.25, 0.0], float)
-    ei = info_sign * np.tile([1, 0, 0, 1, 0, 1], 2).astype(float)
-    return nk, ns, ek, ef, et, em, ei
-
 
 @pytest.mark.parametrize("mode", ["gn", "lm", "staged"])
 def test_failed_factorisation_leaves_the_state_untouched(api, mode):
@@ -617,6 +604,7 @@ def test_alternate_big_front_launch_sequences_agree(api, env, monkeypatch):
     from rustrobotics_amd import synthetic_grid_arrays
     arrays = synthetic_grid_arrays(100, 100)
     ref = api[0].from_arrays(*arrays)
+    s0 = np.array(ref.state())
     eref = ref.optimize(3)
     env, _, val = env.partition("=")
     monkeypatch.setenv(env, val or "1")
@@ -628,6 +616,43 @@ def test_alternate_big_front_launch_sequences_agree(api, env, monkeypatch):
         # placement, one pass or one per super-panel, gathered or built: the same chunks in the same order -- the same bits
         assert np.array_equal(ealt, eref) and np.array_equal(np.array(alt.state()), np.array(ref.state()))
     assert _state_diff_se2(alt.state(), ref.state()) <= 1e-8
+    # optimize() of these two handles (under 48 launches per iteration) is the device-side loop whatever the two graph
+    # switches say: what they switch is compared where it runs
+    if env == "RR_PGO_FORCE_GRAPH":
+        _assert_replays_equal_plain_launches(alt, ref, s0, 3)
+    if env == "RR_PGO_NO_GRAPH":
+        # from 48 launches per iteration optimize() is the host loop: replays of the captured graph, plain launches under the switch
+        monkeypatch.setenv("RR_PGO_FLOW", "0")
+        replayed = api[0].from_arrays(*arrays)
+        monkeypatch.setenv(env, "1")
+        plain = api[0].from_arrays(*arrays)
+        monkeypatch.delenv(env)
+        monkeypatch.delenv("RR_PGO_FLOW")
+        assert replayed.stats()["n_launches_per_iter"] >= 48 and plain.stats()["n_launches_per_iter"] >= 48
+        er, ep = replayed.optimize(3), plain.optimize(3)
+        assert len(er) == 4 and er[-1] < er[0]
+        assert np.array_equal(er, ep) and np.array_equal(np.array(replayed.state()), np.array(plain.state()))
+        assert replayed.global_error() == plain.global_error()
+        sr, sp = replayed.stats(), plain.stats()
+        assert (sr["n_graph_replays"], sr["n_plain_iterations"], sr["n_loop_items"]) == (3, 0, 0)
+        assert (sp["n_graph_replays"], sp["n_plain_iterations"], sp["n_loop_items"]) == (0, 3, 0)
+
+
+def _assert_replays_equal_plain_launches(alt, plain, s0, n):
+    """n iterations from the state s0 through rr_pgo_iterate_async: on `alt` (created under RR_PGO_FORCE_GRAPH) as replays of
+    the captured hipGraph, on `plain` (created without the switch) as plain launches -- the same bits, and the launch
+    counters say that each handle ran its form."""
+    before = plain.stats()
+    for g in (alt, plain):
+        g.set_state(s0)
+        g.iterate_async(n)
+        g.sync()
+    sa, sp = np.array(alt.state()), np.array(plain.state())
+    assert np.array_equal(sa, sp) and not np.array_equal(sa, np.array(s0))
+    assert alt.global_error() == plain.global_error()
+    assert alt.stats()["n_graph_replays"] == n and alt.stats()["n_graph_captures"] == 1
+    after = plain.stats()
+    assert after["n_graph_replays"] == 0 and after["n_plain_iterations"] == before["n_plain_iterations"] + n
 
 
 @pytest.mark.parametrize("case", ["lattice100-f64", "lattice100-f32", "lattice100-mixed", "sphere2500-f64", "torus3D-f64",
@@ -754,8 +779,10 @@ def test_lds_dataflow_launches_are_bit_identical_to_the_level_schedule(api, name
     monkeypatch.setenv("RR_PGO_ND_LEAF", "1000000")
     monkeypatch.setenv("RR_PGO_AMALG_NP", "16")
     ref = api[0].new(g2o_path(name))
+    s0 = np.array(ref.state())
     eref, sref = np.array(ref.optimize(4)), np.array(ref.state())
-    # (RR_PGO_FORCE_GRAPH: the iterations as replays of the captured hipGraph instead of plain launches)
+    # (RR_PGO_FORCE_GRAPH: the iterations as replays of the captured hipGraph instead of plain launches -- of
+    # rr_pgo_iterate_async: optimize() of these handles is the device-side loop under either graph switch)
     # (RR_PGO_SOLVE_THREADS: smaller workgroups for the same fronts -- the sums of a front do not depend on the
     # workgroup size, kernels.hip.h, solve_front)
     for env, val in (("RR_PGO_LDS_FLOW", "0"), ("RR_PGO_LDS_FLOW_GRID", "1"), ("RR_PGO_LDS_FLOW_GRID", "7"), ("RR_PGO_TASK_US", "60"), ("RR_PGO_FORCE_GRAPH", "1"),
@@ -765,6 +792,16 @@ def test_lds_dataflow_launches_are_bit_identical_to_the_level_schedule(api, name
         monkeypatch.delenv(env)
         assert np.array_equal(np.array(alt.optimize(4)), eref), (env, val)
         assert np.array_equal(np.array(alt.state()), sref), (env, val)
+        if env == "RR_PGO_FORCE_GRAPH":
+            _assert_replays_equal_plain_launches(alt, ref, s0, 4)
+        if env == "RR_PGO_NO_GRAPH":   # plain launches, as without the switch: the same bits, and no graph anywhere
+            for g in (alt, ref):
+                g.set_state(s0)
+                g.iterate_async(4)
+                g.sync()
+            assert np.array_equal(np.array(alt.state()), np.array(ref.state())) and alt.global_error() == ref.global_error()
+            st = alt.stats()
+            assert (st["n_plain_iterations"], st["n_graph_replays"], st["n_graph_captures"]) == (4, 0, 0)
     # Levenberg-Marquardt drives the same launches outside the captured graph
     lm = api[0].new(g2o_path(name), api[1].LevenbergMarquardt)
     monkeypatch.setenv("RR_PGO_LDS_FLOW", "0")
@@ -861,6 +898,10 @@ def test_cross_level_flow_launch_is_bit_identical_to_one_launch_per_level(api, n
             monkeypatch.delenv(k)
         assert np.array_equal(np.array(alt.optimize(4)), e2), env
         assert np.array_equal(np.array(alt.state()), s2), env
+        if "RR_PGO_FORCE_GRAPH" in env:
+            # (optimize() of a handle under 48 launches per iteration is the device-side loop, switch or not: the captured graph
+            # -- with the cross-level launch inside it -- is what rr_pgo_iterate_async replays)
+            _assert_replays_equal_plain_launches(alt, xl, np.array(xl.state()), 4)
 
 
 @pytest.mark.parametrize("name,prec", [("sphere2500", "f64"), ("torus3D", "f64"), ("sphere2500", "mixed"), ("lattice100", "f64"), ("lattice100", "f32"),

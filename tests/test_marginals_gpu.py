@@ -154,6 +154,9 @@ def test_replayed_graph_iterations_after_marginals_give_the_same_bits(api, monke
     a.sync()
     b.sync()
     assert np.array_equal(a.state(), b.state())
+    for g in (a, b):   # every one of the ten iterations was a replay of the one captured graph
+        st = g.stats()
+        assert (st["n_graph_replays"], st["n_graph_captures"], st["n_plain_iterations"]) == (10, 1, 0)
 
 
 @pytest.mark.parametrize("env,value", [("RR_PGO_SOLVE_KFORM", "0"), ("RR_PGO_SOLVE_KFORM", "1"),

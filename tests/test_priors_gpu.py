@@ -361,6 +361,7 @@ def test_set_then_clear_is_a_handle_that_never_had_priors(api, solver, monkeypat
     for g in (a, b):
         g.iterate_async(2)
         g.sync()
+        assert g.stats()["n_graph_replays"] == 2 and g.stats()["n_plain_iterations"] == 0   # the captured graph really ran
     arrays = a.graph_arrays()
     node, meas, info = random_priors(np.random.default_rng(13), arrays, [0, 5, 5, len(arrays[0]) - 1], noise=0.3)
     a.set_priors(node, meas, info, robust=[1, 0, 1, 0], keep_anchor=False)

@@ -276,6 +276,10 @@ def test_kernel_set_after_a_captured_iteration_reaches_the_replays(api, monkeypa
     plain.sync()
     assert np.abs(g.state() - plain.state()).max() <= 1e-12
     assert abs(g.global_error() - plain.global_error()) <= 1e-12 * plain.global_error()
+    # four replays of two captured graphs (the one with the kernel was captured anew) against three plain iterations
+    st, sp = g.stats(), plain.stats()
+    assert (st["n_graph_replays"], st["n_graph_captures"], st["n_plain_iterations"]) == (4, 2, 0)
+    assert (sp["n_graph_replays"], sp["n_graph_captures"], sp["n_plain_iterations"]) == (0, 0, 3)
 
 
 # ---- 8. sharded handles -------------------------------------------------------------------------------------------
