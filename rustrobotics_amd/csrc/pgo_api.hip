@@ -395,9 +395,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   T *xch_ = nullptr, *x_ptr_ = nullptr;
   int solve_threads_max_ = 512;     // RR_PGO_SOLVE_THREADS=<n>: cap of the back-substitution workgroup size
   static constexpr int factor_threads_max_ = 1024;   // 16-wave workgroups for steps whose fronts exceed 128 rows (8 waves: intel 4134 against 4318 it/s, r04)
-  struct UpdMap { int64_t offset; int n_tiles; };
-  std::vector<std::vector<UpdMap>> upd_maps_;   // [step][super-panel]: slice of upd_map_buf_ (k_big_update's tile list)
-  std::vector<UpdMap> schur_maps_;              // [step]: k_big_schur's tile list
+  struct UpdMap { int64_t offset; int n_tiles; };   // slice of upd_map_buf_: a tile list of k_big_update or k_big_schur
   static constexpr int schur_tile_ = 64;        // k_big_schur's tile edge (128 x 128 tiles, k_big_schur<T, 4>: measured 13 % slower, r03)
   bool schur_split_ = true;                     // RR_PGO_SCHUR_SPLIT=0: every super-panel's update reaches through the Schur complement (r02)
   DevBuf<int32_t> upd_map_buf_;
@@ -415,7 +413,6 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     int wfill_begin = 0, wfill_end = 0;   // the level's entries in flow_wfill_
     double est_us = 0;         // critical path of the cost model that orders the tasks
   };
-  std::vector<std::unique_ptr<FlowLevel>> flow_levels_;   // per step of sym_.steps (null: launch sequence)
   std::vector<SnMeta> host_task_meta_;   // host copy of task_meta_ (one record per task = per front of a big level)
   std::vector<SnMeta> host_sn_meta_;     // host copy of sn_meta_
   DevBuf<int64_t> flow_wfill_;      // per four W blocks of a front of a flow level: offset and count of scalars in winv (k_flow_reset marks them)
@@ -442,7 +439,31 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   static constexpr bool flow_deep_ = true;   // fast mode: panel steps of blocks 0 and 1 look back over the previous super-panel (see build_flow_levels)
   bool flow_exact_ = false;         // RR_PGO_FLOW_EXACT=1: bit-identical to the launch sequence (tile (0, 0) forms the next super-panel's first block)
   struct SolveFlowLevel { DevBuf<SolveFlowFront> fronts; DevBuf<SolveFlowTask> tasks; int n_tasks = 0; int64_t ticket_word = 0; };
-  std::vector<std::unique_ptr<SolveFlowLevel>> solve_flow_;   // per step: k_big_solve_flow's tasks and counters (null: k_big_solve_sp launches)
+  // What one step of sym_.steps launches, built once by the constructor: every launch function reads it, and
+  // n_launches_per_iter is a sum over it (factor_launches / solve_launches)
+  enum { L11_FLOW, L11_SP, L11_MID };   // back substitution of a big level's pivot blocks: k_big_solve_flow | k_big_solve_sp per super-panel | k_solve_mid
+  struct StepPlan {
+    int kind = STEP_TASKS, nf = 0, task_begin = 0;   // nf: tasks of an LDS step, fronts of a big level
+    int max_nc = 1, maxM = 0, max_nr = 1;            // the level's widest pivot block, tallest front, most rows below a pivot block
+    bool has_rows = false;                           // some front has rows below its pivot block
+    // an LDS step: k_factor_tasks / k_solve_tasks, step 0 of the dataflow schedule k_factor_flow / k_solve_flow
+    size_t factor_lds = 0;                           // bytes
+    int factor_threads = 0, solve_threads = 0;       // workgroup sizes after the caps
+    int solve_lds = 0;                               // scalars of LDS of the step's back substitution (every kind of step)
+    // factorisation of a big level
+    int build_gx = 0, asm_gx = 0;                    // k_big_build's grid x; k_big_assemble's, 0: assembly fused into the build
+    bool any_dup = false, has_root = false;          // k_big_assemble_dup runs; the level holds the gauge root
+    std::vector<int> panel_gx;                       // k_big_panel32's grid x per 32-column block (launch sequence only)
+    std::vector<UpdMap> upd;                         // k_big_update's tile list per super-panel (launch sequence only)
+    UpdMap schur{0, 0};                              // k_big_schur's tile list (none: no split on this level)
+    std::unique_ptr<FlowLevel> flow;                 // null: launch sequence
+    // back substitution of a big level
+    int cb = 0, R = 1;                               // k_big_gemv_partial's column blocks and row slices (launched if has_rows)
+    int l11 = L11_MID, l11_gx = 0, n_sp = 0;         // the L11 form, its grid x, super-panels of the widest pivot block
+    std::unique_ptr<SolveFlowLevel> solve_flow;      // L11_FLOW: k_big_solve_flow's tasks and counters
+    bool in_solve_flow = false;                      // the level's back substitution runs as tasks of k_solve_flow, not as launches
+  };
+  std::vector<StepPlan> plan_;
   bool solve_flow_on_ = true;       // RR_PGO_SOLVE_FLOW=0: one k_big_solve_sp launch per 128 columns
   int flow_schur_min_ = 512;        // RR_PGO_FLOW_SCHUR_MIN=<n>: flow levels with at least n Schur tiles leave them to k_big_schur
   int flow_grid_ = 0;               // persistent workgroups of a flow launch (RR_PGO_FLOW_GRID; default CUs x RRPGO_FLOW_WAVES)
@@ -456,7 +477,6 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   int lds_n_tasks_ = 0, lds_flow_cus_ = 256;
   std::vector<LdsFlowTask> host_stasks_;   // k_solve_flow's tickets: [per narrow level of fronts beyond LDS, top level first: GEMV units, L11 tasks] + the LDS tasks
   int lds_n_stasks_ = 0;
-  std::vector<char> mid_in_flow_;    // per step: the level's back substitution runs as tasks of k_solve_flow, not as launches
   unsigned long long wait_ticks_ = 200000000ull;   // bound of one in-launch wait: 2 s of the 100 MHz wall clock (RR_PGO_FLOW_TIMEOUT_MS)
   // failure injection (rr_pgo_debug_withhold): what was changed, to put it back
   int withheld_child_ = -1, withheld_parent_ = -1, withheld_level_ = -1, withheld_task_ = -1;
@@ -522,7 +542,6 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   DevBuf<int32_t> task_ptr_, task_sn_, fasm_src_, fasm_dst_, fasm_colptr_, fdup_src_, fdup_dst_, scat_, rel_, perm_, sn_rows_;
   DevBuf<SnMeta> sn_meta_, task_meta_;
   DevBuf<ChildMeta> child_meta_;
-  std::vector<int> step_solve_lds_;  // scalars of LDS the back-solve of each step needs
   PinnedBuf<double> host_pair_;      // pinned: chi2, |dx|, and (as an int in slot 2) the device error flag; behind them (32-byte
                                      // aligned) the OPT_RING slots rr_pgo_optimize's device-side loop publishes its iterations in
   PinnedBuf<V4> state_stage_;        // rr_pgo_set_state's staging buffer (made on first use) and the event behind its last copy
@@ -891,6 +910,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
       }
     }
     cmark("front tables");
+    plan_shapes();
     build_flow_levels();   // (after the front records: every flow task carries a copy of its front's)
     build_update_maps();
     cmark("flow levels");
@@ -903,7 +923,8 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     rel_.upload(sym.rel);
     perm_.upload(sym.perm);
     sn_rows_.upload(sym.sn_rows);
-    for (const Step &st : sym.steps) {
+    for (size_t si = 0; si < sym.steps.size(); si++) {
+      const Step &st = sym.steps[si];
       int need = 0;
       if (st.kind == STEP_MID) throw ApiError(RR_PGO_EUNSUPPORTED, "internal: the panel-in-LDS step class has no kernel (SymbolicOptions::panel_budget_elems must be 0)");
       if (st.kind == STEP_TASKS) {
@@ -914,7 +935,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
             // x[rows] and t, padded as solve_front lays them out; k_solve_flow adds an LDS image of L11 where it fits
             const int ncp = (nc + 15) / 16 * 16, base = ((nr + 15) & ~15) + ncp + 2;
             const int cap = (int)((size_t)kMaxLds / sizeof(T));
-            const bool image = sym.lds_flow && &st == &sym.steps[0];
+            const bool image = sym.lds_flow && si == 0;
             need = std::max(need, image && base + ncp * (ncp + 1) <= cap ? base + ncp * (ncp + 1) : base + ncp / 16 * (2 * 16 * 17));
           }
       } else {
@@ -924,30 +945,23 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
         }
       }
       if ((size_t)need * sizeof(T) > (size_t)kMaxLds) throw ApiError(RR_PGO_EUNSUPPORTED, "front too large for the back-substitution scratch");
-      step_solve_lds_.push_back(need);
+      plan_[si].solve_lds = need;
     }
 #ifdef RRPGO_STAMPS
     stamps_.alloc((size_t)sym.S * 12 + 400000);   // per-front phase stamps | launch trace
     stamps_.zero();
 #endif
     plan_mid_solve_tasks();
+    plan_launches();
     cmark("index tables");
     configure_kernels();
     cmark("kernel attrs");
-    n_launches_per_iter = 2;
-    for (const Step &st : sym.steps)
-      n_launches_per_iter += st.kind == STEP_BIG ? count_big_launches(st) + count_big_solve_launches(st) : 2;
-    if (lds_flow_) {   // linearise, k_factor_flow, the levels of fronts beyond LDS, k_solve_flow, update
-      n_launches_per_iter = 4 + (xl_ ? 1 : 0);
-      for (size_t si = 1; si < sym.steps.size(); si++)
-        n_launches_per_iter += (xl_ ? 0 : count_big_launches(sym.steps[si])) + (mid_in_flow_[si] ? 0 : count_big_solve_launches(sym.steps[si]));
-    }
+    // linearise and update, every step's launches; the cross-level form factors all the big levels in one launch
+    n_launches_per_iter = 2 + (xl_ ? 1 : 0);
+    for (const StepPlan &p : plan_) n_launches_per_iter += (xl_ && p.kind == STEP_BIG ? 0 : factor_launches(p)) + solve_launches(p);
   }
 
-  ~Engine() override {
-    if (gn_exec_) (void)hipGraphExecDestroy(gn_exec_);   // streams, events and the pinned buffer release themselves
-    for (hipGraphExec_t e : stage_exec_) if (e) (void)hipGraphExecDestroy(e);
-  }
+  ~Engine() override { drop_graphs(); }   // streams, events and the pinned buffer release themselves
 
   hipStream_t stream() override { return stream_; }
 
@@ -958,10 +972,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   // A dependency always FINISHES (so also starts) before its dependant starts, hence the sorted list is a topological
   // order -- all the ticket scheme needs -- and roughly the order in which tasks become ready.
   void build_flow_levels() {
-    flow_levels_.clear();
-    flow_levels_.resize(sym_.steps.size());
-    solve_flow_.clear();
-    solve_flow_.resize(sym_.steps.size());
+    for (StepPlan &p : plan_) { p.flow.reset(); p.solve_flow.reset(); }
     constexpr double kDiag = 4.0, kPre = 2.5, kNewest = 1.5, kX = 1.5, kLook = 4.5, kTile = 8.0, kTail = 4.5, kHop = 0.7;
     int64_t words = 0;
     int dev = 0, cus = 256;
@@ -1257,14 +1268,14 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
       lvl->wfill_end = (int)(wfill.size() / 2);
       all_tasks[si] = std::move(tasks);
       all_fronts[si] = std::move(fronts);
-      flow_levels_[si] = std::move(lvl);
+      plan_[si].flow = std::move(lvl);
     }
     if (xl_) {
       // the cross-level form needs a task list for EVERY level of fronts beyond LDS (with all Schur tiles as UPDATE tasks a
       // level has several times the tasks of its per-level plan): a level that went over the limit takes the whole graph back to
       // one build + one flow launch per level, planned afresh with the per-level Schur split -- never a refused handle
       bool complete = true;
-      for (size_t si = 0; si < sym_.steps.size(); si++) complete = complete && (sym_.steps[si].kind != STEP_BIG || flow_levels_[si]);
+      for (size_t si = 0; si < sym_.steps.size(); si++) complete = complete && (sym_.steps[si].kind != STEP_BIG || plan_[si].flow);
       if (!complete) {
         xl_refused_ = true;
         build_flow_levels();
@@ -1280,12 +1291,10 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
       for (size_t si = 0; si < sym_.steps.size(); si++) {
         const Step &st = sym_.steps[si];
         if (st.kind != STEP_BIG) continue;
-        const int nf = st.task_end - st.task_begin;
-        int max_nc = 1;
-        for (int z = 0; z < nf; z++) max_nc = std::max(max_nc, sym_.sn_ncols[sym_.task_sn[sym_.task_ptr[st.task_begin + z]]]);
+        const int nf = st.task_end - st.task_begin, max_nc = plan_[si].max_nc;
         if (max_nc < sp_solve_min_nc_) continue;
-        solve_flow_[si] = std::make_unique<SolveFlowLevel>();
-        solve_flow_[si]->ticket_word = words;
+        plan_[si].solve_flow = std::make_unique<SolveFlowLevel>();
+        plan_[si].solve_flow->ticket_word = words;
         words += 32;
         const int max_S = (max_nc + BIG_SUPER - 1) / BIG_SUPER;
         for (int z = 0; z < nf; z++) {
@@ -1307,7 +1316,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
             for (int g = (K0 + 63) / 64 - 1; g >= 0; g--) all_st[si].push_back(SolveFlowTask{z, ell, g});   // columns [64 g, ...) left of K0
           }
         }
-        solve_flow_[si]->n_tasks = (int)all_st[si].size();
+        plan_[si].solve_flow->n_tasks = (int)all_st[si].size();
       }
     if (words == 0) return;
     wfill.resize(wfill.size() + 2, 0);   // never empty
@@ -1315,12 +1324,12 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     flow_flags_.alloc((size_t)words + kDeadFlagWords);
     flow_flags_.zero();
     for (size_t si = 0; si < sym_.steps.size(); si++)
-      if (solve_flow_[si]) {
-        solve_flow_[si]->fronts.upload(all_sf[si]);
-        solve_flow_[si]->tasks.upload(all_st[si]);
+      if (plan_[si].solve_flow) {
+        plan_[si].solve_flow->fronts.upload(all_sf[si]);
+        plan_[si].solve_flow->tasks.upload(all_st[si]);
       }
     for (size_t si = 0; si < sym_.steps.size(); si++)
-      if (flow_levels_[si]) {
+      if (plan_[si].flow) {
         {
           const Step &st = sym_.steps[si];
           std::vector<FlowRec> recs(all_tasks[si].size());
@@ -1331,12 +1340,12 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
             recs[i].m = host_task_meta_[st.task_begin + slot];
             std::memset(recs[i].pad, 0, sizeof(recs[i].pad));
           }
-          flow_levels_[si]->tasks.upload(recs);
+          plan_[si].flow->tasks.upload(recs);
         }
 #ifdef RRPGO_FLOW_TRACE
-        flow_levels_[si]->host_tasks = all_tasks[si];
-        flow_levels_[si]->trace.alloc(all_tasks[si].size() * 16);
-        flow_levels_[si]->trace.zero();
+        plan_[si].flow->host_tasks = all_tasks[si];
+        plan_[si].flow->trace.alloc(all_tasks[si].size() * 16);
+        plan_[si].flow->trace.zero();
 #endif
       }
     if (xl_) {
@@ -1344,7 +1353,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
       // per child_meta entry where the child's `done` counter lives and how many UPDATE tasks it counts
       std::vector<int32_t> sn_done(sym_.S, -1), sn_nupd(sym_.S, 0);
       for (size_t si = 0; si < sym_.steps.size(); si++) {
-        if (!flow_levels_[si]) { if (sym_.steps[si].kind == STEP_BIG) xl_ = false; continue; }
+        if (!plan_[si].flow) { if (sym_.steps[si].kind == STEP_BIG) xl_ = false; continue; }
         const Step &st = sym_.steps[si];
         for (const FlowTask &t : all_tasks[si]) {
           const int slot = t.kind_front & 0xffffff, sn = sym_.task_sn[sym_.task_ptr[st.task_begin + slot]];
@@ -1361,8 +1370,8 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
       xl_child_done_.upload(cd);
       bool first = true;
       for (size_t si = 0; si < sym_.steps.size(); si++) {
-        if (!flow_levels_[si]) continue;
-        if (first) { xl_ticket_word_ = flow_levels_[si]->ticket_word; first = false; }
+        if (!plan_[si].flow) continue;
+        if (first) { xl_ticket_word_ = plan_[si].flow->ticket_word; first = false; }
         const Step &st = sym_.steps[si];
         for (const FlowTask &t : all_tasks[si]) {
           const int slot = t.kind_front & 0xffffff;
@@ -1384,17 +1393,14 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   // -- per super-panel the tiles left of the Schur origin (schur_split_: the Schur complement is ONE pass of k_big_schur
   // at the end of the level; else every tile right of the super-panel), and the Schur tiles themselves
   void build_update_maps() {
-    upd_maps_.assign(sym_.steps.size(), {});
-    schur_maps_.assign(sym_.steps.size(), UpdMap{0, 0});
     std::vector<int32_t> buf;
     for (size_t si = 0; si < sym_.steps.size(); si++) {
       const Step &st = sym_.steps[si];
       if (st.kind != STEP_BIG) continue;
-      const bool flow_level = (bool)flow_levels_[si];   // its per-super-panel tiles are UPDATE tasks; only the Schur pass is a launch
+      const bool flow_level = (bool)plan_[si].flow;   // its per-super-panel tiles are UPDATE tasks; only the Schur pass is a launch
       const int nf = st.task_end - st.task_begin;
       if (nf > 0xffff) throw ApiError(RR_PGO_EUNSUPPORTED, "more than 65535 big fronts in one level");
-      int max_nc = 0;
-      for (int z = 0; z < nf; z++) max_nc = std::max(max_nc, sym_.sn_ncols[sym_.task_sn[sym_.task_ptr[st.task_begin + z]]]);
+      const int max_nc = plan_[si].max_nc;
       auto tri_ok = [](int nt) { if (nt * (nt + 1) / 2 > 0xffff) throw ApiError(RR_PGO_EUNSUPPORTED, "a front of more than 65535 update tiles"); };
       for (int K0 = 0; K0 < max_nc && !flow_level; K0 += BIG_SUPER) {
         UpdMap um{(int64_t)buf.size(), 0};
@@ -1410,9 +1416,9 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
               if (t0 + 64 * by < o) buf.push_back((z << 16) | (bx * (bx + 1) / 2 + by));
         }
         um.n_tiles = (int)((int64_t)buf.size() - um.offset);
-        upd_maps_[si].push_back(um);
+        plan_[si].upd.push_back(um);
       }
-      if (flow_level ? flow_levels_[si]->schur_split : schur_split_) {
+      if (flow_level ? plan_[si].flow->schur_split : schur_split_) {
         UpdMap um{(int64_t)buf.size(), 0};
         for (int z = 0; z < nf; z++) {
           const int sn = sym_.task_sn[sym_.task_ptr[st.task_begin + z]];
@@ -1424,20 +1430,15 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
           for (int t = 0; t < nt * (nt + 1) / 2; t++) buf.push_back((z << 16) | t);
         }
         um.n_tiles = (int)((int64_t)buf.size() - um.offset);
-        schur_maps_[si] = um;
+        plan_[si].schur = um;
       }
     }
     if (!buf.empty()) upd_map_buf_.upload(buf);
   }
-  const UpdMap &upd_map(const Step &st, int sp) const { return upd_maps_[(size_t)(&st - sym_.steps.data())][(size_t)sp]; }
   bool any_flow(size_t from, size_t to) const {   // a factorisation range that must zero the flag block first
-    for (size_t si = from; si < to && si < flow_levels_.size(); si++) if (flow_levels_[si]) return true;
-    for (const auto &p : solve_flow_) if (p) return true;   // the back substitution of ANY level may use its counters afterwards
+    for (size_t si = from; si < to && si < plan_.size(); si++) if (plan_[si].flow) return true;
+    for (const StepPlan &p : plan_) if (p.solve_flow) return true;   // the back substitution of ANY level may use its counters afterwards
     return false;
-  }
-  const FlowLevel *flow_of(const Step &st) const {
-    const size_t si = (size_t)(&st - sym_.steps.data());
-    return si < flow_levels_.size() ? flow_levels_[si].get() : nullptr;
   }
   FlowArgs<T> flow_args() {
     FlowArgs<T> fa;
@@ -1463,7 +1464,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     fa.b = b_.p;
     return fa;
   }
-  void launch_flow(const Step &st, const FlowLevel &lvl) {
+  void launch_flow(const FlowLevel &lvl) {
     FlowArgs<T> fa = flow_args();
     fa.tasks = lvl.tasks.p;
     fa.ticket = flow_flags_.p + lvl.ticket_word;
@@ -1543,18 +1544,91 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     HIPCHK(hipFuncSetAttribute((const void *)k_factor_tasks<T, TH>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds));
     HIPCHK(hipFuncSetAttribute((const void *)k_solve_tasks<T, TH>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds));
   }
-  int level_max_nc(const Step &st) const {
-    int max_nc = 1;
-    for (int t = st.task_begin; t < st.task_end; t++) max_nc = std::max(max_nc, sym_.sn_ncols[sym_.task_sn[sym_.task_ptr[t]]]);
-    return max_nc;
+  // ---- the plan of every step.  First what depends on the fronts alone (build_flow_levels, build_update_maps and
+  // plan_mid_solve_tasks read it and add their tables), then plan_launches: what follows from those tables too.
+  void plan_shapes() {
+    plan_.clear();
+    plan_.resize(sym_.steps.size());
+    for (size_t si = 0; si < plan_.size(); si++) {
+      const Step &st = sym_.steps[si];
+      StepPlan &p = plan_[si];
+      p.kind = st.kind;
+      p.nf = st.task_end - st.task_begin;
+      p.task_begin = st.task_begin;
+      if (st.kind == STEP_TASKS) {
+        // Workgroup size of an LDS-front step: the symbolic phase sizes it for the latency of ONE task (a 16-wave workgroup per
+        // front of > 128 rows).  Smaller workgroups for levels of thousands of tasks were measured slower (r02, lattice, 5244
+        // tasks: 690 us with 1024 threads, 873 with 512, 1045 with 256).
+        p.factor_lds = (size_t)st.max_lds_elems * sizeof(T);
+        p.factor_threads = std::min(st.threads, factor_threads_max_);
+        p.solve_threads = std::min(st.threads, solve_threads_max_);
+        continue;
+      }
+      auto front = [&](int z) { return sym_.task_sn[sym_.task_ptr[st.task_begin + z]]; };
+      int64_t max_asm = 0;
+      for (int z = 0; z < p.nf; z++) {
+        const int s = front(z), nc = sym_.sn_ncols[s], nr = sym_.sn_nrows[s];
+        p.max_nc = std::max(p.max_nc, nc);
+        p.maxM = std::max(p.maxM, nc + nr + 1);
+        p.max_nr = std::max(p.max_nr, nr);
+        p.has_rows = p.has_rows || nr > 0;
+        max_asm = std::max<int64_t>(max_asm, std::max<int64_t>(sym_.fasm_ptr[s + 1] - sym_.fasm_ptr[s], nc));
+        p.any_dup = p.any_dup || sym_.fdup_ptr[s + 1] > sym_.fdup_ptr[s];
+        p.has_root = p.has_root || (gauge_ok_ && s == gauge_root_);
+      }
+      // one pass writes every entry of the level's fronts once: the sum of the children's contributions (gathered
+      // through inverse maps), zeros elsewhere; the H entries and the rhs are added on top -- by the building waves
+      // themselves when the launch is a single round of workgroups (three dependent loads per column at the end of every
+      // workgroup: cheaper than a launch there, dearer on the levels of hundreds of fronts -- lattice 4.62 against 4.68 ms
+      // with every level fused, sphere2500 +1 % fused), else by a k_big_assemble launch
+      p.build_gx = std::min(std::max(((gather_update_ ? std::min(p.maxM, ((p.max_nc + 127) / 128) * 128) : p.maxM) + 3) / 4, 1), 8192);
+      const bool fused = fused_assembly_ && (int64_t)p.build_gx * p.nf <= 2048;
+      p.asm_gx = fused ? 0 : (int)std::min<int64_t>((max_asm + 255) / 256, 2048);
+      // row slices of a level's k_big_gemv_partial launch: enough workgroups to fill the chip, but never thinner than 128 rows
+      // (every slice is a partial sum the solve has to fetch and add per column)
+      p.cb = (p.max_nc + 63) / 64;
+      p.R = std::max(1, std::min(std::min(kGemvSlices, (p.max_nr + 127) / 128), (768 + p.nf * p.cb - 1) / (p.nf * p.cb)));
+      p.n_sp = (p.max_nc + BIG_SUPER - 1) / BIG_SUPER;
+    }
   }
-  // row slices of a level's k_big_gemv_partial launch: enough workgroups to fill the chip, but never thinner than 128 rows
-  // (every slice is a partial sum the solve has to fetch and add per column)
-  int gemv_slices(const Step &st) const {
-    const int nf = st.task_end - st.task_begin, cb = (level_max_nc(st) + 63) / 64;
-    int max_nr = 1;
-    for (int t = st.task_begin; t < st.task_end; t++) max_nr = std::max(max_nr, sym_.sn_nrows[sym_.task_sn[sym_.task_ptr[t]]]);
-    return std::max(1, std::min(std::min(kGemvSlices, (max_nr + 127) / 128), (768 + nf * cb - 1) / (nf * cb)));
+  void plan_launches() {
+    for (StepPlan &p : plan_) {
+      if (p.kind != STEP_BIG) continue;
+      // the launch sequence (a flow level's panel chain and trailing updates are tasks of its one launch): a k_big_panel32
+      // launch per 32 columns, over the rows of the fronts still active there
+      for (int kb = 0; kb < p.max_nc && !p.flow; kb += BIG_NB) {
+        int rows = 0;   // max over fronts still active at column kb of (M - kb)
+        for (int z = 0; z < p.nf; z++) {
+          const int s = sym_.task_sn[sym_.task_ptr[p.task_begin + z]];
+          if (sym_.sn_ncols[s] > kb) rows = std::max(rows, sym_.sn_ncols[s] + sym_.sn_nrows[s] + 1 - kb);
+        }
+        p.panel_gx.push_back((std::max(rows - 1, 1) + 31) / 32);
+      }
+      // L11: per 128-column super-panel over the chip (wide pivot blocks; as one launch of ticketed tasks where the level has
+      // the list), or one workgroup per front
+      p.l11 = p.max_nc < sp_solve_min_nc_ ? L11_MID : p.solve_flow ? L11_FLOW : L11_SP;
+      p.l11_gx = p.l11 == L11_MID  ? p.nf
+                 : p.l11 == L11_SP ? 1 + (p.max_nc + 63) / 64
+                                   : std::min(p.solve_flow->n_tasks, std::max(flow_grid_ / (sizeof(T) == 4 ? RRPGO_FLOW_WAVES : 1), 1));
+    }
+  }
+  // launches of one factorisation / one back substitution of a step (the two gauge launches counted whether or not they run)
+  static int factor_launches(const StepPlan &p) {
+    if (p.kind != STEP_BIG) return 1;
+    int n = 1 + (p.asm_gx > 0) + p.any_dup + 2 * p.has_root + (p.flow ? 1 : 0) + (int)p.panel_gx.size() + (p.schur.n_tiles > 0);
+    for (const UpdMap &um : p.upd) n += um.n_tiles > 0;
+    return n;
+  }
+  static int solve_launches(const StepPlan &p) {
+    if (p.in_solve_flow) return 0;
+    if (p.kind != STEP_BIG) return 1;
+    return p.has_rows + (p.l11 == L11_SP ? p.n_sp : 1);
+  }
+  // the instantiation of a kernel family for a workgroup size: the first of the family's sizes that holds it, else the last
+  template <int TH, int... More, typename F> static void for_threads(int threads, F &&f) {
+    if constexpr (sizeof...(More) == 0) f(std::integral_constant<int, TH>{});
+    else if (threads <= TH) f(std::integral_constant<int, TH>{});
+    else for_threads<More...>(threads, f);
   }
   // Graphs on the dataflow schedule with fronts beyond LDS (sphere2500: 46, six levels): the levels whose pivot blocks are
   // narrower than RR_PGO_SP_SOLVE_MIN columns -- all but the top one or two -- are back-substituted as TASKS of k_solve_flow
@@ -1562,18 +1636,17 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   // The wide top levels stay launches in front of k_solve_flow.  RR_PGO_SOLVE_MID_FLOW=0: every level as launches (the
   // r03 - r05 form; the same sums in the same order: bit-identical).
   void plan_mid_solve_tasks() {
-    mid_in_flow_.assign(sym_.steps.size(), 0);
     if (!lds_flow_) return;
     bool on = true;
     if (const char *e = getenv("RR_PGO_SOLVE_MID_FLOW")) on = std::atoi(e) != 0;
     int top = (int)sym_.steps.size() - 1;
-    while (on && top >= 1 && level_max_nc(sym_.steps[top]) >= sp_solve_min_nc_) top--;   // the wide top levels
+    while (on && top >= 1 && plan_[top].max_nc >= sp_solve_min_nc_) top--;   // the wide top levels
     std::vector<LdsFlowTask> mid;
     int need = 1024;   // a GEMV unit's x[rows] chunk
     for (int i = top; on && i >= 1; i--) {
       const Step &st = sym_.steps[i];
-      if (level_max_nc(st) >= sp_solve_min_nc_) { on = false; break; }   // a wide level under a narrow one: keep every level a launch
-      const int R = gemv_slices(st);
+      if (plan_[i].max_nc >= sp_solve_min_nc_) { on = false; break; }   // a wide level under a narrow one: keep every level a launch
+      const int R = plan_[i].R;
       for (int pass = 1; pass <= 2; pass++)   // the level's GEMV units first, then its L11 tasks
         for (int t = st.task_begin; t < st.task_end; t++) {
           LdsFlowTask r{};
@@ -1595,8 +1668,8 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
         }
     }
     if (on && !mid.empty() && (size_t)need * sizeof(T) <= (size_t)kMaxLds) {
-      for (int i = top; i >= 1; i--) mid_in_flow_[i] = 1;
-      step_solve_lds_[0] = std::max(step_solve_lds_[0], need);
+      for (int i = top; i >= 1; i--) plan_[i].in_solve_flow = true;
+      plan_[0].solve_lds = std::max(plan_[0].solve_lds, need);
       mid.insert(mid.end(), host_stasks_.begin(), host_stasks_.end());
       host_stasks_.swap(mid);
     }
@@ -1617,13 +1690,6 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     HIPCHK(hipFuncSetAttribute((const void *)k_factor_flow<T, 1024>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds));
     HIPCHK(hipFuncSetAttribute((const void *)k_solve_flow<T, 256>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds));
     HIPCHK(hipFuncSetAttribute((const void *)k_solve_flow<T, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds));
-  }
-
-  template <int TH> void launch_factor_tasks(int nt, size_t lds, const FactorArgs<T> &a) {
-    hipLaunchKernelGGL((k_factor_tasks<T, TH>), dim3(nt), dim3(TH), lds, stream_, a);
-  }
-  template <int TH> void launch_solve_tasks(int nt, size_t lds, const FactorArgs<T> &a) {
-    hipLaunchKernelGGL((k_solve_tasks<T, TH>), dim3(nt), dim3(TH), lds, stream_, a);
   }
 
   LinArgs<T, S> lin_args(double lambda, int lm, int write_system, bool reference_prior = false) {
@@ -1803,8 +1869,8 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     if (any_flow(from, to)) {
       // ... and the "not there yet" marks of the W blocks of the range's flow fronts
       int e0 = 0, e1 = 0;
-      for (size_t si = from; si < to && si < flow_levels_.size(); si++)
-        if (flow_levels_[si]) { if (e1 == 0) e0 = flow_levels_[si]->wfill_begin; e1 = flow_levels_[si]->wfill_end; }
+      for (size_t si = from; si < to && si < plan_.size(); si++)
+        if (const FlowLevel *l = plan_[si].flow.get()) { if (e1 == 0) e0 = l->wfill_begin; e1 = l->wfill_end; }
       const int flag_wgs = (int)std::min<int64_t>(((int64_t)flow_flags_.n + 255) / 256, 256);
       hipLaunchKernelGGL(k_flow_reset<T>, dim3((unsigned)(flag_wgs + std::max(e1 - e0, 0))), dim3(256), 0, stream_, flow_flags_.p, (int64_t)flow_flags_.n, flag_wgs,
                          winv_.p, flow_wfill_.p + 2 * e0, xnew_.p, (const int *)err_.p);
@@ -1812,253 +1878,154 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     }
     if (lds_flow_ && from == 0 && to > 0) {
       // every front in LDS: their whole factorisation as ONE launch of ticket-ordered tasks (lds_flow.hip.h)
-      const Step &st = sym_.steps[0];
+      const StepPlan &p = plan_[0];
       pbegin();
-      const size_t lds = (size_t)st.max_lds_elems * sizeof(T);
       const FactorArgs<T> a = factor_args(0);
       const int grid = std::min(lds_n_tasks_, lds_flow_cus_);
       unsigned *ticket = dep_flags_.p + 2 * sym_.S;
-      if (std::min(st.threads, factor_threads_max_) <= 256)
-        hipLaunchKernelGGL((k_factor_flow<T, 256>), dim3(grid), dim3(256), lds, stream_, a, (const LdsFlowTask *)lds_ftasks_.p, lds_n_tasks_, ticket);
-      else if (std::min(st.threads, factor_threads_max_) <= 512)
-        hipLaunchKernelGGL((k_factor_flow<T, 512>), dim3(grid), dim3(512), lds, stream_, a, (const LdsFlowTask *)lds_ftasks_.p, lds_n_tasks_, ticket);
-      else
-        hipLaunchKernelGGL((k_factor_flow<T, 1024>), dim3(grid), dim3(1024), lds, stream_, a, (const LdsFlowTask *)lds_ftasks_.p, lds_n_tasks_, ticket);
+      for_threads<256, 512, 1024>(p.factor_threads, [&](auto th) {
+        hipLaunchKernelGGL((k_factor_flow<T, th()>), dim3(grid), dim3(th()), p.factor_lds, stream_, a, (const LdsFlowTask *)lds_ftasks_.p, lds_n_tasks_, ticket);
+      });
       check_launch("k_factor_flow");
       pend(RR_PGO_K_FACTOR);
       from = 1;
     }
-    if (xl_ && from == 1 && to == sym_.steps.size()) {
+    if (xl_ && from == 1 && to == plan_.size()) {
       pbegin();
       launch_flow_xl();
       pend(RR_PGO_K_BIG_FLOW);
       return;
     }
     for (size_t si = from; si < to; si++) {
-      const Step &st = sym_.steps[si];
+      const StepPlan &p = plan_[si];
       pbegin();
-      if (st.kind == STEP_TASKS) {
-        const int nt = st.task_end - st.task_begin;
-        const size_t lds = (size_t)st.max_lds_elems * sizeof(T);
-        FactorArgs<T> a = factor_args(st.task_begin);
-        const int fth = step_threads(st, nt, factor_threads_max_);
-        if (fth == 64) launch_factor_tasks<64>(nt, lds, a);
-        else if (fth == 128) launch_factor_tasks<128>(nt, lds, a);
-        else if (fth == 256) launch_factor_tasks<256>(nt, lds, a);
-        else if (fth <= 512) launch_factor_tasks<512>(nt, lds, a);
-        else launch_factor_tasks<1024>(nt, lds, a);
+      if (p.kind == STEP_TASKS) {
+        const FactorArgs<T> a = factor_args(p.task_begin);
+        for_threads<64, 128, 256, 512, 1024>(p.factor_threads, [&](auto th) {
+          hipLaunchKernelGGL((k_factor_tasks<T, th()>), dim3(p.nf), dim3(th()), p.factor_lds, stream_, a);
+        });
         pend(RR_PGO_K_FACTOR);
       } else {
-        launch_big_level(st, true);
+        launch_big_level(p);
         pend(RR_PGO_K_BIGFRONT);
       }
     }
   }
-
-  // Workgroup size of an LDS-front step: the symbolic phase sizes it for the latency of ONE task (a 16-wave workgroup per
-  // front of > 128 rows).  Smaller workgroups for levels of thousands of tasks were measured slower (r02, lattice, 5244
-  // tasks: 690 us with 1024 threads, 873 with 512, 1045 with 256).
-  int step_threads(const Step &st, int, int cap) const { return std::min(st.threads, cap); }
 
   // The fronts beyond LDS of one level, batched (grid y / z = front): ONE gather pass builds the pivot columns from
   // the children (k_big_build) and adds the H entries and the right-hand side (k_big_assemble); then either the whole
   // level as one dataflow launch (k_big_flow: levels of few fronts and few tasks), or per 128-column super-panel four
   // left-looking k_big_panel32 launches and one K = 128 trailing update (k_big_update; the first one of a front gathers
   // its tiles from the children, its tile (0, 0) factors and inverts the next super-panel's first diagonal block).
-  // do_launch == false only counts the launches.  (The r01 / r02 alternatives -- right-looking K = 32 steps, whole
-  // super-panels per chain step, the two-stream far update, zero + extend-add assembly, the one-workgroup panel class --
-  // were measured slower and removed in r03: profiles/EXPERIMENTS.md.)
-  int launch_big_level(const Step &st, bool do_launch) {
-    const FactorArgs<T> a = factor_args(st.task_begin);
-    const int nf = st.task_end - st.task_begin;
-    int maxM = 0, max_nc = 0, n = 0;
-    int64_t max_asm = 0;
-    bool any_dup = false;
-    std::vector<int> fr(nf);
-    for (int z = 0; z < nf; z++) {
-      const int s = sym_.task_sn[sym_.task_ptr[st.task_begin + z]];
-      fr[z] = s;
-      maxM = std::max(maxM, sym_.sn_ncols[s] + sym_.sn_nrows[s] + 1);
-      max_nc = std::max(max_nc, sym_.sn_ncols[s]);
-      max_asm = std::max<int64_t>(max_asm, std::max<int64_t>(sym_.fasm_ptr[s + 1] - sym_.fasm_ptr[s], sym_.sn_ncols[s]));
-      any_dup = any_dup || sym_.fdup_ptr[s + 1] > sym_.fdup_ptr[s];
+  // (The r01 / r02 alternatives -- right-looking K = 32 steps, whole super-panels per chain step, the two-stream far
+  // update, zero + extend-add assembly, the one-workgroup panel class -- were measured slower and removed in r03:
+  // profiles/EXPERIMENTS.md.)  Every launch here has its term in factor_launches.
+  void launch_big_level(const StepPlan &p) {
+    const FactorArgs<T> a = factor_args(p.task_begin);
+    hipLaunchKernelGGL(k_big_build<T>, dim3((unsigned)p.build_gx, p.nf), dim3(256), 0, stream_, a, gather_update_ ? 1 : 0, p.asm_gx > 0 ? 0 : 1);
+    check_launch("k_big_build");
+    if (p.asm_gx > 0) {
+      hipLaunchKernelGGL(k_big_assemble<T>, dim3((unsigned)p.asm_gx, p.nf), dim3(256), 0, stream_, a, 1);
+      check_launch("k_big_assemble");
     }
-    auto rows_max = [&](int from) {  // max over fronts still active at column `from` of (M - from)
-      int r = 0;
-      for (int s : fr)
-        if (sym_.sn_ncols[s] > from) r = std::max(r, sym_.sn_ncols[s] + sym_.sn_nrows[s] + 1 - from);
-      return r;
-    };
-    // one pass writes every entry of the level's fronts once: the sum of the children's contributions (gathered
-    // through inverse maps), zeros elsewhere; the H entries and the rhs are added on top -- by the building waves
-    // themselves when the launch is a single round of workgroups (three dependent loads per column at the end of every
-    // workgroup: cheaper than a launch there, dearer on the levels of hundreds of fronts -- lattice 4.62 against 4.68 ms
-    // with every level fused, sphere2500 +1 % fused), else by a k_big_assemble launch
-    const int build_gx = std::min(std::max(((gather_update_ ? std::min(maxM, ((max_nc + 127) / 128) * 128) : maxM) + 3) / 4, 1), 8192);
-    const bool fused = fused_assembly_ && (int64_t)build_gx * nf <= 2048;
-    if (do_launch) {
-      hipLaunchKernelGGL(k_big_build<T>, dim3((unsigned)build_gx, nf), dim3(256), 0, stream_, a, gather_update_ ? 1 : 0, fused ? 1 : 0);
-      check_launch("k_big_build");
-      if (!fused) {
-        hipLaunchKernelGGL(k_big_assemble<T>, dim3((unsigned)std::min<int64_t>((max_asm + 255) / 256, 2048), nf), dim3(256), 0, stream_, a, 1);
-        check_launch("k_big_assemble");
-      }
-      if (any_dup) hipLaunchKernelGGL(k_big_assemble_dup<T>, dim3(1, nf), dim3(64), 0, stream_, a);
-    }
-    n += (fused ? 1 : 2) + (any_dup ? 1 : 0);
-    if (gauge_ok_) {
-      bool has_root = false;
-      for (int s : fr) has_root = has_root || s == gauge_root_;
-      if (has_root) {
-        if (do_launch && gauge_now_) launch_gauge_term();
-        n += 2;
-      }
-    }
-    if (do_launch) pend(RR_PGO_K_BIGFRONT);   // closes the build / assemble segment
-    if (const FlowLevel *lvl = flow_of(st)) {
+    if (p.any_dup) hipLaunchKernelGGL(k_big_assemble_dup<T>, dim3(1, p.nf), dim3(64), 0, stream_, a);
+    if (p.has_root && gauge_now_) launch_gauge_term();
+    pend(RR_PGO_K_BIGFRONT);   // closes the build / assemble segment
+    if (p.flow) {
       // the whole panel chain and every trailing update of the level: ONE launch of ticket-ordered tasks
-      if (do_launch) {
-        pbegin();
-        launch_flow(st, *lvl);
-        pend(RR_PGO_K_BIG_FLOW);
-      }
-      n++;
-      n += launch_schur(st, a, do_launch);
-      if (do_launch) pbegin();   // re-arm: the caller closes the level with pend(BIGFRONT)
-      return n;
+      pbegin();
+      launch_flow(*p.flow);
+      pend(RR_PGO_K_BIG_FLOW);
     }
-    for (int K0 = 0; K0 < max_nc; K0 += BIG_SUPER) {
+    for (size_t sp = 0; sp < p.upd.size(); sp++) {   // the super-panels of the launch sequence (a flow level has none)
       // left-looking inside the super-panel: ONE launch per 32 columns (update from the columns K0..kb, multiply by the
       // inverse diagonal block, next diagonal block).  The level's first block is factored and inverted inside its own
       // row launch (by every workgroup); the first block of a later super-panel comes out of the previous trailing update.
-      if (do_launch) pbegin();
-      const int k_end = std::min(K0 + BIG_SUPER, max_nc);
-      for (int kb = K0; kb < k_end; kb += BIG_NB) {
-        const int rb = rows_max(kb) - 1;
-        if (do_launch) {
-          hipLaunchKernelGGL(k_big_panel32<T>, dim3((std::max(rb, 1) + 31) / 32, nf), dim3(64), 0, stream_, a, kb, K0, kb == 0 ? 1 : 0);
-          check_launch("k_big_panel32");
-        }
-        n++;
-      }
-      if (do_launch) pend(RR_PGO_K_BIG_PANEL, (k_end - K0 + BIG_NB - 1) / BIG_NB);
-      // everything right of the super-panel, Schur complement included: the level's real 64 x 64 tiles as a
-      // one-dimensional grid (upd_maps_: front slot and tile of every grid index)
-      const UpdMap &um = upd_map(st, K0 / BIG_SUPER);
-      if (um.n_tiles == 0) continue;   // schur_split_: a level of single-super-panel fronts has no per-super-panel update at all
-      if (do_launch) {
-        pbegin();
-        hipLaunchKernelGGL((k_big_update<T, 2, RRPGO_UPD_DEPTH>), dim3((unsigned)um.n_tiles), dim3(256), 0, stream_, a, K0,
-                           (gather_update_ && K0 == 0) ? 1 : 0, (const int32_t *)upd_map_buf_.p + um.offset, um.n_tiles, xcd_remap_ ? 1 : 0,
-                           schur_split_ ? schur_tile_ : 0);
-        check_launch("k_big_update");
-        pend(RR_PGO_K_BIG_UPDATE);
-      }
-      n++;
-    }
-    n += launch_schur(st, a, do_launch);
-    if (do_launch) pbegin();   // re-arm: the caller closes the level with pend(BIGFRONT)
-    return n;
-  }
-  // the Schur complements of the level's fronts: ONE pass over all pivot columns (K = nc), each tile written once
-  int launch_schur(const Step &st, const FactorArgs<T> &a, bool do_launch) {
-    const UpdMap &um = schur_maps_[(size_t)(&st - sym_.steps.data())];
-    if (um.n_tiles == 0) return 0;   // no map: no split on this level (or no Schur complement at all)
-    if (do_launch) {
+      const int K0 = (int)sp * BIG_SUPER, k_end = std::min(K0 + BIG_SUPER, p.max_nc);
       pbegin();
-      hipLaunchKernelGGL((k_big_schur<T, 2>), dim3((unsigned)um.n_tiles), dim3(256), 0, stream_, a, gather_update_ ? 1 : 0,
-                         (const int32_t *)upd_map_buf_.p + um.offset, um.n_tiles, xcd_remap_ ? 1 : 0);
+      for (int kb = K0; kb < k_end; kb += BIG_NB) {
+        hipLaunchKernelGGL(k_big_panel32<T>, dim3(p.panel_gx[kb / BIG_NB], p.nf), dim3(64), 0, stream_, a, kb, K0, kb == 0 ? 1 : 0);
+        check_launch("k_big_panel32");
+      }
+      pend(RR_PGO_K_BIG_PANEL, (k_end - K0 + BIG_NB - 1) / BIG_NB);
+      // everything right of the super-panel, Schur complement included: the level's real 64 x 64 tiles as a
+      // one-dimensional grid (StepPlan::upd: front slot and tile of every grid index)
+      const UpdMap &um = p.upd[sp];
+      if (um.n_tiles == 0) continue;   // schur_split_: a level of single-super-panel fronts has no per-super-panel update at all
+      pbegin();
+      hipLaunchKernelGGL((k_big_update<T, 2, RRPGO_UPD_DEPTH>), dim3((unsigned)um.n_tiles), dim3(256), 0, stream_, a, K0,
+                         (gather_update_ && K0 == 0) ? 1 : 0, (const int32_t *)upd_map_buf_.p + um.offset, um.n_tiles, xcd_remap_ ? 1 : 0,
+                         schur_split_ ? schur_tile_ : 0);
+      check_launch("k_big_update");
+      pend(RR_PGO_K_BIG_UPDATE);
+    }
+    if (p.schur.n_tiles > 0) {
+      // the Schur complements of the level's fronts: ONE pass over all pivot columns (K = nc), each tile written once
+      // (no map: no split on this level, or no Schur complement at all)
+      pbegin();
+      hipLaunchKernelGGL((k_big_schur<T, 2>), dim3((unsigned)p.schur.n_tiles), dim3(256), 0, stream_, a, gather_update_ ? 1 : 0,
+                         (const int32_t *)upd_map_buf_.p + p.schur.offset, p.schur.n_tiles, xcd_remap_ ? 1 : 0);
       check_launch("k_big_schur");
       pend(RR_PGO_K_BIG_UPDATE);
     }
-    return 1;
-  }
-  int count_big_launches(const Step &st) { return launch_big_level(st, false); }
-  bool level_has_rows(const Step &st) const {
-    for (int t = st.task_begin; t < st.task_end; t++)
-      if (sym_.sn_nrows[sym_.task_sn[sym_.task_ptr[t]]] > 0) return true;
-    return false;
-  }
-  int count_big_solve_launches(const Step &st) const {
-    int max_nc = 1;
-    for (int t = st.task_begin; t < st.task_end; t++) max_nc = std::max(max_nc, sym_.sn_ncols[sym_.task_sn[sym_.task_ptr[t]]]);
-    const int gemv = level_has_rows(st) ? 1 : 0;
-    if (max_nc >= sp_solve_min_nc_) {
-      const size_t si = (size_t)(&st - sym_.steps.data());
-      return si < solve_flow_.size() && solve_flow_[si] ? gemv + 1 : gemv + (max_nc + BIG_SUPER - 1) / BIG_SUPER;
-    }
-    return gemv + 1;
+    pbegin();   // re-arm: the caller closes the level with pend(BIGFRONT)
   }
 
   void launch_solve() {
     launch_solve_steps(lds_flow_ ? 1 : 0);   // the fronts beyond LDS (and, in the level schedule, everything), top down
     if (lds_flow_) {
-      const Step &st = sym_.steps[0];
+      const StepPlan &p = plan_[0];
       pbegin();
-      const size_t lds = (size_t)step_solve_lds_[0] * sizeof(T);
       FactorArgs<T> a = factor_args(0);
-      a.solve_lds = step_solve_lds_[0];
-      const int sth = std::min(st.threads, solve_threads_max_);
-      const int grid = std::min(lds_n_stasks_, lds_flow_cus_ * (sth <= 256 ? 4 : 2));
+      a.solve_lds = p.solve_lds;
+      const int grid = std::min(lds_n_stasks_, lds_flow_cus_ * (p.solve_threads <= 256 ? 4 : 2));
       unsigned *ticket = dep_flags_.p + 2 * sym_.S + 32;
-      if (sth <= 256)
-        hipLaunchKernelGGL((k_solve_flow<T, 256>), dim3(grid), dim3(256), lds, stream_, a, (const LdsFlowTask *)lds_stasks_.p, lds_n_stasks_, ticket, gemv_part_.p, (int64_t)g_.dim);
-      else
-        hipLaunchKernelGGL((k_solve_flow<T, 512>), dim3(grid), dim3(512), lds, stream_, a, (const LdsFlowTask *)lds_stasks_.p, lds_n_stasks_, ticket, gemv_part_.p, (int64_t)g_.dim);
+      for_threads<256, 512>(p.solve_threads, [&](auto th) {
+        hipLaunchKernelGGL((k_solve_flow<T, th()>), dim3(grid), dim3(th()), (size_t)p.solve_lds * sizeof(T), stream_, a, (const LdsFlowTask *)lds_stasks_.p, lds_n_stasks_,
+                           ticket, gemv_part_.p, (int64_t)g_.dim);
+      });
       check_launch("k_solve_flow");
       pend(RR_PGO_K_SOLVE);
     }
   }
+  // Every launch here has its term in solve_launches.
   void launch_solve_steps(int first_step) {
-    for (int i = (int)sym_.steps.size() - 1; i >= first_step; i--) {   // shared top fronts first, then this rank's subtrees
-      const Step &st = sym_.steps[i];
-      if (mid_in_flow_[(size_t)i]) continue;   // its fronts are tasks of k_solve_flow
-      const size_t lds = (size_t)step_solve_lds_[i] * sizeof(T);
+    for (int i = (int)plan_.size() - 1; i >= first_step; i--) {   // shared top fronts first, then this rank's subtrees
+      const StepPlan &p = plan_[(size_t)i];
+      if (p.in_solve_flow) continue;   // its fronts are tasks of k_solve_flow
+      const size_t lds = (size_t)p.solve_lds * sizeof(T);
       pbegin();
-      if (st.kind == STEP_TASKS) {
-        const int nt = st.task_end - st.task_begin;
-        FactorArgs<T> a = factor_args(st.task_begin);
-        a.solve_lds = step_solve_lds_[i];
-        const int sth = step_threads(st, nt, solve_threads_max_);
-        if (sth <= 64) launch_solve_tasks<64>(nt, lds, a);
-        else if (sth <= 128) launch_solve_tasks<128>(nt, lds, a);
-        else if (sth <= 256) launch_solve_tasks<256>(nt, lds, a);
-        else launch_solve_tasks<512>(nt, lds, a);
+      FactorArgs<T> a = factor_args(p.task_begin);
+      if (p.kind == STEP_TASKS) {
+        a.solve_lds = p.solve_lds;
+        for_threads<64, 128, 256, 512>(p.solve_threads, [&](auto th) {
+          hipLaunchKernelGGL((k_solve_tasks<T, th()>), dim3(p.nf), dim3(th()), lds, stream_, a);
+        });
         pend(RR_PGO_K_SOLVE);
+        continue;
+      }
+      // t = y1 - L21^T x[rows] over the whole chip, then L11 in the level's form (plan_launches)
+      if (p.has_rows) {   // (a level of root fronts -- no rows below the pivot block -- has no L21^T x to form: the solves read no partial sums)
+        hipLaunchKernelGGL(k_big_gemv_partial<T>, dim3(p.cb, p.R, p.nf), dim3(256), 0, stream_, a, gemv_part_.p, (int64_t)g_.dim, p.R);
+        check_launch("k_big_gemv_partial");
+      }
+      if (p.l11 == L11_FLOW) {
+        // wide pivot blocks, the whole level's chain steps and folds as ONE launch of ticketed tasks (flow.hip.h)
+        const SolveFlowLevel &sl = *p.solve_flow;
+        hipLaunchKernelGGL(k_big_solve_flow<T>, dim3((unsigned)p.l11_gx), dim3(1024), 0, stream_, a, (const T *)gemv_part_.p, (int64_t)g_.dim, p.R,
+                           flow_flags_.p, (const SolveFlowFront *)sl.fronts.p, (const SolveFlowTask *)sl.tasks.p, sl.n_tasks,
+                           flow_flags_.p + sl.ticket_word);
+        check_launch("k_big_solve_flow");
+        pend(RR_PGO_K_BIG_SOLVE, 2);
+      } else if (p.l11 == L11_SP) {
+        // wide pivot blocks: one launch per 128-column super-panel, L11 read by the whole chip
+        for (int ell = 0; ell < p.n_sp; ell++) {
+          hipLaunchKernelGGL(k_big_solve_sp<T>, dim3(p.l11_gx, p.nf), dim3(1024), 0, stream_, a, ell, (const T *)gemv_part_.p, (int64_t)g_.dim, p.R);
+          check_launch("k_big_solve_sp");
+        }
+        pend(RR_PGO_K_BIG_SOLVE, 1 + p.n_sp);
       } else {
-        // t = y1 - L21^T x[rows] over the whole chip, then L11: per 128-column super-panel over the chip (wide pivot blocks) or one workgroup per front
-        const int nf = st.task_end - st.task_begin;
-        int max_nc = 1;
-        for (int z = 0; z < nf; z++) max_nc = std::max(max_nc, sym_.sn_ncols[sym_.task_sn[sym_.task_ptr[st.task_begin + z]]]);
-        const int cb = (max_nc + 63) / 64;
-        const int R = gemv_slices(st);
-        const FactorArgs<T> fa = factor_args(st.task_begin);
-        if (level_has_rows(st)) {   // (a level of root fronts -- no rows below the pivot block -- has no L21^T x to form: the solves read no partial sums)
-          hipLaunchKernelGGL(k_big_gemv_partial<T>, dim3(cb, R, nf), dim3(256), 0, stream_, fa, gemv_part_.p, (int64_t)g_.dim, R);
-          check_launch("k_big_gemv_partial");
-        }
-        if (max_nc >= sp_solve_min_nc_) {
-          if (solve_flow_[(size_t)i]) {
-            // wide pivot blocks, the whole level's chain steps and folds as ONE launch of ticketed tasks (flow.hip.h)
-            const SolveFlowLevel &sl = *solve_flow_[(size_t)i];
-            int cus_grid = std::min(sl.n_tasks, std::max(flow_grid_ / (sizeof(T) == 4 ? RRPGO_FLOW_WAVES : 1), 1));
-            hipLaunchKernelGGL(k_big_solve_flow<T>, dim3((unsigned)cus_grid), dim3(1024), 0, stream_, fa, (const T *)gemv_part_.p, (int64_t)g_.dim, R,
-                               flow_flags_.p, (const SolveFlowFront *)sl.fronts.p, (const SolveFlowTask *)sl.tasks.p, sl.n_tasks,
-                               flow_flags_.p + sl.ticket_word);
-            check_launch("k_big_solve_flow");
-            pend(RR_PGO_K_BIG_SOLVE, 2);
-            continue;
-          }
-          // wide pivot blocks: one launch per 128-column super-panel, L11 read by the whole chip
-          const int nsp = (max_nc + BIG_SUPER - 1) / BIG_SUPER;
-          for (int ell = 0; ell < nsp; ell++) {
-            hipLaunchKernelGGL(k_big_solve_sp<T>, dim3(1 + (max_nc + 63) / 64, nf), dim3(1024), 0, stream_, fa, ell, (const T *)gemv_part_.p, (int64_t)g_.dim, R);
-            check_launch("k_big_solve_sp");
-          }
-          pend(RR_PGO_K_BIG_SOLVE, 1 + nsp);
-          continue;
-        }
-        hipLaunchKernelGGL((k_solve_mid<T, 1024>), dim3(nf), dim3(1024), lds, stream_, fa, 1, (const T *)gemv_part_.p, (int64_t)g_.dim, R);
+        hipLaunchKernelGGL((k_solve_mid<T, 1024>), dim3(p.nf), dim3(1024), lds, stream_, a, 1, (const T *)gemv_part_.p, (int64_t)g_.dim, p.R);
         pend(RR_PGO_K_BIG_SOLVE, 2);
       }
     }
@@ -2111,12 +2078,12 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     launch_update(nullptr, 1.0, true, false, true);   // + the reduction of the chi2 / |dx|^2 partials in its last workgroup
   }
 
-  void ensure_gn_graph() {
-    if (gn_exec_) return;
+  // what `body` puts on the stream, as an executable hipGraph
+  template <typename F> hipGraphExec_t capture(F &&body) {
     hipGraph_t graph = nullptr;
     HIPCHK(hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal));
     try {
-      enqueue_gn_iteration();
+      body();
     } catch (...) {
       // a failed launch must not leave the (pooled) stream in capture mode
       (void)hipStreamEndCapture(stream_, &graph);
@@ -2124,9 +2091,23 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
       throw;
     }
     HIPCHK(hipStreamEndCapture(stream_, &graph));
-    const hipError_t ie = hipGraphInstantiate(&gn_exec_, graph, nullptr, nullptr, 0);
+    hipGraphExec_t exec = nullptr;
+    const hipError_t ie = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
     (void)hipGraphDestroy(graph);
-    if (ie != hipSuccess) { gn_exec_ = nullptr; throw ApiError(RR_PGO_ENODEVICE, std::string("hipGraphInstantiate: ") + hipGetErrorString(ie)); }
+    if (ie != hipSuccess) throw ApiError(RR_PGO_ENODEVICE, std::string("hipGraphInstantiate: ") + hipGetErrorString(ie));
+    return exec;
+  }
+  // the captured graphs hold kernels, pointers and arguments of the time of their capture
+  void drop_stage_graphs() {
+    for (hipGraphExec_t &e : stage_exec_) if (e) { (void)hipGraphExecDestroy(e); e = nullptr; }
+  }
+  void drop_graphs() {
+    if (gn_exec_) { (void)hipGraphExecDestroy(gn_exec_); gn_exec_ = nullptr; }
+    drop_stage_graphs();
+  }
+  void ensure_gn_graph() {
+    if (gn_exec_) return;
+    gn_exec_ = capture([&] { enqueue_gn_iteration(); });
     launch_counts[3]++;
   }
 
@@ -2233,7 +2214,6 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
         ensure_gn_graph();
       }
       reset_counter();
-      int done = 0;
       for (int i = 0; i < iters; i++) {
         if (eager) enqueue_gn_iteration();
         else HIPCHK(hipGraphLaunch(gn_exec_, stream_));
@@ -2242,10 +2222,8 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
         read_slot(i, &chi, &nrm);
         errors[ne++] = chi;
         if (norms) norms[i] = nrm;
-        done = i + 1;
         if (nrm < tolerance) break;  // :298-300
       }
-      (void)done;
       errors[ne++] = chi2_now();
     } else {
       double lambda = 0.01;  // :254
@@ -2542,10 +2520,10 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     if (k_flops) *k_flops = kform_flops_;
   }
   void mark_flow_fronts(std::vector<char> &in_flow) override {
-    for (size_t si = 0; si < flow_levels_.size(); si++)
-      if (flow_levels_[si])
+    for (size_t si = 0; si < plan_.size(); si++)
+      if (plan_[si].flow)
         for (int t = sym_.steps[si].task_begin; t < sym_.steps[si].task_end; t++)
-          in_flow[sym_.task_sn[sym_.task_ptr[t]]] = flow_levels_[si]->schur_split ? 1 : 2;   // 2: its Schur tiles are UPDATE tasks too
+          in_flow[sym_.task_sn[sym_.task_ptr[t]]] = plan_[si].flow->schur_split ? 1 : 2;   // 2: its Schur tiles are UPDATE tasks too
   }
   // diagnostic builds: the task list and the stamps of the `level`-th flow level (-1: no such level)
   int flow_trace(int level, std::vector<int32_t> &tasks, std::vector<unsigned long long> &stamps, int *nf, double *est_us) override {
@@ -2554,10 +2532,10 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
       if (level != 0) return -1;
       tasks.resize(xl_host_.size() * 4);
       size_t i = 0;
-      for (size_t si = 0; si < flow_levels_.size(); si++) {
-        if (!flow_levels_[si]) continue;
+      for (size_t si = 0; si < plan_.size(); si++) {
+        if (!plan_[si].flow) continue;
         const Step &st = sym_.steps[si];
-        for (int k2 = 0; k2 < flow_levels_[si]->n_tasks; k2++, i++) {
+        for (int k2 = 0; k2 < plan_[si].flow->n_tasks; k2++, i++) {
           const FlowTask &t = xl_host_[i].t;
           const int sn = sym_.task_sn[sym_.task_ptr[st.task_begin + (t.kind_front & 0xffffff)]];
           tasks[4 * i] = (t.kind_front & ~0xffffff) | sn;
@@ -2571,10 +2549,10 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
       return (int)xl_host_.size();
     }
     int k = 0;
-    for (size_t si = 0; si < flow_levels_.size(); si++) {
-      if (!flow_levels_[si]) continue;
+    for (size_t si = 0; si < plan_.size(); si++) {
+      if (!plan_[si].flow) continue;
       if (k++ != level) continue;
-      FlowLevel &l = *flow_levels_[si];
+      FlowLevel &l = *plan_[si].flow;
       tasks.resize(l.host_tasks.size() * 4);
       if (!l.host_tasks.empty()) std::memcpy(tasks.data(), l.host_tasks.data(), l.host_tasks.size() * sizeof(FlowTask));
       stamps.resize(l.trace.n);
@@ -2601,7 +2579,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   }
   void set_exchange_buffer(int which, void *ptr, int64_t n) override {
     if (!sharded_) throw ApiError(RR_PGO_EINVAL, "handle is not sharded");
-    for (hipGraphExec_t &e : stage_exec_) if (e) { (void)hipGraphExecDestroy(e); e = nullptr; }   // captured pointers
+    drop_stage_graphs();   // captured pointers
     if (which == 0 && n >= xch_n_) xch_ = (T *)ptr;
     else if (which == 1 && n >= 2) scal_ = (double *)ptr;
     else throw ApiError(RR_PGO_EINVAL, "exchange buffer index / size mismatch");
@@ -2649,20 +2627,8 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     if (stg < 0 || stg > 2) throw ApiError(RR_PGO_EINVAL, "stage must be 0, 1 or 2");
     if (stg == 2 || lm || no_graph_) { enqueue_stage(stg, lambda, lm); return; }
     if (!stage_exec_[stg]) {   // Gauss-Newton stages replay a captured graph like the unsharded iteration
-      hipGraph_t graph = nullptr;
       if (stg == 1) gauge_now_ = gauge_ok_;   // what stage 0 (lm == 0) set; the capture must not depend on call order
-      HIPCHK(hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal));
-      try {
-        enqueue_stage(stg, 0.0, 0);
-      } catch (...) {
-        (void)hipStreamEndCapture(stream_, &graph);
-        if (graph) (void)hipGraphDestroy(graph);
-        throw;
-      }
-      HIPCHK(hipStreamEndCapture(stream_, &graph));
-      const hipError_t ie = hipGraphInstantiate(&stage_exec_[stg], graph, nullptr, nullptr, 0);
-      (void)hipGraphDestroy(graph);
-      if (ie != hipSuccess) { stage_exec_[stg] = nullptr; throw ApiError(RR_PGO_ENODEVICE, std::string("hipGraphInstantiate: ") + hipGetErrorString(ie)); }
+      stage_exec_[stg] = capture([&] { enqueue_stage(stg, 0.0, 0); });
     }
     if (stg == 0) gauge_now_ = gauge_ok_;
     HIPCHK(hipGraphLaunch(stage_exec_[stg], stream_));
@@ -2679,11 +2645,6 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     throw_on_flag(*eflag);
   }
 
-  // Test-only failure injection: make ONE hand-off of a dataflow launch never arrive, so that the waits behind it run
-  // into their time bound (RR_PGO_FLOW_TIMEOUT_MS).  mode 1: k_factor_flow -- the root front's last foreign child's flag
-  // is looked for in a word nobody sets; 2: k_solve_flow -- the same for the parent flag of one front; 3: k_big_flow --
-  // the first PANEL task of the first flow level publishes its X blocks in the dead words behind the live flags;
-  // 0: everything back.  The captured graphs hold pointers, not contents: no re-capture.
   // ---- robust kernels (include/rr_pgo.h, rr_pgo_set_robust_kernel)
   void set_robust(int kind, double delta, const int32_t *mask) override {
     std::vector<uint8_t> m;
@@ -2697,8 +2658,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     robust_kind_ = kind;
     robust_delta_ = kind != ROBUST_NONE ? delta : 1.0;
     // the captured graphs hold the old kernel and its arguments
-    if (gn_exec_) { (void)hipGraphExecDestroy(gn_exec_); gn_exec_ = nullptr; }
-    for (hipGraphExec_t &e : stage_exec_) if (e) { (void)hipGraphExecDestroy(e); e = nullptr; }
+    drop_graphs();
     // the edge-parallel experiment forms have no robust instantiation: the pull form runs while a kernel is set
     edge_lin_ = edge_lin_env_ && kind == ROBUST_NONE;
     edge_lin_wave_ = edge_lin_wave_env_ && kind == ROBUST_NONE;
@@ -2805,8 +2765,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     prior_order_.swap(order);
     gauge_now_ = false;   // (set again by the next linearisation that writes a system)
     // the captured graphs hold the old kernel and its arguments
-    if (gn_exec_) { (void)hipGraphExecDestroy(gn_exec_); gn_exec_ = nullptr; }
-    for (hipGraphExec_t &e : stage_exec_) if (e) { (void)hipGraphExecDestroy(e); e = nullptr; }
+    drop_graphs();
   }
   const PriorSet &priors() const override { return priors_; }
   void prior_errors(double *s_out, double *w_out) override {
@@ -3404,6 +3363,11 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     }
   }
 
+  // Test-only failure injection: make ONE hand-off of a dataflow launch never arrive, so that the waits behind it run
+  // into their time bound (RR_PGO_FLOW_TIMEOUT_MS).  mode 1: k_factor_flow -- the root front's last foreign child's flag
+  // is looked for in a word nobody sets; 2: k_solve_flow -- the same for the parent flag of one front; 3: k_big_flow --
+  // the first PANEL task of the first flow level publishes its X blocks in the dead words behind the live flags;
+  // 0: everything back.  The captured graphs hold pointers, not contents: no re-capture.
   void debug_withhold(int mode) override {
     HIPCHK(hipStreamSynchronize(stream_));
     if (mode == 0) {
@@ -3416,7 +3380,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
         withheld_parent_ = -1;
       }
       if (withheld_level_ >= 0) {
-        FlowRec *dst = withheld_level_ == (1 << 30) ? xl_recs_.p : flow_levels_[withheld_level_]->tasks.p;
+        FlowRec *dst = withheld_level_ == (1 << 30) ? xl_recs_.p : plan_[withheld_level_].flow->tasks.p;
         HIPCHK(hipMemcpy(dst + withheld_task_, &withheld_rec_, sizeof(FlowRec), hipMemcpyHostToDevice));
         withheld_level_ = -1;
       }
@@ -3460,9 +3424,9 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
       throw ApiError(RR_PGO_EUNSUPPORTED, "no PANEL task in the cross-level list");
     }
     if (mode == 3) {
-      for (size_t si = 0; si < flow_levels_.size(); si++) {
-        if (!flow_levels_[si]) continue;
-        FlowLevel &l = *flow_levels_[si];
+      for (size_t si = 0; si < plan_.size(); si++) {
+        if (!plan_[si].flow) continue;
+        FlowLevel &l = *plan_[si].flow;
         std::vector<FlowRec> recs((size_t)l.n_tasks);
         HIPCHK(hipMemcpy(recs.data(), l.tasks.p, recs.size() * sizeof(FlowRec), hipMemcpyDeviceToHost));
         for (int t = 0; t < l.n_tasks; t++)
@@ -3718,7 +3682,6 @@ void analyze_handle(rr_pgo &h, const rr_pgo_options *opt_in, double parse_ms) {
         if (leaf < h.g->n_nodes()) cl.push_back({leaf, np_fixed ? so.amalg_np : 16, true});
     Symbolic best;
     double best_crit = -1.0;
-    int best_leaf = 0;
     // the candidates differ in where they STOP dissecting, not in how a set is split: the deepest dissection runs once (its halves on
     // threads of their own) and records its splits, every candidate replays them (symbolic.h, NdSplitTable)
     NdSplitTable splits;
@@ -3754,7 +3717,7 @@ void analyze_handle(rr_pgo &h, const rr_pgo_options *opt_in, double parse_ms) {
         // cross-level launch for its big fronts): the estimate does not see that, the measurement does (torus3D, r05: the
         // candidate with the smallest estimate ran 40 launches per iteration and 2 % slower than r04's tree)
         const double eff = cands[c].est_critical_us * (so.lds_flow && !cands[c].lds_flow ? 1.15 : 1.0);
-        if (best_crit < 0 || eff < best_crit) { best_crit = eff; best_leaf = list[c].leaf; best = std::move(cands[c]); }
+        if (best_crit < 0 || eff < best_crit) { best_crit = eff; best = std::move(cands[c]); }
       }
     };
     if (err.empty()) run(cl);
@@ -3768,7 +3731,6 @@ void analyze_handle(rr_pgo &h, const rr_pgo_options *opt_in, double parse_ms) {
           if (cl[i].leaf != (1 << 30)) cl.push_back({cl[i].leaf, 72, true});
       run(cl);
     }
-    (void)best_leaf;
     if (err.empty()) fresh = std::move(best);
   } else {
     err = analyze(*h.g, so, fresh);
