@@ -230,6 +230,42 @@ int32_t rr_pgo_num_priors(const rr_pgo *h);
  * be NULL.  The counterpart of rr_pgo_edge_errors, which stays edges-only.  EUNSUPPORTED as for rr_pgo_set_priors. */
 int rr_pgo_prior_errors(rr_pgo *h, double *s_out, double *weight_out /* may be NULL */);
 
+/* ---- fixed nodes (build-defined; what g2o's setFixed and GTSAM's constrained keys do) ----
+ * A fixed node is held constant EXACTLY: its dx is exactly zero, its state bits never change, and every covariance and gate
+ * is conditional on it.  (A prior with a huge Omega is a soft constraint: the node still moves by b / Omega, and its
+ * Sigma is Omega^-1, not 0.)  With F the set of fixed nodes, every entry point that linearises builds this system:
+ *   fixed node i in F:   H_ii = I exactly -- no lambda, no 1e7, no prior terms, no edge terms --, b_i = 0;
+ *   an edge with at least one endpoint in F:   its off-diagonal block(s) are exactly zero;
+ *   free node j:   H_jj and b_j are what they are without the set, bit for bit, including the full w A^T Omega A,
+ *                  w A^T Omega e contribution of edges whose other end is fixed (what eliminating dx_i = 0 leaves behind);
+ *   chi2 is unchanged: every edge and every prior counts, fixed-fixed edges included (a constant); priors on a fixed node
+ *                  still count in chi2 and in rr_pgo_prior_errors and add nothing to H or b.
+ * The sparsity pattern of H, the analysis and the factorisation do not change: the factor has the same size, the fixed
+ * columns are unit columns, and the solves give dx_i = 0 there.
+ * rr_pgo_set_fixed REPLACES the whole set; node: [n_fixed] node indices, copied; a node listed twice counts once.
+ * n_fixed == 0 clears the set: the handle then behaves, bit for bit, as one that never had fixed nodes (the same kernels,
+ * the same launch counts), and keep_anchor is forced back to 1.
+ * keep_anchor: as for rr_pgo_set_priors.  The 1e7 term on rr_pgo_anchor_node is applied only while BOTH settings say keep;
+ * if the anchor node itself is fixed its row is the identity row and the term is moot.  With keep_anchor == 0 the fixed set
+ * (plus any priors) must fix the gauge of every connected component: the CALLER'S responsibility; a singular system ends
+ * as RR_PGO_ENOTSPD.
+ * The set holds from the next linearisation on.  Untouched: the state, the Levenberg-Marquardt lambda, the robust
+ * setting, the prior list.  Captured graphs are dropped, as by rr_pgo_set_priors.  On RR_PGO_F32 / RR_PGO_MIXED handles the
+ * gauge transfer is off while the set is non-empty.
+ * rr_pgo_update ignores its dx entries for fixed nodes and does not move them -- the update inside every iteration and
+ * Levenberg-Marquardt's undo included --, fixed nodes add nothing to |dx|, and rr_pgo_linearize_solve writes 0.0 for them.
+ * rr_pgo_set_state still overwrites every node: that is how a fixed node is moved.
+ * rr_pgo_marginals, rr_pgo_covariances, rr_pgo_gate_edges, rr_pgo_gate_joint: Sigma is the covariance conditional on the
+ * fixed nodes, (H_ff)^-1 on the free nodes; every block with a fixed node in it, its own diagonal block included, is
+ * returned as zeros; a gate candidate with a fixed endpoint a gets S = Omega^-1 + B Sigma_bb B^T, one with both S = Omega^-1.
+ * rr_pgo_extend carries the set and keep_anchor; old indices do not change, new nodes are free.
+ * RR_PGO_EINVAL, decided before anything changes, the message names the entry: n_fixed < 0, null node with n_fixed > 0, a
+ * node out of range.  RR_PGO_EUNSUPPORTED (the message says which): sharded handles; handles created under
+ * RR_PGO_EDGE_LINEARIZE=1 or =2. */
+int rr_pgo_set_fixed(rr_pgo *h, int32_t n_fixed, const int32_t *node, int32_t keep_anchor);
+int32_t rr_pgo_num_fixed(const rr_pgo *h);           /* distinct fixed nodes */
+int rr_pgo_get_fixed(const rr_pgo *h, int32_t *out); /* ascending node indices, rr_pgo_num_fixed entries */
+
 /* ---- marginal covariances (build-defined; the reference has none) ----------
  * Blocks of Sigma = H^-1 at the current state (H as rr_pgo_linearize_solve(h, 0, 0) builds it: anchor prior 1e7 included,
  * lambda = 0, robust weights included while a kernel is set; with a prior list, rr_pgo_set_priors, H is the one with the

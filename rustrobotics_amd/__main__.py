@@ -15,6 +15,10 @@
       named any number of times.  With --free-anchor the 1e7 term on the anchor node is dropped and the priors alone fix
       the gauge.  Both apply before --robust and the optimisation; the report prints the priors' share of the final cost
 
+  --fix ID,ID,...  (both modes): hold these g2o vertex ids constant (rr_pgo_set_fixed): they never move, and the
+      covariances and gates printed afterwards are conditional on them.  With --free-anchor the fixed set (plus any
+      priors) fixes the gauge.  Applied before --robust and the optimisation
+
   --marginals FILE  (example mode): after the optimisation, one line per node -- id, d, the upper triangle of its d x d
       covariance block (rr_pgo_marginals; f64 handles whose fronts all live in LDS)
 
@@ -180,6 +184,15 @@ def parse_priors_file(path, index, node_kind):
             meas.extend(vals[:nm])
             info.extend(vals[nm:])
     return node, meas, info
+
+
+def fix_indices(ids, index):
+    """The node indices of the g2o vertex ids of --fix.  `index` maps a vertex id to the node's index.  Needs no device.
+    An unknown vertex is a SystemExit that names it."""
+    missing = [i for i in ids if i not in index]
+    if missing:
+        raise SystemExit(f"--fix: no vertex with id {missing[0]} in the graph")
+    return [index[i] for i in ids]
 
 
 def apply_priors_file(g, path, free_anchor):
@@ -375,7 +388,9 @@ def main(argv=None):
     ap.add_argument("--priors", metavar="FILE", default=None,
                     help="absolute priors, one per line: NODE_ID, measurement, upper triangle of the information")
     ap.add_argument("--free-anchor", action="store_true",
-                    help="with --priors: drop the 1e7 term on the anchor node, the priors alone fix the gauge")
+                    help="with --priors and / or --fix: drop the 1e7 term on the anchor node, they alone fix the gauge")
+    ap.add_argument("--fix", type=_ids_arg, metavar="ID,ID,...", default=None,
+                    help="hold these g2o vertex ids constant: they never move, covariances and gates are conditional on them")
     ap.add_argument("--marginals", metavar="FILE", default=None,
                     help="after the optimisation write every node's covariance block: id, d, upper triangle")
     ap.add_argument("--joint", type=_ids_arg, metavar="ID,ID,...", default=None,
@@ -395,14 +410,16 @@ def main(argv=None):
         ap.error("--accept needs --gate FILE")
     if a.guess and not a.extend:
         ap.error("--guess needs --extend FILE")
-    if a.free_anchor and not a.priors:
-        ap.error("--free-anchor needs --priors FILE")
+    if a.free_anchor and not (a.priors or a.fix):
+        ap.error("--free-anchor needs --priors FILE or --fix ID,ID,...")
     solver = PoseGraphSolver[a.solver]
 
     def new():
         g = PoseGraph.new(a.file, solver, precision=a.precision)
         if a.priors:
             apply_priors_file(g, a.priors, a.free_anchor)
+        if a.fix:
+            g.set_fixed(fix_indices(a.fix, _node_index(g)), keep_anchor=not a.free_anchor)
         if a.robust:
             g.set_robust_kernel(*a.robust)
         return g
@@ -413,6 +430,8 @@ def main(argv=None):
         g = new()
         if a.priors:
             print(f"{g.num_priors} priors from {a.priors}" + (", anchor term dropped" if a.free_anchor else ""))
+        if a.fix:
+            print(f"{g.num_fixed} vertices held fixed" + (", anchor term dropped" if a.free_anchor else ""))
         g.optimize(50 if a.iterations is None else a.iterations, True, a.plot)
         if a.priors:
             print_prior_share(g)

@@ -37,6 +37,7 @@ EXPORTS = (
     "rr_pgo_marginals", "rr_pgo_marginals_times", "rr_pgo_covariances", "rr_pgo_covariances_times",
     "rr_pgo_gate_edges", "rr_pgo_gate_times", "rr_pgo_gate_joint", "rr_pgo_gate_joint_times",
     "rr_pgo_extend", "rr_pgo_extend_times", "rr_pgo_set_priors", "rr_pgo_num_priors", "rr_pgo_prior_errors",
+    "rr_pgo_set_fixed", "rr_pgo_num_fixed", "rr_pgo_get_fixed",
 )
 
 
@@ -151,6 +152,10 @@ def load():
     L.rr_pgo_num_priors.argtypes = [vp]
     L.rr_pgo_num_priors.restype = C.c_int32
     L.rr_pgo_prior_errors.argtypes = [vp, dp, dp]
+    L.rr_pgo_set_fixed.argtypes = [vp, C.c_int32, ip, C.c_int32]
+    L.rr_pgo_num_fixed.argtypes = [vp]
+    L.rr_pgo_num_fixed.restype = C.c_int32
+    L.rr_pgo_get_fixed.argtypes = [vp, ip]
     if L.rr_pgo_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH} speaks ABI version {L.rr_pgo_abi_version()}, this mirror {ABI_VERSION}: rebuild the library")
     _lib = L

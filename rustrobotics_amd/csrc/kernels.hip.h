@@ -198,6 +198,8 @@ template <typename T, typename TC = T> struct LinArgs {
   const typename VecT<TC>::V4 *prior_meas;   // SE(3): 2 per prior, packed like a pose
   const TC *prior_info;                  // SE(3): 21 per prior, row-major upper triangle
   const uint8_t *prior_robust;           // per prior: 1 = robustified while a kernel is set
+  // fixed nodes (rr_pgo_set_fixed; read by every instantiation of k_linearize): per node, 1 = held constant; null = none
+  const uint8_t *fixed;
 };
 template <typename A> __device__ __forceinline__ void opt_reset_in_first_thread(const A &a) {
   if (a.reset_ctrl && blockIdx.x == 0 && threadIdx.x == 0) {
@@ -618,6 +620,20 @@ template <typename A> __device__ __forceinline__ void opt_publish_chi2_in_last_b
 // node's kind from a fixed identity pose, evaluated through the frame of an edge's `to` role (robust scaling of W, J^T W,
 // diagonal block, right-hand side); the lane that evaluates it adds its chi2 term.  The priors of a node are summed in
 // their fixed CSR order by the same lanes and the same group_sum8: no atomics, the same bits in every run.
+// Fixed nodes (rr_pgo_set_fixed): LinArgs::fixed, a byte per node, null while the set is empty.  It is a run-time argument
+// of EVERY instantiation, not a template argument: a handle with a fixed set and its unfixed twin run the same machine
+// code, so a free node's block and b have the twin's bits by construction.  (Two instantiations do not promise that:
+// single-precision SE(3) code is packed and contracted by the compiler per function, and the PR = true kernels round some
+// entries differently from their PR = false twins.)  The flags gate no arithmetic: they are LOADED AHEAD of it (fx_self
+// with the node's pose, fx_other with the incidence record) and USED only behind the stores they overrule: the from-role
+// lane of an edge with a fixed endpoint stores a zero block over the one it computed, and lane 0 of a fixed node's group
+// stores the identity block and b = 0 over its sums.  chi2 is untouched.
+// Keep the loads where they are.  A variant that evaluated a.fixed[node] | a.fixed[inc.y] behind the off-diagonal stores,
+// and a.fixed[node] behind the store of b, gave a wrong b in the mixed SE(3) instantiations (k_linearize<float, double, *, 6>,
+// the ones that spill): component 4 of EVERY free node's b, e.g. 112.46 for 976.79 at node 0 of the 12-pose test graph, with
+// all of H and chi2 right.  Whether the source or the compiler is at fault was not found (profiles/EXPERIMENTS.md, r20);
+// tests/test_fixed_gpu.py::test_assembled_system_is_the_unfixed_one_with_identity_rows compares every entry of H and b with
+// the unfixed twin's in f64, mixed and f32 and is the guard: run it after any edit to this kernel or a change of compiler.
 template <typename TO, typename T, int RK = ROBUST_NONE, int D = 3, bool PR = false>
 __global__ void __launch_bounds__(LIN_THREADS) k_linearize(LinArgs<TO, T> a) {
   using V4 = typename VecT<T>::V4;
@@ -639,8 +655,10 @@ __global__ void __launch_bounds__(LIN_THREADS) k_linearize(LinArgs<TO, T> a) {
 #pragma unroll
   for (int t = 0; t < D; t++) bv[t] = 0;
   int nd = D;
+  bool fx_self = false;   // rr_pgo_set_fixed: this group's node is held constant
   if (node >= 0) {
     if constexpr (D == 3) nd = a.node_dim[node];
+    fx_self = a.fixed && a.fixed[node];
     V4 self[NV];
 #pragma unroll
     for (int v = 0; v < NV; v++) self[v] = a.pose[NV * node + v];
@@ -648,6 +666,7 @@ __global__ void __launch_bounds__(LIN_THREADS) k_linearize(LinArgs<TO, T> a) {
     for (int q = a.inc_ptr[node] + sub; q < q1; q += LIN_GROUP) {
       const int2 inc = a.inc_list[q];
       const int ent = inc.x;
+      const bool fx_other = a.fixed && a.fixed[inc.y];   // rr_pgo_set_fixed: requested with the far pose, used behind the stores
       // sharded runs: an edge contributes to diagonal blocks, right-hand side and chi2 on ONE rank (bit 2, its
       // owner -- the other ranks' copies of a far endpoint are stale); the off-diagonal block of an edge between
       // two shared nodes is written by every rank (bit 3)
@@ -747,6 +766,21 @@ __global__ void __launch_bounds__(LIN_THREADS) k_linearize(LinArgs<TO, T> a) {
 #pragma unroll
               for (int j = 0; j < 6; j++) dst[tr ? j * 6 + i : i * 6 + j] = (TO)row_dot<6, T>(JW[i], &Bm[0][j], 6);
           }
+          // rr_pgo_set_fixed: the block of an edge with a fixed endpoint (this node, or the other one) is overwritten with
+          // zeros -- a second store of the same lane, behind everything the loop does otherwise
+          if (fx_self | fx_other) {
+            if constexpr (D == 3) {
+              TO *dst = a.hvals + (rec.slot >> 1);
+              const int cnt = ((ent >> 1) & 1) ? 6 : 9;   // 3 x 2 (landmark) or 3 x 3
+#pragma unroll
+              for (int t = 0; t < 9; t++)
+                if (t < cnt) dst[t] = (TO)0;
+            } else {
+              TO *dst = a.hvals + (a.e_slot[k] >> 1);
+#pragma unroll
+              for (int t = 0; t < 36; t++) dst[t] = (TO)0;
+            }
+          }
         }
       }
     }
@@ -844,6 +878,19 @@ __global__ void __launch_bounds__(LIN_THREADS) k_linearize(LinArgs<TO, T> a) {
 #pragma unroll
       for (int t = 0; t < D; t++)
         if (t < nd) bo[t] = (TO)(-bv[t]);
+      // rr_pgo_set_fixed: a fixed node's group has walked its incidences and priors as ever (the chi2 terms of its from-role
+      // edges and of its priors count, it owns off-diagonal stores); what it just stored -- edge and prior terms, lambda, the
+      // anchor term -- is overwritten with the identity block and b = 0
+      if (fx_self) {
+#pragma unroll
+        for (int i = 0; i < D; i++)
+#pragma unroll
+          for (int j = 0; j < D; j++)
+            if (i < nd && j < nd) d[i * nd + j] = i == j ? (TO)1 : (TO)0;
+#pragma unroll
+        for (int t = 0; t < D; t++)
+          if (t < nd) bo[t] = (TO)0;
+      }
     }
   }
   double tot = block_sum<double, LIN_THREADS>(chi, red);
@@ -4248,6 +4295,7 @@ template <typename T, typename TC = T> struct UpdArgs {
   const uint8_t *norm_counts;  // sharded runs: per node, 1 = this rank adds the node's |dx|^2 (every node counted once)
   const int *gate;             // non-null: the launch does nothing unless *gate != 0 (Levenberg-Marquardt's undo inside
                                // rr_pgo_optimize: OptCtrl::reject, decided on the device by the launch before this one)
+  const uint8_t *fixed;        // rr_pgo_set_fixed: per node, 1 = held constant (skipped; dx_ref_out gets 0); null = none
   FinArgs fin;
 };
 
@@ -4346,7 +4394,16 @@ __global__ void __launch_bounds__(UPD_THREADS) k_update(UpdArgs<TO, T> a) {
   const FinPre fin_pre = finalize_preload<UPD_THREADS>(a.fin);   // requested ahead of the node work
   const bool failed = a.err && a.err[0] != 0;   // a failed factorisation: the state stays
   if (node >= 0 && !failed) {
-    if constexpr (D == 3) nrm = update_node(a, node);
+    if (a.fixed && a.fixed[node]) {
+      // a fixed node is skipped, not updated with zero (SE(3) renormalises the quaternion): its state bits stay, it adds
+      // nothing to |dx|^2 and the exported step is 0
+      if (a.dx_ref_out) {
+        int nd = D;
+        if constexpr (D == 3) nd = a.node_dim[node];
+        TO *dst = a.dx_ref_out + a.node_offset[node];
+        for (int t = 0; t < nd; t++) dst[t] = (TO)0;
+      }
+    } else if constexpr (D == 3) nrm = update_node(a, node);
     else nrm = update_node_se3(a, node);
   }
   if (a.export_only) return;

@@ -280,6 +280,10 @@ struct EngineBase {
   virtual void set_priors(const PriorSet &ps) = 0;                             // rr_pgo_set_priors (arguments checked)
   virtual const PriorSet &priors() const = 0;
   virtual void prior_errors(double *s_out, double *w_out) = 0;                 // rr_pgo_prior_errors
+  virtual void refuse_fixed(const char *who) const = 0;                        // EUNSUPPORTED where fixed nodes cannot be held
+  virtual void set_fixed(const std::vector<int32_t> &nodes, int keep_anchor) = 0;   // rr_pgo_set_fixed (distinct, ascending, checked)
+  virtual const std::vector<int32_t> &fixed() const = 0;
+  virtual int fixed_keep_anchor() const = 0;
   // rr_pgo_marginals (arguments checked; off: [nq + 1] offsets of the blocks in out) / rr_pgo_marginals_times
   virtual void marginals(int nq, const int32_t *na, const int32_t *nb, const int64_t *off, double *out) = 0;
   // rr_pgo_covariances (arguments checked; off as for marginals) / rr_pgo_covariances_times
@@ -578,6 +582,12 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   DevBuf<V4> prior_meas_;              // SE(3)
   DevBuf<S> prior_info3_;              // SE(3)
   DevBuf<uint8_t> prior_robust_;
+  // fixed nodes (rr_pgo_set_fixed): the distinct nodes in ascending order, and one byte per node on the device (arena;
+  // allocated by the first non-empty set).  While the set is empty k_linearize and k_update get a null pointer.
+  std::vector<int32_t> fixed_nodes_;
+  std::vector<uint8_t> fixed_host_;    // [n_nodes] while the set is non-empty (the queries' plans read it)
+  int fixed_keep_anchor_ = 1;
+  DevBuf<uint8_t> fixed_;
   DevBuf<V4> guess_stage_;           // rr_pgo_extend's initial guess: the old state and the new nodes behind it (made by that call)
   int host_counter_ = 0;             // mirrors the device slot counter
 
@@ -1695,7 +1705,8 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   LinArgs<T, S> lin_args(double lambda, int lm, int write_system, bool reference_prior = false) {
     // Gauss-Newton with a single-precision factor: no anchor prior, the root front carries the gauge term
     // (not with priors: the gauge term assumes that H without the anchor term is singular along the SE(2) gauge)
-    if (write_system) gauge_now_ = gauge_ok_ && !lm && !reference_prior && priors_.n() == 0;
+    // (nor with fixed nodes, rr_pgo_set_fixed: their identity rows are no part of that singular system)
+    if (write_system) gauge_now_ = gauge_ok_ && !lm && !reference_prior && priors_.n() == 0 && fixed_nodes_.empty();
     LinArgs<T, S> a;
     a.n_nodes = n_list_;
     a.node_list = node_list_.p;
@@ -1713,7 +1724,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     a.hvals = hvals_.p;
     a.b = b_.p;
     a.chi2_partial = chi_partial_.p;
-    a.anchor = ((write_system && gauge_now_) || !priors_.keep_anchor) ? -1 : g_.anchor_node;
+    a.anchor = ((write_system && gauge_now_) || !priors_.keep_anchor || !fixed_keep_anchor_) ? -1 : g_.anchor_node;
     a.lambda = lm ? (S)lambda : (S)0;
     a.write_system = write_system;
     a.adds_diag = norm_counts_.p;
@@ -1724,6 +1735,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     opt_lin_fields(a, lm);
     robust_fields(a);
     prior_fields(a);
+    a.fixed = fixed_nodes_.empty() ? nullptr : fixed_.p;   // (every instantiation reads it)
     return a;
   }
   void robust_fields(LinArgs<T, S> &a) const {
@@ -2056,6 +2068,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     u.export_only = export_only ? 1 : 0;
     u.err = dx_ref_in ? nullptr : err_.p;
     u.gate = gate;
+    u.fixed = fixed_nodes_.empty() ? nullptr : fixed_.p;
     u.fin = fin;
     if (is3d_) hipLaunchKernelGGL((k_update<T, S, 6>), dim3(n_upd_blocks_), dim3(UPD_THREADS), 0, stream_, u);
     else hipLaunchKernelGGL((k_update<T, S, 3>), dim3(n_upd_blocks_), dim3(UPD_THREADS), 0, stream_, u);
@@ -2768,6 +2781,32 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     drop_graphs();
   }
   const PriorSet &priors() const override { return priors_; }
+
+  // ---- fixed nodes (include/rr_pgo.h, rr_pgo_set_fixed)
+  void refuse_fixed(const char *who) const override {
+    const std::string w = who;
+    if (sharded_ || world_ > 1) throw ApiError(RR_PGO_EUNSUPPORTED, w + ": sharded handle (the ranks' node lists and diagonal ownership are not taught the fixed nodes)");
+    if (edge_lin_env_) throw ApiError(RR_PGO_EUNSUPPORTED, w + ": handle created under RR_PGO_EDGE_LINEARIZE (the edge-parallel linearisation forms are not taught the fixed nodes)");
+  }
+  void set_fixed(const std::vector<int32_t> &nodes, int keep_anchor) override {   // nodes: distinct, ascending, in range
+    refuse_fixed("rr_pgo_set_fixed");
+    const int N = g_.n_nodes();
+    std::vector<uint8_t> flag((size_t)N, 0);
+    for (int32_t v : nodes) flag[(size_t)v] = 1;
+    HIPCHK(hipStreamSynchronize(stream_));   // launches already enqueued read the old set
+    if (!nodes.empty()) upload_grow(fixed_, flag);
+    else flag.clear();
+    fixed_nodes_ = nodes;
+    fixed_host_.swap(flag);
+    fixed_keep_anchor_ = nodes.empty() ? 1 : (keep_anchor != 0 ? 1 : 0);
+    gauge_now_ = false;   // (set again by the next linearisation that writes a system)
+    // the captured graphs hold the old kernel and its arguments
+    drop_graphs();
+  }
+  const std::vector<int32_t> &fixed() const override { return fixed_nodes_; }
+  int fixed_keep_anchor() const override { return fixed_keep_anchor_; }
+  bool is_fixed(int v) const { return !fixed_host_.empty() && fixed_host_[(size_t)v] != 0; }
+
   void prior_errors(double *s_out, double *w_out) override {
     refuse_priors("rr_pgo_prior_errors");
     const int P = priors_.n();
@@ -2922,7 +2961,9 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
                                                 " (query " + std::to_string(q) + ") share no front of the factor: only pairs joined by an edge are guaranteed");
             const int hi = std::max(li, lj), lo = std::min(li, lj);
             if (lo >= nc) throw ApiError(RR_PGO_ENODEVICE, "rr_pgo_marginals: internal: pair outside its front's panel");
-            src[(size_t)(off[q] + (int64_t)i * db + j)] = sel_soff_[f] + (int64_t)lo * n + hi;
+            // (a block with a fixed node is zero: Sigma is conditional on the fixed nodes; the selected inverse of the identity
+            // rows holds I in the node's own block)
+            src[(size_t)(off[q] + (int64_t)i * db + j)] = is_fixed(va) || is_fixed(vb) ? (int64_t)-1 : sel_soff_[f] + (int64_t)lo * n + hi;
           }
       }
       DevBuf<int64_t> d_src;
@@ -3071,6 +3112,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
         const int v = nodes[k], f = front_of(v), d = node_dim(g_.node_kind[v]), p0 = sym.node_pcol[v];
         TsTask &t = tmp[task_of[f]];
         if (t.n_unit == 0) t.unit_ptr = (int32_t)pl.unit.size();
+        if (is_fixed(v)) continue;   // rr_pgo_set_fixed: the seed of a fixed node is E_s = 0, so Z_s = 0 and its blocks are zero
         for (int i = 0; i < d; i++) pl.unit.push_back(((p0 + i - sym.sn_col0[f]) << 5) | (node_col[v] + i));
         t.n_unit += d;
       }
@@ -3985,6 +4027,7 @@ static void extend_handle(rr_pgo *h, int32_t n_new_nodes, const int32_t *node_ki
     nh->engine->set_robust(rk, rdelta, masked ? mask.data() : nullptr);
   }
   if (h->engine->priors().n() > 0) apply_priors(*nh, h->engine->priors());   // node indices do not change
+  if (!h->engine->fixed().empty()) nh->engine->set_fixed(h->engine->fixed(), h->engine->fixed_keep_anchor());   // new nodes are free
   // ---- the swap: nothing below can fail.  The old engine (its stream drained above, the copy out of its buffers waited for)
   // goes with nh.  Every field changes sides (the engines refer to the pointees of g and symp, which do not move).
   std::swap(*h, *nh);
@@ -4346,6 +4389,33 @@ int rr_pgo_set_priors(rr_pgo *h, int32_t n_priors, const int32_t *node, const do
 }
 
 int32_t rr_pgo_num_priors(const rr_pgo *h) { return h ? h->engine->priors().n() : 0; }
+
+int rr_pgo_set_fixed(rr_pgo *h, int32_t n_fixed, const int32_t *node, int32_t keep_anchor) {
+  if (!h) { g_last_error = "null argument"; return RR_PGO_EINVAL; }
+  if (n_fixed < 0) { g_last_error = "rr_pgo_set_fixed: n_fixed < 0"; return RR_PGO_EINVAL; }
+  if (n_fixed > 0 && !node) { g_last_error = "rr_pgo_set_fixed: null argument (node is required)"; return RR_PGO_EINVAL; }
+  if (const int rc = guarded([&] { h->engine->refuse_fixed("rr_pgo_set_fixed"); })) return rc;
+  const int N = h->g->n_nodes();
+  for (int p = 0; p < n_fixed; p++)
+    if (node[p] < 0 || node[p] >= N) {
+      g_last_error = "rr_pgo_set_fixed: entry " + std::to_string(p) + ": node index " + std::to_string(node[p]) + " out of range";
+      return RR_PGO_EINVAL;
+    }
+  std::vector<int32_t> nodes(node, node + n_fixed);
+  std::sort(nodes.begin(), nodes.end());
+  nodes.erase(std::unique(nodes.begin(), nodes.end()), nodes.end());   // a node listed twice counts once
+  return guarded([&] { h->engine->set_fixed(nodes, keep_anchor); });
+}
+
+int32_t rr_pgo_num_fixed(const rr_pgo *h) { return h ? (int32_t)h->engine->fixed().size() : 0; }
+
+int rr_pgo_get_fixed(const rr_pgo *h, int32_t *out) {
+  if (!h) { g_last_error = "null argument"; return RR_PGO_EINVAL; }
+  const std::vector<int32_t> &f = h->engine->fixed();
+  if (!f.empty() && !out) { g_last_error = "rr_pgo_get_fixed: null argument (out is required)"; return RR_PGO_EINVAL; }
+  if (!f.empty()) std::memcpy(out, f.data(), f.size() * sizeof(int32_t));
+  return RR_PGO_OK;
+}
 
 int rr_pgo_prior_errors(rr_pgo *h, double *s_out, double *weight_out) {
   if (!h || !s_out) { g_last_error = "null argument"; return RR_PGO_EINVAL; }

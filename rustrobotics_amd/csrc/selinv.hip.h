@@ -152,11 +152,12 @@ __global__ void __launch_bounds__(THREADS) k_selinv_level(SelArgs<T> a, int begi
 static_assert(SELINV_GPART == 4, "the sum of the partial products in k_selinv_level is written out for four parts");
 
 // out[t] = svals[src[t]]: the host lists, per output scalar, where it lives (symmetric fill of diagonal blocks and the
-// permutation back to the reference's scalar order within a node are in the list)
+// permutation back to the reference's scalar order within a node are in the list); src < 0: the entry is 0 (a block with a
+// fixed node of rr_pgo_set_fixed: the covariance is conditional on that node)
 template <typename T>
 __global__ void __launch_bounds__(256) k_marg_gather(const T *svals, const int64_t *src, double *out, int64_t count) {
   const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (t < count) out[t] = (double)svals[src[t]];
+  if (t < count) out[t] = src[t] < 0 ? 0.0 : (double)svals[src[t]];
 }
 
 }  // namespace rrpgo

@@ -318,6 +318,29 @@ class PoseGraph:
         _check(_lib.load().rr_pgo_prior_errors(self._h, _dp(s), _dp(w)))
         return s, w
 
+    # -- fixed nodes (include/rr_pgo.h, "fixed nodes") --------------------------------------
+    def set_fixed(self, nodes, keep_anchor=True):
+        """Replace the set of nodes held constant (node indices; a node listed twice counts once).  A fixed node never
+        moves, its dx is 0, and covariances and gates are conditional on it.  keep_anchor False drops the 1e7 anchor
+        term: the fixed set (plus any priors) then fixes the gauge.  Takes effect from the next linearisation on; an
+        empty list clears."""
+        nodes = np.ascontiguousarray(nodes, np.int32).reshape(-1)
+        _check(_lib.load().rr_pgo_set_fixed(self._h, len(nodes), _ip(nodes) if len(nodes) else None, 1 if keep_anchor else 0))
+
+    def clear_fixed(self):
+        """Back to a handle without fixed nodes (the anchor term is kept again)."""
+        _check(_lib.load().rr_pgo_set_fixed(self._h, 0, None, 1))
+
+    @property
+    def num_fixed(self):
+        return _lib.load().rr_pgo_num_fixed(self._h)
+
+    def fixed_nodes(self):
+        """The distinct fixed nodes, ascending."""
+        out = np.zeros(self.num_fixed, np.int32)
+        _check(_lib.load().rr_pgo_get_fixed(self._h, _ip(out) if len(out) else None))
+        return out
+
     # -- marginal covariances (include/rr_pgo.h, "marginal covariances") -----------------
     def marginal_blocks(self, node_a=None, node_b=None):
         """rr_pgo_marginals as it is: (values, offsets) of the queried blocks of Sigma = H^-1 at the current state.
