@@ -22,6 +22,7 @@
 #include <string>
 #include <thread>
 #include <unordered_map>
+#include <utility>
 #include <vector>
 
 #include "../../include/rr_pgo.h"
@@ -489,7 +490,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   static constexpr int kDeadFlagWords = 4096;   // flag words behind the live ones that no consumer ever looks at
   // gauge transfer (single-precision factor, Gauss-Newton; kernels.hip.h "gauge transfer")
   bool gauge_ok_ = false;            // the root front is a big front with an SE2 pivot node
-  bool gauge_now_ = false;           // the system being factored was linearised without the anchor prior
+  bool stage_gauge_ = false;         // sharded handle: the gauge stage 0 linearised in -- written by stage 0 alone, read by stage 1 alone
   int gauge_root_ = -1;              // supernode that takes the rank-3 term
   DevBuf<int32_t> gauge_col_node_;
   DevBuf<T> gauge_v_;
@@ -554,12 +555,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   DevBuf<V4> pose_saved_;            // ... and its device-side copy
   OptSlot *opt_ring_ = nullptr;      // = host_pair_ + 4: host-coherent, written by the device, polled by optimize_pipelined
   DevBuf<OptCtrl> opt_ctrl_;         // the loop state of the running rr_pgo_optimize call (kernels.hip.h, OptCtrl)
-  bool opt_active_ = false;          // launches enqueued now belong to a pipelined rr_pgo_optimize call ...
-  bool opt_first_ = false;           // ... and the next linearisation is the call's first launch: it resets the loop state
-  bool opt_lambda_dev_ = false;      // ... Levenberg-Marquardt: the linearisation reads lambda from the loop state
-  int opt_publish_ = 0;              // ... LinArgs::publish of the next linearisation
-  double opt_lambda0_ = 0.01;
-  bool stop_dirty_ = false;          // the stop word err_[1] may be set: cleared before the next launch outside such a call
+  bool stop_dirty_ = false;          // the stop word err_[1] may be set: cleared before the next launch outside a pipelined rr_pgo_optimize call
   bool sync_optimize_ = false;       // RR_PGO_SYNC_OPTIMIZE=1: rr_pgo_optimize with one host round trip per iteration (the r01 - r05
                                      // form, bit-identical: the parity alternative; always with the edge-parallel linearisation)
   int n_lin_blocks_ = 0, n_upd_blocks_ = 0;
@@ -1702,11 +1698,22 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     HIPCHK(hipFuncSetAttribute((const void *)k_solve_flow<T, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds));
   }
 
-  LinArgs<T, S> lin_args(double lambda, int lm, int write_system, bool reference_prior = false) {
-    // Gauss-Newton with a single-precision factor: no anchor prior, the root front carries the gauge term
-    // (not with priors: the gauge term assumes that H without the anchor term is singular along the SE(2) gauge)
-    // (nor with fixed nodes, rr_pgo_set_fixed: their identity rows are no part of that singular system)
-    if (write_system) gauge_now_ = gauge_ok_ && !lm && !reference_prior && priors_.n() == 0 && fixed_nodes_.empty();
+  // ---- what a launch is told by whoever enqueues it.  One linearisation: chi2 only, or the system too; gauge: without the anchor prior --
+  // the enqueuer hands the SAME value to the factorisation (the root front takes the gauge term) and to the update of the solved step
+  struct Lin { int write_system; bool gauge; int lm; double lambda; };
+  // Gauss-Newton with a single-precision factor: no anchor prior, the root front carries the gauge term
+  // (not with priors: the gauge term assumes that H without the anchor term is singular along the SE(2) gauge)
+  // (nor with fixed nodes, rr_pgo_set_fixed: their identity rows are no part of that singular system)
+  bool gauge_rule(int lm, bool reference_prior = false) const { return gauge_ok_ && !lm && !reference_prior && priors_.n() == 0 && fixed_nodes_.empty(); }
+  static Lin lin_chi2() { return Lin{0, false, 0, 0.0}; }
+  Lin lin_system(double lambda, int lm) const { return Lin{1, gauge_rule(lm), lm, lambda}; }
+  Lin lin_reference_system(double lambda, int lm) const { return Lin{1, gauge_rule(lm, true), lm, lambda}; }   // rr_pgo_assemble: always the anchor prior
+  // ... and what one inside a pipelined rr_pgo_optimize call carries on top (absent: a launch outside such a call).  reset: the call's
+  // first launch, it resets the loop state (lambda to lambda0); publish: LinArgs::publish; lambda_dev: lambda from the loop state
+  struct OptLin { bool reset; double lambda0; int publish; bool lambda_dev; };
+  // a solved step: exported in reference order, the state untouched | applied | + the reduction in k_update's last workgroup | + a pipelined call's decisions
+  enum StepUse { STEP_EXPORT, STEP_APPLY, STEP_APPLY_REDUCE, STEP_APPLY_REDUCE_OPT };
+  LinArgs<T, S> lin_args(const Lin &m, const OptLin *opt) const {
     LinArgs<T, S> a;
     a.n_nodes = n_list_;
     a.node_list = node_list_.p;
@@ -1724,15 +1731,23 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     a.hvals = hvals_.p;
     a.b = b_.p;
     a.chi2_partial = chi_partial_.p;
-    a.anchor = ((write_system && gauge_now_) || !priors_.keep_anchor || !fixed_keep_anchor_) ? -1 : g_.anchor_node;
-    a.lambda = lm ? (S)lambda : (S)0;
-    a.write_system = write_system;
+    a.anchor = ((m.write_system && m.gauge) || !priors_.keep_anchor || !fixed_keep_anchor_) ? -1 : g_.anchor_node;
+    a.lambda = m.lm ? (S)m.lambda : (S)0;
+    a.write_system = m.write_system;
     a.adds_diag = norm_counts_.p;
     a.zero_words = lds_flow_ ? dep_flags_.p : nullptr;
     a.n_zero_words = lds_flow_ ? 2 * sym_.S + 64 : 0;
     a.fill_words = lds_flow_ ? reinterpret_cast<unsigned *>(x_ptr_) : nullptr;
     a.n_fill_words = lds_flow_ ? (int)((size_t)g_.dim * sizeof(T) / 4) : 0;
-    opt_lin_fields(a, lm);
+    a.ctrl = opt ? opt_ctrl_.p : nullptr;
+    a.err = err_.p;
+    a.lambda_from_ctrl = (opt && opt->lambda_dev) ? 1 : 0;
+    a.reset_ctrl = (opt && opt->reset) ? 1 : 0;
+    a.reset_lambda = opt ? opt->lambda0 : 0.01;
+    a.reset_tolerance = 1e-4;   // :253
+    a.publish = opt ? opt->publish : 0;
+    a.ring_host = opt_ring_;
+    a.blocks_done = blocks_done_.p + 1;
     robust_fields(a);
     prior_fields(a);
     a.fixed = fixed_nodes_.empty() ? nullptr : fixed_.p;   // (every instantiation reads it)
@@ -1749,20 +1764,6 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     a.prior_meas = prior_meas_.p;
     a.prior_info = prior_info3_.p;
     a.prior_robust = prior_robust_.p;
-  }
-  // what a linearisation inside a pipelined rr_pgo_optimize call carries: the reset of the loop state (first launch of
-  // the call), lambda from the device (Levenberg-Marquardt)
-  void opt_lin_fields(LinArgs<T, S> &a, int lm) {
-    a.ctrl = opt_active_ ? opt_ctrl_.p : nullptr;
-    a.err = err_.p;
-    a.lambda_from_ctrl = (opt_active_ && opt_lambda_dev_ && lm) ? 1 : 0;
-    a.reset_ctrl = (opt_active_ && opt_first_) ? 1 : 0;
-    a.reset_lambda = opt_lambda0_;
-    a.reset_tolerance = 1e-4;   // :253
-    a.publish = opt_active_ ? opt_publish_ : 0;
-    a.ring_host = opt_ring_;
-    a.blocks_done = blocks_done_.p + 1;
-    opt_first_ = false;
   }
 
   FactorArgs<T> factor_args(int task_begin) {
@@ -1831,33 +1832,31 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     if (e != hipSuccess) throw ApiError(RR_PGO_ENODEVICE, std::string("kernel launch failed (") + what + "): " + hipGetErrorString(e));
   }
 
-  // a pipelined rr_pgo_optimize call may have left its stop word set: every path outside such a call starts here -- the plain
-  // launches in launch_linearize, the replays BEFORE ensure_gn_graph (a replay never passes through launch_linearize, and a
-  // captured graph must hold no memset node, whatever ran before its capture)
+  // a pipelined rr_pgo_optimize call may have left its stop word set: every path outside such a call starts here -- the plain launches
+  // in launch_linearize, the replays in ensure_gn_graph (before the capture: a captured graph must hold no memset node)
   void clear_stop_word() {
-    if (stop_dirty_ && !opt_active_) {
+    if (stop_dirty_) {
       HIPCHK(hipMemsetAsync(err_.p + 1, 0, sizeof(int), stream_));
       stop_dirty_ = false;
     }
   }
 
-  void launch_linearize(double lambda, int lm, int write_system, bool reference_prior = false) {
-    clear_stop_word();
+  void launch_linearize(const Lin &m, const OptLin *opt = nullptr) {
+    if (!opt) clear_stop_word();
     pbegin();
+    const LinArgs<T, S> la = lin_args(m, opt);
     if (!is3d_ && edge_lin_) {
       // the edge-parallel form (experiment knob RR_PGO_EDGE_LINEARIZE): clear + prior, one thread per edge, mirror
-      const LinArgs<T, S> la = lin_args(lambda, lm, write_system, reference_prior);
       const unsigned nb = (unsigned)((g_.n_nodes() + 255) / 256);
       if (lds_flow_) {
         hipLaunchKernelGGL(k_fill_words, dim3(4), dim3(256), 0, stream_, dep_flags_.p, 2 * sym_.S + 64, 0u);
         hipLaunchKernelGGL(k_fill_words, dim3(16), dim3(256), 0, stream_, reinterpret_cast<unsigned *>(x_ptr_), (int)((size_t)g_.dim * sizeof(T) / 4), X_PENDING_WORD);
       }
-      if (write_system) hipLaunchKernelGGL((k_lin_init<T, S>), dim3(nb), dim3(256), 0, stream_, la);
+      if (m.write_system) hipLaunchKernelGGL((k_lin_init<T, S>), dim3(nb), dim3(256), 0, stream_, la);
       if (edge_lin_wave_) hipLaunchKernelGGL((k_linearize_wave_edges<T, S>), dim3(n_lin_blocks_), dim3(256), 0, stream_, la, g_.n_edges());
       else hipLaunchKernelGGL((k_linearize_edges<T, S>), dim3(n_lin_blocks_), dim3(LIN_THREADS), 0, stream_, la, g_.n_edges());
-      if (write_system) hipLaunchKernelGGL((k_lin_finish<T, S>), dim3(nb), dim3(256), 0, stream_, la);
+      if (m.write_system) hipLaunchKernelGGL((k_lin_finish<T, S>), dim3(nb), dim3(256), 0, stream_, la);
     } else {
-      const LinArgs<T, S> la = lin_args(lambda, lm, write_system, reference_prior);
       if (robust_kind_ == ROBUST_HUBER) launch_pull<ROBUST_HUBER>(la);
       else if (robust_kind_ == ROBUST_CAUCHY) launch_pull<ROBUST_CAUCHY>(la);
       else launch_pull<ROBUST_NONE>(la);
@@ -1875,8 +1874,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     else hipLaunchKernelGGL((k_linearize<T, S, RK, 3>), dim3(n_lin_blocks_), dim3(LIN_THREADS), 0, stream_, la);
   }
 
-  void launch_factor() { launch_factor_range(0, sym_.steps.size()); }
-  void launch_factor_range(size_t from, size_t to) {
+  void launch_factor_range(size_t from, size_t to, bool gauge) {
     // tickets and completion flags of the flow levels (one small kernel per factorisation; flow.hip.h, k_flow_reset)
     if (any_flow(from, to)) {
       // ... and the "not there yet" marks of the W blocks of the range's flow fronts
@@ -1918,7 +1916,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
         });
         pend(RR_PGO_K_FACTOR);
       } else {
-        launch_big_level(p);
+        launch_big_level(p, gauge);
         pend(RR_PGO_K_BIGFRONT);
       }
     }
@@ -1932,7 +1930,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   // (The r01 / r02 alternatives -- right-looking K = 32 steps, whole super-panels per chain step, the two-stream far
   // update, zero + extend-add assembly, the one-workgroup panel class -- were measured slower and removed in r03:
   // profiles/EXPERIMENTS.md.)  Every launch here has its term in factor_launches.
-  void launch_big_level(const StepPlan &p) {
+  void launch_big_level(const StepPlan &p, bool gauge) {
     const FactorArgs<T> a = factor_args(p.task_begin);
     hipLaunchKernelGGL(k_big_build<T>, dim3((unsigned)p.build_gx, p.nf), dim3(256), 0, stream_, a, gather_update_ ? 1 : 0, p.asm_gx > 0 ? 0 : 1);
     check_launch("k_big_build");
@@ -1941,7 +1939,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
       check_launch("k_big_assemble");
     }
     if (p.any_dup) hipLaunchKernelGGL(k_big_assemble_dup<T>, dim3(1, p.nf), dim3(64), 0, stream_, a);
-    if (p.has_root && gauge_now_) launch_gauge_term();
+    if (p.has_root && gauge) launch_gauge_term();
     pend(RR_PGO_K_BIGFRONT);   // closes the build / assemble segment
     if (p.flow) {
       // the whole panel chain and every trailing update of the level: ONE launch of ticket-ordered tasks
@@ -2043,13 +2041,19 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     }
   }
 
-  void launch_update(const T *dx_ref_in, double sign, bool write_ref, bool export_only = false, bool fused_finalize = false, const int *gate = nullptr) {
+  // k_update: launch_step  the solved step -> reference order (dx_ref_) and, unless STEP_EXPORT, onto the state; gauge: Lin::gauge of its system
+  //           launch_dx    sign * dx_ref_ onto the state: a caller's step, Levenberg-Marquardt's undo (never the anchor gauge); gate: only where that device word says so
+  void launch_step(bool gauge, StepUse use) {
     FinArgs fin{};
-    if (fused_finalize) {
+    if (use >= STEP_APPLY_REDUCE) {
       fin.enabled = 1; fin.chi_partial = chi_partial_.p; fin.n_chi = n_lin_blocks_; fin.hist = hist_.p; fin.counter = counter_.p;
       fin.advance = 1; fin.ring = HIST; fin.blocks_done = blocks_done_.p;
-      if (opt_active_) { fin.ctrl = opt_ctrl_.p; fin.ring_host = opt_ring_; fin.err = err_.p; }
+      if (use == STEP_APPLY_REDUCE_OPT) { fin.ctrl = opt_ctrl_.p; fin.ring_host = opt_ring_; fin.err = err_.p; }
     }
+    launch_update(nullptr, 1.0, gauge, use == STEP_EXPORT, nullptr, fin);
+  }
+  void launch_dx(double sign, const int *gate = nullptr) { launch_update(dx_ref_.p, sign, false, false, gate, FinArgs{}); }
+  void launch_update(const T *dx_ref_in, double sign, bool gauge, bool export_only, const int *gate, const FinArgs &fin) {
     pbegin();
     UpdArgs<T, S> u;
     u.n_nodes = n_list_;
@@ -2061,10 +2065,10 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     u.node_offset = node_offset_.p;
     u.x = x_ptr_;
     u.dx_ref_in = dx_ref_in;
-    u.dx_ref_out = write_ref ? dx_ref_.p : nullptr;
+    u.dx_ref_out = dx_ref_in ? nullptr : dx_ref_.p;
     u.sign = (S)sign;
     u.norm_partial = norm_partial_.p;
-    u.gauge_anchor = (!is3d_ && !dx_ref_in && gauge_now_) ? g_.anchor_node : -1;
+    u.gauge_anchor = (!is3d_ && !dx_ref_in && gauge) ? g_.anchor_node : -1;
     u.export_only = export_only ? 1 : 0;
     u.err = dx_ref_in ? nullptr : err_.p;
     u.gate = gate;
@@ -2076,19 +2080,22 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     pend(RR_PGO_K_UPDATE);
   }
 
-  void launch_finalize(bool chi, bool norm, bool advance) {
+  enum Partials { CHI2_PARTIALS, NORM_PARTIALS };
+  void launch_finalize(Partials which) {   // the sum of the chi2 or of the |dx|^2 partials -> the current slot
     pbegin();
-    hipLaunchKernelGGL(k_finalize_slot, dim3(1), dim3(256), 0, stream_, chi_partial_.p, chi ? n_lin_blocks_ : 0,
-                       norm_partial_.p, norm ? n_upd_blocks_ : 0, hist_.p, counter_.p, advance ? 1 : 0);
+    hipLaunchKernelGGL(k_finalize_slot, dim3(1), dim3(256), 0, stream_, chi_partial_.p, which == CHI2_PARTIALS ? n_lin_blocks_ : 0,
+                       norm_partial_.p, which == NORM_PARTIALS ? n_upd_blocks_ : 0, hist_.p, counter_.p, 0);
     pend(RR_PGO_K_REDUCE);
   }
 
+  // linearise and factor (what the factor queries need), and the back substitution behind them: the system of `m`, in its gauge
+  void enqueue_factor(const Lin &m, const OptLin *opt = nullptr) { launch_linearize(m, opt); launch_factor_range(0, sym_.steps.size(), m.gauge); }
+  void enqueue_solve(const Lin &m, const OptLin *opt = nullptr) { enqueue_factor(m, opt); launch_solve(); }
   // one Gauss-Newton iteration: chi2(state) -> slot.chi, |dx| -> slot.norm, slot++
-  void enqueue_gn_iteration() {
-    launch_linearize(0.0, 0, 1);
-    launch_factor();
-    launch_solve();
-    launch_update(nullptr, 1.0, true, false, true);   // + the reduction of the chi2 / |dx|^2 partials in its last workgroup
+  void enqueue_gn_iteration(const OptLin *opt = nullptr) {
+    const Lin m = lin_system(0.0, 0);
+    enqueue_solve(m, opt);
+    launch_step(m.gauge, opt ? STEP_APPLY_REDUCE_OPT : STEP_APPLY_REDUCE);   // + the reduction of the chi2 / |dx|^2 partials in its last workgroup
   }
 
   // what `body` puts on the stream, as an executable hipGraph
@@ -2119,6 +2126,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     drop_stage_graphs();
   }
   void ensure_gn_graph() {
+    clear_stop_word();   // before the capture and before every replay: the graph holds no memset, and its replays pass no launch_linearize
     if (gn_exec_) return;
     gn_exec_ = capture([&] { enqueue_gn_iteration(); });
     launch_counts[3]++;
@@ -2160,8 +2168,8 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
 
   double chi2_now() {
     reset_counter();
-    launch_linearize(0.0, 0, 0);
-    launch_finalize(true, false, false);
+    launch_linearize(lin_chi2());
+    launch_finalize(CHI2_PARTIALS);
     double c = 0;
     read_slot(0, &c, nullptr);
     return c;
@@ -2180,10 +2188,9 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
 
   void linearize_solve(double lambda, int lm, double *dx_out) override {
     if (sharded_) throw ApiError(RR_PGO_EUNSUPPORTED, "sharded handle: drive it with rr_pgo_stage + the two collectives");
-    launch_linearize(lambda, lm, 1);
-    launch_factor();
-    launch_solve();
-    launch_update(nullptr, 1.0, true, true);   // permuted solution -> reference order (and the anchor gauge), state untouched
+    const Lin m = lin_system(lambda, lm);
+    enqueue_solve(m);
+    launch_step(m.gauge, STEP_EXPORT);   // permuted solution -> reference order (and the anchor gauge), state untouched
     std::vector<T> tmp((size_t)g_.dim);
     HIPCHK(hipMemcpyAsync(tmp.data(), dx_ref_.p, tmp.size() * sizeof(T), hipMemcpyDeviceToHost, stream_));
     HIPCHK(hipStreamSynchronize(stream_));
@@ -2196,7 +2203,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     std::vector<T> tmp((size_t)g_.dim);
     for (int i = 0; i < g_.dim; i++) tmp[i] = (T)dx[i];
     HIPCHK(hipMemcpyAsync(dx_ref_.p, tmp.data(), tmp.size() * sizeof(T), hipMemcpyHostToDevice, stream_));
-    launch_update(dx_ref_.p, sign, false);
+    launch_dx(sign);
     HIPCHK(hipStreamSynchronize(stream_));
   }
 
@@ -2222,10 +2229,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
       // (optimize() reads two scalars back after every iteration, so the enqueueing is not hidden behind the device as it is
       // in iterate_async: dozens of launches stay one graph launch here.)  RR_PGO_FORCE_GRAPH=1: always the graph.
       const bool eager = (no_graph_ || n_launches_per_iter <= 8) && !gn_exec_ && !force_graph_;
-      if (!eager) {
-        clear_stop_word();   // before the capture: the graph holds no memset, and its replays pass no launch_linearize
-        ensure_gn_graph();
-      }
+      if (!eager) ensure_gn_graph();
       reset_counter();
       for (int i = 0; i < iters; i++) {
         if (eager) enqueue_gn_iteration();
@@ -2245,17 +2249,16 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
       for (int i = 0; i < iters; i++) {
         reset_counter();
         launch_counts[0]++;
-        launch_linearize(lambda, 1, 1);
-        launch_factor();
-        launch_solve();
-        launch_update(nullptr, 1.0, true);
-        launch_finalize(false, true, false);
-        launch_linearize(0.0, 0, 0);
-        launch_finalize(true, false, false);
+        const Lin m = lin_system(lambda, 1);
+        enqueue_solve(m);
+        launch_step(m.gauge, STEP_APPLY);
+        launch_finalize(NORM_PARTIALS);
+        launch_linearize(lin_chi2());
+        launch_finalize(CHI2_PARTIALS);
         double error, nrm;
         read_slot(0, &error, &nrm);
         if (last_error < error) {  // :276-281
-          launch_update(dx_ref_.p, -1.0, false);
+          launch_dx(-1.0);
           lambda *= 2.0;
         } else {
           lambda /= 2.0;
@@ -2283,38 +2286,35 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   //   Levenberg-Marquardt   item 0: the initial error (:255); item k: iteration k - 1 = step, chi2, decision, gated undo
   // The host keeps ONE item queued behind the one that is running (enqueueing an item takes a fraction of its run time), polls
   // the ring, and stops enqueueing when it sees the stop: optimize(100) that stops after 6 iterations pays one skipped item.
-  void enqueue_opt_item(bool lm, long k, int iters) {
+  // the running call, owned by optimize_pipelined; reset_due: no launch of it has been enqueued yet, the first one resets the loop state
+  struct OptCall { bool lm; double lambda0; bool reset_due; };
+  void enqueue_opt_item(OptCall &call, long k, int iters) {
+    const bool reset = std::exchange(call.reset_due, false);   // for the item's first launch; every linearisation is also told what it publishes and where its lambda comes from
     OptItemArgs oi{};
     oi.chi_partial = chi_partial_.p; oi.norm_partial = norm_partial_.p; oi.n_chi = n_lin_blocks_; oi.n_norm = 0; oi.mode = 0;
     oi.ctrl = opt_ctrl_.p; oi.ring = opt_ring_; oi.err = err_.p;
-    struct Pub { int &p; ~Pub() { p = 0; } } pub{opt_publish_};
     launch_counts[2]++;
-    if (!lm) {
+    if (!call.lm) {
       // an iteration: its linearisation publishes only when the stop word is set (then the rest of the item is empty
       // launches); the item behind the last iteration: chi2 only, published by the linearisation's last workgroup
-      opt_publish_ = k < iters ? 1 : 2;
-      if (k < iters) enqueue_gn_iteration();
-      else launch_linearize(0.0, 0, 0);
+      const OptLin o{reset, call.lambda0, k < iters ? 1 : 2, false};
+      if (k < iters) enqueue_gn_iteration(&o);
+      else launch_linearize(lin_chi2(), &o);
       return;
     }
-    if (k == 0) {
-      launch_linearize(0.0, 0, 0);
-      hipLaunchKernelGGL(k_opt_item, dim3(1), dim3(256), 0, stream_, oi);
-      check_launch("k_opt_item");
-      return;
+    if (k > 0) {
+      // (as Gauss-Newton's: behind the stop this linearisation publishes the skipped item, every launch behind it returns at its stop word)
+      const Lin m = lin_system(0.0, 1);
+      const OptLin o{reset, call.lambda0, 1, true};   // lambda: OptCtrl::lambda
+      enqueue_solve(m, &o);
+      launch_step(m.gauge, STEP_APPLY);
+      oi.n_norm = n_upd_blocks_; oi.mode = 1;
     }
-    // (as Gauss-Newton's: behind the stop this linearisation publishes the skipped item, every launch behind it returns at its stop word)
-    opt_publish_ = 1;
-    launch_linearize(0.0, 1, 1);   // lambda: OptCtrl::lambda
-    opt_publish_ = 0;
-    launch_factor();
-    launch_solve();
-    launch_update(nullptr, 1.0, true);
-    launch_linearize(0.0, 0, 0);
-    oi.n_norm = n_upd_blocks_; oi.mode = 1;
+    const OptLin chi_only{k == 0 && reset, call.lambda0, 0, false};   // (k_opt_item publishes)
+    launch_linearize(lin_chi2(), &chi_only);
     hipLaunchKernelGGL(k_opt_item, dim3(1), dim3(256), 0, stream_, oi);
     check_launch("k_opt_item");
-    launch_update(dx_ref_.p, -1.0, false, false, false, &opt_ctrl_.p->reject);   // :277, when the device decided so
+    if (k > 0) launch_dx(-1.0, &opt_ctrl_.p->reject);   // :277, when the device decided so
   }
   // the slot of item `idx` (0-based); false: the stream went idle or failed without publishing it
   bool wait_opt_slot(long idx, OptSlot *out) {
@@ -2342,16 +2342,16 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     const bool lm = solver != RR_PGO_GAUSS_NEWTON;
     const long total = (long)iters + 1;
     for (int i = 0; i < OPT_RING; i++) opt_ring_[i].seq = 0ull;   // (nothing of an earlier call is in flight: every call consumes what it enqueued)
-    struct Scope {   // whatever happens, the launches behind this call are plain ones again and know about the stop word
+    struct Scope {   // whatever happens, the launches behind this call know about the stop word
       Engine *e;
       bool done = false;
       ~Scope() {
-        e->opt_active_ = false; e->opt_first_ = false; e->stop_dirty_ = true;
+        e->stop_dirty_ = true;
         // left by an exception (a failed launch, a lost item): what is still enqueued must not publish into the next call's ring
         if (!done) (void)hipStreamSynchronize(e->stream_);
       }
     } scope{this};
-    opt_active_ = true; opt_first_ = true; opt_lambda_dev_ = lm; opt_lambda0_ = 0.01;   // :254
+    OptCall call{lm, 0.01, true};   // :254
     // TWO whole items in the queue: the device never waits for the host.  The item behind the stop is its linearisation (which
     // publishes the final chi2: the call returns on that) and a handful of launches that read the stop word and nothing else
     //  -- they are still on the stream when the call returns, and whatever is enqueued next runs behind them
@@ -2359,7 +2359,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     int ne = 0, dev_err = 0;
     bool stop_seen = false;
     while (true) {
-      while (enq < total && enq < seen + 2 && !stop_seen) enqueue_opt_item(lm, enq++, iters);
+      while (enq < total && enq < seen + 2 && !stop_seen) enqueue_opt_item(call, enq++, iters);
       if (seen >= enq) break;
       OptSlot sl;
       if (!wait_opt_slot(seen, &sl)) {
@@ -2495,7 +2495,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
 
   void assemble(double lambda, int lm, std::vector<double> &hv, std::vector<double> &b) override {
     refuse_rank_partial("rr_pgo_assemble");
-    launch_linearize(lambda, lm, 1, true);   // always the reference's system (anchor prior), whatever the factor's gauge
+    launch_linearize(lin_reference_system(lambda, lm));   // always the reference's system (anchor prior), whatever the factor's gauge
     std::vector<T> th((size_t)sym_.n_hvals), tb((size_t)g_.dim);
     HIPCHK(hipMemcpyAsync(th.data(), hvals_.p, th.size() * sizeof(T), hipMemcpyDeviceToHost, stream_));
     HIPCHK(hipMemcpyAsync(tb.data(), b_.p, tb.size() * sizeof(T), hipMemcpyDeviceToHost, stream_));
@@ -2516,7 +2516,6 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
       for (int i = 0; i < iters; i++) { enqueue_gn_iteration(); launch_counts[0]++; }
       return;
     }
-    clear_stop_word();   // before the capture: the graph holds no memset, and its replays pass no launch_linearize
     ensure_gn_graph();
     for (int i = 0; i < iters; i++) { HIPCHK(hipGraphLaunch(gn_exec_, stream_)); launch_counts[1]++; }
   }
@@ -2597,16 +2596,16 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     else if (which == 1 && n >= 2) scal_ = (double *)ptr;
     else throw ApiError(RR_PGO_EINVAL, "exchange buffer index / size mismatch");
   }
-  void enqueue_stage(int stg, double lambda, int lm) {
+  void enqueue_stage(int stg, double lambda, int lm, bool gauge) {   // gauge: Lin::gauge of the pair's system (stage 2: unused)
     const size_t n_local = world_ > 1 ? (size_t)sym_.n_local_steps : sym_.steps.size();
     if (stg == 0) {
       // linearise this rank's nodes (own + shared top separators), factor its own subtrees, publish the
       // boundary fronts' update matrices in this rank's chunk of buffer 0
-      launch_linearize(lambda, lm, 1);
+      launch_linearize(Lin{1, gauge, lm, lambda});
       if (n_shared_ > 0)   // this rank's partial sums of the shared nodes' diagonal blocks and rhs, behind its update matrices
         hipLaunchKernelGGL(k_pack_shared<T>, dim3((n_shared_ + 255) / 256), dim3(256), 0, stream_, shared_src_.p, n_shared_,
                            (const T *)hvals_.p, (const T *)b_.p, xch_ + (int64_t)rank_ * sym_.xch_chunk + sym_.xch_shared_off);
-      launch_factor_range(0, n_local);
+      launch_factor_range(0, n_local, gauge);
       if (n_pack_ > 0) {
         hipLaunchKernelGGL(k_pack_boundary<T>, dim3(std::min(pack_max_nu_, 1024), n_pack_), dim3(256), 0, stream_,
                            factor_args(0), pack_list_.p);
@@ -2623,14 +2622,14 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
                            (const T *)xch_, sym_.xch_chunk, sym_.xch_shared_off, world_);
       if (world_ > 1)
         hipLaunchKernelGGL(k_merge_err<T>, dim3(1), dim3(64), 0, stream_, err_.p, (const T *)xch_, sym_.xch_chunk, sym_.xch_flag_off, world_);
-      launch_factor_range(n_local, sym_.steps.size());
+      launch_factor_range(n_local, sym_.steps.size(), gauge);
       launch_solve();
-      launch_update(nullptr, 1.0, true);
+      launch_step(gauge, STEP_APPLY);
       hipLaunchKernelGGL(k_finalize_partial, dim3(1), dim3(256), 0, stream_, chi_partial_.p, n_lin_blocks_, norm_partial_.p,
                          n_upd_blocks_, scal_);
     } else {
       // chi2 of the current state only (the last entry of optimize()'s error list): partial sum -> buffer 1
-      launch_linearize(0.0, 0, 0);
+      launch_linearize(lin_chi2());
       hipLaunchKernelGGL(k_finalize_partial, dim3(1), dim3(256), 0, stream_, chi_partial_.p, n_lin_blocks_, norm_partial_.p, 0, scal_);
     }
     check_launch("stage");
@@ -2638,12 +2637,12 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   void stage(int stg, double lambda, int lm) override {
     if (!sharded_) throw ApiError(RR_PGO_EINVAL, "handle is not sharded");
     if (stg < 0 || stg > 2) throw ApiError(RR_PGO_EINVAL, "stage must be 0, 1 or 2");
-    if (stg == 2 || lm || no_graph_) { enqueue_stage(stg, lambda, lm); return; }
-    if (!stage_exec_[stg]) {   // Gauss-Newton stages replay a captured graph like the unsharded iteration
-      if (stg == 1) gauge_now_ = gauge_ok_;   // what stage 0 (lm == 0) set; the capture must not depend on call order
-      stage_exec_[stg] = capture([&] { enqueue_stage(stg, 0.0, 0); });
-    }
-    if (stg == 0) gauge_now_ = gauge_ok_;
+    // stage 1 factors the top fronts in the gauge stage 0 linearised in, whatever lm it is given; the captured graphs hold the
+    // Gauss-Newton gauge, so a stage 1 behind a Levenberg-Marquardt stage 0 that differs in it is plain launches
+    if (stg == 0) stage_gauge_ = gauge_rule(lm);
+    if (stg == 2 || lm || no_graph_ || stage_gauge_ != gauge_rule(0)) { enqueue_stage(stg, lambda, lm, stage_gauge_); return; }
+    if (!stage_exec_[stg])   // Gauss-Newton stages replay a captured graph like the unsharded iteration
+      stage_exec_[stg] = capture([&] { enqueue_stage(stg, 0.0, 0, gauge_rule(0)); });
     HIPCHK(hipGraphLaunch(stage_exec_[stg], stream_));
   }
   // (chi2, |dx|) of the last stage-1 / stage-2 call, valid once the caller has all-reduced buffer 1
@@ -2776,7 +2775,6 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     priors_ = ps;
     if (P == 0) priors_.keep_anchor = 1;
     prior_order_.swap(order);
-    gauge_now_ = false;   // (set again by the next linearisation that writes a system)
     // the captured graphs hold the old kernel and its arguments
     drop_graphs();
   }
@@ -2799,7 +2797,6 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     fixed_nodes_ = nodes;
     fixed_host_.swap(flag);
     fixed_keep_anchor_ = nodes.empty() ? 1 : (keep_anchor != 0 ? 1 : 0);
-    gauge_now_ = false;   // (set again by the next linearisation that writes a system)
     // the captured graphs hold the old kernel and its arguments
     drop_graphs();
   }
@@ -2972,8 +2969,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
       d_out.alloc((size_t)n_vals);
       HIPCHK(hipMemcpyAsync(d_src.p, src.data(), src.size() * sizeof(int64_t), hipMemcpyHostToDevice, stream_));
       HIPCHK(hipEventRecord(query_ev_[0], stream_));
-      launch_linearize(0.0, 0, 1);
-      launch_factor();
+      enqueue_factor(lin_system(0.0, 0));
       HIPCHK(hipEventRecord(query_ev_[1], stream_));
       SelArgs<T> a;
       a.meta = sel_meta_.p;
@@ -3207,8 +3203,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     if (n == 0) return;
     auto first_of = [&](int u) { return cuts ? (int)cuts[u] : u; };   // the first pair of part u (no table: a part is a pair)
     HIPCHK(hipEventRecord(query_ev_[0], stream_));
-    launch_linearize(0.0, 0, 1);
-    launch_factor();
+    enqueue_factor(lin_system(0.0, 0));
     HIPCHK(hipEventRecord(query_ev_[1], stream_));
     bool first = true;   // the factorisation of this call has not been waited for yet
     std::vector<std::pair<int, int>> todo{{0, cuts ? n_parts : n}};   // ranges of parts still to run, the next one last

@@ -98,8 +98,11 @@ def queries():
 
 
 def shards():
-    for label, arrays in (("lattice 40x25", synthetic_grid_arrays(40, 25)), ("parking-garage", PoseGraph.new(path("parking-garage")).graph_arrays())):
-        sh, coll = sharding.emulate(arrays, 2, "f64")
+    # (the 60 x 40 lattice in f32: a single-precision factor with a big root front, the stages with the gauge transfer on)
+    for label, arrays, precision in (("lattice 40x25", synthetic_grid_arrays(40, 25), "f64"),
+                                     ("parking-garage", PoseGraph.new(path("parking-garage")).graph_arrays(), "f64"),
+                                     ("lattice 60x40 f32", synthetic_grid_arrays(60, 40), "f32")):
+        sh, coll = sharding.emulate(arrays, 2, precision)
         e, n = sharding.gauss_newton(sh, 5, coll)
         out("two ranks, " + label, np.array(e), np.array(n), np.array(sharding.gather_state(sh)))
 

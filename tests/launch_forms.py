@@ -174,7 +174,8 @@ def s3(h, s0):
 
 
 def s4(h, s0):
-    """replay on the converged state, and entry points that set the host's view of the gauge between two replays"""
+    """replay on the converged state, and entry points that linearise in a gauge of their own (chi2 only; the reference's
+    system with lambda) or in the iteration's between two replays"""
     h.set_state(s0)
     e, n = h.optimize(CAP)
     h.iterate(2)
@@ -183,5 +184,25 @@ def s4(h, s0):
     t.append(("dx", h.linearize_and_solve()))
     t.append(("chi2 between", h.global_error()))
     t += [("assemble %d" % i, x) for i, x in enumerate(h.assemble(0.37, True))]
+    h.iterate(1)
+    return t + [("state", h.state()), ("chi2", h.global_error())]
+
+
+def s7(h, s0):
+    """entry points whose system is linearised, factored and updated in another gauge than the iteration's, between iterations:
+    the Levenberg-Marquardt form of linearize_and_solve (the gauge transfer is off for that system alone), a caller's step under
+    both signs (never the anchor gauge), the Gauss-Newton form.  Every sequence of launches is told its gauge by whoever enqueues
+    it, so none of them may change what the next one computes."""
+    h.set_state(s0)
+    e, n = h.optimize(CAP)
+    h.iterate(1)
+    t = [("errors", e), ("norms", n), ("state after 1", h.state())]
+    dx = h.linearize_and_solve(0.37, True)
+    t.append(("dx lm", dx))
+    h.update_nodes(dx, 1.0)
+    t.append(("state +dx", h.state()))
+    h.update_nodes(dx, -1.0)
+    t.append(("state -dx", h.state()))
+    t.append(("dx", h.linearize_and_solve()))
     h.iterate(1)
     return t + [("state", h.state()), ("chi2", h.global_error())]

@@ -4,7 +4,7 @@ DESIGN.md promises one answer from the device-side loop of rr_pgo_optimize, its 
 with replays of the captured hipGraph (what rr_pgo_optimize IS on handles of >= 48 launches per iteration), and
 rr_pgo_iterate_async with plain launches or with replays.  Here each of them is run through sequences in which a call
 leaves something behind for the next one -- the stop word of a call that ended by the stop rule or by a failed
-factorisation, a graph captured before or behind such a call, the host's view of the gauge -- and compared, bit for bit,
+factorisation, a graph captured before or behind such a call, a system linearised in another gauge -- and compared, bit for bit,
 with a handle on which nothing but the state is carried from call to call: the host loop with plain launches
 (launch_forms.py, form "ref").  That handle itself is held against the CPU oracle once per graph.
 
@@ -144,9 +144,73 @@ def test_graph_captured_behind_a_stop_is_the_graph_captured_before_it(api, graph
 @pytest.mark.parametrize("graph,precision,form", CASE_FORMS)
 def test_replays_on_the_converged_state_around_other_entry_points(api, graph, precision, form, monkeypatch):
     """S4: optimize(50) and iterate_async(2) with no restart in between, then linearize_and_solve(), global_error() and
-    assemble(0.37, True) -- each sets the host's view of the gauge the last system was linearised in -- between two further
+    assemble(0.37, True) -- each linearises in a gauge of its own, handed to its launches and to no other -- between two further
     iterate_async(1).  A replay holds its own arguments and must not care."""
     _run(api, lf.s4, graph, precision, form, "GaussNewton", monkeypatch)
+
+
+# S7: both single-precision cases (the gauge transfer exists only with a single-precision factor; of these only the lattice
+# has the big root front that takes it: test_the_f32_lattice_exercises_the_gauge_transfer), and the two forms of fp64 handle
+S7_CASES = [("se2", "f64"), ("se2", "f32"), ("lattice", "f32"), ("lattice-levels", "f64")]
+
+
+@pytest.mark.parametrize("solver", ["GaussNewton", "LevenbergMarquardt"])
+@pytest.mark.parametrize("graph,precision,form", [pytest.param(g, p, f, id="%s-%s-%s" % (g, p, f)) for g, p in S7_CASES for f in _forms(g)])
+def test_systems_in_another_gauge_between_iterations(api, graph, precision, form, solver, monkeypatch):
+    """S7: optimize(50), iterate_async(1), then linearize_and_solve(0.37, True) -- the Levenberg-Marquardt form: no gauge
+    transfer for this system, in its linearisation, its factorisation and its update alike -- update_nodes(dx, 1.0) and
+    update_nodes(dx, -1.0) -- a caller's step never gets the anchor gauge -- linearize_and_solve() and iterate_async(1): both
+    dx, the state after each update, the final state and chi2, under both solvers."""
+    _run(api, lf.s7, graph, precision, form, solver, monkeypatch)
+
+
+def test_the_f32_lattice_exercises_the_gauge_transfer(api, monkeypatch):
+    """The precondition of the ("lattice", "f32") cases: on this lattice the gauge transfer is really on -- the first
+    linearize_and_solve() of a handle created under RR_PGO_GAUGE=0 (anchor prior, no gauge term, no anchor gauge in the update)
+    differs from the default handle's in at least one bit.  Both are steps of the same system: they agree to single precision."""
+    default = Handle(api, "lattice", "ref", monkeypatch, "f32")
+    monkeypatch.setenv("RR_PGO_GAUGE", "0")
+    try:
+        off = Handle(api, "lattice", "ref", monkeypatch, "f32")
+    finally:
+        monkeypatch.delenv("RR_PGO_GAUGE")
+    a, b = default.linearize_and_solve(), off.linearize_and_solve()
+    print("gauge on / off: first step differs in", int((a != b).sum()), "of", a.size, "entries, max", np.abs(a - b).max(), "of", np.abs(a).max())
+    assert np.all(np.isfinite(a)) and np.all(np.isfinite(b)) and np.abs(a).max() > 0
+    assert not np.array_equal(a, b)
+
+
+@pytest.mark.parametrize("precision", ["f64", "f32"])
+def test_stage_one_follows_stage_zero_as_replays_and_as_plain_launches(api, precision, monkeypatch):
+    """The two stages of a sharded handle (one rank, the 100 x 100 lattice), as replays of their captured graphs (default) and
+    as plain launches (RR_PGO_NO_GRAPH=1): two Gauss-Newton pairs stage(0), stage(1); one pair stage(0, 0.37, True), stage(1)
+    -- stage 1 left at its default lm: it factors the top fronts and updates in the gauge stage 0 linearised in, not in the
+    one its captured graph holds; one more Gauss-Newton pair.  The scalars after every pair and the final state are equal bit
+    for bit, and chi2 fell."""
+    arrays = lf.arrays_of("lattice")
+
+    def run(env):
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        try:
+            g = api[0].from_arrays(*arrays, precision=precision, sharded=True)
+        finally:
+            for k in env:
+                monkeypatch.delenv(k)
+        g.stage(2)
+        t = [("chi2 before", g.stage_scalars()[0])]
+        for i, first in enumerate([(0,), (0,), (0, 0.37, True), (0,)]):
+            g.stage(*first)
+            g.stage(1)
+            t.append(("scalars %d" % i, np.array(g.stage_scalars())))
+        g.stage(2)
+        return t + [("state", np.array(g.state())), ("chi2", g.stage_scalars()[0])]
+
+    replays, plain = run({}), run({"RR_PGO_NO_GRAPH": "1"})
+    assert lf.same(replays, plain) is None, (precision, lf.same(replays, plain))
+    got = dict(replays)
+    print(precision, [(k, v) for k, v in replays if k != "state"])
+    assert np.all(np.isfinite(got["state"])) and got["scalars 3"][0] < got["chi2 before"] and got["chi2"] < got["chi2 before"]
 
 
 @pytest.mark.parametrize("form", ["a", "b"])
