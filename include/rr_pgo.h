@@ -306,6 +306,39 @@ int rr_pgo_covariances(rr_pgo *h, int32_t n_query, const int32_t *node_a, const 
 /* ms[3]: HIP-event times of the last rr_pgo_covariances call -- linearise + factor, tree solve, products + gather. */
 int rr_pgo_covariances_times(const rr_pgo *h, double *ms);
 
+/* The rectangular block Sigma[rows, cols]: rows = the scalars of row_node[0 .. n_row) stacked in that order, cols = the
+ * scalars of col_node[0 .. n_col) likewise, each node's scalars in the order rr_pgo_linearize_solve's dx uses.
+ * out: R x C doubles, row-major, R = sum of the row nodes' dims, C = sum of the column nodes' dims.
+ * row_node == NULL: n_row must be rr_pgo_num_nodes; the rows are all nodes in node order, i.e. R = rr_pgo_dim and
+ * row i is scalar i of dx -- the block columns Sigma[:, col_node], what a search for the nodes within a pose's
+ * uncertainty starts from.  Same H as rr_pgo_covariances (current state, lambda = 0, robust weights while a kernel is set,
+ * the priors of rr_pgo_set_priors, the anchor term only while both keep_anchor settings say keep).
+ * row_offset [n_row + 1], col_offset [n_col + 1] (either may be NULL): the first row / column of every node in out.  Call
+ * with out == NULL to get *n_vals = R * C (and the offsets).  n_vals is required.  A node may appear any number of times in
+ * either list: repeated rows and columns are copies, same bits.  n_col == 0, or n_row == 0 with a non-NULL row_node:
+ * RR_PGO_OK, nothing is launched, *n_vals = 0.
+ * Computed as X = L^-T (L^-1 E_cols): the forward solve of rr_pgo_covariances over the root paths of the column nodes,
+ * then a backward sweep over the union of the root paths of the row nodes (every front for row_node == NULL), one launch
+ * per level of the tree each way.  The bits of block (r, c) depend on the graph, the state, r and c alone -- not on the
+ * other rows or columns of the call, their order, repeats, or a cut of the list.  Sigma(r, c) and the transpose of
+ * Sigma(c, r) agree to rounding, NOT bit for bit, and a block agrees with rr_pgo_covariances -- which stays the
+ * bit-symmetric call -- to rounding.
+ * Fixed nodes (rr_pgo_set_fixed): every entry in a fixed node's rows or columns is +0.0; the rest is (H_ff)^-1.
+ * The call linearises, factors, solves forward and backward and gathers on the handle's stream, then synchronises once;
+ * the state, the Levenberg-Marquardt lambda, rr_pgo_optimize's results, captured graphs and the robust setting are untouched.
+ * RR_PGO_EINVAL, decided before anything is launched or written, the message names the entry: negative counts, col_node ==
+ * NULL with n_col > 0, row_node == NULL with n_row != rr_pgo_num_nodes, a node out of range, n_vals == NULL.
+ * RR_PGO_ENOTSPD: a non-positive pivot, nothing is written.  RR_PGO_EUNSUPPORTED: the cases and messages of
+ * rr_pgo_covariances.  RR_PGO_ENOMEM: one column node alone needs more workspace (forward and backward blocks of its pass)
+ * than the handle's bound, the message gives the bytes; a longer list is cut between column nodes, never between rows, and
+ * the cut changes no bit. */
+int rr_pgo_cross_covariances(rr_pgo *h, int32_t n_row, const int32_t *row_node, int32_t n_col, const int32_t *col_node,
+                             double *out, int64_t *row_offset /* [n_row + 1], may be NULL */,
+                             int64_t *col_offset /* [n_col + 1], may be NULL */, int64_t *n_vals /* R * C */);
+/* ms[3]: HIP-event times of the last rr_pgo_cross_covariances call -- linearise + factor, forward + backward solve,
+ * gather + copy. */
+int rr_pgo_cross_covariances_times(const rr_pgo *h, double *ms);
+
 /* ---- Mahalanobis gate of candidate loop closures (build-defined; the reference has none) ----
  * For candidate c -- an edge of kind edge_kind[c] from node edge_from[c] to node edge_to[c] with measurement z and
  * information Omega, in rr_pgo_graph_desc packing (measurements and packed upper triangles follow each other in candidate

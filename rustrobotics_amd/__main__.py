@@ -25,6 +25,10 @@
   --joint ID,ID,...  (example mode): after the optimisation, the joint covariance of the listed g2o vertex ids -- any
       nodes, joined by an edge or not (rr_pgo_covariances) -- one matrix row per line
 
+  --cross FILE --columns ID,ID,... [--rows ID,ID,...]  (example mode): after the optimisation, the rectangular block
+      Sigma[rows, columns] of the listed g2o vertex ids (rr_pgo_cross_covariances; no --rows: every vertex) -- one line per
+      (row vertex, column vertex) block: the two ids, d_r, d_c, the d_r x d_c values row-major -- and the call's three times
+
   --gate FILE  (example mode): after the optimisation, gate the candidate edges of FILE -- EDGE_SE2 / EDGE_SE2_XY /
       EDGE_SE3:QUAT lines in the loader's field order, between vertex ids of the loaded graph, not part of it -- and print
       one line per candidate: ids, Mahalanobis distance d2, e^T Omega e, accept / reject at the 0.95 chi-square quantile
@@ -109,6 +113,29 @@ def print_joint(g, ids):
     print(f"joint covariance of vertices {','.join(str(i) for i in ids)} ({J.shape[0]} x {J.shape[0]}):")
     for row in J:
         print(" ".join(f"{v:.17g}" for v in row))
+
+
+def write_cross(g, path, columns, rows):
+    import numpy as np
+    index = _node_index(g)
+    for flag, ids in (("--columns", columns), ("--rows", rows or [])):
+        missing = [i for i in ids if i not in index]
+        if missing:
+            raise SystemExit(f"{flag}: no vertex with id {missing[0]} in the file")
+    by_index = sorted(index, key=index.get)
+    row_ids = rows if rows else by_index
+    dim = np.take((3, 2, 6), g.graph_arrays()[0])
+    X = g.cross_covariance([index[i] for i in rows] if rows else None, [index[i] for i in columns])
+    ro = np.concatenate([[0], np.cumsum([dim[index[i]] for i in row_ids])]).astype(int)
+    co = np.concatenate([[0], np.cumsum([dim[index[i]] for i in columns])]).astype(int)
+    with open(path, "w") as f:
+        for r, i in enumerate(row_ids):
+            for c, j in enumerate(columns):
+                blk = X[ro[r]:ro[r + 1], co[c]:co[c + 1]]
+                f.write(f"{i} {j} {blk.shape[0]} {blk.shape[1]} " + " ".join(f"{v:.17g}" for v in blk.ravel()) + "\n")
+    t = g.cross_covariances_times()
+    print(f"cross covariances of {len(row_ids)} x {len(columns)} vertices ({X.shape[0]} x {X.shape[1]} scalars) written to {path}; "
+          f"linearise + factor {t[0]:.3f} ms, forward + backward solve {t[1]:.3f} ms, gather + copy {t[2]:.3f} ms")
 
 
 GATE_TAGS = {"EDGE_SE2": 0, "EDGE_SE2_XY": 1, "EDGE_SE3:QUAT": 2}
@@ -395,6 +422,11 @@ def main(argv=None):
                     help="after the optimisation write every node's covariance block: id, d, upper triangle")
     ap.add_argument("--joint", type=_ids_arg, metavar="ID,ID,...", default=None,
                     help="after the optimisation print the joint covariance of these g2o vertex ids (any nodes)")
+    ap.add_argument("--cross", metavar="FILE", default=None,
+                    help="after the optimisation write the blocks of Sigma[rows, columns]: the two ids, d_r, d_c, the values")
+    ap.add_argument("--columns", type=_ids_arg, metavar="ID,ID,...", default=None, help="with --cross: the column vertices")
+    ap.add_argument("--rows", type=_ids_arg, metavar="ID,ID,...", default=None,
+                    help="with --cross: the row vertices (default: every vertex, in the graph's order)")
     ap.add_argument("--gate", metavar="FILE", default=None,
                     help="after the optimisation gate the candidate EDGE_* lines of FILE: d2, e^T Omega e, accept / reject")
     ap.add_argument("--accept", action="store_true",
@@ -408,6 +440,10 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if a.accept and not a.gate:
         ap.error("--accept needs --gate FILE")
+    if a.cross and not a.columns:
+        ap.error("--cross needs --columns ID,ID,...")
+    if (a.columns or a.rows) and not a.cross:
+        ap.error("--columns and --rows need --cross FILE")
     if a.guess and not a.extend:
         ap.error("--guess needs --extend FILE")
     if a.free_anchor and not (a.priors or a.fix):
@@ -439,6 +475,8 @@ def main(argv=None):
             write_marginals(g, a.marginals)
         if a.joint:
             print_joint(g, a.joint)
+        if a.cross:
+            write_cross(g, a.cross, a.columns, a.rows)
         if a.gate:
             print_gate(g, a.gate)
         if a.gate_joint:

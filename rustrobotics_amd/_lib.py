@@ -35,6 +35,7 @@ EXPORTS = (
     "rr_pgo_node_owner", "rr_pgo_trim", "rr_pgo_set_robust_kernel", "rr_pgo_edge_errors", "rr_pgo_solve_form",
     "rr_pgo_launch_counts",
     "rr_pgo_marginals", "rr_pgo_marginals_times", "rr_pgo_covariances", "rr_pgo_covariances_times",
+    "rr_pgo_cross_covariances", "rr_pgo_cross_covariances_times",
     "rr_pgo_gate_edges", "rr_pgo_gate_times", "rr_pgo_gate_joint", "rr_pgo_gate_joint_times",
     "rr_pgo_extend", "rr_pgo_extend_times", "rr_pgo_set_priors", "rr_pgo_num_priors", "rr_pgo_prior_errors",
     "rr_pgo_set_fixed", "rr_pgo_num_fixed", "rr_pgo_get_fixed",
@@ -142,6 +143,9 @@ def load():
     L.rr_pgo_marginals_times.argtypes = [vp, dp]
     L.rr_pgo_covariances.argtypes = [vp, C.c_int32, ip, ip, dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.rr_pgo_covariances_times.argtypes = [vp, dp]
+    L.rr_pgo_cross_covariances.argtypes = [vp, C.c_int32, ip, C.c_int32, ip, dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                           C.POINTER(C.c_int64)]
+    L.rr_pgo_cross_covariances_times.argtypes = [vp, dp]
     L.rr_pgo_gate_edges.argtypes = [vp, C.c_int32, ip, ip, ip, dp, dp, dp, dp, dp, C.POINTER(C.c_int64)]
     L.rr_pgo_gate_times.argtypes = [vp, dp]
     L.rr_pgo_gate_joint.argtypes = [vp, C.c_int32, ip, ip, ip, dp, dp, C.c_int32, ip, ip, dp, dp, dp, C.POINTER(C.c_int64)]

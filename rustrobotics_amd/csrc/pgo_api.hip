@@ -251,7 +251,7 @@ struct PriorSet {
 };
 
 struct EngineBase {
-  enum Query { Q_MARGINALS, Q_COVARIANCES, Q_GATE, Q_GATE_JOINT };   // the factor queries, in the order of their ABI functions
+  enum Query { Q_MARGINALS, Q_COVARIANCES, Q_GATE, Q_GATE_JOINT, Q_CROSS };   // the factor queries, in the order of their ABI functions
   virtual ~EngineBase() = default;
   virtual void chi2(double *out) = 0;
   virtual void linearize_solve(double lambda, int lm, double *dx_out) = 0;
@@ -298,7 +298,11 @@ struct EngineBase {
   // rr_pgo_gate_joint_times
   virtual void gate_joint(int n_sets, const int32_t *set_ptr, const int32_t *from, const int32_t *to, const int32_t *dim,
                           const int64_t *ioff, std::vector<GateCand> &cand, double *d2, double *prefix, double *innov) = 0;
-  // the four rr_pgo_*_times: the three phases of the last call of query `which`, in ms
+  // rr_pgo_cross_covariances (arguments checked; row_node null: every node; roff / coff: [n + 1] first scalar of every row /
+  // column node in out, R x C row-major) / rr_pgo_cross_covariances_times
+  virtual void cross_covariances(int n_row, const int32_t *row_node, int n_col, const int32_t *col_node, const int64_t *roff,
+                                 const int64_t *coff, double *out) = 0;
+  // the five rr_pgo_*_times: the three phases of the last call of query `which`, in ms
   virtual void last_query_times(Query which, double *ms) const = 0;
   // rr_pgo_extend (arguments checked).  The state buffer is in node order, so a grown graph's buffer starts with the old one.
   virtual const void *pose_dev() const = 0;
@@ -512,8 +516,8 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   std::vector<int32_t> front_depth_, col_front_;   // depth of a front (a root: 0); permuted scalar column -> front
   EventHolder query_ev_[4];
   // the last call of each query (EngineBase::Query): linearise + factor | selected inverse or tree solve | the query's own
-  // kernel (gather; products + gather; gate kernel + copy; joint kernel + copy)
-  double query_ms_[4][3] = {};
+  // kernel (gather; products + gather; gate kernel + copy; joint kernel + copy; gather + copy)
+  double query_ms_[5][3] = {};
   // marginal covariances (selinv.hip.h; rr_pgo_marginals): everything made on the first call
   DevBuf<T> svals_;                  // the selected inverse, a front's image laid out like its factor image (less the rhs row)
   DevBuf<SelMeta> sel_meta_;
@@ -539,6 +543,11 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   // per set its record, the pivot columns of its fronts and the Z rows of its candidates' nodes there
   DevBuf<JointSet> joint_set_;
   DevBuf<int32_t> joint_fnc_, joint_fz_;
+  // Sigma[rows, cols] (rr_pgo_cross_covariances): the covariance plan of the column nodes and its workspace above, plus the
+  // backward-active fronts by level, their rows in V, the rows and columns of out in V, and V itself
+  DevBuf<int32_t> cross_order_, cross_fvrow_, cross_rsrc_;
+  DevBuf<int64_t> cross_csrc_;
+  DevBuf<T> ts_v_;
   static constexpr int kGemvSlices = 16;   // row slices of the multi-workgroup L21^T x product
   DevBuf<double> chi_partial_, norm_partial_, hist_;
   DevBuf<int> counter_, err_, blocks_done_;
@@ -3035,6 +3044,8 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     }
     if constexpr (std::is_same<T, double>::value)
       HIPCHK(hipFuncSetAttribute((const void *)k_tree_fwd<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ts_lds_));
+    if constexpr (std::is_same<T, double>::value)
+      HIPCHK(hipFuncSetAttribute((const void *)k_tree_bwd<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ts_lds_));
     ts_ready_ = true;
   }
 
@@ -3196,9 +3207,16 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   // upload lies in the second); time_copy: the third ends behind the copy to the host.
   // cuts (optional): a table of n_parts + 1 ascending cut points, cuts[0] = 0 and cuts[n_parts] = n -- the list is then cut
   // at these points only, in halves by the index of the part (`what` names a part); stage and launch still get pair indices.
+  // extra (optional): bytes(plan) = workspace of a pass beside Z + U, counted against the bound; solve(plan) is enqueued
+  // behind the forward solve, inside the second interval.
+  struct TsExtra {
+    std::function<size_t(const TsPlan &)> bytes;
+    std::function<void(const TsPlan &)> solve;
+  };
   template <typename Stage, typename Launch>
   void tree_query(const char *who, const char *what, int n, const int32_t *a, const int32_t *b, const int64_t *off, double *ms,
-                  bool time_copy, Stage &&stage, Launch &&launch, const int32_t *cuts = nullptr, int n_parts = 0) {
+                  bool time_copy, Stage &&stage, Launch &&launch, const int32_t *cuts = nullptr, int n_parts = 0,
+                  const TsExtra *extra = nullptr) {
     for (int k = 0; k < 3; k++) ms[k] = 0;
     if (n == 0) return;
     auto first_of = [&](int u) { return cuts ? (int)cuts[u] : u; };   // the first pair of part u (no table: a part is a pair)
@@ -3214,7 +3232,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
       todo.pop_back();
       TsPlan pl;
       covariances_plan(q0, q1, a, b, off, pl);
-      const size_t ws = (size_t)(pl.zrows + pl.urows) * TS_MC * sizeof(T);
+      const size_t ws = (size_t)(pl.zrows + pl.urows) * TS_MC * sizeof(T) + (extra ? extra->bytes(pl) : 0);
       if (ws > ts_ws_bytes_) {
         if (u1 - u0 <= 1) throw ApiError(RR_PGO_ENOMEM, std::string(who) + ": one " + what + " needs " + std::to_string(ws) + " bytes of workspace");
         const int mid = u0 + (u1 - u0) / 2;
@@ -3226,6 +3244,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
       stage(q0, q1, pl);
       if (!first) HIPCHK(hipEventRecord(query_ev_[1], stream_));
       ts_forward(pl);
+      if (extra) extra->solve(pl);
       HIPCHK(hipEventRecord(query_ev_[2], stream_));
       const auto dest = launch(q0, q1);
       size_t n_out = 0;
@@ -3267,6 +3286,107 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
         check_launch("k_cov_pairs");
         return std::array<TsDest, 1>{{{out + off[q0], (size_t)(off[q1] - off[q0])}}};
       });
+    }
+  }
+
+  // ---- Sigma[rows, cols] (include/rr_pgo.h, rr_pgo_cross_covariances; treesolve.hip.h, k_tree_bwd, k_cross_gather): the plan
+  // of the columns is the covariance plan of the pairs (col, col), cut between column nodes; the backward sweep runs over the
+  // union of the root paths of the row nodes, the same fronts for every chunk
+  void cross_covariances(int n_row, const int32_t *row_node, int n_col, const int32_t *col_node, const int64_t *roff,
+                         const int64_t *coff, double *out) override {
+    static constexpr const char *who = "rr_pgo_cross_covariances";
+    require_f64_unsharded_lds_factor(who);
+    if constexpr (f64_) {
+      covariances_prepare(who);
+      const Symbolic &sym = sym_;
+      const int S_ = sym.S;
+      const int64_t R = roff[n_row], C = coff[n_col];
+      // ---- the backward-active fronts by depth, root level first (within a level: descending front index, as sel_order_)
+      std::vector<int32_t> fvrow((size_t)S_, -1), order, level_ptr;
+      if (!row_node) std::fill(fvrow.begin(), fvrow.end(), 0);
+      else
+        for (int k = 0; k < n_row; k++)
+          for (int f = front_of(row_node[k]); f >= 0 && fvrow[f] < 0; f = sym.sn_parent[f]) fvrow[f] = 0;
+      const int max_depth = *std::max_element(front_depth_.begin(), front_depth_.end());
+      level_ptr.assign((size_t)max_depth + 2, 0);
+      for (int f = 0; f < S_; f++)
+        if (fvrow[f] == 0) level_ptr[(size_t)front_depth_[f] + 1]++;
+      for (int d = 0; d <= max_depth; d++) level_ptr[(size_t)d + 1] += level_ptr[d];
+      order.resize((size_t)level_ptr[(size_t)max_depth + 1]);
+      {
+        std::vector<int32_t> fill(level_ptr.begin(), level_ptr.end() - 1);
+        for (int f = S_ - 1; f >= 0; f--)
+          if (fvrow[f] == 0) order[(size_t)fill[front_depth_[f]]++] = f;
+      }
+      int64_t vrows = 0;   // rows of V per chunk
+      for (int32_t f : order) {
+        fvrow[f] = (int32_t)std::min<int64_t>(vrows, 0x7fffffff);   // (a plan beyond the workspace bound is dropped before these are read)
+        vrows += (int64_t)sym.sn_ncols[f] + sym.sn_nrows[f];
+      }
+      // ---- row of out -> row of a chunk's part of V: reference scalar r of the node -> its permuted pivot row
+      std::vector<int32_t> rsrc((size_t)R);
+      for (int k = 0; k < n_row; k++) {
+        const int v = row_node ? row_node[k] : k, f = front_of(v), d = node_dim(g_.node_kind[v]), p0 = sym.node_pcol[v];
+        for (int i = 0; i < d; i++)
+          rsrc[(size_t)(roff[k] + sym.perm[p0 + i] - g_.node_offset[v])] = is_fixed(v) ? -1 : fvrow[f] + (p0 + i - sym.sn_col0[f]);
+      }
+      std::vector<int64_t> csrc;
+      std::vector<TsDest> dest;
+      TsExtra extra;
+      extra.bytes = [&](const TsPlan &pl) { return (size_t)pl.n_chunks * (size_t)vrows * TS_MC * sizeof(T); };
+      extra.solve = [&](const TsPlan &pl) {
+        TsBwdArgs<T> a;
+        a.meta = ts_meta_.p;
+        a.order = cross_order_.p;
+        a.fvrow = cross_fvrow_.p;
+        a.czrow = ts_czrow_.p;
+        a.rel = rel_.p;
+        a.lvals = lvals_.p;
+        a.winv = winv_.p;
+        a.Z = ts_z_.p;
+        a.V = ts_v_.p;
+        a.vrows = vrows;
+        a.S = S_;
+        if constexpr (std::is_same<T, double>::value)
+          for (size_t l = 0; l + 1 < level_ptr.size(); l++) {
+            const int begin = level_ptr[l], count = level_ptr[l + 1] - begin;
+            if (count <= 0) continue;
+            hipLaunchKernelGGL((k_tree_bwd<T>), dim3((unsigned)count, (unsigned)pl.n_chunks), dim3(TS_THREADS), ts_lds_, stream_, a, begin);
+          }
+        check_launch("k_tree_bwd");
+      };
+      tree_query(who, "column node", n_col, col_node, col_node, coff, query_ms_[Q_CROSS], true, [&](int q0, int q1, const TsPlan &pl) {
+        // column of this part's out -> (chunk, column) in V: reference scalar r of the node -> its column in the chunk
+        const int64_t Cp = coff[q1] - coff[q0];
+        csrc.assign((size_t)Cp, -1);
+        for (int q = q0; q < q1; q++) {
+          const CovQuery &cq = pl.query[q - q0];
+          if (is_fixed(col_node[q])) continue;
+          for (int r = 0; r < cq.da; r++) csrc[(size_t)(coff[q] - coff[q0] + r)] = (int64_t)cq.chunk_a * vrows * TS_MC + cq.ca[r];
+        }
+        ts_fill(cross_order_, order);
+        ts_fill(cross_fvrow_, fvrow);
+        ts_fill(cross_rsrc_, rsrc);
+        ts_fill(cross_csrc_, csrc);
+        ts_grow(ts_v_, (size_t)pl.n_chunks * (size_t)vrows * TS_MC);
+        ts_grow(ts_out_, (size_t)(R * Cp));
+      }, [&](int q0, int q1) -> const std::vector<TsDest> & {
+        const int64_t Cp = coff[q1] - coff[q0];
+        CrossArgs<T> c;
+        c.V = ts_v_.p;
+        c.rsrc = cross_rsrc_.p;
+        c.csrc = cross_csrc_.p;
+        c.out = ts_out_.p;
+        c.R = R;
+        c.C = Cp;
+        if (R * Cp > 0) hipLaunchKernelGGL((k_cross_gather<T>), dim3((unsigned)((R * Cp + 255) / 256)), dim3(256), 0, stream_, c);
+        check_launch("k_cross_gather");
+        dest.clear();
+        if (Cp == C) dest.push_back({out, (size_t)(R * C)});
+        else
+          for (int64_t i = 0; i < R; i++) dest.push_back({out + i * C + coff[q0], (size_t)Cp});   // a part holds some columns of every row
+        return dest;
+      }, nullptr, 0, &extra);
     }
   }
 
@@ -4270,6 +4390,40 @@ int rr_pgo_covariances(rr_pgo *h, int32_t n_query, const int32_t *node_a, const 
 int rr_pgo_covariances_times(const rr_pgo *h, double *ms) {
   if (!h || !ms) { g_last_error = "null argument"; return RR_PGO_EINVAL; }
   return guarded([&] { h->engine->last_query_times(EngineBase::Q_COVARIANCES, ms); });
+}
+
+int rr_pgo_cross_covariances(rr_pgo *h, int32_t n_row, const int32_t *row_node, int32_t n_col, const int32_t *col_node,
+                             double *out, int64_t *row_offset, int64_t *col_offset, int64_t *n_vals) {
+  static const std::string who = "rr_pgo_cross_covariances: ";
+  if (!h || !n_vals) { g_last_error = who + "null argument (n_vals is required)"; return RR_PGO_EINVAL; }
+  if (n_row < 0 || n_col < 0) { g_last_error = who + "negative counts"; return RR_PGO_EINVAL; }
+  if (n_col > 0 && !col_node) { g_last_error = who + "col_node is required"; return RR_PGO_EINVAL; }
+  const int N = h->g->n_nodes();
+  if (!row_node && n_row != N) { g_last_error = who + "row_node == NULL asks for every node: n_row must be rr_pgo_num_nodes"; return RR_PGO_EINVAL; }
+  std::vector<int64_t> roff((size_t)n_row + 1, 0), coff((size_t)n_col + 1, 0);
+  for (int k = 0; k < n_row; k++) {
+    const int v = row_node ? row_node[k] : k;
+    if (v < 0 || v >= N) { g_last_error = who + "row " + std::to_string(k) + ": node index out of range"; return RR_PGO_EINVAL; }
+    roff[(size_t)k + 1] = roff[k] + node_dim(h->g->node_kind[v]);
+  }
+  for (int k = 0; k < n_col; k++) {
+    const int v = col_node[k];
+    if (v < 0 || v >= N) { g_last_error = who + "column " + std::to_string(k) + ": node index out of range"; return RR_PGO_EINVAL; }
+    coff[(size_t)k + 1] = coff[k] + node_dim(h->g->node_kind[v]);
+  }
+  const bool empty = n_col == 0 || n_row == 0;
+  int rc = RR_PGO_OK;
+  if (out && !empty) rc = guarded([&] { h->engine->cross_covariances(n_row, row_node, n_col, col_node, roff.data(), coff.data(), out); });
+  if (rc != RR_PGO_OK) return rc;
+  *n_vals = empty ? 0 : roff[n_row] * coff[n_col];
+  if (row_offset) std::copy(roff.begin(), roff.end(), row_offset);
+  if (col_offset) std::copy(coff.begin(), coff.end(), col_offset);
+  return RR_PGO_OK;
+}
+
+int rr_pgo_cross_covariances_times(const rr_pgo *h, double *ms) {
+  if (!h || !ms) { g_last_error = "null argument"; return RR_PGO_EINVAL; }
+  return guarded([&] { h->engine->last_query_times(EngineBase::Q_CROSS, ms); });
 }
 
 // Cholesky of the d x d matrix in w (row stride ld), in place in the lower triangle; false: not positive definite

@@ -8,7 +8,9 @@
 //   k_tree_fwd    one workgroup per (chunk of TS_MC columns, active front), one launch per level of the tree, deepest first
 //   k_cov_pairs   one workgroup per query: Sigma_ab = sum over the common path's pivot rows of Z_a[row]^T Z_b[row]
 //   k_gate_pairs  one workgroup per candidate edge: its Mahalanobis distance from the same Z
-//   k_gate_joint  one workgroup per set of candidate edges: their joint distance from the same Z (the end of this file)
+//   k_gate_joint  one workgroup per set of candidate edges: their joint distance from the same Z
+//   k_tree_bwd    one workgroup per (chunk, backward-active front), one launch per level, root level first: X = L^-T Z
+//   k_cross_gather  the rectangular block Sigma[rows, cols] out of X (the end of this file)
 //
 // Columns.  The distinct queried nodes are ordered by (front, pivot column) -- fronts are numbered in elimination order, so
 // neighbours share paths -- and packed, whole nodes at a time, into chunks of TS_MC = 32 columns (unused columns stay zero).
@@ -609,6 +611,158 @@ __global__ void __launch_bounds__(COV_THREADS) k_gate_joint(JointArgs<T> a) {
       a.d2[blockIdx.x] = fail == Ds ? (double)d2 : __builtin_nan("");
     }
   }
+}
+
+// ---- Sigma[rows, cols] by a backward solve (rr_pgo_cross_covariances)
+//
+// With Z = L^-1 E_cols from k_tree_fwd, X = L^-T Z holds the columns Sigma[:, cols].  For front f with pivot rows P, rows
+// below R and panel [L11; L21]:   X_P = L11^-T (Y_P - L21^T X_R),   Y_P = the front's rows of Z, X_R = rows of its ancestors'
+// solution -- so X on a set of row nodes needs the fronts on their root paths only (the BACKWARD-ACTIVE fronts), root first.
+// The set is the same for every chunk: one workgroup per (chunk, front of a level).
+// Workspace.  V: per (chunk, backward-active front) its whole block [X_P; X_R], nc + nr rows of TS_MC scalars.  A child
+// gathers its X_R as V_parent[rel[r]] -- the extend-add map read backwards, the mirror image of U in k_tree_fwd.
+//
+// Determinism.  No atomics.  Every scalar of V is produced by one wave in an operation order that depends on the front and
+// the row alone: columns of an MFMA tile are independent, X_R is a copy of the parent's scalars, the products over the rows
+// below run in ascending row order and the pivot blocks from the right in a fixed order.  A front's block depends on Z and
+// on its ancestors' blocks only, never on which other fronts are backward-active, and a front that the forward plan of the
+// chunk does not hold reads Y_P = 0, which is what k_tree_fwd leaves in a column whose node lies elsewhere.  Hence the bits
+// of Sigma(r, c) depend on the graph, the state, r and c alone: not on the other rows or columns of the call, their order,
+// repeats, the chunk a column falls in or a cut of the plan.
+template <typename T> struct TsBwdArgs {
+  const TsMeta *meta;
+  const int32_t *order;           // the backward-active fronts by level, root level first
+  const int32_t *fvrow;           // [front]: first row of the front's block in a chunk's part of V, -1 = not backward-active
+  const int32_t *czrow;           // as CovArgs
+  const int32_t *rel;
+  const T *lvals, *winv, *Z;
+  T *V;
+  int64_t vrows;                  // rows of V per chunk
+  int32_t S;
+};
+
+// The block [T_P; X_R], (nc + nr) x TS_MC, lives in LDS (row stride TS_LD) as in k_tree_fwd; L^T goes from lvals in global
+// memory straight into the A operands: A(i, k) = L(k, i), a lane's four k are consecutive scalars of one panel column.
+template <typename T>
+__global__ void __launch_bounds__(TS_THREADS) k_tree_bwd(TsBwdArgs<T> a, int begin) {
+  using MM = Mfma16<T>;
+  constexpr int NW = TS_THREADS / 64, LD = TS_LD, NCT = TS_MC / 16;
+  extern __shared__ __align__(16) unsigned char smem_raw[];
+  __shared__ T ws[256];                  // W_b: ws[k * 16 + i] = W(k, i) = W^T(i, k)
+  T *B = reinterpret_cast<T *>(smem_raw);
+  const int tid = threadIdx.x, lane = tid & 63, li = lane & 15, lk = lane >> 4;
+  const int wave = wave_index();
+  const int f = a.order[begin + blockIdx.x], chunk = blockIdx.y;
+  const TsMeta m = a.meta[f];
+  const int nc = m.nc, nr = m.nr, n = nc + nr, M = n + 1;
+  const T *Lg = a.lvals + m.loff;
+  const T *Wg = a.winv + (int64_t)m.wblk * 256;
+  const int64_t vbase = (int64_t)chunk * a.vrows;
+  // ---- Y_P: the front's rows of Z where the chunk's forward plan holds the front, else zero
+  {
+    const int zr = a.czrow[(int64_t)chunk * a.S + f];
+    const T *Zg = a.Z + (int64_t)max(zr, 0) * TS_MC;
+    for (int e = tid; e < nc * TS_MC; e += TS_THREADS) B[(e >> 5) * LD + (e & 31)] = zr >= 0 ? Zg[e] : (T)0;
+  }
+  // ---- X_R: the parent's block through this front's rel map (a root has no rows below)
+  if (nr > 0) {
+    const int p = m.parent;
+    const int pn = p >= 0 ? a.meta[p].nc + a.meta[p].nr : 0;
+    const T *Vp = a.V + (vbase + (p >= 0 ? a.fvrow[p] : 0)) * TS_MC;
+    const int32_t *rel = a.rel + m.rel_ptr;
+    for (int e = tid; e < nr * TS_MC; e += TS_THREADS) {
+      const int row = rel[e >> 5];
+      B[(nc + (e >> 5)) * LD + (e & 31)] = (unsigned)row < (unsigned)pn ? Vp[(int64_t)row * TS_MC + (e & 31)] : (T)0;
+    }
+  }
+  __syncthreads();
+  // ---- T = Y_P - L21^T X_R: a tile of 16 pivot rows x 16 columns is one wave's, the rows below in ascending order
+  if (nr > 0) {
+    const int nti = (nc + 15) >> 4;
+    for (int tile = wave; tile < nti * NCT; tile += NW) {
+      const int ib = tile / NCT, jb = tile - ib * NCT;
+      const int i0 = 16 * ib, col = 16 * jb + li;
+      typename MM::Acc acc;
+#pragma unroll
+      for (int r = 0; r < 4; r++) acc[r] = B[min(i0 + MM::row(lane, r), nc - 1) * LD + col];
+      const T *Lc = Lg + (int64_t)min(i0 + li, nc - 1) * M + nc;   // rows past nc of the last tile are computed and dropped
+      for (int k4 = 0; k4 < nr; k4 += 4) {
+        const int k = k4 + lk, kc = min(k, nr - 1);
+        const T lv = Lc[kc];
+        acc = MM::mma(k < nr ? -lv : (T)0, B[(nc + kc) * LD + col], acc);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        const int row = i0 + MM::row(lane, r);
+        if (row < nc) B[row * LD + col] = acc[r];
+      }
+    }
+    __syncthreads();
+  }
+  // ---- pivot square, by 16-column blocks from the right: X_b = W_b^T T_b, then T_j -= L_bj^T X_b for the earlier blocks
+  for (int b = ((nc + 15) >> 4) - 1; b >= 0; b--) {
+    const int c0 = 16 * b, cw = min(16, nc - c0);
+    if (tid < 256) ws[tid] = Wg[b * 256 + tid];
+    __syncthreads();
+    if (wave < NCT) {   // a column tile of the block is one wave's: read whole, then written
+      const int col = 16 * wave + li;
+      typename MM::Acc x = {0, 0, 0, 0};
+      T bv[4];
+#pragma unroll
+      for (int s = 0; s < 4; s++) bv[s] = B[(c0 + min(4 * s + lk, cw - 1)) * LD + col];
+#pragma unroll
+      for (int s = 0; s < 4; s++) {
+        const int k = 4 * s + lk;
+        const T wv = (li <= k && k < cw) ? ws[k * 16 + li] : (T)0;   // W^T is upper triangular; rows past a partial block are padding
+        x = MM::mma(wv, k < cw ? bv[s] : (T)0, x);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        const int i = MM::row(lane, r);
+        if (i < cw) B[(c0 + i) * LD + col] = x[r];
+      }
+    }
+    __syncthreads();
+    for (int tile = wave; tile < b * NCT; tile += NW) {   // (the earlier blocks are full ones)
+      const int ib = tile / NCT, jb = tile - ib * NCT;
+      const int i0 = 16 * ib, col = 16 * jb + li;
+      typename MM::Acc acc;
+#pragma unroll
+      for (int r = 0; r < 4; r++) acc[r] = B[(i0 + MM::row(lane, r)) * LD + col];
+      const T *Lc = Lg + (int64_t)(i0 + li) * M + c0;
+#pragma unroll
+      for (int s = 0; s < 4; s++) {
+        const int k = 4 * s + lk, kc = min(k, cw - 1);
+        const T lv = Lc[kc];
+        acc = MM::mma(k < cw ? -lv : (T)0, B[(c0 + kc) * LD + col], acc);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; r++) B[(i0 + MM::row(lane, r)) * LD + col] = acc[r];
+    }
+    __syncthreads();
+  }
+  // ---- V = [X_P; X_R], what the children gather from
+  T *Vg = a.V + (vbase + a.fvrow[f]) * TS_MC;
+  for (int e = tid; e < n * TS_MC; e += TS_THREADS) Vg[e] = B[(e >> 5) * LD + (e & 31)];
+}
+
+template <typename T> struct CrossArgs {
+  const T *V;
+  const int32_t *rsrc;            // [R]: row of out -> row of the node's scalar in a chunk's part of V, -1 = a fixed node
+  const int64_t *csrc;            // [C]: column of out -> flat offset of (chunk, column) in V, -1 = a fixed node
+  double *out;                    // R x C, row-major
+  int64_t R, C;
+};
+
+// One thread per scalar of out; every entry of a fixed node's rows and columns is +0.0 (Sigma is conditional on them).
+template <typename T>
+__global__ void __launch_bounds__(256) k_cross_gather(CrossArgs<T> a) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= a.R * a.C) return;
+  const int64_t i = t / a.C, j = t - i * a.C;
+  const int32_t r = a.rsrc[i];
+  const int64_t c = a.csrc[j];
+  a.out[t] = (r < 0 || c < 0) ? 0.0 : (double)a.V[c + (int64_t)r * TS_MC];
 }
 
 }  // namespace rrpgo

@@ -432,6 +432,37 @@ class PoseGraph:
         """HIP-event milliseconds of the last covariance call: (linearise + factor, tree solve, products + gather)."""
         return self._times(_lib.load().rr_pgo_covariances_times)
 
+    # -- Sigma[rows, cols] by a backward solve (include/rr_pgo.h, rr_pgo_cross_covariances) ----
+    def cross_covariance(self, rows, cols):
+        """rr_pgo_cross_covariances: the (R, C) block Sigma[rows, cols] at the current state -- the scalars of the nodes
+        of `rows` stacked in that order by the scalars of the nodes of `cols`, each node's in dx's order.  rows None: every
+        node in node order, so row i is scalar i of dx.  A node may repeat in either list."""
+        L = _lib.load()
+        r = None if rows is None else np.ascontiguousarray(rows, np.int32)
+        c = np.ascontiguousarray(cols, np.int32)
+        if c.ndim != 1 or (r is not None and r.ndim != 1):
+            raise ValueError("rows and cols are flat lists of node indices")
+        nr, nc = (self.num_nodes if r is None else len(r)), len(c)
+        roff, coff = np.zeros(nr + 1, np.int64), np.zeros(nc + 1, np.int64)
+        nv = C.c_int64()
+        pr, pc = (None if r is None else _ip(r)), (_ip(c) if nc else None)
+        pro, pco = roff.ctypes.data_as(C.POINTER(C.c_int64)), coff.ctypes.data_as(C.POINTER(C.c_int64))
+        _check(L.rr_pgo_cross_covariances(self._h, nr, pr, nc, pc, None, pro, pco, C.byref(nv)))
+        out = np.zeros((int(roff[-1]), int(coff[-1])))
+        if nv.value:
+            _check(L.rr_pgo_cross_covariances(self._h, nr, pr, nc, pc, _dp(out), pro, pco, C.byref(nv)))
+        return out
+
+    def covariance_columns(self, cols):
+        """The block columns Sigma[:, cols], (dim, C): how the nodes of `cols` co-vary with every scalar of the graph, for
+        one forward solve on their root paths and one backward sweep of the tree."""
+        return self.cross_covariance(None, cols)
+
+    def cross_covariances_times(self):
+        """HIP-event milliseconds of the last cross_covariance call: (linearise + factor, forward + backward solve,
+        gather + copy)."""
+        return self._times(_lib.load().rr_pgo_cross_covariances_times)
+
     # -- Mahalanobis gate of candidate loop closures (include/rr_pgo.h, rr_pgo_gate_edges) ----
     def gate_edges(self, edge_kind, edge_from, edge_to, edge_meas, edge_info, return_innovation=False):
         """rr_pgo_gate_edges: (d2, chi2) of candidate edges that are not part of the graph, in rr_pgo_graph_desc packing --
