@@ -400,6 +400,49 @@ int rr_pgo_gate_joint(rr_pgo *h, int32_t n_cand,
 /* ms[3]: HIP-event times of the last rr_pgo_gate_joint call -- linearise + factor, tree solve, joint kernel + copy. */
 int rr_pgo_gate_joint_times(const rr_pgo *h, double *ms);
 
+/* ---- audit of the edges that ARE in the graph (build-defined; the reference has none) --------
+ * For queried edge edge[q] (edge == NULL: every edge in order, n_query must be rr_pgo_num_edges; an edge may be listed any
+ * number of times), joining nodes a and b, with e, A, B as for rr_pgo_gate_edges at the current state:
+ *   Omega_w = w Omega                              w: the weight the handle's robust kernel gives the edge at this state (1
+ *                                                  without a kernel or for an unmasked edge); what the edge contributed to H
+ *   P = [A B] Sigma_{ab,ab} [A B]^T                formed as G^T G exactly as for rr_pgo_gate_edges; Sigma = H^-1, H as for
+ *                                                  rr_pgo_covariances (robust weights, priors, fixed nodes, the anchor term
+ *                                                  while both keep_anchor settings say keep)
+ *   R = Omega_w^-1 - P                             the covariance of the edge's residual
+ *   d2_out[q] = e^T R^-1 e                         the leave-one-out distance: to first order the d2 that rr_pgo_gate_edges gives
+ *                                                  the edge as a candidate for the graph without it, at that graph's optimum
+ *                                                  (Woodbury: S_without = Omega_w^-1 R^-1 Omega_w^-1).  Compare with a
+ *                                                  chi-square quantile of d_e degrees of freedom.
+ *   redundancy_out[q] = trace(R Omega_w) / d_e     (may be NULL) in [0, 1].  1: the rest of the graph determines the residual
+ *                                                  completely.  0: a bridge -- an odometry edge on no loop, a landmark seen
+ *                                                  once -- nothing else constrains the edge, R is zero up to rounding and d2
+ *                                                  carries no information: read the redundancy before d2.
+ *   chi2_out[q] = e^T Omega e                      (may be NULL) unweighted, as rr_pgo_edge_errors
+ *   resid_out (may be NULL): R per query, d_e x d_e row-major, packed; resid_offset (may be NULL): [n_query + 1] offsets.
+ * PARTIAL redundancy.  The redundancy is the MEAN of the eigenvalues of R Omega_w, which lie in [0, 1] one per direction of the
+ * residual, and the rest of the graph may determine some directions only: a pose-landmark graph in which nothing but this edge
+ * fixes a pose's heading has edges at redundancy 0.05 .. 0.4 whose R is singular to rounding in one direction.  d2 of such an
+ * edge carries no information either -- NaN, or 1e13 and up, rounding decides -- and removing it would leave that direction
+ * unconstrained.  redundancy_out alone does not show this; resid_out does: take the smallest eigenvalue of
+ * Omega^1/2 R Omega^1/2 against the largest (the Python mirror's redundancy_min and suspect_edges do, and never name such an
+ * edge).  A non-positive pivot of R -- at redundancy near 0, or in such a direction -- gives d2 = NaN.
+ * An endpoint in the fixed set drops out of G;
+ * with both endpoints fixed P = 0, the redundancy is 1 and d2 = e^T Omega_w e.  R is symmetric bit for bit; the bits of an
+ * edge's outputs depend on the graph, the state and that edge alone, not on the rest of the list, its order or repeats.
+ * One linearisation, one factorisation and one tree solve per call on the handle's stream, then one synchronisation; the
+ * state, the Levenberg-Marquardt lambda, rr_pgo_optimize's results, captured graphs and the robust setting are untouched.
+ * The cost grows with the number of distinct endpoint nodes (32 columns per pass over their root paths).
+ * RR_PGO_EUNSUPPORTED first (the message says which): sharded handles, RR_PGO_F32 / RR_PGO_MIXED handles, graphs with fronts
+ * beyond LDS.  RR_PGO_EINVAL, decided before anything is launched or written: n_query < 0, null d2_out with n_query > 0,
+ * edge == NULL with n_query != rr_pgo_num_edges, an edge index out of range.  n_query == 0: RR_PGO_OK, nothing is launched.
+ * RR_PGO_ENOTSPD: a non-positive pivot of H; nothing is written.  RR_PGO_ENOMEM: one edge alone needs more workspace than
+ * the handle's bound (the message gives the bytes); longer lists are cut, which changes no bit. */
+int rr_pgo_check_edges(rr_pgo *h, int32_t n_query, const int32_t *edge,
+                       double *d2_out, double *redundancy_out, double *chi2_out,
+                       double *resid_out, int64_t *resid_offset);
+/* ms[3]: HIP-event times of the last rr_pgo_check_edges call -- linearise + factor, tree solve, kernel + copy. */
+int rr_pgo_check_edges_times(const rr_pgo *h, double *ms);
+
 /* ---- growing a live handle (build-defined; the reference builds a new PoseGraph) --------
  * Append n_new_nodes nodes and n_new_edges edges, in rr_pgo_graph_desc packing.  New nodes get the indices
  * N .. N + n_new_nodes - 1 (N = rr_pgo_num_nodes before the call), new edges come after the existing ones; old node indices,
@@ -441,6 +484,26 @@ int rr_pgo_extend(rr_pgo *h,
 /* ms[3] of the last rr_pgo_extend call: symbolic analysis and engine construction (host wall clock), state carry + initial
  * guess (HIP events). */
 int rr_pgo_extend_times(const rr_pgo *h, double *ms);
+
+/* ---- taking edges out of a live handle (build-defined) --------
+ * Remove the edges edge[0 .. n_remove) (a duplicate counts once).  The remaining edges keep their order and are renumbered
+ * compactly; nodes, node indices and dx offsets do not change.  The anchor rule is applied to what remains -- the from-node of
+ * the first remaining pose-pose edge -- so rr_pgo_anchor_node MAY CHANGE when the first pose-pose edge goes.
+ * After the call the handle is the handle rr_pgo_create would return for the remaining graph, with the handle's options and
+ * under the environment as it is at the call -- except that the device state of every node is the old device state bit for
+ * bit (copied device to device, as rr_pgo_extend carries it).
+ * Carried over: the solver option; the robust kernel's kind and delta; its edge mask with the removed entries cut out (a NULL
+ * mask stays NULL); the prior list with its robust flags; the fixed set; both keep_anchor settings.  NOT carried: what
+ * rr_pgo_extend does not carry.  Atomic as rr_pgo_extend: any failure leaves the handle as it was, with the same bits.
+ * RR_PGO_EINVAL, decided before anything changes: n_remove < 0, null edge with n_remove > 0, an index out of range, a node
+ * left without any edge (the message names the node).  A removal that only disconnects the graph is the caller's
+ * responsibility, as with keep_anchor == 0: the system then ends as RR_PGO_ENOTSPD, and redundancy_out of rr_pgo_check_edges
+ * (0 for a bridge) is the warning.  n_remove == 0: RR_PGO_OK, nothing changes.  RR_PGO_EUNSUPPORTED: sharded handles.
+ * RR_PGO_F32 / RR_PGO_MIXED handles and graphs with fronts beyond LDS are supported: the rebuild is the constructor. */
+int rr_pgo_remove_edges(rr_pgo *h, int32_t n_remove, const int32_t *edge);
+/* ms[3] of the last rr_pgo_remove_edges call: symbolic analysis and engine construction (host wall clock), state carry
+ * (HIP events). */
+int rr_pgo_remove_edges_times(const rr_pgo *h, double *ms);
 
 /* ---- inspection of the assembled system (parity tests) ------------------- */
 

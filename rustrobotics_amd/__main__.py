@@ -334,6 +334,30 @@ def accept_gated(g, path, iterations):
     _reoptimize(g, f"--accept: {len(keep)} of {len(kind)} candidates added ({' '.join(f'{ids[c][0]}-{ids[c][1]}' for c in keep)})", iterations)
 
 
+def check_edges_report(g, remove, iterations):
+    """--check-edges: the edges that disagree with the rest of the graph (rr_pgo_check_edges), worst first; with
+    --remove-suspects they leave the live handle (rr_pgo_remove_edges) and the optimisation runs again."""
+    from .mapping import gate_thresholds
+    ids = {k: v for v, k in _node_index(g).items()}
+    kind, ef, et = g.graph_arrays()[2:5]
+    c = g.check_edges(return_residual=True)
+    suspects = g.suspect_edges(checked=c)      # (from the one query)
+    thr = gate_thresholds(kind)
+    bridges = int((c["redundancy"] < 0.01).sum())
+    from .mapping import SINGULAR_DIRECTION
+    partial = int(((c["redundancy"] >= 0.01) & (c["redundancy_min"] <= SINGULAR_DIRECTION)).sum())
+    print(f"check of {g.num_edges} edges (suspect: redundancy >= 0.01, no direction of the residual unconstrained, d2 above the 0.95 "
+          f"chi-square quantile); {bridges} edges below redundancy 0.01 and {partial} with an unconstrained direction carry no information:")
+    for k in suspects:
+        print(f"edge {k} {ids[int(ef[k])]} {ids[int(et[k])]} d2 {c['d2'][k]:.9g} redundancy {c['redundancy'][k]:.6g} "
+              f"chi2 {c['chi2'][k]:.9g} threshold {thr[k]:g}")
+    if not len(suspects):
+        print("no suspect edge")
+    if remove and len(suspects):
+        g.remove_edges(suspects)
+        _reoptimize(g, f"--remove-suspects: {len(suspects)} edges removed", iterations)
+
+
 def extend_from_file(g, path, guess, iterations):
     nkind, nid, nstate, kind, a, b, meas, info = parse_extend_file(path, _node_index(g), g.num_nodes)
     g.extend(kind, a, b, meas, info, node_kind=nkind if nkind else None,
@@ -437,7 +461,13 @@ def main(argv=None):
                     help="with --extend: ignore the file's vertex values, initialise the new vertices on the device")
     ap.add_argument("--gate-joint", metavar="FILE", default=None,
                     help="after the optimisation gate the SET lines of FILE jointly: D_s, d2, threshold, accept / reject, prefixes")
+    ap.add_argument("--check-edges", action="store_true",
+                    help="after the optimisation audit the graph's own edges: leave-one-out d2, redundancy, e^T Omega e of the suspects")
+    ap.add_argument("--remove-suspects", action="store_true",
+                    help="with --check-edges: take the suspects out of the live handle, optimise again, print chi2 before and after")
     a = ap.parse_args(argv)
+    if a.remove_suspects and not a.check_edges:
+        ap.error("--remove-suspects needs --check-edges")
     if a.accept and not a.gate:
         ap.error("--accept needs --gate FILE")
     if a.cross and not a.columns:
@@ -485,6 +515,8 @@ def main(argv=None):
             accept_gated(g, a.gate, 50 if a.iterations is None else a.iterations)
         if a.extend:
             extend_from_file(g, a.extend, a.guess, 50 if a.iterations is None else a.iterations)
+        if a.check_edges:
+            check_edges_report(g, a.remove_suspects, 50 if a.iterations is None else a.iterations)
         return 0
     iters = 10 if a.iterations is None else a.iterations
     new().optimize(iters, False, False)   # warm-up: library load, HIP context

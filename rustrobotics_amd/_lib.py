@@ -37,6 +37,7 @@ EXPORTS = (
     "rr_pgo_marginals", "rr_pgo_marginals_times", "rr_pgo_covariances", "rr_pgo_covariances_times",
     "rr_pgo_cross_covariances", "rr_pgo_cross_covariances_times",
     "rr_pgo_gate_edges", "rr_pgo_gate_times", "rr_pgo_gate_joint", "rr_pgo_gate_joint_times",
+    "rr_pgo_check_edges", "rr_pgo_check_edges_times", "rr_pgo_remove_edges", "rr_pgo_remove_edges_times",
     "rr_pgo_extend", "rr_pgo_extend_times", "rr_pgo_set_priors", "rr_pgo_num_priors", "rr_pgo_prior_errors",
     "rr_pgo_set_fixed", "rr_pgo_num_fixed", "rr_pgo_get_fixed",
 )
@@ -152,6 +153,10 @@ def load():
     L.rr_pgo_gate_joint_times.argtypes = [vp, dp]
     L.rr_pgo_extend.argtypes = [vp, C.c_int32, ip, C.POINTER(C.c_uint32), dp, C.c_int32, ip, ip, ip, dp, dp]
     L.rr_pgo_extend_times.argtypes = [vp, dp]
+    L.rr_pgo_check_edges.argtypes = [vp, C.c_int32, ip, dp, dp, dp, dp, C.POINTER(C.c_int64)]
+    L.rr_pgo_check_edges_times.argtypes = [vp, dp]
+    L.rr_pgo_remove_edges.argtypes = [vp, C.c_int32, ip]
+    L.rr_pgo_remove_edges_times.argtypes = [vp, dp]
     L.rr_pgo_set_priors.argtypes = [vp, C.c_int32, ip, dp, dp, ip, C.c_int32]
     L.rr_pgo_num_priors.argtypes = [vp]
     L.rr_pgo_num_priors.restype = C.c_int32

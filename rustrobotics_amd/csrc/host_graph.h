@@ -70,6 +70,41 @@ struct HostGraph {
   std::string finalize();
 };
 
+// rr_pgo_remove_edges: the lowest node that has an edge now and none once the edges flagged in `gone` are taken out, -1: none
+inline int first_orphan_node(int n_nodes, int n_edges, const int32_t *from, const int32_t *to, const char *gone) {
+  std::vector<int32_t> before((size_t)n_nodes, 0), after((size_t)n_nodes, 0);
+  for (int k = 0; k < n_edges; k++)
+    for (const int v : {from[k], to[k]}) {
+      before[(size_t)v]++;
+      if (!gone[k]) after[(size_t)v]++;
+    }
+  for (int v = 0; v < n_nodes; v++)
+    if (before[(size_t)v] > 0 && after[(size_t)v] == 0) return v;
+  return -1;
+}
+
+// rr_pgo_remove_edges: g = og without the edges flagged in `gone` -- the nodes as they are, the remaining edges in their order
+// (so compactly renumbered), their measurements and information packed anew; g is not finalized.  Returns the old index of
+// every edge of g.
+inline std::vector<int32_t> copy_without_edges(const HostGraph &og, const char *gone, HostGraph &g) {
+  g.node_kind = og.node_kind;
+  g.node_id = og.node_id;
+  g.node_state = og.node_state;
+  std::vector<int32_t> keep;
+  for (int k = 0; k < og.n_edges(); k++) {
+    if (gone[k]) continue;
+    const int ek = og.edge_kind[k];
+    keep.push_back(k);
+    g.edge_kind.push_back(ek);
+    g.edge_from.push_back(og.edge_from[k]);
+    g.edge_to.push_back(og.edge_to[k]);
+    const double *m = &og.edge_meas[og.edge_meas_off[k]], *w = &og.edge_info[og.edge_info_off[k]];
+    g.edge_meas.insert(g.edge_meas.end(), m, m + edge_meas_len(ek));
+    g.edge_info.insert(g.edge_info.end(), w, w + edge_info_len(ek));
+  }
+  return keep;
+}
+
 // parse_g2o, g2o.rs:35-143.  Returns "" or an error message; io_error set when
 // the file could not be read (Err(io) in the reference) as opposed to malformed.
 std::string load_g2o(const char *path, HostGraph &g, bool &io_error);

@@ -251,7 +251,7 @@ struct PriorSet {
 };
 
 struct EngineBase {
-  enum Query { Q_MARGINALS, Q_COVARIANCES, Q_GATE, Q_GATE_JOINT, Q_CROSS };   // the factor queries, in the order of their ABI functions
+  enum Query { Q_MARGINALS, Q_COVARIANCES, Q_GATE, Q_GATE_JOINT, Q_CROSS, Q_CHECK, N_QUERY };   // the factor queries, in the order of their ABI functions
   virtual ~EngineBase() = default;
   virtual void chi2(double *out) = 0;
   virtual void linearize_solve(double lambda, int lm, double *dx_out) = 0;
@@ -293,6 +293,11 @@ struct EngineBase {
   // of the innovation covariances in innov; chi2 and innov may be null) / rr_pgo_gate_times
   virtual void gate_edges(int n, const int32_t *from, const int32_t *to, const int64_t *soff, std::vector<GateCand> &cand,
                           double *d2, double *chi2, double *innov) = 0;
+  // rr_pgo_check_edges (arguments checked; cand: the queried edges' records as for gate_edges, pad = the mask bit; soff: [n + 1]
+  // offsets of the residual covariances in resid; red, chi2 and resid may be null) / rr_pgo_check_edges_times
+  virtual void check_edges(int n, const int32_t *from, const int32_t *to, const int64_t *soff, std::vector<GateCand> &cand,
+                           double *d2, double *red, double *chi2, double *resid) = 0;
+  virtual void refuse_factor_query(const char *who) const = 0;   // what every factor query refuses, before its arguments are read
   // rr_pgo_gate_joint (arguments checked; set s is the records [set_ptr[s], set_ptr[s + 1]) of from / to / cand, the sets
   // expanded one after the other; dim: D_s; ioff: [n_sets + 1] offsets of the sets' S in innov; prefix and innov may be null) /
   // rr_pgo_gate_joint_times
@@ -302,7 +307,7 @@ struct EngineBase {
   // column node in out, R x C row-major) / rr_pgo_cross_covariances_times
   virtual void cross_covariances(int n_row, const int32_t *row_node, int n_col, const int32_t *col_node, const int64_t *roff,
                                  const int64_t *coff, double *out) = 0;
-  // the five rr_pgo_*_times: the three phases of the last call of query `which`, in ms
+  // the six rr_pgo_*_times: the three phases of the last call of query `which`, in ms
   virtual void last_query_times(Query which, double *ms) const = 0;
   // rr_pgo_extend (arguments checked).  The state buffer is in node order, so a grown graph's buffer starts with the old one.
   virtual const void *pose_dev() const = 0;
@@ -517,7 +522,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   EventHolder query_ev_[4];
   // the last call of each query (EngineBase::Query): linearise + factor | selected inverse or tree solve | the query's own
   // kernel (gather; products + gather; gate kernel + copy; joint kernel + copy; gather + copy)
-  double query_ms_[5][3] = {};
+  double query_ms_[N_QUERY][3] = {};
   // marginal covariances (selinv.hip.h; rr_pgo_marginals): everything made on the first call
   DevBuf<T> svals_;                  // the selected inverse, a front's image laid out like its factor image (less the rhs row)
   DevBuf<SelMeta> sel_meta_;
@@ -3429,6 +3434,51 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     }
   }
 
+  // ---- audit of the graph's own edges (include/rr_pgo.h, rr_pgo_check_edges; treesolve.hip.h, k_check_edges): the gate's plan
+  // and records, for edges of the graph; the robust kind and delta travel in the arguments
+  void refuse_factor_query(const char *who) const override { require_f64_unsharded_lds_factor(who); }
+  void check_edges(int n, const int32_t *from, const int32_t *to, const int64_t *soff, std::vector<GateCand> &cand, double *d2,
+                   double *red, double *chi2, double *resid) override {
+    static constexpr const char *who = "rr_pgo_check_edges";
+    require_f64_unsharded_lds_factor(who);
+    if constexpr (f64_) {
+      covariances_prepare(who);
+      auto n_resid = [&](int c0, int c1) { return resid ? (size_t)(soff[c1] - soff[c0]) : 0; };
+      tree_query(who, "edge", n, from, to, soff, query_ms_[Q_CHECK], true, [&](int c0, int c1, const TsPlan &pl) {
+        const size_t nc = (size_t)(c1 - c0);
+        for (int c = c0; c < c1; c++) {
+          cand[c].cq = pl.query[c - c0];
+          cand[c].fa = front_of(from[c]);
+          cand[c].fb = front_of(to[c]);
+        }
+        ts_grow(gate_cand_, nc);
+        HIPCHK(hipMemcpyAsync(gate_cand_.p, cand.data() + c0, nc * sizeof(GateCand), hipMemcpyHostToDevice, stream_));
+        ts_grow(ts_out_, 3 * nc + n_resid(c0, c1));
+      }, [&](int c0, int c1) {
+        const size_t nc = (size_t)(c1 - c0);
+        CheckArgs<T> a;
+        a.meta = ts_meta_.p;
+        a.cand = gate_cand_.p;
+        a.czrow = ts_czrow_.p;
+        a.Z = ts_z_.p;
+        a.pose = pose_.p;
+        a.d2 = ts_out_.p;
+        a.chi2 = ts_out_.p + nc;
+        a.red = ts_out_.p + 2 * nc;
+        a.rout = resid ? ts_out_.p + 3 * nc : nullptr;
+        a.delta = (T)robust_delta_;
+        a.delta2 = (T)(robust_delta_ * robust_delta_);
+        a.S = sym_.S;
+        a.rkind = robust_kind_;
+        if (is3d_) hipLaunchKernelGGL((k_check_edges<T, 6>), dim3((unsigned)nc), dim3(COV_THREADS), 0, stream_, a);
+        else hipLaunchKernelGGL((k_check_edges<T, 3>), dim3((unsigned)nc), dim3(COV_THREADS), 0, stream_, a);
+        check_launch("k_check_edges");
+        return std::array<TsDest, 4>{{{d2 + c0, nc}, {chi2 ? chi2 + c0 : nullptr, nc}, {red ? red + c0 : nullptr, nc},
+                                      {resid ? resid + soff[c0] : nullptr, n_resid(c0, c1)}}};
+      });
+    }
+  }
+
   // ---- joint compatibility of sets of candidate edges (include/rr_pgo.h, rr_pgo_gate_joint; treesolve.hip.h, k_gate_joint):
   // the plan is the covariance plan of the sets' pairs (from, to), one after the other, cut at set boundaries only
   void gate_joint(int n_sets, const int32_t *set_ptr, const int32_t *from, const int32_t *to, const int32_t *dim,
@@ -3639,6 +3689,7 @@ struct rr_pgo {
   std::vector<int32_t> blk_rows, blk_cols;   // assemble() block list
   std::vector<int64_t> blk_offs;
   double extend_ms[3] = {0, 0, 0};   // the last rr_pgo_extend: analysis, engine (host wall clock), state carry + guess (HIP events)
+  double remove_ms[3] = {0, 0, 0};   // the last rr_pgo_remove_edges: analysis, engine (host wall clock), state carry (HIP events)
 };
 
 struct rr_pgo_synth {
@@ -4151,6 +4202,54 @@ static void extend_handle(rr_pgo *h, int32_t n_new_nodes, const int32_t *node_ki
   h->extend_ms[2] = ms_dev;
 }
 
+// rr_pgo_remove_edges behind its argument checks: the graph without the listed edges, its analysis and engine built completely,
+// the device state and the settings carried as rr_pgo_extend carries them, then the swap
+static void remove_handle(rr_pgo *h, int32_t n_remove, const int32_t *edge) {
+  const HostGraph &og = *h->g;
+  const int N = og.n_nodes(), E = og.n_edges();
+  std::vector<char> gone((size_t)E, 0);
+  for (int q = 0; q < n_remove; q++) {
+    if (edge[q] < 0 || edge[q] >= E)
+      throw ApiError(RR_PGO_EINVAL, "rr_pgo_remove_edges: entry " + std::to_string(q) + ": edge index " + std::to_string(edge[q]) + " out of range");
+    gone[edge[q]] = 1;   // a duplicate counts once
+  }
+  const int orphan = first_orphan_node(N, E, og.edge_from.data(), og.edge_to.data(), gone.data());
+  if (orphan >= 0)
+    throw ApiError(RR_PGO_EINVAL, "rr_pgo_remove_edges: node " + std::to_string(orphan) + " would be left without any edge");
+  // ---- the remaining graph: edges in their order, renumbered compactly; nodes as they are
+  auto nh = std::make_unique<rr_pgo>();
+  HostGraph &g = *nh->g;
+  const std::vector<int32_t> keep = copy_without_edges(og, gone.data(), g);
+  const std::string err = g.finalize();   // (the anchor rule on what remains)
+  if (!err.empty()) throw ApiError(RR_PGO_EINVAL, "rr_pgo_remove_edges: " + err);
+  // ---- from here on the device.  The old stream is drained: its last launches wrote the state that is carried.
+  HIPCHK(hipStreamSynchronize(h->engine->stream()));
+  const double t0 = now_ms();
+  analyze_handle(*nh, &h->opt, 0.0);
+  const double t1 = now_ms();
+  build_engine(*nh);
+  const double t2 = now_ms();
+  double ms_dev = 0;
+  nh->engine->adopt_state(h->engine->pose_dev(), (size_t)N, &ms_dev);
+  int rk = ROBUST_NONE;
+  double rdelta = 1.0;
+  bool masked = false;
+  std::vector<int32_t> mask, kept_mask;
+  h->engine->robust_setting(&rk, &rdelta, &masked, mask);
+  if (rk != ROBUST_NONE) {
+    if (masked)
+      for (int k : keep) kept_mask.push_back(mask[k]);
+    nh->engine->set_robust(rk, rdelta, masked ? kept_mask.data() : nullptr);
+  }
+  if (h->engine->priors().n() > 0) apply_priors(*nh, h->engine->priors());   // node indices do not change
+  if (!h->engine->fixed().empty()) nh->engine->set_fixed(h->engine->fixed(), h->engine->fixed_keep_anchor());
+  // ---- the swap, as in extend_handle: nothing below can fail
+  std::swap(*h, *nh);
+  h->remove_ms[0] = t1 - t0;
+  h->remove_ms[1] = t2 - t1;
+  h->remove_ms[2] = ms_dev;
+}
+
 }  // namespace
 
 extern "C" {
@@ -4175,6 +4274,24 @@ int rr_pgo_extend(rr_pgo *h, int32_t n_new_nodes, const int32_t *node_kind, cons
 int rr_pgo_extend_times(const rr_pgo *h, double *ms) {
   if (!h || !ms) { g_last_error = "null argument"; return RR_PGO_EINVAL; }
   for (int i = 0; i < 3; i++) ms[i] = h->extend_ms[i];
+  return RR_PGO_OK;
+}
+
+int rr_pgo_remove_edges(rr_pgo *h, int32_t n_remove, const int32_t *edge) {
+  if (!h) { g_last_error = "rr_pgo_remove_edges: no handle"; return RR_PGO_EINVAL; }
+  if (n_remove < 0) { g_last_error = "rr_pgo_remove_edges: n_remove < 0"; return RR_PGO_EINVAL; }
+  if (n_remove > 0 && !edge) { g_last_error = "rr_pgo_remove_edges: null argument (edge is required)"; return RR_PGO_EINVAL; }
+  if (h->opt.world_size > 1 || h->opt.sharded) {
+    g_last_error = "rr_pgo_remove_edges: sharded handle (every rank would have to shrink and re-partition the same graph): create new handles on the remaining graph";
+    return RR_PGO_EUNSUPPORTED;
+  }
+  if (n_remove == 0) return RR_PGO_OK;
+  return guarded([&] { remove_handle(h, n_remove, edge); });
+}
+
+int rr_pgo_remove_edges_times(const rr_pgo *h, double *ms) {
+  if (!h || !ms) { g_last_error = "null argument"; return RR_PGO_EINVAL; }
+  for (int i = 0; i < 3; i++) ms[i] = h->remove_ms[i];
   return RR_PGO_OK;
 }
 
@@ -4447,14 +4564,14 @@ static bool small_cholesky(double *w, int d, int ld) {
 // their records -- kind, nodes, measurement, Omega and Omega^-1 -- with soff, the [n_cand + 1] offsets of d_e x d_e blocks
 static int gate_candidates(const char *api, const rr_pgo *h, int32_t n_cand, const int32_t *edge_kind, const int32_t *edge_from,
                            const int32_t *edge_to, const double *edge_meas, const double *edge_info, std::vector<GateCand> &cand,
-                           std::vector<int64_t> &soff) {
+                           std::vector<int64_t> &soff, const char *what = "candidate") {
   const HostGraph &g = *h->g;
   const int N = g.n_nodes(), D = g.has_se3 ? 6 : 3;
   cand.assign((size_t)n_cand, GateCand{});
   soff.assign((size_t)n_cand + 1, 0);
   int64_t mo = 0, io = 0;
   for (int c = 0; c < n_cand; c++) {
-    const std::string who = std::string(api) + ": candidate " + std::to_string(c) + ": ";
+    const std::string who = std::string(api) + ": " + what + " " + std::to_string(c) + ": ";
     auto bad = [&](const std::string &what) { g_last_error = who + what; return RR_PGO_EINVAL; };
     const int kind = edge_kind[c], a = edge_from[c], b = edge_to[c];
     if (kind != EDGE_SE2 && kind != EDGE_SE2_XY && kind != EDGE_SE3) return bad("unknown edge kind " + std::to_string(kind));
@@ -4643,6 +4760,54 @@ int rr_pgo_gate_joint(rr_pgo *h, int32_t n_cand, const int32_t *edge_kind, const
 int rr_pgo_gate_joint_times(const rr_pgo *h, double *ms) {
   if (!h || !ms) { g_last_error = "null argument"; return RR_PGO_EINVAL; }
   return guarded([&] { h->engine->last_query_times(EngineBase::Q_GATE_JOINT, ms); });
+}
+
+int rr_pgo_check_edges(rr_pgo *h, int32_t n_query, const int32_t *edge, double *d2_out, double *redundancy_out, double *chi2_out,
+                       double *resid_out, int64_t *resid_offset) {
+  static constexpr const char *api = "rr_pgo_check_edges";
+  auto bad = [&](const std::string &what) { g_last_error = std::string(api) + ": " + what; return RR_PGO_EINVAL; };
+  if (!h) return bad("no handle");
+  if (const int rc = guarded([&] { h->engine->refuse_factor_query(api); })) return rc;
+  const HostGraph &g = *h->g;
+  const int E = g.n_edges();
+  if (n_query < 0) return bad("n_query < 0");
+  if (n_query == 0) {
+    if (resid_offset) resid_offset[0] = 0;
+    return RR_PGO_OK;
+  }
+  if (!d2_out) return bad("null argument (d2_out is required)");
+  if (!edge && n_query != E) return bad("edge == NULL means every edge: n_query must be rr_pgo_num_edges = " + std::to_string(E));
+  for (int q = 0; edge && q < n_query; q++)
+    if (edge[q] < 0 || edge[q] >= E) return bad("query " + std::to_string(q) + ": edge index " + std::to_string(edge[q]) + " out of range");
+  // ---- the queried edges as the gate's candidates, from the host copy of the graph
+  std::vector<int32_t> kind((size_t)n_query), from((size_t)n_query), to((size_t)n_query);
+  std::vector<double> meas, info;
+  for (int q = 0; q < n_query; q++) {
+    const int k = edge ? edge[q] : q, ek = g.edge_kind[k];
+    kind[q] = ek;
+    from[q] = g.edge_from[k];
+    to[q] = g.edge_to[k];
+    const double *m = &g.edge_meas[g.edge_meas_off[k]], *w = &g.edge_info[g.edge_info_off[k]];
+    meas.insert(meas.end(), m, m + edge_meas_len(ek));
+    info.insert(info.end(), w, w + edge_info_len(ek));
+  }
+  std::vector<GateCand> cand;
+  std::vector<int64_t> soff;
+  if (const int rc = gate_candidates(api, h, n_query, kind.data(), from.data(), to.data(), meas.data(), info.data(), cand, soff, "query")) return rc;
+  int rk = ROBUST_NONE;
+  double rdelta = 1.0;
+  bool masked = false;
+  std::vector<int32_t> mask;
+  h->engine->robust_setting(&rk, &rdelta, &masked, mask);
+  for (int q = 0; q < n_query; q++) cand[q].pad = rk != ROBUST_NONE && (!masked || mask[edge ? edge[q] : q]) ? 1 : 0;
+  const int rc = guarded([&] { h->engine->check_edges(n_query, from.data(), to.data(), soff.data(), cand, d2_out, redundancy_out, chi2_out, resid_out); });
+  if (rc == RR_PGO_OK && resid_offset) std::copy(soff.begin(), soff.end(), resid_offset);
+  return rc;
+}
+
+int rr_pgo_check_edges_times(const rr_pgo *h, double *ms) {
+  if (!h || !ms) { g_last_error = "null argument"; return RR_PGO_EINVAL; }
+  return guarded([&] { h->engine->last_query_times(EngineBase::Q_CHECK, ms); });
 }
 
 int rr_pgo_iterate_async(rr_pgo *h, int32_t iters) {

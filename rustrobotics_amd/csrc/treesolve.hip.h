@@ -8,6 +8,7 @@
 //   k_tree_fwd    one workgroup per (chunk of TS_MC columns, active front), one launch per level of the tree, deepest first
 //   k_cov_pairs   one workgroup per query: Sigma_ab = sum over the common path's pivot rows of Z_a[row]^T Z_b[row]
 //   k_gate_pairs  one workgroup per candidate edge: its Mahalanobis distance from the same Z
+//   k_check_edges one workgroup per edge of the graph: its leave-one-out distance and redundancy from the same Z
 //   k_gate_joint  one workgroup per set of candidate edges: their joint distance from the same Z
 //   k_tree_bwd    one workgroup per (chunk, backward-active front), one launch per level, root level first: X = L^-T Z
 //   k_cross_gather  the rectangular block Sigma[rows, cols] out of X (the end of this file)
@@ -376,6 +377,121 @@ __global__ void __launch_bounds__(COV_THREADS) k_gate_pairs(GateArgs<T> a) {
     }
     a.chi2[blockIdx.x] = (double)c2;
     // S = L L^T in place (lower triangle), y = L^-1 e, d2 = y^T y
+    bool ok = true;
+    T d2 = 0;
+    for (int c = 0; c < de; c++) {
+      T d = sS[c * D + c];
+      for (int k = 0; k < c; k++) d = fma(-sS[c * D + k], sS[c * D + k], d);
+      if (!(d > (T)0)) { ok = false; break; }
+      const T l = sqrt(d), inv = (T)1 / l;
+      sS[c * D + c] = l;
+      for (int r = c + 1; r < de; r++) {
+        T v = sS[r * D + c];
+        for (int k = 0; k < c; k++) v = fma(-sS[r * D + k], sS[c * D + k], v);
+        sS[r * D + c] = v * inv;
+      }
+      T y = se[c];
+      for (int k = 0; k < c; k++) y = fma(-sS[c * D + k], se[k], y);
+      y *= inv;
+      se[c] = y;
+      d2 = fma(y, y, d2);
+    }
+    a.d2[blockIdx.x] = ok ? (double)d2 : __builtin_nan("");
+  }
+}
+
+// ---- audit of the graph's own edges (rr_pgo_check_edges)
+//
+// For edge c of the graph with error e, Jacobians A, B, information Omega and robust weight w at the current state:
+//   Omega_w = w Omega (what the edge gave H),   P = G^T G as above,   R = Omega_w^-1 - P = Omega^-1 / w - P,
+//   d2 = e^T R^-1 e (the gate's distance of the edge against the graph without it, to first order),
+//   r = trace(R Omega_w) / d_e (1: the rest of the graph determines the residual; 0: a bridge, R = 0 up to rounding).
+// The record is the gate's; its pad word holds the mask bit (1: the handle's robust kernel applies to this edge).
+template <typename T> struct CheckArgs {
+  const TsMeta *meta;
+  const GateCand *cand;
+  const int32_t *czrow;           // as CovArgs
+  const T *Z;
+  const typename VecT<T>::V4 *pose;
+  double *d2, *chi2, *red, *rout; // rout null: R is not asked for
+  T delta, delta2;                // of the robust kernel
+  int32_t S, rkind;               // rkind: ROBUST_*
+};
+
+// One workgroup per queried edge; D as in k_gate_pairs, and the same walk.  Lane 0 of wave 0 has s = e^T Omega e and w(s) ready
+// (the linearisation's own robust_weight) when the slices are added: entry (i, j) of the lower triangle is
+// Omega^-1(i, j) / w - P(i, j), mirrored, so R is symmetric bit for bit.  r is summed row by row, column by column, by one
+// lane.  A non-positive pivot of R (an edge at r near 0, or one whose residual the rest of the graph determines in some
+// directions only: rounding decides) gives d2 = NaN; r and R are written all the same.
+template <typename T, int D>
+__global__ void __launch_bounds__(COV_THREADS) k_check_edges(CheckArgs<T> a) {
+  constexpr int NS = COV_THREADS / 64;
+  __shared__ T part[NS * 32], sA[D * D], sB[D * D], se[D], sS[D * D], sw[1];
+  const GateCand *q = a.cand + blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63, slice = wave_index();
+  const int kind = q->kind;
+  const int de = kind == 1 ? 2 : D, db = kind == 1 ? 2 : D, ntri = de * (de + 1) / 2;
+  if (lane == 0 && slice < 2) gate_linearize<T, D>(q, a.pose, slice, se, sA, sB);
+  __syncthreads();
+  if (tid == 0) {
+    T W[D][D], e[D];   // e^T Omega e by the linearisation's own edge_chi2 (Omega and a landmark edge's e are zero padded)
+#pragma unroll
+    for (int r = 0; r < D; r++) {
+      e[r] = r < de ? se[r] : (T)0;
+#pragma unroll
+      for (int c = 0; c < D; c++) W[r][c] = (T)q->info[r * D + c];
+    }
+    const T c2 = edge_chi2<D, T>(W, e);
+    T w = 1;
+    if (q->pad & 1) {
+      if (a.rkind == ROBUST_HUBER) w = robust_weight<ROBUST_HUBER, T>(c2, a.delta, a.delta2);
+      else if (a.rkind == ROBUST_CAUCHY) w = robust_weight<ROBUST_CAUCHY, T>(c2, a.delta, a.delta2);
+    }
+    a.chi2[blockIdx.x] = (double)c2;
+    sw[0] = w;
+  }
+  // ---- entry t = (i, j), j <= i, of the lower triangle; lanes past the triangle repeat its last entry
+  const int t = min(lane, ntri - 1);
+  int i = 0;
+  while ((i + 1) * (i + 2) / 2 <= t) i++;
+  const int j = t - i * (i + 1) / 2;
+  T Ai[D], Aj[D], Bi[D], Bj[D];
+  int cola[D], colb[D];
+#pragma unroll
+  for (int k = 0; k < D; k++) {
+    Ai[k] = sA[i * D + k];
+    Aj[k] = sA[j * D + k];
+    Bi[k] = sB[i * D + k];   // (the columns of B past d_b are zero: pose-landmark)
+    Bj[k] = sB[j * D + k];
+    cola[k] = q->cq.ca[k];
+    colb[k] = q->cq.cb[min(k, db - 1)];
+  }
+  const int32_t *za_tab = a.czrow + (int64_t)q->cq.chunk_a * a.S, *zb_tab = a.czrow + (int64_t)q->cq.chunk_b * a.S;
+  const int lca = q->cq.lca;
+  T acc = 0;
+  acc = gate_walk<T, D, true, false>(a.meta, a.Z, za_tab, zb_tab, q->fa, lca, slice, NS, cola, colb, Ai, Aj, Bi, Bj, acc);
+  acc = gate_walk<T, D, false, true>(a.meta, a.Z, za_tab, zb_tab, q->fb, lca, slice, NS, cola, colb, Ai, Aj, Bi, Bj, acc);
+  if (lca >= 0) acc = gate_walk<T, D, true, true>(a.meta, a.Z, za_tab, zb_tab, lca, -1, slice, NS, cola, colb, Ai, Aj, Bi, Bj, acc);
+  if (lane < 32) part[slice * 32 + lane] = acc;
+  __syncthreads();
+  if (tid < ntri) {
+    T s = part[tid];
+#pragma unroll
+    for (int k = 1; k < NS; k++) s += part[k * 32 + tid];
+    const T r = (T)q->cov[i * D + j] / sw[0] - s;
+    sS[i * D + j] = r;
+    sS[j * D + i] = r;
+  }
+  __syncthreads();
+  if (a.rout && tid < de * de) a.rout[q->cq.ooff + tid] = (double)sS[(tid / de) * D + tid % de];   // both halves from the lower triangle
+  __syncthreads();
+  if (tid == 0) {
+    const T w = sw[0];
+    T tr = 0;   // trace(R Omega_w)
+    for (int r = 0; r < de; r++)
+      for (int c = 0; c < de; c++) tr = fma(sS[r * D + c], w * (T)q->info[c * D + r], tr);
+    a.red[blockIdx.x] = (double)(tr / (T)de);
+    // R = L L^T in place (lower triangle), y = L^-1 e, d2 = y^T y
     bool ok = true;
     T d2 = 0;
     for (int c = 0; c < de; c++) {

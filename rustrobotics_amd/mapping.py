@@ -72,6 +72,36 @@ def gate_joint_thresholds(edge_kind, sets, threshold=None):
     return np.full(dims.shape, float(threshold))
 
 
+def directional_redundancy(R, omega, redundancy):
+    """The smallest redundancy of an edge over the directions of its residual.  The eigenvalues of R Omega_w lie in [0, 1]
+    and their mean is the redundancy r; the smallest one says how well the rest of the graph determines the WORST determined
+    direction.  It is 0 when part of the residual is a bridge -- a pose seen by one landmark only has its heading fixed by
+    nothing else, whatever r says -- and R is then singular to rounding and d2 carries no information (NaN, or a huge
+    number that rounding picks).  R, omega: d_e x d_e, omega the UNWEIGHTED information; the robust weight cancels:
+    lambda_min(R Omega_w) = r d_e lambda_min(R Omega) / trace(R Omega)."""
+    L = np.linalg.cholesky(np.asarray(omega, np.float64))
+    lam = np.linalg.eigvalsh(L.T @ np.asarray(R, np.float64) @ L)
+    tr = float(np.sum(lam))
+    return float(redundancy) * len(lam) * float(lam[0]) / tr if tr > 0.0 else 0.0
+
+
+# An eigenvalue of R Omega_w below this is not told from 0: R = Omega_w^-1 - P is a difference of matrices of size 1, and half
+# of the 16 digits is the usual line between a number and its rounding (the numerical-rank convention).
+SINGULAR_DIRECTION = float(np.sqrt(np.finfo(np.float64).eps))
+
+
+def select_suspects(kind, d2, redundancy, redundancy_min, threshold=None, min_redundancy=0.01, min_directional=SINGULAR_DIRECTION):
+    """Positions of the suspects among checked edges, by falling d2: redundancy at least min_redundancy, no direction of the
+    residual that nothing else constrains (the smallest directional redundancy above min_directional: R is singular to
+    rounding otherwise, and d2 is NaN or a number that rounding picks), and d2 above the threshold of
+    gate_thresholds(kind, threshold).  A NaN d2 is no suspect."""
+    d2 = np.asarray(d2, np.float64)
+    ok = (np.asarray(redundancy) >= min_redundancy) & (np.asarray(redundancy_min) > min_directional)
+    with np.errstate(invalid="ignore"):
+        hit = np.flatnonzero(ok & (d2 > gate_thresholds(kind, threshold)))
+    return hit[np.argsort(-d2[hit], kind="stable")]
+
+
 def _check(rc):
     if rc != 0:
         raise PoseGraphError(rc, _lib.load().rr_pgo_last_error().decode())
@@ -587,6 +617,63 @@ class PoseGraph:
         """Milliseconds of the last extend call: (symbolic analysis, engine construction -- host wall clock; state carry +
         initial guess -- HIP events)."""
         return self._times(_lib.load().rr_pgo_extend_times)
+
+    # -- audit of the graph's own edges (include/rr_pgo.h, rr_pgo_check_edges, rr_pgo_remove_edges) ----
+    def check_edges(self, edges=None, return_residual=False):
+        """rr_pgo_check_edges: a dict with, per queried edge (None: every edge), d2 = e^T R^-1 e -- the leave-one-out
+        distance, R = Omega_w^-1 - J Sigma J^T the covariance of the residual -- redundancy = trace(R Omega_w) / d_e in
+        [0, 1] (0: a bridge, d2 then says nothing) and chi2 = e^T Omega e.  With return_residual also R, the list of the
+        d_e x d_e matrices, and redundancy_min, the smallest directional redundancy (directional_redundancy): where it is
+        near 0 part of the residual is a bridge and d2 says nothing either, whatever the mean r is."""
+        L = _lib.load()
+        idx = None if edges is None else np.ascontiguousarray(edges, np.int32).ravel()
+        n = self.num_edges if idx is None else len(idx)
+        d2, red, chi2 = np.zeros(n), np.zeros(n), np.zeros(n)
+        off = np.zeros(n + 1, np.int64)
+        vals = np.zeros(36 * max(n, 1)) if return_residual else None
+        _check(L.rr_pgo_check_edges(self._h, n, None if idx is None else _ip(idx), _dp(d2), _dp(red), _dp(chi2),
+                                    None if vals is None else _dp(vals), off.ctypes.data_as(C.POINTER(C.c_int64))))
+        out = {"d2": d2, "redundancy": red, "chi2": chi2}
+        if return_residual:
+            dims = [int(round(np.sqrt(off[c + 1] - off[c]))) for c in range(n)]
+            out["R"] = [vals[off[c]:off[c + 1]].reshape(dims[c], dims[c]).copy() for c in range(n)]
+            ek, ei = self.graph_arrays()[2], self.graph_arrays()[6]
+            io = np.concatenate([[0], np.cumsum(np.take(GATE_INFO_LEN, ek))]).astype(int)
+            rmin = np.zeros(n)
+            for c in range(n):
+                k = c if idx is None else int(idx[c])
+                W = np.zeros((dims[c], dims[c]))
+                W[np.triu_indices(dims[c])] = ei[io[k]:io[k + 1]]
+                rmin[c] = directional_redundancy(out["R"][c], W + np.triu(W, 1).T, red[c])
+            out["redundancy_min"] = rmin
+        return out
+
+    def suspect_edges(self, threshold=None, min_redundancy=0.01, edges=None, checked=None, min_directional=SINGULAR_DIRECTION):
+        """Indices of the edges (of `edges`; None: every edge) that disagree with the rest of the graph: redundancy at least
+        min_redundancy and d2 above the threshold -- a scalar, a mapping from edge kind to a scalar, or None: the 0.95
+        chi-square quantile of the edge's dimension -- sorted by falling d2.  An edge part of whose residual nothing else
+        constrains (smallest directional redundancy at most min_directional: R singular to rounding, d2 meaningless
+        whatever r says) is never named.  checked: the result of check_edges(edges, return_residual=True), if the caller
+        has it already."""
+        idx = np.arange(self.num_edges, dtype=np.int32) if edges is None else np.ascontiguousarray(edges, np.int32).ravel()
+        c = self.check_edges(None if edges is None else idx, return_residual=True) if checked is None else checked
+        kind = self.graph_arrays()[2][idx]
+        return idx[select_suspects(kind, c["d2"], c["redundancy"], c["redundancy_min"], threshold, min_redundancy, min_directional)]
+
+    def check_edges_times(self):
+        """HIP-event milliseconds of the last check_edges call: (linearise + factor, tree solve, kernel + copy)."""
+        return self._times(_lib.load().rr_pgo_check_edges_times)
+
+    def remove_edges(self, edges):
+        """rr_pgo_remove_edges: take the listed edges out of this handle (a duplicate counts once).  The remaining edges keep
+        their order and are renumbered compactly; the estimate stays on the device, bit for bit; anchor_node may change."""
+        idx = np.ascontiguousarray(edges, np.int32).ravel()
+        _check(_lib.load().rr_pgo_remove_edges(self._h, len(idx), _ip(idx)))
+
+    def remove_edges_times(self):
+        """Milliseconds of the last remove_edges call: (symbolic analysis, engine construction -- host wall clock; state
+        carry -- HIP events)."""
+        return self._times(_lib.load().rr_pgo_remove_edges_times)
 
     # -- PoseGraph::plot, :375-431 -------------------------------------------------------
     def plot_data(self):
