@@ -60,8 +60,25 @@ enum {
 /* enum PoseGraphSolver, pose_graph_optimization.rs:28-32 */
 enum { RR_PGO_GAUSS_NEWTON = 0, RR_PGO_LEVENBERG_MARQUARDT = 1 };
 /* enum Node variants, :147-154 ; enum Edge variants, :20-26 */
-enum { RR_PGO_NODE_SE2 = 0, RR_PGO_NODE_XY = 1, RR_PGO_NODE_SE3 = 2 };
-enum { RR_PGO_EDGE_SE2 = 0, RR_PGO_EDGE_SE2_XY = 1, RR_PGO_EDGE_SE3 = 2 };
+enum { RR_PGO_NODE_SE2 = 0, RR_PGO_NODE_XY = 1, RR_PGO_NODE_SE3 = 2, RR_PGO_NODE_XYZ = 3 };
+enum { RR_PGO_EDGE_SE2 = 0, RR_PGO_EDGE_SE2_XY = 1, RR_PGO_EDGE_SE3 = 2, RR_PGO_EDGE_SE3_XYZ = 3 };
+/* 3-D point landmarks: RR_PGO_NODE_XYZ and RR_PGO_EDGE_SE3_XYZ (build-defined; the reference has none).
+ *   node   state x y z, 3 scalars of the step, additive: l <- l + sign * dl, no renormalisation.
+ *   edge   from an SE3 pose (t, q) to an XYZ landmark l, measurement z = x y z, information 6 values (3 x 3 upper triangle,
+ *          row-major).  With p = R(q)^T (l - t), the landmark in the pose's frame, e = p - z (3 scalars): g2o's
+ *          EDGE_SE3_TRACKXYZ with an identity sensor offset.  Under the library's increments (the pose's right increment
+ *          X <- X (dt, Exp(dw)), the landmark's addition) the Jacobians are A = [ -I | [p]x ] and B = R(q)^T; the tests pin
+ *          both to central differences in 50-digit arithmetic.
+ *   graph  an XYZ node counts as 3-D: with SE2 or XY nodes the graph is "mixed 2D / 3D" and refused.  The edge is not a
+ *          pose-pose edge and never sets rr_pgo_anchor_node; landmarks without any pose-pose edge leave the anchor at -1, as in 2-D.
+ *   prior  on an XYZ node: the SE3_XYZ edge from the fixed identity pose, e = l - z, B = I, 3 + 6 values.
+ *   fixed  an XYZ node gets an identity 3 x 3 block and b = 0; its state bits never change.
+ *   extend (guess mode) l = t + R z from the edge's `from` pose only: a landmark does not determine the pose that saw it.
+ *   gate / check / joint: d_e = 3.
+ *   Handles in RR_PGO_F64, RR_PGO_F32 and RR_PGO_MIXED; sharded handles on a graph with an XYZ node are RR_PGO_EUNSUPPORTED.
+ *   g2o text: VERTEX_TRACKXYZ id x y z; EDGE_SE3_TRACKXYZ from to param_id x y z i11 i12 i13 i22 i23 i33 (param_id: an
+ *   unsigned integer, otherwise ignored); PARAMS_SE3OFFSET id x y z qx qy qz qw is accepted only as exactly 0 0 0 0 0 0 1 --
+ *   any other offset is RR_PGO_EPARSE, "sensor offsets are not supported": a deliberate restriction. */
 /* arithmetic type of the device path (the reference is f64 throughout).
  * RR_PGO_MIXED: state, measurements, error / Jacobians / gradient and chi2 in f64; H, its factor and
  * the solve in f32.  The gradient is exact, so Gauss-Newton converges to the f64 minimum while the
@@ -74,13 +91,13 @@ typedef struct rr_pgo_graph_desc {
   int32_t n_nodes;
   const int32_t *node_kind;   /* [n_nodes] RR_PGO_NODE_*; scalar offsets follow this order (g2o.rs:60-77) */
   const uint32_t *node_id;    /* [n_nodes] g2o ids, may be NULL (then id = index) */
-  const double *node_state;   /* packed in node order: SE2 x,y,theta | XY x,y | SE3 x,y,z,qx,qy,qz,qw */
+  const double *node_state;   /* packed in node order: SE2 x,y,theta | XY x,y | SE3 x,y,z,qx,qy,qz,qw | XYZ x,y,z */
   int32_t n_edges;
   const int32_t *edge_kind;   /* [n_edges] RR_PGO_EDGE_*, file order (order defines the prior, :330-336) */
   const int32_t *edge_from;   /* [n_edges] dense node index (lut/nodes lookups of :312-320 done by the caller) */
   const int32_t *edge_to;
-  const double *edge_meas;    /* packed in edge order: SE2 x,y,theta | SE2_XY x,y | SE3 x,y,z,qx,qy,qz,qw */
-  const double *edge_info;    /* packed upper triangles, row-major: 6 | 3 | 21 values (g2o.rs:82,100,117) */
+  const double *edge_meas;    /* packed in edge order: SE2 x,y,theta | SE2_XY x,y | SE3 x,y,z,qx,qy,qz,qw | SE3_XYZ x,y,z */
+  const double *edge_info;    /* packed upper triangles, row-major: 6 | 3 | 21 | 6 values (g2o.rs:82,100,117) */
 } rr_pgo_graph_desc;
 
 typedef struct rr_pgo_options {
@@ -167,7 +184,7 @@ int rr_pgo_update(rr_pgo *h, const double *dx, double sign);
 int rr_pgo_optimize(rr_pgo *h, int32_t num_iterations, double *errors_out,
                     int32_t *n_errors, double *norms_out);
 
-/* State read-back: SE2 -> x, y, atan2(im,re) ; XY -> x, y ; SE3 -> x,y,z,qx,qy,qz,qw,
+/* State read-back: SE2 -> x, y, atan2(im,re) ; XY -> x, y ; SE3 -> x,y,z,qx,qy,qz,qw ; XYZ -> x,y,z,
  * node order.  (Field access on PoseGraph.nodes in the reference.) */
 int rr_pgo_get_state(rr_pgo *h, double *out);
 /* Overwrite the state (same packing); used to restart a benchmark run.  Returns once the copy is enqueued on the handle's
@@ -199,8 +216,9 @@ int rr_pgo_edge_errors(rr_pgo *h, double *chi2_out, double *weight_out);
 
 /* ---- absolute priors on poses and landmarks (build-defined; the reference has only the anchor term) ----
  * A prior on node i is the edge of the node's own kind from a FIXED identity pose to node i: an SE2 pose takes an
- * RR_PGO_EDGE_SE2 term, an XY landmark an RR_PGO_EDGE_SE2_XY term, an SE3 pose an RR_PGO_EDGE_SE3 term, with measurement z
- * and information Omega packed exactly as an edge's are (3 | 2 | 7 and 6 | 3 | 21 values).  So e = Log(Z^-1 X_i) for poses,
+ * RR_PGO_EDGE_SE2 term, an XY landmark an RR_PGO_EDGE_SE2_XY term, an SE3 pose an RR_PGO_EDGE_SE3 term, an XYZ landmark an
+ * RR_PGO_EDGE_SE3_XYZ term, with measurement z
+ * and information Omega packed exactly as an edge's are (3 | 2 | 7 | 3 and 6 | 3 | 21 | 6 values).  So e = Log(Z^-1 X_i) for poses,
  * e = l - z for landmarks, B = de/d(node) as the linearisation computes it for such an edge at the current state, and
  *   H_ii += w B^T Omega B,   b_i gets w B^T Omega e before the negation,   chi2 += rho(e^T Omega e)
  * with w and rho of the handle's robust kernel when the prior is flagged robust and a kernel is set, else w = 1, rho(s) = s.
@@ -356,7 +374,7 @@ int rr_pgo_cross_covariances_times(const rr_pgo *h, double *ms);
  * state, the Levenberg-Marquardt lambda, rr_pgo_optimize's results, captured graphs and the robust setting are untouched.
  * RR_PGO_EINVAL, decided before anything is launched or written, the message names the candidate: n_cand < 0, a null
  * required pointer, a node out of range, from == to, an unknown kind, a kind that does not fit its nodes (SE2: two SE2
- * poses; SE2_XY: from an SE2 pose to an XY landmark; SE3: two SE3 poses), Omega not positive definite, a non-finite
+ * poses; SE2_XY: from an SE2 pose to an XY landmark; SE3: two SE3 poses; SE3_XYZ: from an SE3 pose to an XYZ landmark), Omega not positive definite, a non-finite
  * measurement.  n_cand == 0: RR_PGO_OK.  RR_PGO_ENOTSPD: a non-positive pivot of H.
  * RR_PGO_EUNSUPPORTED (the message says which): sharded handles, RR_PGO_F32 / RR_PGO_MIXED handles, graphs with fronts
  * beyond LDS (rr_pgo_stats::n_big_fronts != 0). */
@@ -458,7 +476,7 @@ int rr_pgo_check_edges_times(const rr_pgo *h, double *ms);
  * node_state == NULL with n_new_nodes > 0: the new nodes are initialised on the device.  The host plans steps from structure
  * alone: the ready set starts as the old nodes; the new edges are scanned in order, again and again, until a scan adds no
  * step; an edge with exactly one ready endpoint whose other endpoint is a new node not yet ready is a step when it determines
- * that node -- to = from (+) z for every kind (SE2: X_to = X_from Z; SE2_XY: l = t + R z; SE3: X_to = X_from Z), from = to (+) z^-1
+ * that node -- to = from (+) z for every kind (SE2: X_to = X_from Z; SE2_XY and SE3_XYZ: l = t + R z; SE3: X_to = X_from Z), from = to (+) z^-1
  * for pose-pose edges only -- and makes it ready.  A new node no step reaches is RR_PGO_EINVAL (the message names it), decided
  * before anything changes.  One kernel (k_guess_nodes) executes the steps in the state's arithmetic type, dependent steps in
  * list order, (cos, sin) and quaternions renormalised; the guessed values of the new nodes are copied into the host graph

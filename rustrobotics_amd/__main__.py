@@ -138,7 +138,20 @@ def write_cross(g, path, columns, rows):
           f"linearise + factor {t[0]:.3f} ms, forward + backward solve {t[1]:.3f} ms, gather + copy {t[2]:.3f} ms")
 
 
-GATE_TAGS = {"EDGE_SE2": 0, "EDGE_SE2_XY": 1, "EDGE_SE3:QUAT": 2}
+GATE_TAGS = {"EDGE_SE2": 0, "EDGE_SE2_XY": 1, "EDGE_SE3:QUAT": 2, "EDGE_SE3_TRACKXYZ": 3}
+
+
+_PARAM_ID = {"EDGE_SE3_TRACKXYZ": ", a parameter id"}   # what the messages about such a line add
+
+
+def _edge_values(tok):
+    """The numbers of an edge line behind its two vertex ids.  EDGE_SE3_TRACKXYZ carries the id of its sensor-offset
+    parameter there first (g2o text, as the loader reads it): an unsigned integer, otherwise ignored."""
+    if tok[0] == "EDGE_SE3_TRACKXYZ":
+        if int(tok[3]) < 0:
+            raise ValueError(tok[3])
+        return [float(t) for t in tok[4:]]
+    return [float(t) for t in tok[3:]]
 
 
 def parse_gate_file(path, index, sets=None, flag="--gate"):
@@ -167,11 +180,11 @@ def parse_gate_file(path, index, sets=None, flag="--gate"):
             nm, ni = GATE_MEAS_LEN[k], GATE_INFO_LEN[k]
             try:
                 i, j = int(tok[1]), int(tok[2])
-                vals = [float(t) for t in tok[3:]]
+                vals = _edge_values(tok)
             except (ValueError, IndexError):
-                raise SystemExit(f"{flag}: {path}:{no}: expected two vertex ids and {nm + ni} numbers after {tok[0]}")
+                raise SystemExit(f"{flag}: {path}:{no}: expected two vertex ids{_PARAM_ID.get(tok[0], '')} and {nm + ni} numbers after {tok[0]}")
             if len(vals) != nm + ni:
-                raise SystemExit(f"{flag}: {path}:{no}: expected {nm + ni} values after the ids, got {len(vals)}")
+                raise SystemExit(f"{flag}: {path}:{no}: expected {nm + ni} values after the ids{_PARAM_ID.get(tok[0], '')}, got {len(vals)}")
             for v in (i, j):
                 if v not in index:
                     raise SystemExit(f"{flag}: {path}:{no}: no vertex with id {v} in the graph")
@@ -237,7 +250,7 @@ def print_prior_share(g):
     print(f"priors: {len(s)} priors carry {share:.9g} of the final cost {total:.9g} ({100.0 * share / total if total else 0.0:.3g} %)")
 
 
-VERTEX_TAGS = {"VERTEX_SE2": 0, "VERTEX_XY": 1, "VERTEX_SE3:QUAT": 2}
+VERTEX_TAGS = {"VERTEX_SE2": 0, "VERTEX_XY": 1, "VERTEX_SE3:QUAT": 2, "VERTEX_TRACKXYZ": 3}
 
 
 def parse_extend_file(path, index, n_nodes=None, flag="--extend"):
@@ -279,11 +292,11 @@ def parse_extend_file(path, index, n_nodes=None, flag="--extend"):
             nm, ni = GATE_MEAS_LEN[k], GATE_INFO_LEN[k]
             try:
                 i, j = int(tok[1]), int(tok[2])
-                vals = [float(t) for t in tok[3:]]
+                vals = _edge_values(tok)
             except (ValueError, IndexError):
-                raise SystemExit(f"{flag}: {path}:{no}: expected two vertex ids and {nm + ni} numbers after {tok[0]}")
+                raise SystemExit(f"{flag}: {path}:{no}: expected two vertex ids{_PARAM_ID.get(tok[0], '')} and {nm + ni} numbers after {tok[0]}")
             if len(vals) != nm + ni:
-                raise SystemExit(f"{flag}: {path}:{no}: expected {nm + ni} values after the ids, got {len(vals)}")
+                raise SystemExit(f"{flag}: {path}:{no}: expected {nm + ni} values after the ids{_PARAM_ID.get(tok[0], '')}, got {len(vals)}")
             edges.append((no, k, i, j, vals))
     kind, a, b, meas, info = [], [], [], [], []
     for no, k, i, j, vals in edges:   # (an edge may come before the vertex line it names)

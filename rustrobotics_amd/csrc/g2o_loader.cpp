@@ -4,7 +4,9 @@
 //     str::lines() does), tokens split on ' ' ONLY, empty tokens dropped (:52);
 //   * tags VERTEX_SE2 / VERTEX_XY / VERTEX_SE3:QUAT / EDGE_SE2 / EDGE_SE2_XY /
 //     EDGE_SE3:QUAT, anything else is an error (unimplemented!() at :138);
-//   * scalar offsets grow by 3 / 2 / 6 in vertex FILE order (:60-77);
+//   * build-defined, the reference has none: VERTEX_TRACKXYZ, EDGE_SE3_TRACKXYZ and an identity PARAMS_SE3OFFSET
+//     (3-D point landmarks, include/rr_pgo.h);
+//   * scalar offsets grow by 3 / 2 / 6 (TRACKXYZ: 3) in vertex FILE order (:60-77);
 //   * edges keep FILE order (:94-95,111-112,135-136);
 //   * information matrices are given as row-major upper triangles (:82,100,117).
 // A condition that panics in the reference (empty line, wrong value count, edge
@@ -79,15 +81,16 @@ std::string HostGraph::finalize() {
   node_state_off.assign(N, 0);
   int off = 0;
   int64_t soff = 0;
-  has_se3 = has_2d = false;
+  has_se3 = has_2d = has_xyz = false;
   for (int i = 0; i < N; i++) {
     int k = node_kind[i];
-    if (k < NODE_SE2 || k > NODE_SE3) return "bad node kind";
+    if (k < NODE_SE2 || k > NODE_XYZ) return "bad node kind";
     node_offset[i] = off;
     node_state_off[i] = soff;
     off += node_dim(k);
     soff += node_state_len(k);
-    (k == NODE_SE3 ? has_se3 : has_2d) = true;
+    (node_is_3d(k) ? has_se3 : has_2d) = true;
+    if (k == NODE_XYZ) has_xyz = true;
   }
   dim = off;
   if ((int64_t)node_state.size() != soff) return "node_state length does not match node kinds";
@@ -98,14 +101,15 @@ std::string HostGraph::finalize() {
   anchor_node = -1;
   for (int k = 0; k < E; k++) {
     int ek = edge_kind[k];
-    if (ek < EDGE_SE2 || ek > EDGE_SE3) return "bad edge kind";
+    if (ek < EDGE_SE2 || ek > EDGE_SE3_XYZ) return "bad edge kind";
     int a = edge_from[k], b = edge_to[k];
     if (a < 0 || a >= N || b < 0 || b >= N)
       return "edge " + std::to_string(k) + " references an unknown vertex";
     int ka = node_kind[a], kb = node_kind[b];
     bool ok = (ek == EDGE_SE2 && ka == NODE_SE2 && kb == NODE_SE2) ||
               (ek == EDGE_SE2_XY && ka == NODE_SE2 && kb == NODE_XY) ||
-              (ek == EDGE_SE3 && ka == NODE_SE3 && kb == NODE_SE3);
+              (ek == EDGE_SE3 && ka == NODE_SE3 && kb == NODE_SE3) ||
+              (ek == EDGE_SE3_XYZ && ka == NODE_SE3 && kb == NODE_XYZ);
     if (!ok)  // unreachable!() in the reference, pose_graph_optimization.rs:315-320,342-347
       return "edge " + std::to_string(k) + ": endpoint kinds do not match the edge kind";
     if (a == b) return "edge " + std::to_string(k) + " is a self loop";
@@ -125,7 +129,7 @@ namespace {
 
 // what one thread parses: a run of whole lines
 struct ParsedPart {
-  std::vector<int32_t> node_kind, edge_kind, node_line;
+  std::vector<int32_t> node_kind, edge_kind, node_line, edge_line;
   std::vector<uint32_t> node_id, from_id, to_id;
   std::vector<double> node_state, edge_meas, edge_info;
   long lines = 0;        // lines consumed (up to and including the failing one)
@@ -154,20 +158,37 @@ void parse_part(const char *text, size_t begin, size_t end, ParsedPart &out) {
     if (tok.empty()) return fail("empty line");  // line[0] panics in the reference (:53)
 
     int kind = -1, nvals = 0;
-    bool is_edge = false;
+    bool is_edge = false, is_track = false;
     if (tok[0] == "VERTEX_SE2") { kind = NODE_SE2; nvals = 3; }
     else if (tok[0] == "VERTEX_XY") { kind = NODE_XY; nvals = 2; }
     else if (tok[0] == "VERTEX_SE3:QUAT") { kind = NODE_SE3; nvals = 7; }
     else if (tok[0] == "EDGE_SE2") { kind = EDGE_SE2; nvals = 9; is_edge = true; }
     else if (tok[0] == "EDGE_SE2_XY") { kind = EDGE_SE2_XY; nvals = 5; is_edge = true; }
     else if (tok[0] == "EDGE_SE3:QUAT") { kind = EDGE_SE3; nvals = 28; is_edge = true; }
+    else if (tok[0] == "VERTEX_TRACKXYZ") { kind = NODE_XYZ; nvals = 3; }
+    else if (tok[0] == "EDGE_SE3_TRACKXYZ") { kind = EDGE_SE3_XYZ; nvals = 9; is_edge = true; is_track = true; }
+    else if (tok[0] == "PARAMS_SE3OFFSET") {
+      // the sensor offset of EDGE_SE3_TRACKXYZ: only the identity is supported, and the line then says nothing
+      static const double ident[7] = {0, 0, 0, 0, 0, 0, 1};
+      uint32_t id = 0;
+      if (tok.size() != 9) return fail("expected 7 values after the id");
+      if (!to_u32(tok[1], id)) return fail("bad parameter id");
+      for (int i = 0; i < 7; i++) {
+        double x;
+        if (!to_f64(tok[2 + i], x)) return fail("bad number '" + std::string(tok[2 + i]) + "'");
+        if (!(x == ident[i])) return fail("sensor offsets are not supported");
+      }
+      continue;
+    }
     else return fail("unsupported tag '" + std::string(tok[0]) + "'");
 
-    const size_t first = is_edge ? 3 : 2;
+    // EDGE_SE3_TRACKXYZ carries the id of its PARAMS_SE3OFFSET behind the vertex ids: an unsigned integer, otherwise ignored
+    const size_t first = is_track ? 4 : is_edge ? 3 : 2;
     if (tok.size() != first + (size_t)nvals)
       return fail("expected " + std::to_string(nvals) + " values after the ids");
-    uint32_t id0 = 0, id1 = 0;
+    uint32_t id0 = 0, id1 = 0, pid = 0;
     if (!to_u32(tok[1], id0) || (is_edge && !to_u32(tok[2], id1))) return fail("bad vertex id");
+    if (is_track && !to_u32(tok[3], pid)) return fail("bad parameter id");
     double v[28];
     for (int i = 0; i < nvals; i++)
       if (!to_f64(tok[first + i], v[i])) return fail("bad number '" + std::string(tok[first + i]) + "'");
@@ -179,6 +200,7 @@ void parse_part(const char *text, size_t begin, size_t end, ParsedPart &out) {
       out.node_state.insert(out.node_state.end(), v, v + nvals);
     } else {
       out.edge_kind.push_back(kind);
+      out.edge_line.push_back((int32_t)out.lines);
       out.from_id.push_back(id0);
       out.to_id.push_back(id1);
       const int nm = edge_meas_len(kind);
@@ -215,6 +237,7 @@ std::string load_g2o(const char *path, HostGraph &g, bool &io_error) {
   parallel_indices(nparts, nparts, [&](int k) { parse_part(text.data(), cut[k], cut[k + 1], parts[k]); });
   std::unordered_map<uint32_t, int32_t> index_of;  // id -> dense index (lut + nodes maps of the reference)
   std::vector<uint32_t> from_id, to_id;
+  std::vector<long> node_line, edge_line;   // file lines, for the errors of the 3-D landmark tags below
   size_t nn = 0, ne = 0;
   for (const ParsedPart &p : parts) { nn += p.node_kind.size(); ne += p.edge_kind.size(); }
   index_of.reserve(nn * 2);
@@ -229,12 +252,14 @@ std::string load_g2o(const char *path, HostGraph &g, bool &io_error) {
         return "line " + std::to_string(line0 + p.node_line[i]) + ": duplicate vertex id " + std::to_string(p.node_id[i]);
       g.node_kind.push_back(p.node_kind[i]);
       g.node_id.push_back(p.node_id[i]);
+      node_line.push_back(line0 + p.node_line[i]);
     }
     if (!p.error.empty()) return "line " + std::to_string(line0 + p.lines) + ": " + p.error;
     g.node_state.insert(g.node_state.end(), p.node_state.begin(), p.node_state.end());
     g.edge_kind.insert(g.edge_kind.end(), p.edge_kind.begin(), p.edge_kind.end());
     from_id.insert(from_id.end(), p.from_id.begin(), p.from_id.end());
     to_id.insert(to_id.end(), p.to_id.begin(), p.to_id.end());
+    for (const int32_t l : p.edge_line) edge_line.push_back(line0 + l);
     g.edge_meas.insert(g.edge_meas.end(), p.edge_meas.begin(), p.edge_meas.end());
     g.edge_info.insert(g.edge_info.end(), p.edge_info.begin(), p.edge_info.end());
     line0 += p.lines;
@@ -248,6 +273,21 @@ std::string load_g2o(const char *path, HostGraph &g, bool &io_error) {
       return "edge " + std::to_string(k) + " references an unknown vertex";
     g.edge_from[k] = a->second;
     g.edge_to[k] = b->second;
+  }
+  // what finalize() rejects without a place in the file, said with the line for the 3-D landmark tags: a 2-D vertex next to a
+  // VERTEX_TRACKXYZ (the line of whichever comes second), an EDGE_SE3_TRACKXYZ that does not go from a pose to a landmark
+  {
+    long first_2d = 0, first_xyz = 0;
+    for (size_t i = 0; i < g.node_kind.size(); i++) {
+      const bool xyz = g.node_kind[i] == NODE_XYZ, flat = !node_is_3d(g.node_kind[i]);
+      if (xyz && !first_xyz) first_xyz = node_line[i];
+      if (flat && !first_2d) first_2d = node_line[i];
+      if (first_xyz && first_2d)
+        return "line " + std::to_string(std::max(first_xyz, first_2d)) + ": mixed 2D / 3D graphs are not supported";
+    }
+    for (size_t k = 0; k < E; k++)
+      if (g.edge_kind[k] == EDGE_SE3_XYZ && (g.node_kind[g.edge_from[k]] != NODE_SE3 || g.node_kind[g.edge_to[k]] != NODE_XYZ))
+        return "line " + std::to_string(edge_line[k]) + ": EDGE_SE3_TRACKXYZ goes from an SE3 pose to an XYZ landmark";
   }
   return g.finalize();
 }

@@ -8,19 +8,34 @@
 
 namespace rrpgo {
 
-enum NodeKind : int32_t { NODE_SE2 = 0, NODE_XY = 1, NODE_SE3 = 2 };
-enum EdgeKind : int32_t { EDGE_SE2 = 0, EDGE_SE2_XY = 1, EDGE_SE3 = 2 };
+enum NodeKind : int32_t { NODE_SE2 = 0, NODE_XY = 1, NODE_SE3 = 2, NODE_XYZ = 3 };
+enum EdgeKind : int32_t { EDGE_SE2 = 0, EDGE_SE2_XY = 1, EDGE_SE3 = 2, EDGE_SE3_XYZ = 3 };
 
-inline int node_dim(int kind) { return kind == NODE_SE2 ? 3 : kind == NODE_XY ? 2 : 6; }
-inline int node_state_len(int kind) { return kind == NODE_SE2 ? 3 : kind == NODE_XY ? 2 : 7; }
-inline int edge_dim(int kind) { return kind == EDGE_SE2 ? 3 : kind == EDGE_SE2_XY ? 2 : 6; }
-inline int edge_meas_len(int kind) { return kind == EDGE_SE2 ? 3 : kind == EDGE_SE2_XY ? 2 : 7; }
-inline int edge_info_len(int kind) { return kind == EDGE_SE2 ? 6 : kind == EDGE_SE2_XY ? 3 : 21; }
+inline int node_dim(int kind) { return kind == NODE_SE2 ? 3 : kind == NODE_XY ? 2 : kind == NODE_XYZ ? 3 : 6; }
+inline int node_state_len(int kind) { return kind == NODE_SE2 ? 3 : kind == NODE_XY ? 2 : kind == NODE_XYZ ? 3 : 7; }
+inline int edge_dim(int kind) { return kind == EDGE_SE2 ? 3 : kind == EDGE_SE2_XY ? 2 : kind == EDGE_SE3_XYZ ? 3 : 6; }
+inline int edge_meas_len(int kind) { return kind == EDGE_SE2 ? 3 : kind == EDGE_SE2_XY ? 2 : kind == EDGE_SE3_XYZ ? 3 : 7; }
+inline int edge_info_len(int kind) { return kind == EDGE_SE2 ? 6 : kind == EDGE_SE2_XY ? 3 : kind == EDGE_SE3_XYZ ? 6 : 21; }
+inline bool node_is_3d(int kind) { return kind == NODE_SE3 || kind == NODE_XYZ; }
 // a prior on a node is the edge of the node's own kind from a fixed identity pose (rr_pgo_set_priors)
-inline int prior_edge_kind(int node_kind) { return node_kind == NODE_SE2 ? EDGE_SE2 : node_kind == NODE_XY ? EDGE_SE2_XY : EDGE_SE3; }
+inline int prior_edge_kind(int node_kind) {
+  return node_kind == NODE_SE2 ? EDGE_SE2 : node_kind == NODE_XY ? EDGE_SE2_XY : node_kind == NODE_XYZ ? EDGE_SE3_XYZ : EDGE_SE3;
+}
+// The device keeps the information of every edge of a 3-D graph as the 21 entries of a 6 x 6 upper triangle: an SE3_XYZ
+// edge's 6 values (3 x 3 upper triangle) go to the upper-left block, the rest is zero.  w: edge_info_len(kind) values.
+template <typename S> inline void pack_info_3d(int kind, const double *w, S out[21]) {
+  if (kind != EDGE_SE3_XYZ) {
+    for (int t = 0; t < 21; t++) out[t] = (S)w[t];
+    return;
+  }
+  for (int t = 0; t < 21; t++) out[t] = (S)0;
+  out[0] = (S)w[0]; out[1] = (S)w[1]; out[2] = (S)w[2];   // row 0: (0,0) (0,1) (0,2)
+  out[6] = (S)w[3]; out[7] = (S)w[4];                     // row 1: (1,1) (1,2)
+  out[11] = (S)w[5];                                      // row 2: (2,2)
+}
 
 // The device form of a node's state and of an edge's measurement (the two numberings coincide), as two 4-vectors:
-//   SE2  x, y, cos, sin | -      XY  x, y, 0, 0 | -      SE3  t (3), 0 | q (4) / |q|
+//   SE2  x, y, cos, sin | -      XY  x, y, 0, 0 | -      SE3  t (3), 0 | q (4) / |q|      XYZ  x, y, z, 0 | 0, 0, 0, 0
 // the quaternion normalised like UnitQuaternion::from_quaternion, the norm in double.  Every conversion in the library is
 // one of these two functions; the callers cast to the arithmetic type where they build the vectors.
 inline double quat_norm(const double *q) { return std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]); }
@@ -34,6 +49,8 @@ inline int pack_state(int kind, const double *s, double p[8]) {
     const double n = quat_norm(s + 3);
     p[2] = s[2];
     for (int t = 0; t < 4; t++) p[4 + t] = s[3 + t] / n;
+  } else if (kind == NODE_XYZ) {
+    p[2] = s[2];
   }
   return node_state_len(kind);
 }
@@ -45,6 +62,8 @@ inline int unpack_state(int kind, const double p[8], double *s) {
   } else if (kind == NODE_SE3) {
     s[2] = p[2];
     for (int t = 0; t < 4; t++) s[3 + t] = p[4 + t];
+  } else if (kind == NODE_XYZ) {
+    s[2] = p[2];
   }
   return node_state_len(kind);
 }
@@ -55,13 +74,14 @@ struct HostGraph {
   std::vector<uint32_t> node_id;
   std::vector<int32_t> node_offset;     // scalar offset, vertex file order (g2o.rs:60-77)
   std::vector<int64_t> node_state_off;  // offset into node_state
-  std::vector<double> node_state;       // SE2 x,y,theta | XY x,y | SE3 x,y,z,qx,qy,qz,qw
+  std::vector<double> node_state;       // SE2 x,y,theta | XY x,y | SE3 x,y,z,qx,qy,qz,qw | XYZ x,y,z
   std::vector<int32_t> edge_kind, edge_from, edge_to;
   std::vector<int64_t> edge_meas_off, edge_info_off;
   std::vector<double> edge_meas, edge_info;
   int32_t dim = 0;          // `len`
   int32_t anchor_node = -1; // from-node of the first pose-pose edge (prior, :330-336)
-  bool has_se3 = false, has_2d = false;
+  bool has_se3 = false, has_2d = false;   // has_se3: the graph is 3-D (SE3 poses, XYZ landmarks)
+  bool has_xyz = false;                   // ... and has XYZ landmarks
 
   int n_nodes() const { return (int)node_kind.size(); }
   int n_edges() const { return (int)edge_kind.size(); }

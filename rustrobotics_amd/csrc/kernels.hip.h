@@ -165,7 +165,7 @@ template <typename T, typename TC = T> struct LinArgs {
                                          // the far pose is requested together with the edge record, not after it (sharded runs: see Engine)
   const int32_t *node_list;              // sharded runs: the nodes this rank linearises (own + shared), else null;
                                          // n_nodes is then the length of the list
-  const uint8_t *node_dim;               // SE(2): 3 (pose) or 2 (XY landmark); SE(3) does not read it
+  const uint8_t *node_dim;               // SE(2): 3 (pose) or 2 (XY landmark); SE(3): 6 or 3 (XYZ landmark), read by the LM kernels alone
   const int32_t *node_offset;            // reference scalar offset
   const int64_t *diag_off;
   T *hvals;
@@ -365,6 +365,39 @@ __device__ void edge_linearize_3d(int role, const T ti[3], const T qi[4], const 
   }
 }
 
+// SE3 pose (tp, qp) -> XYZ landmark l (RR_PGO_EDGE_SE3_XYZ; build-defined, include/rr_pgo.h): the landmark in the pose's
+// frame against the measured point,
+//   p = R(qp)^T (l - tp) ,  e = p - z                                             (3 scalars)
+//   pose: the right increment above ;  landmark: l <- l + dl
+//   A = [ -I , [p]x ]  (role 0, w.r.t. the pose) ,  B = R(qp)^T  (role 1, w.r.t. the landmark)
+// e and the requested Jacobian zero padded to 6 and 6 x 6, so that the frame of k_linearize takes them as they are.
+template <typename T>
+__device__ void edge_linearize_3d_point(int role, const T tp[3], const T qp[4], const T l[3], const T z[3], T e[6], T J[6][6]) {
+  const T qc[4] = {-qp[0], -qp[1], -qp[2], qp[3]};
+  const T d[3] = {l[0] - tp[0], l[1] - tp[1], l[2] - tp[2]};
+  T p[3];
+  q_rot(qc, d, p);
+  e[0] = p[0] - z[0]; e[1] = p[1] - z[1]; e[2] = p[2] - z[2];
+  e[3] = 0; e[4] = 0; e[5] = 0;
+#pragma unroll
+  for (int r = 0; r < 6; r++)
+#pragma unroll
+    for (int c = 0; c < 6; c++) J[r][c] = 0;
+  if (role) {
+    T Rt[3][3];
+    q_to_rot(qc, Rt);
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+#pragma unroll
+      for (int c = 0; c < 3; c++) J[r][c] = Rt[r][c];
+  } else {
+    J[0][0] = -1; J[1][1] = -1; J[2][2] = -1;
+    J[0][4] = -p[2]; J[0][5] = p[1];
+    J[1][3] = p[2];  J[1][5] = -p[0];
+    J[2][3] = -p[1]; J[2][4] = p[0];
+  }
+}
+
 // ---- operand loaders: the one definition of each unpacking
 template <typename T> __device__ __forceinline__ void info_2d(const EdgeRec<T> &rec, T (&W)[3][3]) {
   const typename VecT<T>::V4 wa = rec.info_a;
@@ -414,6 +447,11 @@ template <typename T>
 __device__ __forceinline__ void prior_linearize_3d(const T tx[3], const T qx[4], const T tz[3], const T qz[4], T e[6], T B[6][6]) {
   const T t0[3] = {(T)0, (T)0, (T)0}, q0[4] = {(T)0, (T)0, (T)0, (T)1};
   edge_linearize_3d<T>(1, t0, q0, tx, qx, tz, qz, e, B);
+}
+template <typename T>   // an XYZ landmark: e = l - z, B = I (the identity pose rotates and shifts nothing, exactly)
+__device__ __forceinline__ void prior_linearize_3d_point(const T l[3], const T z[3], T e[6], T B[6][6]) {
+  const T t0[3] = {(T)0, (T)0, (T)0}, q0[4] = {(T)0, (T)0, (T)0, (T)1};
+  edge_linearize_3d_point<T>(1, t0, q0, l, z, e, B);
 }
 
 // Robust kernels (include/rr_pgo.h, rr_pgo_set_robust_kernel): rho(s) and the IRLS weight w = rho'(s) at s = e^T W e.
@@ -634,268 +672,26 @@ template <typename A> __device__ __forceinline__ void opt_publish_chi2_in_last_b
 // all of H and chi2 right.  Whether the source or the compiler is at fault was not found (profiles/EXPERIMENTS.md, r20);
 // tests/test_fixed_gpu.py::test_assembled_system_is_the_unfixed_one_with_identity_rows compares every entry of H and b with
 // the unfixed twin's in f64, mixed and f32 and is the guard: run it after any edit to this kernel or a change of compiler.
+// The body is linearize_pull.inc, included by the two kernels below behind `constexpr bool LM`.
+// LM: the 3-D graph has XYZ landmarks (RR_PGO_NODE_XYZ / RR_PGO_EDGE_SE3_XYZ), D = 6 only.  false is the code of every pure
+// SE(3) handle, token for token: every LM path is behind `if constexpr (LM)` with the old text in its else branch, and the
+// kernels of handles with landmarks have the new name k_linearize_lm, so k_linearize<..., 6, ...> stays the instantiation it
+// was (see the note on the spilling instantiations above; a body shared through a forceinline function was tried and changed
+// the code of every instantiation, profiles/EXPERIMENTS.md).  true reads node_dim like D = 3 does; bit 1 of the incidence word marks an SE3_XYZ edge, evaluated by
+// edge_linearize_3d_point in the padded form (e and J zero beyond 3, the 6 information values in the upper-left 3 x 3 of a
+// zeroed W: the frame -- robust weight, J^T W, sums, chi2, priors -- is untouched); a landmark's diagonal block is 3 x 3, the
+// edge's off-diagonal block 6 x 3 (or its transpose), as D = 3 stores 2 x 2 and 3 x 2.
 template <typename TO, typename T, int RK = ROBUST_NONE, int D = 3, bool PR = false>
 __global__ void __launch_bounds__(LIN_THREADS) k_linearize(LinArgs<TO, T> a) {
-  using V4 = typename VecT<T>::V4;
-  constexpr int NV = D / 3;             // V4s per node and per measurement
-  constexpr int NT = D * (D + 1) / 2;   // lower triangle of the diagonal block, row-major: (0,0),(1,0),(1,1),...
-  __shared__ double red[LIN_THREADS / 64];
-  const int gid = blockIdx.x * LIN_THREADS + threadIdx.x;
-  for (int i = gid; i < a.n_zero_words; i += gridDim.x * LIN_THREADS) a.zero_words[i] = 0u;
-  for (int i = gid; i < a.n_fill_words; i += gridDim.x * LIN_THREADS) a.fill_words[i] = X_PENDING_WORD;
-  opt_reset_in_first_thread(a);
-  const LinPre lin_pre = opt_publish_preload(a);
-  const T lambda = a.lambda_from_ctrl ? (T)a.ctrl->lambda : a.lambda;
-  const int slot = gid / LIN_GROUP, sub = gid % LIN_GROUP;
-  const int node = listed_node(a, slot);
-  double chi = 0.0;
-  T hd[NT], bv[D];
-#pragma unroll
-  for (int t = 0; t < NT; t++) hd[t] = 0;
-#pragma unroll
-  for (int t = 0; t < D; t++) bv[t] = 0;
-  int nd = D;
-  bool fx_self = false;   // rr_pgo_set_fixed: this group's node is held constant
-  if (node >= 0) {
-    if constexpr (D == 3) nd = a.node_dim[node];
-    fx_self = a.fixed && a.fixed[node];
-    V4 self[NV];
-#pragma unroll
-    for (int v = 0; v < NV; v++) self[v] = a.pose[NV * node + v];
-    const int q1 = a.inc_ptr[node + 1];
-    for (int q = a.inc_ptr[node] + sub; q < q1; q += LIN_GROUP) {
-      const int2 inc = a.inc_list[q];
-      const int ent = inc.x;
-      const bool fx_other = a.fixed && a.fixed[inc.y];   // rr_pgo_set_fixed: requested with the far pose, used behind the stores
-      // sharded runs: an edge contributes to diagonal blocks, right-hand side and chi2 on ONE rank (bit 2, its
-      // owner -- the other ranks' copies of a far endpoint are stale); the off-diagonal block of an edge between
-      // two shared nodes is written by every rank (bit 3)
-      if (!(ent & 12)) continue;
-      const bool owns = ent & 4;
-      const int k = ent >> 4, role = ent & 1;
-      // ---- per dimension: the operands, e and J = the Jacobian of this endpoint (A in the from role, B in the to role)
-      T W[D][D], e[D], J[D][D];
-      [[maybe_unused]] EdgeRec<T> rec;                                 // SE(2)
-      [[maybe_unused]] T B2[3][3];                                     // SE(2): B comes with A
-      [[maybe_unused]] T ts[3], qs[4], to[3], qo[4], tz[3], qz[4];     // SE(3): B is evaluated where it is needed
-      if constexpr (D == 3) {
-        rec = a.e_rec[k];
-        const V4 other = a.pose[inc.y];
-        info_2d<T>(rec, W);
-        T A[3][3];
-        edge_linearize_2d<T>((ent >> 1) & 1, role ? other : self[0], role ? self[0] : other, rec.meas, e, A, B2);
-#pragma unroll
-        for (int r = 0; r < 3; r++)
-#pragma unroll
-          for (int c = 0; c < 3; c++) J[r][c] = role ? B2[r][c] : A[r][c];
-      } else {
-        pose_3d<T>(self[0], self[1], ts, qs);
-        pose_3d<T>(a.pose[2 * inc.y], a.pose[2 * inc.y + 1], to, qo);
-        pose_3d<T>(a.e_meas[2 * k], a.e_meas[2 * k + 1], tz, qz);
-        info_3d<T>(a.e_info + (int64_t)k * 21, W);
-        if (role) edge_linearize_3d<T>(1, to, qo, ts, qs, tz, qz, e, J);
-        else edge_linearize_3d<T>(0, ts, qs, to, qo, tz, qz, e, J);
-      }
-      // ---- the frame
-      T s_rob = 0;
-      bool rob = false;
-      if constexpr (RK != ROBUST_NONE) {
-        s_rob = edge_chi2<D, T>(W, e);
-        rob = !a.robust_mask || a.robust_mask[k];
-        if (rob) {   // masked-off edges keep W as it is
-          const T w = robust_weight<RK, T>(s_rob, a.robust_delta, a.robust_delta2);
-#pragma unroll
-          for (int i = 0; i < D; i++)
-#pragma unroll
-            for (int j = 0; j < D; j++) W[i][j] *= w;
-        }
-      }
-      T JW[D][D];   // J^T W
-#pragma unroll
-      for (int i = 0; i < D; i++)
-#pragma unroll
-        for (int j = 0; j < D; j++) {
-          T s = 0;
-#pragma unroll
-          for (int r = 0; r < D; r++) s += J[r][i] * W[r][j];
-          JW[i][j] = s;
-        }
-      if (a.write_system && owns) {
-        int t = 0;
-#pragma unroll
-        for (int i = 0; i < D; i++)
-#pragma unroll
-          for (int j = 0; j <= i; j++) {
-            T s = 0;
-#pragma unroll
-            for (int r = 0; r < D; r++) s += JW[i][r] * J[r][j];
-            hd[t++] += s;
-          }
-#pragma unroll
-        for (int i = 0; i < D; i++) bv[i] += row_dot<D, T>(JW[i], e, 1);
-      }
-      if (role == 0) {
-        // chi2 term e^T W e (:555,568), accumulated in f64; rho(e^T W e) under a robust kernel
-        if constexpr (RK == ROBUST_NONE) {
-          if (owns) chi += (double)edge_chi2<D, T>(W, e);   // every edge's term is owned by one rank
-        } else {
-          if (owns) chi += (double)(rob ? robust_rho<RK, T>(s_rob, a.robust_delta, a.robust_delta2) : s_rob);
-        }
-        if (a.write_system && (ent & 8)) {
-          // ---- per dimension: the off-diagonal block H[from rows, to cols] = A^T W B and where it goes
-          if constexpr (D == 3) {
-            const int64_t so = rec.slot;
-            TO *dst = a.hvals + (so >> 1);
-            const bool tr = so & 1;
-            const int d2 = ((ent >> 1) & 1) ? 2 : 3;
-#pragma unroll
-            for (int i = 0; i < 3; i++)
-#pragma unroll
-              for (int j = 0; j < 3; j++) {
-                if (j >= d2) continue;
-                dst[tr ? j * 3 + i : i * d2 + j] = (TO)row_dot<3, T>(JW[i], &B2[0][j], 3);
-              }
-          } else {
-            T e2[6], Bm[6][6];
-            edge_linearize_3d<T>(1, ts, qs, to, qo, tz, qz, e2, Bm);
-            const int64_t so = a.e_slot[k];
-            TO *dst = a.hvals + (so >> 1);
-            const bool tr = so & 1;
-#pragma unroll
-            for (int i = 0; i < 6; i++)
-#pragma unroll
-              for (int j = 0; j < 6; j++) dst[tr ? j * 6 + i : i * 6 + j] = (TO)row_dot<6, T>(JW[i], &Bm[0][j], 6);
-          }
-          // rr_pgo_set_fixed: the block of an edge with a fixed endpoint (this node, or the other one) is overwritten with
-          // zeros -- a second store of the same lane, behind everything the loop does otherwise
-          if (fx_self | fx_other) {
-            if constexpr (D == 3) {
-              TO *dst = a.hvals + (rec.slot >> 1);
-              const int cnt = ((ent >> 1) & 1) ? 6 : 9;   // 3 x 2 (landmark) or 3 x 3
-#pragma unroll
-              for (int t = 0; t < 9; t++)
-                if (t < cnt) dst[t] = (TO)0;
-            } else {
-              TO *dst = a.hvals + (a.e_slot[k] >> 1);
-#pragma unroll
-              for (int t = 0; t < 36; t++) dst[t] = (TO)0;
-            }
-          }
-        }
-      }
-    }
-    if constexpr (PR) {
-      const int p1 = a.prior_ptr[node + 1];
-      for (int p = a.prior_ptr[node] + sub; p < p1; p += LIN_GROUP) {
-        T W[D][D], e[D], J[D][D];
-        // ---- per dimension: the operands, e and J = B of the edge identity -> node
-        if constexpr (D == 3) {
-          const EdgeRec<T> rec = a.prior_rec[p];
-          info_2d<T>(rec, W);
-          prior_linearize_2d<T>(nd == 2 ? 1 : 0, self[0], rec.meas, e, J);
-        } else {
-          T ts[3], qs[4], tz[3], qz[4];
-          pose_3d<T>(self[0], self[1], ts, qs);
-          pose_3d<T>(a.prior_meas[2 * p], a.prior_meas[2 * p + 1], tz, qz);
-          info_3d<T>(a.prior_info + (int64_t)p * 21, W);
-          prior_linearize_3d<T>(ts, qs, tz, qz, e, J);
-        }
-        // ---- the frame, as for an edge in its `to` role
-        T s_rob = 0;
-        bool rob = false;
-        if constexpr (RK != ROBUST_NONE) {
-          s_rob = edge_chi2<D, T>(W, e);
-          rob = a.prior_robust[p] != 0;
-          if (rob) {
-            const T w = robust_weight<RK, T>(s_rob, a.robust_delta, a.robust_delta2);
-#pragma unroll
-            for (int i = 0; i < D; i++)
-#pragma unroll
-              for (int j = 0; j < D; j++) W[i][j] *= w;
-          }
-        }
-        if (a.write_system) {
-          T JW[D][D];   // J^T W
-#pragma unroll
-          for (int i = 0; i < D; i++)
-#pragma unroll
-            for (int j = 0; j < D; j++) {
-              T s = 0;
-#pragma unroll
-              for (int r = 0; r < D; r++) s += J[r][i] * W[r][j];
-              JW[i][j] = s;
-            }
-          int t = 0;
-#pragma unroll
-          for (int i = 0; i < D; i++)
-#pragma unroll
-            for (int j = 0; j <= i; j++) {
-              T s = 0;
-#pragma unroll
-              for (int r = 0; r < D; r++) s += JW[i][r] * J[r][j];
-              hd[t++] += s;
-            }
-#pragma unroll
-          for (int i = 0; i < D; i++) bv[i] += row_dot<D, T>(JW[i], e, 1);
-        }
-        if constexpr (RK == ROBUST_NONE) chi += (double)edge_chi2<D, T>(W, e);
-        else chi += (double)(rob ? robust_rho<RK, T>(s_rob, a.robust_delta, a.robust_delta2) : s_rob);
-      }
-    }
-  }
-  if (a.write_system) {
-#pragma unroll
-    for (int t = 0; t < NT; t++) hd[t] = group_sum8(hd[t]);
-#pragma unroll
-    for (int t = 0; t < D; t++) bv[t] = group_sum8(bv[t]);
-    if (node >= 0 && sub == 0) {
-      T add = lambda;
-      if (node == a.anchor) add += (T)10000000.0;
-      if (a.adds_diag && !a.adds_diag[node]) add = 0;
-      // ---- per dimension: the diagonal block's layout
-      TO *d = a.hvals + a.diag_off[node];
-      if constexpr (D == 3) {
-        if (nd == 3) {
-          d[0] = (TO)(hd[0] + add); d[1] = (TO)hd[1];         d[2] = (TO)hd[3];
-          d[3] = (TO)hd[1];         d[4] = (TO)(hd[2] + add); d[5] = (TO)hd[4];
-          d[6] = (TO)hd[3];         d[7] = (TO)hd[4];         d[8] = (TO)(hd[5] + add);
-        } else {
-          d[0] = (TO)(hd[0] + add); d[1] = (TO)hd[1];
-          d[2] = (TO)hd[1];         d[3] = (TO)(hd[2] + add);
-        }
-      } else {
-        int t = 0;
-#pragma unroll
-        for (int i = 0; i < 6; i++)
-#pragma unroll
-          for (int j = 0; j <= i; j++) {
-            const T v = hd[t++] + (i == j ? add : (T)0);
-            d[i * 6 + j] = (TO)v;
-            d[j * 6 + i] = (TO)v;
-          }
-      }
-      TO *bo = a.b + a.node_offset[node];
-#pragma unroll
-      for (int t = 0; t < D; t++)
-        if (t < nd) bo[t] = (TO)(-bv[t]);
-      // rr_pgo_set_fixed: a fixed node's group has walked its incidences and priors as ever (the chi2 terms of its from-role
-      // edges and of its priors count, it owns off-diagonal stores); what it just stored -- edge and prior terms, lambda, the
-      // anchor term -- is overwritten with the identity block and b = 0
-      if (fx_self) {
-#pragma unroll
-        for (int i = 0; i < D; i++)
-#pragma unroll
-          for (int j = 0; j < D; j++)
-            if (i < nd && j < nd) d[i * nd + j] = i == j ? (TO)1 : (TO)0;
-#pragma unroll
-        for (int t = 0; t < D; t++)
-          if (t < nd) bo[t] = (TO)0;
-      }
-    }
-  }
-  double tot = block_sum<double, LIN_THREADS>(chi, red);
-  if (threadIdx.x == 0) a.chi2_partial[blockIdx.x] = tot;
-  opt_publish_chi2_in_last_block(a, lin_pre, red);
+  constexpr bool LM = false;
+#include "linearize_pull.inc"
+}
+// the pull form of a 3-D graph with XYZ landmarks
+template <typename TO, typename T, int RK = ROBUST_NONE, bool PR = false>
+__global__ void __launch_bounds__(LIN_THREADS) k_linearize_lm(LinArgs<TO, T> a) {
+  constexpr bool LM = true;
+  constexpr int D = 6;
+#include "linearize_pull.inc"
 }
 
 // ---- the EDGE-PARALLEL form of the same linearisation (the north star's wording; RR_PGO_EDGE_LINEARIZE=1) ----
@@ -1152,21 +948,37 @@ __global__ void __launch_bounds__(256) k_linearize_wave_edges(LinArgs<TO, T> a, 
   if (threadIdx.x == 0) a.chi2_partial[blockIdx.x] = tot;
 }
 
+// s = e^T W e of an SE3_XYZ term (3-D graphs with landmarks, is3d == 2), by the code of k_linearize_lm: edge_linearize_3d_point,
+// the 21-entry information, edge_chi2_3d.  Called by the LM instantiations of k_edge_errors and k_prior_errors alone: the LM = false
+// ones, which every handle without landmarks launches, are the code they were (rr_pgo_check_edges' chi2 equals rr_pgo_edge_errors'
+// bit for bit on SE(3) graphs only while both keep their arithmetic; their fp32 sums depend on how the compiler pairs them, r17).
+template <typename TC>
+__device__ __noinline__ TC point_term_s(typename VecT<TC>::V4 pt, typename VecT<TC>::V4 pq, typename VecT<TC>::V4 lm,
+                                        typename VecT<TC>::V4 zm, const TC *info) {
+  TC t[3], q[4], l[3], z[3], W[6][6], e[6], J[6][6];
+  pose_3d<TC>(pt, pq, t, q);
+  l[0] = lm.x; l[1] = lm.y; l[2] = lm.z;
+  z[0] = zm.x; z[1] = zm.y; z[2] = zm.z;
+  info_3d<TC>(info, W);
+  edge_linearize_3d_point<TC>(0, t, q, l, z, e, J);
+  return edge_chi2_3d<TC>(W, e);
+}
+
 // rr_pgo_edge_errors: one thread per edge, s = e^T W e and the robust weight w(s) at the current state, in f64 (file order).
 // The same error code as the linearisation kernels (edge_linearize_2d / edge_linearize_3d), in TC.
 template <typename TC> struct EdgeErrArgs {
-  int n_edges, is3d, kind;               // kind: ROBUST_*
+  int n_edges, is3d, kind;               // is3d: 1 SE(3) poses only, 2 with XYZ landmarks; kind: ROBUST_*
   const EdgeRec<TC> *e_rec;              // SE(2)
   const typename VecT<TC>::V4 *pose;     // SE(2): 1 per node; SE(3): 2 per node
   const int2 *e_idx;                     // SE(3)
   const typename VecT<TC>::V4 *e_meas;   // SE(3): 2 per edge
   const TC *e_info;                      // SE(3): 21 per edge
-  const uint8_t *node_dim;               // SE(2): 3 (pose) or 2 (landmark: the edge into it is pose-landmark)
+  const uint8_t *node_dim;               // 3 (SE2 pose / XYZ landmark), 2 (XY landmark) or 6: the edge into a landmark is pose-landmark
   TC delta, delta2;
   const uint8_t *mask;                   // null: every edge
   double *s_out, *w_out;
 };
-template <typename TC> __global__ void __launch_bounds__(256) k_edge_errors(EdgeErrArgs<TC> a) {
+template <typename TC, bool LM = false> __global__ void __launch_bounds__(256) k_edge_errors(EdgeErrArgs<TC> a) {
   const int k = blockIdx.x * 256 + threadIdx.x;
   if (k >= a.n_edges) return;
   TC s;
@@ -1176,6 +988,8 @@ template <typename TC> __global__ void __launch_bounds__(256) k_edge_errors(Edge
     info_2d<TC>(rec, W);
     edge_linearize_2d<TC>(a.node_dim[rec.to] == 2 ? 1 : 0, a.pose[rec.from], a.pose[rec.to], rec.meas, e, A, B);
     s = edge_chi2_2d<TC>(W, e);
+  } else if (LM && a.node_dim[a.e_idx[k].y] == 3) {   // LM: the instantiation of 3-D graphs with landmarks (is3d == 2)
+    s = point_term_s<TC>(a.pose[2 * a.e_idx[k].x], a.pose[2 * a.e_idx[k].x + 1], a.pose[2 * a.e_idx[k].y], a.e_meas[2 * k], a.e_info + (int64_t)k * 21);
   } else {
     const int2 ft = a.e_idx[k];
     using V4 = typename VecT<TC>::V4;
@@ -1208,18 +1022,18 @@ template <typename TC> __global__ void __launch_bounds__(256) k_edge_errors(Edge
 // rr_pgo_prior_errors: one thread per prior (CSR order; the host puts them back in the call's order), s = e^T Omega e and the
 // robust weight of flagged priors at the current state, in f64.  The error code of k_linearize's prior loop, in TC.
 template <typename TC> struct PriorErrArgs {
-  int n_priors, is3d, kind;              // kind: ROBUST_*
+  int n_priors, is3d, kind;              // is3d: 1 SE(3) poses only, 2 with XYZ landmarks; kind: ROBUST_*
   const int32_t *node;                   // per prior
   const EdgeRec<TC> *rec;                // SE(2)
   const typename VecT<TC>::V4 *pose;     // SE(2): 1 per node; SE(3): 2 per node
   const typename VecT<TC>::V4 *meas;     // SE(3): 2 per prior
   const TC *info;                        // SE(3): 21 per prior
-  const uint8_t *node_dim;               // SE(2): 3 (pose) or 2 (landmark)
+  const uint8_t *node_dim;               // 3 (SE2 pose / XYZ landmark), 2 (XY landmark) or 6
   TC delta, delta2;
   const uint8_t *robust;                 // per prior
   double *s_out, *w_out;
 };
-template <typename TC> __global__ void __launch_bounds__(256) k_prior_errors(PriorErrArgs<TC> a) {
+template <typename TC, bool LM = false> __global__ void __launch_bounds__(256) k_prior_errors(PriorErrArgs<TC> a) {
   const int p = blockIdx.x * 256 + threadIdx.x;
   if (p >= a.n_priors) return;
   const int node = a.node[p];
@@ -1230,6 +1044,9 @@ template <typename TC> __global__ void __launch_bounds__(256) k_prior_errors(Pri
     info_2d<TC>(rec, W);
     prior_linearize_2d<TC>(a.node_dim[node] == 2 ? 1 : 0, a.pose[node], rec.meas, e, B);
     s = edge_chi2_2d<TC>(W, e);
+  } else if (LM && a.node_dim[node] == 3) {   // LM (is3d == 2): a prior on an XYZ landmark, the point edge from the identity pose
+    using V4 = typename VecT<TC>::V4;
+    s = point_term_s<TC>(V4{(TC)0, (TC)0, (TC)0, (TC)0}, V4{(TC)0, (TC)0, (TC)0, (TC)1}, a.pose[2 * node], a.meas[2 * p], a.info + (int64_t)p * 21);
   } else {
     TC tx[3], qx[4], tz[3], qz[4], W[6][6], e[6], B[6][6];
     pose_3d<TC>(a.pose[2 * node], a.pose[2 * node + 1], tx, qx);
@@ -1252,13 +1069,14 @@ template <typename TC> __global__ void __launch_bounds__(256) k_prior_errors(Pri
 //   GUESS_SE2      X_dst = X_src Z           GUESS_SE2_INV   X_dst = X_src Z^-1
 //   GUESS_XY       l_dst = t_src + R_src z
 //   GUESS_SE3      X_dst = X_src Z           GUESS_SE3_INV   X_dst = X_src Z^-1
+//   GUESS_XYZ      l_dst = t_src + R_src z
 // Every step has at most one earlier step it depends on (the one that produced its source), so the steps form trees; the
 // host lays them out tree by tree, list order kept within a tree, and ONE THREAD walks one tree: no hand-off between
 // threads, no atomics, the same bits under every schedule.  (cos, sin) and quaternions are renormalised, in TC.
-enum { GUESS_SE2 = 0, GUESS_SE2_INV = 1, GUESS_XY = 2, GUESS_SE3 = 3, GUESS_SE3_INV = 4 };
+enum { GUESS_SE2 = 0, GUESS_SE2_INV = 1, GUESS_XY = 2, GUESS_SE3 = 3, GUESS_SE3_INV = 4, GUESS_XYZ = 5 };
 template <typename TC> struct GuessStep {
   int32_t src, dst, op, pad;
-  typename VecT<TC>::V4 m0, m1;   // SE(2): (x, y, cos, sin), -- ; landmark: (x, y, 0, 0), -- ; SE(3): (t, 0), unit q
+  typename VecT<TC>::V4 m0, m1;   // SE(2): (x, y, cos, sin), -- ; landmark: (x, y, 0, 0), -- ; SE(3): (t, 0), unit q; XYZ: (z, 0), --
 };
 template <typename TC>
 __global__ void __launch_bounds__(64) k_guess_nodes(typename VecT<TC>::V4 *pose, int n_pose_nodes, int is3d, const GuessStep<TC> *steps,
@@ -1288,6 +1106,13 @@ __global__ void __launch_bounds__(64) k_guess_nodes(typename VecT<TC>::V4 *pose,
       const V4 pt = pose[2 * st.src], pq = pose[2 * st.src + 1];
       const TC t[3] = {pt.x, pt.y, pt.z}, q[4] = {pq.x, pq.y, pq.z, pq.w};
       const TC zt[3] = {st.m0.x, st.m0.y, st.m0.z};
+      if (st.op == GUESS_XYZ) {
+        TC d[3];
+        q_rot<TC>(q, zt, d);
+        pose[2 * st.dst] = V4{t[0] + d[0], t[1] + d[1], t[2] + d[2], (TC)0};
+        pose[2 * st.dst + 1] = V4{(TC)0, (TC)0, (TC)0, (TC)0};
+        continue;
+      }
       const TC sg = st.op == GUESS_SE3_INV ? (TC)-1 : (TC)1;
       const TC zq[4] = {sg * st.m1.x, sg * st.m1.y, sg * st.m1.z, st.m1.w};   // the conjugate for Z^-1
       TC r[4], d[3];
@@ -4281,7 +4106,7 @@ template <typename T, typename TC> __global__ void __launch_bounds__(256) k_big_
 template <typename T, typename TC = T> struct UpdArgs {
   int n_nodes;
   typename VecT<TC>::V4 *pose;
-  const uint8_t *node_dim;   // SE(2): 3 (pose) or 2 (XY landmark); SE(3): null
+  const uint8_t *node_dim;   // SE(2): 3 (pose) or 2 (XY landmark); SE(3): 6 or 3 (XYZ landmark), read by k_update_lm alone
   const int32_t *node_pcol, *node_offset;
   const T *x;          // permuted solution (used when dx_ref_in == nullptr)
   const T *dx_ref_in;  // reference-order step supplied by the caller (rr_pgo_update)
@@ -4381,35 +4206,42 @@ __device__ __forceinline__ double update_node_se3(const UpdArgs<TO, T> &a, int n
   return nrm;
 }
 
+// XYZ landmark (3-D graphs, k_update_lm): l <- l + sign * dl, no renormalisation; returns the node's |dl|^2 term
+template <typename TO, typename T>
+__device__ __forceinline__ double update_node_xyz(const UpdArgs<TO, T> &a, int node) {
+  double nrm = 0.0;
+  T d[3];
+  const TO *src = a.dx_ref_in ? a.dx_ref_in + a.node_offset[node] : a.x + a.node_pcol[node];
+#pragma unroll
+  for (int t = 0; t < 3; t++) d[t] = (T)src[t];
+  if (a.dx_ref_out) {
+    TO *dst = a.dx_ref_out + a.node_offset[node];
+#pragma unroll
+    for (int t = 0; t < 3; t++) dst[t] = src[t];
+  }
+  if (a.export_only) return nrm;
+#pragma unroll
+  for (int t = 0; t < 3; t++) { nrm += (double)d[t] * (double)d[t]; d[t] *= a.sign; }
+  if (a.norm_counts && !a.norm_counts[node]) nrm = 0.0;
+  auto pt = a.pose[2 * node];
+  pt.x += d[0]; pt.y += d[1]; pt.z += d[2];
+  a.pose[2 * node] = pt;
+  return nrm;
+}
+
 // The update's frame, SE(2) (D = 3) and SE(3) (D = 6): only the node's own update is per dimension.
+// The body is update_frame.inc, included by the two kernels below behind `constexpr bool LM`.  LM (D = 6): the graph has
+// XYZ landmarks -- node_dim is read and a landmark takes update_node_xyz; false is the code of every pure SE(3) handle.
 template <typename TO, typename T, int D = 3>
 __global__ void __launch_bounds__(UPD_THREADS) k_update(UpdArgs<TO, T> a) {
-  __shared__ double red[UPD_THREADS / 64];
-  const int node = listed_node(a, blockIdx.x * UPD_THREADS + threadIdx.x);
-  double nrm = 0.0;
-  // rr_pgo_optimize: enqueued behind the iteration that met the stop rule (:298-300) -- the state, the partials, the slot
-  // counter and the ring stay as that iteration left them
-  if (opt_stopped(a.err)) return;
-  if (a.gate && *a.gate == 0) return;
-  const FinPre fin_pre = finalize_preload<UPD_THREADS>(a.fin);   // requested ahead of the node work
-  const bool failed = a.err && a.err[0] != 0;   // a failed factorisation: the state stays
-  if (node >= 0 && !failed) {
-    if (a.fixed && a.fixed[node]) {
-      // a fixed node is skipped, not updated with zero (SE(3) renormalises the quaternion): its state bits stay, it adds
-      // nothing to |dx|^2 and the exported step is 0
-      if (a.dx_ref_out) {
-        int nd = D;
-        if constexpr (D == 3) nd = a.node_dim[node];
-        TO *dst = a.dx_ref_out + a.node_offset[node];
-        for (int t = 0; t < nd; t++) dst[t] = (TO)0;
-      }
-    } else if constexpr (D == 3) nrm = update_node(a, node);
-    else nrm = update_node_se3(a, node);
-  }
-  if (a.export_only) return;
-  double tot = block_sum<double, UPD_THREADS>(nrm, red);
-  if (threadIdx.x == 0) a.norm_partial[blockIdx.x] = tot;
-  if (a.fin.enabled) finalize_in_last_block<UPD_THREADS>(a.fin, fin_pre, a.norm_partial, (int)gridDim.x, red);
+  constexpr bool LM = false;
+#include "update_frame.inc"
+}
+template <typename TO, typename T>
+__global__ void __launch_bounds__(UPD_THREADS) k_update_lm(UpdArgs<TO, T> a) {
+  constexpr bool LM = true;
+  constexpr int D = 6;
+#include "update_frame.inc"
 }
 
 }  // namespace rrpgo

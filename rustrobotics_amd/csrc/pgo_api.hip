@@ -368,7 +368,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     double p[8];
     const int n = pack_state(kind, s, p);
     v[0] = V4{(S)p[0], (S)p[1], (S)p[2], (S)p[3]};
-    if (kind == NODE_SE3) v[1] = V4{(S)p[4], (S)p[5], (S)p[6], (S)p[7]};
+    if (kind == NODE_SE3 || kind == NODE_XYZ) v[1] = V4{(S)p[4], (S)p[5], (S)p[6], (S)p[7]};   // (XYZ: zeros)
     return n;
   }
   static int unpack_v4(int kind, const V4 *v, double *s) {
@@ -393,6 +393,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   DevBuf<uint8_t> node_dim_;
   DevBuf<S> e_info3_;   // SE(3): 21 information entries per edge
   bool is3d_ = false;
+  bool has_lm_ = false;   // a 3-D graph with XYZ landmarks: the LM kernels (k_linearize_lm, k_update_lm) run
   // sharding over ranks
   int rank_ = 0, world_ = 1;
   bool sharded_ = false;            // driven by rr_pgo_stage (world_size > 1, or opt.sharded with one rank)
@@ -624,6 +625,9 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     const int N = g.n_nodes(), E = g.n_edges();
     // ---- graph arrays
     is3d_ = g.has_se3;
+    has_lm_ = g.has_xyz;
+    if (has_lm_ && sharded_)
+      throw ApiError(RR_PGO_EUNSUPPORTED, "sharded handle on a graph with XYZ landmarks (the ranks' exchange of SE(3) fronts is not taught the 3-scalar nodes)");
     std::vector<uint8_t> ndim(N);
     for (int i = 0; i < N; i++) ndim[i] = (uint8_t)node_dim(g.node_kind[i]);
     node_dim_.upload(ndim);
@@ -633,7 +637,8 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
       // The loops are split by dimension and the 2-D ones name their two kinds, so that each compiles to its own forms alone.
       const size_t per = is3d_ ? 2 : 1;
       std::vector<V4> pose(per * (size_t)N);
-      if (is3d_) for (int i = 0; i < N; i++) pack_v4(NODE_SE3, &g.node_state[g.node_state_off[i]], &pose[2 * (size_t)i]);
+      if (is3d_ && has_lm_) for (int i = 0; i < N; i++) pack_v4(g.node_kind[i] == NODE_XYZ ? NODE_XYZ : NODE_SE3, &g.node_state[g.node_state_off[i]], &pose[2 * (size_t)i]);
+      else if (is3d_) for (int i = 0; i < N; i++) pack_v4(NODE_SE3, &g.node_state[g.node_state_off[i]], &pose[2 * (size_t)i]);
       else for (int i = 0; i < N; i++) pack_v4(g.node_kind[i] == NODE_SE2 ? NODE_SE2 : NODE_XY, &g.node_state[g.node_state_off[i]], &pose[i]);
       pose_.upload(pose);
       if (!is3d_) {
@@ -663,9 +668,9 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
         for (int k = 0; k < E; k++) {
           eidx[k] = int2{g.edge_from[k], g.edge_to[k]};
           eslot[k] = edge_slot(k);
-          pack_v4(EDGE_SE3, &g.edge_meas[g.edge_meas_off[k]], &emeas[2 * (size_t)k]);
-          const double *w = &g.edge_info[g.edge_info_off[k]];
-          for (int t = 0; t < 21; t++) einfo[21 * (size_t)k + t] = (S)w[t];
+          // (an SE3_XYZ edge: the point and a zero V4; its 6 information values in the upper-left 3 x 3 of the 21)
+          pack_v4(g.edge_kind[k] == EDGE_SE3_XYZ ? EDGE_SE3_XYZ : EDGE_SE3, &g.edge_meas[g.edge_meas_off[k]], &emeas[2 * (size_t)k]);
+          pack_info_3d<S>(g.edge_kind[k], &g.edge_info[g.edge_info_off[k]], &einfo[21 * (size_t)k]);
         }
         e_idx_.upload(eidx);
         e_slot_.upload(eslot);
@@ -684,7 +689,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
       const int pf = world_ > 1 ? sym.node_part[g.edge_from[k]] : 0, pt = world_ > 1 ? sym.node_part[g.edge_to[k]] : 0;
       const int owns = (pf >= 0 ? pf : pt >= 0 ? pt : 0) == rank_ ? 1 : 0;
       const int offd = role == 0 && (owns || (pf < 0 && pt < 0)) ? 1 : 0;
-      inc[q] = int2{(k << 4) | (offd << 3) | (owns << 2) | ((g.edge_kind[k] == EDGE_SE2_XY ? 1 : 0) << 1) | role,
+      inc[q] = int2{(k << 4) | (offd << 3) | (owns << 2) | ((g.edge_kind[k] == EDGE_SE2_XY || g.edge_kind[k] == EDGE_SE3_XYZ ? 1 : 0) << 1) | role,
                     role ? g.edge_from[k] : g.edge_to[k]};
     }
     inc_ptr_.upload(sym.inc_ptr);
@@ -1739,7 +1744,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     a.e_slot = e_slot_.p;
     a.inc_ptr = inc_ptr_.p;
     a.inc_list = inc_list_.p;
-    a.node_dim = is3d_ ? nullptr : node_dim_.p;
+    a.node_dim = (is3d_ && !has_lm_) ? nullptr : node_dim_.p;
     a.node_offset = node_offset_.p;
     a.diag_off = diag_off_.p;
     a.hvals = hvals_.p;
@@ -1879,6 +1884,11 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     pend(RR_PGO_K_LINEARIZE);
   }
   template <int RK> void launch_pull(const LinArgs<T, S> &la) {   // the pull form of either dimension under robust kernel RK
+    if (has_lm_) {   // a 3-D graph with XYZ landmarks: the LM instantiations (a pure SE(3) handle launches the kernels it always did)
+      if (priors_.n() > 0) hipLaunchKernelGGL((k_linearize_lm<T, S, RK, true>), dim3(n_lin_blocks_), dim3(LIN_THREADS), 0, stream_, la);
+      else hipLaunchKernelGGL((k_linearize_lm<T, S, RK, false>), dim3(n_lin_blocks_), dim3(LIN_THREADS), 0, stream_, la);
+      return;
+    }
     if (priors_.n() > 0) {   // (a handle without priors launches the kernels it always did)
       if (is3d_) hipLaunchKernelGGL((k_linearize<T, S, RK, 6, true>), dim3(n_lin_blocks_), dim3(LIN_THREADS), 0, stream_, la);
       else hipLaunchKernelGGL((k_linearize<T, S, RK, 3, true>), dim3(n_lin_blocks_), dim3(LIN_THREADS), 0, stream_, la);
@@ -2074,7 +2084,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     u.node_list = node_list_.p;
     u.norm_counts = norm_counts_.p;
     u.pose = pose_.p;
-    u.node_dim = is3d_ ? nullptr : node_dim_.p;
+    u.node_dim = (is3d_ && !has_lm_) ? nullptr : node_dim_.p;
     u.node_pcol = node_pcol_.p;
     u.node_offset = node_offset_.p;
     u.x = x_ptr_;
@@ -2088,7 +2098,8 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     u.gate = gate;
     u.fixed = fixed_nodes_.empty() ? nullptr : fixed_.p;
     u.fin = fin;
-    if (is3d_) hipLaunchKernelGGL((k_update<T, S, 6>), dim3(n_upd_blocks_), dim3(UPD_THREADS), 0, stream_, u);
+    if (has_lm_) hipLaunchKernelGGL((k_update_lm<T, S>), dim3(n_upd_blocks_), dim3(UPD_THREADS), 0, stream_, u);
+    else if (is3d_) hipLaunchKernelGGL((k_update<T, S, 6>), dim3(n_upd_blocks_), dim3(UPD_THREADS), 0, stream_, u);
     else hipLaunchKernelGGL((k_update<T, S, 3>), dim3(n_upd_blocks_), dim3(UPD_THREADS), 0, stream_, u);
     check_launch("k_update");
     pend(RR_PGO_K_UPDATE);
@@ -2430,7 +2441,8 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     }
     state_in_.assign(st, st + n_in);
     V4 *pose = state_stage_.p;
-    if (is3d_) for (int i = 0; i < N; i++) st += pack_v4(NODE_SE3, st, pose + 2 * (size_t)i);   // (split as in the constructor)
+    if (is3d_ && has_lm_) for (int i = 0; i < N; i++) st += pack_v4(g_.node_kind[i] == NODE_XYZ ? NODE_XYZ : NODE_SE3, st, pose + 2 * (size_t)i);
+    else if (is3d_) for (int i = 0; i < N; i++) st += pack_v4(NODE_SE3, st, pose + 2 * (size_t)i);   // (split as in the constructor)
     else for (int i = 0; i < N; i++) st += pack_v4(g_.node_kind[i] == NODE_SE2 ? NODE_SE2 : NODE_XY, st, pose + i);
     HIPCHK(hipMemcpyAsync(pose_saved_.p, pose, pose_.n * sizeof(V4), hipMemcpyHostToDevice, stream_));
     HIPCHK(hipEventRecord(state_stage_ev_, stream_));
@@ -2472,7 +2484,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
       GuessStep<S> &d = ds[k];
       d.src = h.src; d.dst = h.dst; d.op = h.op; d.pad = 0;
       V4 m[2] = {};
-      pack_v4(h.op == GUESS_XY ? EDGE_SE2_XY : h.op == GUESS_SE3 || h.op == GUESS_SE3_INV ? EDGE_SE3 : EDGE_SE2, h.m, m);
+      pack_v4(h.op == GUESS_XY ? EDGE_SE2_XY : h.op == GUESS_XYZ ? EDGE_SE3_XYZ : h.op == GUESS_SE3 || h.op == GUESS_SE3_INV ? EDGE_SE3 : EDGE_SE2, h.m, m);
       d.m0 = m[0];
       d.m1 = m[1];
     }
@@ -2698,7 +2710,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     out.alloc(2 * (size_t)E);
     EdgeErrArgs<S> a;
     a.n_edges = E;
-    a.is3d = is3d_ ? 1 : 0;
+    a.is3d = is3d_ ? (has_lm_ ? 2 : 1) : 0;
     a.kind = robust_kind_;
     a.e_rec = e_rec_.p;
     a.pose = pose_.p;
@@ -2711,7 +2723,8 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     a.mask = robust_mask_.n ? robust_mask_.p : nullptr;
     a.s_out = out.p;
     a.w_out = out.p + E;
-    hipLaunchKernelGGL((k_edge_errors<S>), dim3((E + 255) / 256), dim3(256), 0, stream_, a);
+    if (has_lm_) hipLaunchKernelGGL((k_edge_errors<S, true>), dim3((E + 255) / 256), dim3(256), 0, stream_, a);
+    else hipLaunchKernelGGL((k_edge_errors<S>), dim3((E + 255) / 256), dim3(256), 0, stream_, a);
     check_launch("k_edge_errors");
     std::vector<double> host(2 * (size_t)E);
     HIPCHK(hipMemcpyAsync(host.data(), out.p, host.size() * sizeof(double), hipMemcpyDeviceToHost, stream_));
@@ -2760,8 +2773,9 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
       pnode[c] = node;
       rob[c] = ps.robust[p];
       if (is3d_) {
-        pack_v4(EDGE_SE3, m, &meas[2 * (size_t)c]);
-        for (int t = 0; t < 21; t++) info[21 * (size_t)c + t] = (S)w[t];
+        const int ek = prior_edge_kind(g_.node_kind[node]);   // SE3, or SE3_XYZ on a landmark
+        pack_v4(ek, m, &meas[2 * (size_t)c]);
+        pack_info_3d<S>(ek, w, &info[21 * (size_t)c]);
         continue;
       }
       EdgeRec<S> &r = rec[c];   // (slot stays 0: a prior has no off-diagonal block)
@@ -2826,7 +2840,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     out.alloc(2 * (size_t)P);
     PriorErrArgs<S> a;
     a.n_priors = P;
-    a.is3d = is3d_ ? 1 : 0;
+    a.is3d = is3d_ ? (has_lm_ ? 2 : 1) : 0;
     a.kind = robust_kind_;
     a.node = prior_node_.p;
     a.rec = prior_rec_.p;
@@ -2839,7 +2853,8 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     a.robust = prior_robust_.p;
     a.s_out = out.p;
     a.w_out = out.p + P;
-    hipLaunchKernelGGL((k_prior_errors<S>), dim3((P + 255) / 256), dim3(256), 0, stream_, a);
+    if (has_lm_) hipLaunchKernelGGL((k_prior_errors<S, true>), dim3((P + 255) / 256), dim3(256), 0, stream_, a);
+    else hipLaunchKernelGGL((k_prior_errors<S>), dim3((P + 255) / 256), dim3(256), 0, stream_, a);
     check_launch("k_prior_errors");
     std::vector<double> host(2 * (size_t)P);
     HIPCHK(hipMemcpyAsync(host.data(), out.p, host.size() * sizeof(double), hipMemcpyDeviceToHost, stream_));
@@ -3426,7 +3441,8 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
         a.chi2 = ts_out_.p + nc;
         a.sout = innov ? ts_out_.p + 2 * nc : nullptr;
         a.S = sym_.S;
-        if (is3d_) hipLaunchKernelGGL((k_gate_pairs<T, 6>), dim3((unsigned)nc), dim3(COV_THREADS), 0, stream_, a);
+        if (has_lm_) hipLaunchKernelGGL((k_gate_pairs<T, 6, true>), dim3((unsigned)nc), dim3(COV_THREADS), 0, stream_, a);
+        else if (is3d_) hipLaunchKernelGGL((k_gate_pairs<T, 6>), dim3((unsigned)nc), dim3(COV_THREADS), 0, stream_, a);
         else hipLaunchKernelGGL((k_gate_pairs<T, 3>), dim3((unsigned)nc), dim3(COV_THREADS), 0, stream_, a);
         check_launch("k_gate_pairs");
         return std::array<TsDest, 3>{{{d2 + c0, nc}, {chi2 ? chi2 + c0 : nullptr, nc}, {innov ? innov + soff[c0] : nullptr, n_innov(c0, c1)}}};
@@ -3470,7 +3486,8 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
         a.delta2 = (T)(robust_delta_ * robust_delta_);
         a.S = sym_.S;
         a.rkind = robust_kind_;
-        if (is3d_) hipLaunchKernelGGL((k_check_edges<T, 6>), dim3((unsigned)nc), dim3(COV_THREADS), 0, stream_, a);
+        if (has_lm_) hipLaunchKernelGGL((k_check_edges<T, 6, true>), dim3((unsigned)nc), dim3(COV_THREADS), 0, stream_, a);
+        else if (is3d_) hipLaunchKernelGGL((k_check_edges<T, 6>), dim3((unsigned)nc), dim3(COV_THREADS), 0, stream_, a);
         else hipLaunchKernelGGL((k_check_edges<T, 3>), dim3((unsigned)nc), dim3(COV_THREADS), 0, stream_, a);
         check_launch("k_check_edges");
         return std::array<TsDest, 4>{{{d2 + c0, nc}, {chi2 ? chi2 + c0 : nullptr, nc}, {red ? red + c0 : nullptr, nc},
@@ -3562,7 +3579,8 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
         a.d2 = ts_out_.p;
         a.prefix = ts_out_.p + ns;
         a.sout = innov ? ts_out_.p + ns + nc : nullptr;
-        if (is3d_) hipLaunchKernelGGL((k_gate_joint<T, 6>), dim3((unsigned)ns), dim3(COV_THREADS), 0, stream_, a);
+        if (has_lm_) hipLaunchKernelGGL((k_gate_joint<T, 6, true>), dim3((unsigned)ns), dim3(COV_THREADS), 0, stream_, a);
+        else if (is3d_) hipLaunchKernelGGL((k_gate_joint<T, 6>), dim3((unsigned)ns), dim3(COV_THREADS), 0, stream_, a);
         else hipLaunchKernelGGL((k_gate_joint<T, 3>), dim3((unsigned)ns), dim3(COV_THREADS), 0, stream_, a);
         check_launch("k_gate_joint");
         return std::array<TsDest, 3>{{{d2 + s0, ns}, {prefix ? prefix + q0 : nullptr, nc}, {innov ? innov + ioff[s0] : nullptr, n_innov(s0, s1)}}};
@@ -4053,8 +4071,8 @@ static int plan_guess_steps(const HostGraph &g, int n_old, int e_old, std::vecto
       int src, dst, op;
       if (ready[f] && !ready[t] && t >= n_old) {
         src = f; dst = t;
-        op = ek == EDGE_SE2 ? GUESS_SE2 : ek == EDGE_SE2_XY ? GUESS_XY : GUESS_SE3;
-      } else if (ready[t] && !ready[f] && f >= n_old && ek != EDGE_SE2_XY) {   // (a landmark does not determine the pose that saw it)
+        op = ek == EDGE_SE2 ? GUESS_SE2 : ek == EDGE_SE2_XY ? GUESS_XY : ek == EDGE_SE3_XYZ ? GUESS_XYZ : GUESS_SE3;
+      } else if (ready[t] && !ready[f] && f >= n_old && ek != EDGE_SE2_XY && ek != EDGE_SE3_XYZ) {   // (a landmark does not determine the pose that saw it)
         src = t; dst = f;
         op = ek == EDGE_SE2 ? GUESS_SE2_INV : GUESS_SE3_INV;
       } else {
@@ -4128,7 +4146,7 @@ static void extend_handle(rr_pgo *h, int32_t n_new_nodes, const int32_t *node_ki
   const size_t state_old = g.node_state.size();
   for (int i = 0; i < n_new_nodes; i++) {
     const int node = n_old + i;
-    if (node_kind[i] < NODE_SE2 || node_kind[i] > NODE_SE3)
+    if (node_kind[i] < NODE_SE2 || node_kind[i] > NODE_XYZ)
       throw ApiError(RR_PGO_EINVAL, "rr_pgo_extend: new node " + std::to_string(i) + " (node " + std::to_string(node) + "): bad node kind " + std::to_string(node_kind[i]));
     const uint32_t id = node_id ? node_id[i] : (uint32_t)node;
     const auto ins = ids.emplace(id, node);
@@ -4142,12 +4160,12 @@ static void extend_handle(rr_pgo *h, int32_t n_new_nodes, const int32_t *node_ki
   for (int k = 0; k < n_new_edges; k++) {
     const std::string who = "rr_pgo_extend: new edge " + std::to_string(k) + " (edge " + std::to_string(e_old + k) + ")";
     const int ek = edge_kind[k], a = edge_from[k], b = edge_to[k];
-    if (ek < EDGE_SE2 || ek > EDGE_SE3) throw ApiError(RR_PGO_EINVAL, who + ": bad edge kind " + std::to_string(ek));
+    if (ek < EDGE_SE2 || ek > EDGE_SE3_XYZ) throw ApiError(RR_PGO_EINVAL, who + ": bad edge kind " + std::to_string(ek));
     if (a < 0 || a >= n_total || b < 0 || b >= n_total) throw ApiError(RR_PGO_EINVAL, who + " references an unknown vertex");
     if (a == b) throw ApiError(RR_PGO_EINVAL, who + " is a self loop");
     const int ka = g.node_kind[a], kb = g.node_kind[b];
     const bool ok = (ek == EDGE_SE2 && ka == NODE_SE2 && kb == NODE_SE2) || (ek == EDGE_SE2_XY && ka == NODE_SE2 && kb == NODE_XY) ||
-                    (ek == EDGE_SE3 && ka == NODE_SE3 && kb == NODE_SE3);
+                    (ek == EDGE_SE3 && ka == NODE_SE3 && kb == NODE_SE3) || (ek == EDGE_SE3_XYZ && ka == NODE_SE3 && kb == NODE_XYZ);
     if (!ok) throw ApiError(RR_PGO_EINVAL, who + ": endpoint kinds do not match the edge kind");
     g.edge_kind.push_back(ek);
     g.edge_from.push_back(a);
@@ -4335,7 +4353,7 @@ int rr_pgo_create(const rr_pgo_graph_desc *d, const rr_pgo_options *opt, rr_pgo 
     for (int i = 0; i < d->n_nodes; i++) g.node_id[i] = d->node_id ? d->node_id[i] : (uint32_t)i;
     size_t ns = 0;
     for (int i = 0; i < d->n_nodes; i++) {
-      if (g.node_kind[i] < 0 || g.node_kind[i] > 2) throw ApiError(RR_PGO_EINVAL, "bad node kind");
+      if (g.node_kind[i] < NODE_SE2 || g.node_kind[i] > NODE_XYZ) throw ApiError(RR_PGO_EINVAL, "bad node kind");
       ns += node_state_len(g.node_kind[i]);
     }
     g.node_state.assign(d->node_state, d->node_state + ns);
@@ -4344,7 +4362,7 @@ int rr_pgo_create(const rr_pgo_graph_desc *d, const rr_pgo_options *opt, rr_pgo 
     g.edge_to.assign(d->edge_to, d->edge_to + d->n_edges);
     size_t nm = 0, ni = 0;
     for (int k = 0; k < d->n_edges; k++) {
-      if (g.edge_kind[k] < 0 || g.edge_kind[k] > 2) throw ApiError(RR_PGO_EINVAL, "bad edge kind");
+      if (g.edge_kind[k] < EDGE_SE2 || g.edge_kind[k] > EDGE_SE3_XYZ) throw ApiError(RR_PGO_EINVAL, "bad edge kind");
       nm += edge_meas_len(g.edge_kind[k]);
       ni += edge_info_len(g.edge_kind[k]);
     }
@@ -4574,13 +4592,14 @@ static int gate_candidates(const char *api, const rr_pgo *h, int32_t n_cand, con
     const std::string who = std::string(api) + ": " + what + " " + std::to_string(c) + ": ";
     auto bad = [&](const std::string &what) { g_last_error = who + what; return RR_PGO_EINVAL; };
     const int kind = edge_kind[c], a = edge_from[c], b = edge_to[c];
-    if (kind != EDGE_SE2 && kind != EDGE_SE2_XY && kind != EDGE_SE3) return bad("unknown edge kind " + std::to_string(kind));
+    if (kind != EDGE_SE2 && kind != EDGE_SE2_XY && kind != EDGE_SE3 && kind != EDGE_SE3_XYZ) return bad("unknown edge kind " + std::to_string(kind));
     if (a < 0 || a >= N || b < 0 || b >= N) return bad("node index out of range");
     if (a == b) return bad("from == to");
     const int ka = g.node_kind[a], kb = g.node_kind[b];
     if (kind == EDGE_SE2 && (ka != NODE_SE2 || kb != NODE_SE2)) return bad("an SE2 edge needs two SE2 poses");
     if (kind == EDGE_SE2_XY && (ka != NODE_SE2 || kb != NODE_XY)) return bad("an SE2_XY edge goes from an SE2 pose to an XY landmark");
     if (kind == EDGE_SE3 && (ka != NODE_SE3 || kb != NODE_SE3)) return bad("an SE3 edge needs two SE3 poses");
+    if (kind == EDGE_SE3_XYZ && (ka != NODE_SE3 || kb != NODE_XYZ)) return bad("an SE3_XYZ edge goes from an SE3 pose to an XYZ landmark");
     const int nm = edge_meas_len(kind), ni = edge_info_len(kind), de = edge_dim(kind);
     const double *m = edge_meas + mo, *w = edge_info + io;
     mo += nm;

@@ -232,7 +232,7 @@ struct GateCand {
   CovQuery cq;                    // of the pair (a, b); ooff: offset of S (d_e x d_e, row-major) in sout
   int32_t fa, fb;                 // the fronts of a and of b
   int32_t na, nb, kind, pad;      // the two nodes; RR_PGO_EDGE_*
-  double meas[8];                 // 2-D: x, y, cos, sin | SE(3): t (3), -, q (4, normalised)
+  double meas[8];                 // 2-D: x, y, cos, sin | SE(3): t (3), -, q (4, normalised) | SE3_XYZ: x, y, z, then zeros
   double info[36], cov[36];       // Omega and Omega^-1, row stride D (3 or 6), zero padded
 };
 static_assert(sizeof(GateCand) == 712, "GateCand is one 712-byte record");
@@ -247,9 +247,16 @@ template <typename T> struct GateArgs {
   int32_t S;
 };
 
+// error dimension of a candidate of RR_PGO_EDGE_* `kind` in a graph of pose dimension D; a landmark edge's `to` node has as many scalars
+// LM: the kernel instantiation of a 3-D graph with XYZ landmarks (kind 3 occurs); false is the code of every other handle
+template <int D, bool LM> __device__ __forceinline__ int gate_edge_dim(int kind) {
+  if constexpr (LM) return kind == 3 ? 3 : D;
+  else return kind == 1 ? 2 : D;
+}
+
 // A candidate's error e and Jacobians A, B (row-major D x D) at the current state, by the linearisation's own code.
 // role 0: e and A, and in 2-D also B; role 1: B of SE3 (a second lane shares the work; in 2-D it has none).
-template <typename T, int D>
+template <typename T, int D, bool LM = false>
 __device__ __forceinline__ void gate_linearize(const GateCand *q, const typename VecT<T>::V4 *pose, int role, T *se, T *sA, T *sB) {
   using V4 = typename VecT<T>::V4;
   if constexpr (D == 3) {
@@ -274,7 +281,12 @@ __device__ __forceinline__ void gate_linearize(const GateCand *q, const typename
     const T tz[3] = {(T)q->meas[0], (T)q->meas[1], (T)q->meas[2]};
     const T qz[4] = {(T)q->meas[4], (T)q->meas[5], (T)q->meas[6], (T)q->meas[7]};
     T e[6], J[6][6];
-    edge_linearize_3d<T>(role, ti, qi, tj, qj, tz, qz, e, J);
+    if constexpr (LM) {
+      if (q->kind == 3) edge_linearize_3d_point<T>(role, ti, qi, tj, tz, e, J);   // RR_PGO_EDGE_SE3_XYZ, zero padded
+      else edge_linearize_3d<T>(role, ti, qi, tj, qj, tz, qz, e, J);
+    } else {
+      edge_linearize_3d<T>(role, ti, qi, tj, qj, tz, qz, e, J);
+    }
     T *dst = role ? sB : sA;
 #pragma unroll
     for (int i = 0; i < 6; i++) {
@@ -323,15 +335,15 @@ __device__ __forceinline__ T gate_walk(const TsMeta *meta, const T *Z, const int
 // (e, A) and B with the linearisation's own code.  A wave is one slice of rows (row = slice, slice + 8, ... of every front);
 // lane t of it accumulates entry t of P's lower triangle.  The eight slices are added in slice order, then lane 0 of wave 0
 // factors S = Omega^-1 + P in LDS.  A non-positive pivot of S (Omega is checked on the host: rounding only) gives d2 = NaN.
-template <typename T, int D>
+template <typename T, int D, bool LM = false>
 __global__ void __launch_bounds__(COV_THREADS) k_gate_pairs(GateArgs<T> a) {
   constexpr int NS = COV_THREADS / 64;
   __shared__ T part[NS * 32], sA[D * D], sB[D * D], se[D], sS[D * D];
   const GateCand *q = a.cand + blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63, slice = wave_index();
   const int kind = q->kind;
-  const int de = kind == 1 ? 2 : D, db = kind == 1 ? 2 : D, ntri = de * (de + 1) / 2;
-  if (lane == 0 && slice < 2) gate_linearize<T, D>(q, a.pose, slice, se, sA, sB);
+  const int de = gate_edge_dim<D, LM>(kind), db = de, ntri = de * (de + 1) / 2;
+  if (lane == 0 && slice < 2) gate_linearize<T, D, LM>(q, a.pose, slice, se, sA, sB);
   __syncthreads();
   // ---- entry t = (i, j), j <= i, of the lower triangle; lanes past the triangle repeat its last entry
   const int t = min(lane, ntri - 1);
@@ -423,15 +435,15 @@ template <typename T> struct CheckArgs {
 // Omega^-1(i, j) / w - P(i, j), mirrored, so R is symmetric bit for bit.  r is summed row by row, column by column, by one
 // lane.  A non-positive pivot of R (an edge at r near 0, or one whose residual the rest of the graph determines in some
 // directions only: rounding decides) gives d2 = NaN; r and R are written all the same.
-template <typename T, int D>
+template <typename T, int D, bool LM = false>
 __global__ void __launch_bounds__(COV_THREADS) k_check_edges(CheckArgs<T> a) {
   constexpr int NS = COV_THREADS / 64;
   __shared__ T part[NS * 32], sA[D * D], sB[D * D], se[D], sS[D * D], sw[1];
   const GateCand *q = a.cand + blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63, slice = wave_index();
   const int kind = q->kind;
-  const int de = kind == 1 ? 2 : D, db = kind == 1 ? 2 : D, ntri = de * (de + 1) / 2;
-  if (lane == 0 && slice < 2) gate_linearize<T, D>(q, a.pose, slice, se, sA, sB);
+  const int de = gate_edge_dim<D, LM>(kind), db = de, ntri = de * (de + 1) / 2;
+  if (lane == 0 && slice < 2) gate_linearize<T, D, LM>(q, a.pose, slice, se, sA, sB);
   __syncthreads();
   if (tid == 0) {
     T W[D][D], e[D];   // e^T Omega e by the linearisation's own edge_chi2 (Omega and a landmark edge's e are zero padded)
@@ -565,7 +577,7 @@ __device__ __forceinline__ void wave_lds_sync() {
 // candidates.  Lane k < D_s of every wave forms G_r[k] for GJ_RB of the wave's rows into the wave's LDS vector, then lane
 // (ti, tj), tj <= ti, adds the rows' outer products into its tile.  The eight waves' tiles are added in wave order, one turn
 // each, into S in LDS; wave 0 factors S, lane = row, with e as row D_s of the same recurrence (that row of L is y).
-template <typename T, int D>
+template <typename T, int D, bool LM = false>
 __global__ void __launch_bounds__(COV_THREADS) k_gate_joint(JointArgs<T> a) {
   constexpr int NS = COV_THREADS / 64, MD = GJ_MAX_DIM, LD = GJ_LD, TL = GJ_TILE, RB = GJ_RB, MC = GJ_MAX_CAND;
   __shared__ T sA[MC * D * D], sB[MC * D * D], se[MC * D], sS[(MD + 1) * LD], gw[NS * RB * MD];
@@ -576,11 +588,11 @@ __global__ void __launch_bounds__(COV_THREADS) k_gate_joint(JointArgs<T> a) {
   const int m = js.m, Ds = js.dim;
   // ---- linearise; wave 2 lays the stacked vector out meanwhile
   if (lane < m && wave < (D == 3 ? 1 : 2))
-    gate_linearize<T, D>(cq + lane, a.pose, wave, se + lane * D, sA + lane * D * D, sB + lane * D * D);
+    gate_linearize<T, D, LM>(cq + lane, a.pose, wave, se + lane * D, sA + lane * D * D, sB + lane * D * D);
   if (tid == 128) {
     int o = 0;
     for (int c = 0; c < m; c++) {
-      const int de = cq[c].kind == 1 ? 2 : D;
+      const int de = gate_edge_dim<D, LM>(cq[c].kind);
       s_o[c] = o;
       for (int i = 0; i < de && o < MD; i++, o++) {   // (the host has checked D_s <= MD)
         s_c[o] = c;
@@ -596,7 +608,7 @@ __global__ void __launch_bounds__(COV_THREADS) k_gate_joint(JointArgs<T> a) {
   T Ai[D], Bi[D];
   int cola[D], colb[D];
   {
-    const int i = live ? s_i[lane] : 0, db = cq[c].kind == 1 ? 2 : D;
+    const int i = live ? s_i[lane] : 0, db = gate_edge_dim<D, LM>(cq[c].kind);
 #pragma unroll
     for (int k = 0; k < D; k++) {
       Ai[k] = live ? sA[c * D * D + i * D + k] : (T)0;

@@ -34,18 +34,23 @@ class PoseGraphError(RuntimeError):
 
 
 # 0.95 quantiles of the chi-square distribution with 2, 3 and 6 degrees of freedom (the default gate), and the error
-# dimension, measurement length and packed information length of an edge by kind (RR_PGO_EDGE_SE2, _SE2_XY, _SE3)
+# dimension, measurement length and packed information length of an edge by kind (RR_PGO_EDGE_SE2, _SE2_XY, _SE3, _SE3_XYZ)
 CHI2_95_2, CHI2_95_3, CHI2_95_6 = 5.991, 7.815, 12.592
-GATE_DEFAULT_THRESHOLD = {0: CHI2_95_3, 1: CHI2_95_2, 2: CHI2_95_6}
+GATE_DEFAULT_THRESHOLD = {0: CHI2_95_3, 1: CHI2_95_2, 2: CHI2_95_6, 3: CHI2_95_3}
 # ... and with 1 .. 48 degrees of freedom (CHI2_95[d]; the default of PoseGraph.gate_joint_accept: d = D_s)
 CHI2_95 = (None,
            3.841, 5.991, 7.815, 9.488, 11.070, 12.592, 14.067, 15.507, 16.919, 18.307, 19.675, 21.026,
            22.362, 23.685, 24.996, 26.296, 27.587, 28.869, 30.144, 31.410, 32.671, 33.924, 35.172, 36.415,
            37.652, 38.885, 40.113, 41.337, 42.557, 43.773, 44.985, 46.194, 47.400, 48.602, 49.802, 50.998,
            52.192, 53.384, 54.572, 55.758, 56.942, 58.124, 59.304, 60.481, 61.656, 62.830, 64.001, 65.171)
-GATE_EDGE_DIM = (3, 2, 6)
-GATE_MEAS_LEN = (3, 2, 7)
-GATE_INFO_LEN = (6, 3, 21)
+GATE_EDGE_DIM = (3, 2, 6, 3)
+GATE_MEAS_LEN = (3, 2, 7, 3)
+GATE_INFO_LEN = (6, 3, 21, 6)
+# the same by node kind (RR_PGO_NODE_SE2, _XY, _SE3, _XYZ): scalars of the step and of the state; a node's state has the
+# length of the measurement of the edge of its kind
+NODE_DIM = (3, 2, 6, 3)
+NODE_STATE_LEN = GATE_MEAS_LEN
+KNOWN_KINDS = (0, 1, 2, 3)
 
 
 def gate_thresholds(edge_kind, threshold=None):
@@ -208,9 +213,9 @@ class PoseGraph:
         n, m = d.n_nodes, d.n_edges
         nk = np.ctypeslib.as_array(d.node_kind, (n,)).copy() if n else np.zeros(0, np.int32)
         ek = np.ctypeslib.as_array(d.edge_kind, (m,)).copy() if m else np.zeros(0, np.int32)
-        ns = int(sum({0: 3, 1: 2, 2: 7}[int(k)] for k in nk))
-        nm = int(sum({0: 3, 1: 2, 2: 7}[int(k)] for k in ek))
-        ni = int(sum({0: 6, 1: 3, 2: 21}[int(k)] for k in ek))
+        ns = int(np.sum(np.take(NODE_STATE_LEN, nk)))
+        nm = int(np.sum(np.take(GATE_MEAS_LEN, ek)))
+        ni = int(np.sum(np.take(GATE_INFO_LEN, ek)))
         return (nk, np.ctypeslib.as_array(d.node_state, (ns,)).copy(), ek,
                 np.ctypeslib.as_array(d.edge_from, (m,)).copy(), np.ctypeslib.as_array(d.edge_to, (m,)).copy(),
                 np.ctypeslib.as_array(d.edge_meas, (nm,)).copy(), np.ctypeslib.as_array(d.edge_info, (ni,)).copy())
@@ -506,7 +511,7 @@ class PoseGraph:
         info = np.ascontiguousarray(edge_info, np.float64).ravel()
         if kind.ndim != 1 or a.shape != kind.shape or b.shape != kind.shape:
             raise ValueError("edge_kind, edge_from and edge_to need the same length")
-        known = np.isin(kind, (0, 1, 2))   # (an unknown kind is the library's to refuse: the lengths are then not checked)
+        known = np.isin(kind, KNOWN_KINDS)   # (an unknown kind is the library's to refuse: the lengths are then not checked)
         if np.all(known):
             if len(meas) != int(np.sum(np.take(GATE_MEAS_LEN, kind))) or len(info) != int(np.sum(np.take(GATE_INFO_LEN, kind))):
                 raise ValueError("edge_meas / edge_info do not have the length the edge kinds ask for")
@@ -525,7 +530,7 @@ class PoseGraph:
 
     def gate(self, edge_kind, edge_from, edge_to, edge_meas, edge_info, threshold=None):
         """Boolean mask d2 <= threshold of the candidates (True: accept).  threshold: a scalar, a mapping from edge kind
-        (0 SE2, 1 SE2_XY, 2 SE3) to a scalar, or None: the 0.95 chi-square quantile of the edge's dimension."""
+        (0 SE2, 1 SE2_XY, 2 SE3, 3 SE3_XYZ) to a scalar, or None: the 0.95 chi-square quantile of the edge's dimension."""
         d2, _ = self.gate_edges(edge_kind, edge_from, edge_to, edge_meas, edge_info)
         return d2 <= gate_thresholds(edge_kind, threshold)
 
@@ -548,7 +553,7 @@ class PoseGraph:
         info = np.ascontiguousarray(edge_info, np.float64).ravel()
         if kind.ndim != 1 or a.shape != kind.shape or b.shape != kind.shape:
             raise ValueError("edge_kind, edge_from and edge_to need the same length")
-        if np.all(np.isin(kind, (0, 1, 2))):   # (an unknown kind is the library's to refuse)
+        if np.all(np.isin(kind, KNOWN_KINDS)):   # (an unknown kind is the library's to refuse)
             if len(meas) != int(np.sum(np.take(GATE_MEAS_LEN, kind))) or len(info) != int(np.sum(np.take(GATE_INFO_LEN, kind))):
                 raise ValueError("edge_meas / edge_info do not have the length the edge kinds ask for")
         sets = [np.asarray(s, np.int32).ravel() for s in sets]
@@ -593,7 +598,7 @@ class PoseGraph:
         info = np.ascontiguousarray(edge_info, np.float64).ravel()
         if a.shape != kind.shape or b.shape != kind.shape:
             raise ValueError("edge_kind, edge_from and edge_to need the same length")
-        if np.all(np.isin(kind, (0, 1, 2))):   # (an unknown kind is the library's to refuse: the lengths are then not checked)
+        if np.all(np.isin(kind, KNOWN_KINDS)):   # (an unknown kind is the library's to refuse: the lengths are then not checked)
             if len(meas) != int(np.sum(np.take(GATE_MEAS_LEN, kind))) or len(info) != int(np.sum(np.take(GATE_INFO_LEN, kind))):
                 raise ValueError("edge_meas / edge_info do not have the length the edge kinds ask for")
         nk = np.zeros(0, np.int32) if node_kind is None else np.ascontiguousarray(node_kind, np.int32).ravel()
@@ -602,7 +607,7 @@ class PoseGraph:
         st = ids = None
         if node_state is not None:
             st = np.ascontiguousarray(node_state, np.float64).ravel()
-            if np.all(np.isin(nk, (0, 1, 2))) and len(st) != int(np.sum(np.take(GATE_MEAS_LEN, nk))):
+            if np.all(np.isin(nk, KNOWN_KINDS)) and len(st) != int(np.sum(np.take(GATE_MEAS_LEN, nk))):
                 raise ValueError("node_state does not have the length the node kinds ask for")
         if node_id is not None:
             ids = np.ascontiguousarray(node_id, np.uint32).ravel()
@@ -678,19 +683,22 @@ class PoseGraph:
     # -- PoseGraph::plot, :375-431 -------------------------------------------------------
     def plot_data(self):
         """What the reference's figure shows: the poses (blue circles), the same poses joined in the order of their ids
-        (red line), the landmarks if there are any (red stars).  SE(3) graphs are `todo!()` in the reference (:398-399)."""
+        (red line), the landmarks if there are any (red stars).  SE(3) graphs are `todo!()` in the reference (:398-399) and stay
+        refused, so that a caller of the reference's figure meets the reference's behaviour; a 3-D graph with XYZ landmarks has
+        no counterpart there (build-defined kinds), and is shown as its x-y projection, landmarks as points like the 2-D ones."""
         L = _lib.load()
         d = _lib.GraphDesc()
         _check(L.rr_pgo_get_graph(self._h, C.byref(d)))
         n = d.n_nodes
         kinds = np.ctypeslib.as_array(d.node_kind, (n,)) if n else np.zeros(0, np.int32)
-        if np.any(kinds == 2):
+        if np.any(kinds == 2) and not np.any(kinds == 3):
             raise PoseGraphError(_lib.EUNSUPPORTED, "plot of an SE(3) graph: todo!() in the reference (pose_graph_optimization.rs:398-399)")
         ids = np.ctypeslib.as_array(d.node_id, (n,)).astype(np.int64) if (n and d.node_id) else np.arange(n)
         st = self.state()
-        offs = np.concatenate([[0], np.cumsum(np.where(kinds == 0, 3, 2))])[:-1]
+        # (a 3-D graph with XYZ landmarks, build-defined: its x-y projection, the landmarks as points like the 2-D ones)
+        offs = np.concatenate([[0], np.cumsum(np.take(NODE_STATE_LEN, kinds))])[:-1].astype(np.int64)
         xy = np.stack([st[offs], st[offs + 1]], 1) if n else np.zeros((0, 2))
-        pose = kinds == 0
+        pose = (kinds == 0) | (kinds == 2)
         order = np.argsort(ids[pose], kind="stable")
         return {"poses": xy[pose], "poses_seq": xy[pose][order], "landmarks": xy[~pose],
                 "file": f"img/{self.name}-{self.iteration}-{self.solver.name}.svg"}
