@@ -298,7 +298,8 @@ int rr_pgo_get_fixed(const rr_pgo *h, int32_t *out); /* ascending node indices, 
  * the handle's stream, then synchronises; the state, the Levenberg-Marquardt lambda and rr_pgo_optimize's results are
  * untouched.  A non-positive pivot: RR_PGO_ENOTSPD.
  * RR_PGO_EUNSUPPORTED (the message says which): sharded handles, RR_PGO_F32 / RR_PGO_MIXED handles, graphs with fronts
- * beyond LDS (rr_pgo_stats::n_big_fronts != 0). */
+ * beyond LDS (rr_pgo_stats::n_big_fronts != 0; there the message points to rr_pgo_covariances with
+ * rr_pgo_set_query_big_fronts). */
 int rr_pgo_marginals(rr_pgo *h, int32_t n_query, const int32_t *node_a, const int32_t *node_b,
                      double *out, int64_t *out_offset, int64_t *n_vals);
 /* ms[3]: HIP-event times of the last rr_pgo_marginals call -- linearise + factor, selected inverse, gather. */
@@ -318,7 +319,7 @@ int rr_pgo_marginals_times(const rr_pgo *h, double *ms);
  * Levenberg-Marquardt lambda, rr_pgo_optimize's results and captured graphs are untouched.
  * RR_PGO_EINVAL: an out-of-range node or n_query < 0 (nothing is written).  RR_PGO_ENOTSPD: a non-positive pivot.
  * RR_PGO_EUNSUPPORTED (the message says which): sharded handles, RR_PGO_F32 / RR_PGO_MIXED handles, graphs with fronts
- * beyond LDS (rr_pgo_stats::n_big_fronts != 0). */
+ * beyond LDS unless rr_pgo_set_query_big_fronts (rr_pgo_stats::n_big_fronts != 0). */
 int rr_pgo_covariances(rr_pgo *h, int32_t n_query, const int32_t *node_a, const int32_t *node_b,
                        double *out, int64_t *out_offset, int64_t *n_vals);
 /* ms[3]: HIP-event times of the last rr_pgo_covariances call -- linearise + factor, tree solve, products + gather. */
@@ -347,7 +348,7 @@ int rr_pgo_covariances_times(const rr_pgo *h, double *ms);
  * RR_PGO_EINVAL, decided before anything is launched or written, the message names the entry: negative counts, col_node ==
  * NULL with n_col > 0, row_node == NULL with n_row != rr_pgo_num_nodes, a node out of range, n_vals == NULL.
  * RR_PGO_ENOTSPD: a non-positive pivot, nothing is written.  RR_PGO_EUNSUPPORTED: the cases and messages of
- * rr_pgo_covariances.  RR_PGO_ENOMEM: one column node alone needs more workspace (forward and backward blocks of its pass)
+ * rr_pgo_covariances (graphs with fronts beyond LDS unless rr_pgo_set_query_big_fronts).  RR_PGO_ENOMEM: one column node alone needs more workspace (forward and backward blocks of its pass)
  * than the handle's bound, the message gives the bytes; a longer list is cut between column nodes, never between rows, and
  * the cut changes no bit. */
 int rr_pgo_cross_covariances(rr_pgo *h, int32_t n_row, const int32_t *row_node, int32_t n_col, const int32_t *col_node,
@@ -377,7 +378,7 @@ int rr_pgo_cross_covariances_times(const rr_pgo *h, double *ms);
  * poses; SE2_XY: from an SE2 pose to an XY landmark; SE3: two SE3 poses; SE3_XYZ: from an SE3 pose to an XYZ landmark), Omega not positive definite, a non-finite
  * measurement.  n_cand == 0: RR_PGO_OK.  RR_PGO_ENOTSPD: a non-positive pivot of H.
  * RR_PGO_EUNSUPPORTED (the message says which): sharded handles, RR_PGO_F32 / RR_PGO_MIXED handles, graphs with fronts
- * beyond LDS (rr_pgo_stats::n_big_fronts != 0). */
+ * beyond LDS unless rr_pgo_set_query_big_fronts (rr_pgo_stats::n_big_fronts != 0). */
 int rr_pgo_gate_edges(rr_pgo *h, int32_t n_cand,
                       const int32_t *edge_kind, const int32_t *edge_from, const int32_t *edge_to,
                       const double *edge_meas, const double *edge_info,
@@ -408,7 +409,8 @@ int rr_pgo_gate_times(const rr_pgo *h, double *ms);
  * of rr_pgo_gate_edges, n_sets < 0, a null required pointer (with n_sets > 0: the candidate arrays, set_ptr, set_cand,
  * d2_out), set_ptr[0] != 0 or set_ptr decreasing, an empty set, a set_cand out of range, more than
  * RR_PGO_GATE_JOINT_MAX_CAND candidates in a set, D_s > RR_PGO_GATE_JOINT_MAX_DIM.  n_sets == 0: RR_PGO_OK, nothing is read.
- * RR_PGO_ENOTSPD and RR_PGO_EUNSUPPORTED as for rr_pgo_gate_edges.  RR_PGO_ENOMEM: one set alone needs more workspace than
+ * RR_PGO_ENOTSPD and RR_PGO_EUNSUPPORTED as for rr_pgo_gate_edges (graphs with fronts beyond LDS unless
+ * rr_pgo_set_query_big_fronts).  RR_PGO_ENOMEM: one set alone needs more workspace than
  * the handle's bound (the message gives the bytes); longer lists are cut at set boundaries, which changes no bit. */
 int rr_pgo_gate_joint(rr_pgo *h, int32_t n_cand,
                       const int32_t *edge_kind, const int32_t *edge_from, const int32_t *edge_to,
@@ -451,7 +453,7 @@ int rr_pgo_gate_joint_times(const rr_pgo *h, double *ms);
  * state, the Levenberg-Marquardt lambda, rr_pgo_optimize's results, captured graphs and the robust setting are untouched.
  * The cost grows with the number of distinct endpoint nodes (32 columns per pass over their root paths).
  * RR_PGO_EUNSUPPORTED first (the message says which): sharded handles, RR_PGO_F32 / RR_PGO_MIXED handles, graphs with fronts
- * beyond LDS.  RR_PGO_EINVAL, decided before anything is launched or written: n_query < 0, null d2_out with n_query > 0,
+ * beyond LDS unless rr_pgo_set_query_big_fronts.  RR_PGO_EINVAL, decided before anything is launched or written: n_query < 0, null d2_out with n_query > 0,
  * edge == NULL with n_query != rr_pgo_num_edges, an edge index out of range.  n_query == 0: RR_PGO_OK, nothing is launched.
  * RR_PGO_ENOTSPD: a non-positive pivot of H; nothing is written.  RR_PGO_ENOMEM: one edge alone needs more workspace than
  * the handle's bound (the message gives the bytes); longer lists are cut, which changes no bit. */
@@ -460,6 +462,20 @@ int rr_pgo_check_edges(rr_pgo *h, int32_t n_query, const int32_t *edge,
                        double *resid_out, int64_t *resid_offset);
 /* ms[3]: HIP-event times of the last rr_pgo_check_edges call -- linearise + factor, tree solve, kernel + copy. */
 int rr_pgo_check_edges_times(const rr_pgo *h, double *ms);
+
+/* ---- factor queries on fronts beyond LDS (build-defined) --------
+ * Let rr_pgo_covariances, rr_pgo_cross_covariances, rr_pgo_gate_edges, rr_pgo_gate_joint and rr_pgo_check_edges answer on
+ * graphs with fronts beyond LDS.  Default 0: such graphs are refused as before, same code, same message -- the refusal is
+ * what callers and tests of the earlier interface rely on, so the capability is asked for per handle.
+ * With the switch on, a front beyond LDS (rr_pgo_stats::n_big_fronts of them) keeps its block of the tree solve in the
+ * call's workspace and is solved by kernels of its own, one or two more launches per level of the tree that
+ * holds such a front; every "bit for bit" sentence of the five queries holds on these graphs too.  On a handle without such
+ * fronts the switch changes no bit of any result and no launch.  The setter is RR_PGO_OK on every handle (RR_PGO_EINVAL:
+ * no handle); sharded and RR_PGO_F32 / RR_PGO_MIXED handles keep their own refusals, which are checked first.
+ * rr_pgo_extend and rr_pgo_remove_edges carry the switch.  rr_pgo_marginals does not read it and keeps refusing such graphs.
+ * Captured graphs, the state, the Levenberg-Marquardt lambda and the robust, prior and fixed settings are untouched. */
+int rr_pgo_set_query_big_fronts(rr_pgo *h, int32_t on);
+int32_t rr_pgo_get_query_big_fronts(const rr_pgo *h);   /* 0 or 1; 0 without a handle */
 
 /* ---- growing a live handle (build-defined; the reference builds a new PoseGraph) --------
  * Append n_new_nodes nodes and n_new_edges edges, in rr_pgo_graph_desc packing.  New nodes get the indices
@@ -483,7 +499,7 @@ int rr_pgo_check_edges_times(const rr_pgo *h, double *ms);
  * (rr_pgo_get_graph shows them, the analysis sees what a fresh handle on that graph would).
  * Carried over: the solver option; the robust kernel's kind and delta; its edge mask, extended with 1 for every new edge (a
  * fresh closure is robustified; a NULL mask stays NULL); the prior list of rr_pgo_set_priors with its robust flags and
- * keep_anchor (node indices do not change).  NOT carried: captured graphs, the tree and selected-inverse tables of
+ * keep_anchor (node indices do not change); the rr_pgo_set_query_big_fronts switch.  NOT carried: captured graphs, the tree and selected-inverse tables of
  * the queries, rr_pgo_set_state's memo of the previous state, the Levenberg-Marquardt lambda and the *_times of earlier calls;
  * rr_pgo_stream may return another stream.  Pointers from an earlier rr_pgo_get_graph become invalid.
  * Atomic: the new graph, analysis and engine are built completely and then swapped in; the old stream is synchronised before
@@ -511,7 +527,7 @@ int rr_pgo_extend_times(const rr_pgo *h, double *ms);
  * under the environment as it is at the call -- except that the device state of every node is the old device state bit for
  * bit (copied device to device, as rr_pgo_extend carries it).
  * Carried over: the solver option; the robust kernel's kind and delta; its edge mask with the removed entries cut out (a NULL
- * mask stays NULL); the prior list with its robust flags; the fixed set; both keep_anchor settings.  NOT carried: what
+ * mask stays NULL); the prior list with its robust flags; the fixed set; both keep_anchor settings; the rr_pgo_set_query_big_fronts switch.  NOT carried: what
  * rr_pgo_extend does not carry.  Atomic as rr_pgo_extend: any failure leaves the handle as it was, with the same bits.
  * RR_PGO_EINVAL, decided before anything changes: n_remove < 0, null edge with n_remove > 0, an index out of range, a node
  * left without any edge (the message names the node).  A removal that only disconnects the graph is the caller's

@@ -298,6 +298,8 @@ struct EngineBase {
   virtual void check_edges(int n, const int32_t *from, const int32_t *to, const int64_t *soff, std::vector<GateCand> &cand,
                            double *d2, double *red, double *chi2, double *resid) = 0;
   virtual void refuse_factor_query(const char *who) const = 0;   // what every factor query refuses, before its arguments are read
+  virtual void set_query_big_fronts(int on) = 0;                  // rr_pgo_set_query_big_fronts / rr_pgo_get_query_big_fronts
+  virtual int query_big_fronts() const = 0;
   // rr_pgo_gate_joint (arguments checked; set s is the records [set_ptr[s], set_ptr[s + 1]) of from / to / cand, the sets
   // expanded one after the other; dim: D_s; ioff: [n_sets + 1] offsets of the sets' S in innov; prefix and innov may be null) /
   // rr_pgo_gate_joint_times
@@ -538,7 +540,10 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   size_t ts_lds_ = 0;
   size_t ts_ws_bytes_ = TS_WS_BYTES;   // bound of Z + U of one pass (RR_PGO_TS_WS_BYTES=<n>, read at creation)
   bool ts_ready_ = false;
+  bool query_big_ = false;             // rr_pgo_set_query_big_fronts: fronts beyond LDS go to the k_tree_*_big kernels
+  bool ts_trace_ = false;              // RR_PGO_QUERY_TRACE=1, read at creation: every pass of a tree query describes its plan on stderr
   DevBuf<TsTask> ts_tasks_;
+  DevBuf<TsSlab> ts_slab_, cross_slab_;   // slabs of the fronts beyond LDS, by level: rows below (forward), pivot rows (backward)
   DevBuf<int32_t> ts_child_, ts_unit_, ts_czrow_;
   DevBuf<CovQuery> ts_query_;
   DevBuf<T> ts_z_, ts_u_;
@@ -767,6 +772,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     if (const char *e = getenv("RR_PGO_FLOW_SCHUR_MIN")) flow_schur_min_ = std::atoi(e);
     if (const char *e = getenv("RR_PGO_TS_WS_BYTES"))
       if (const long long v = std::atoll(e); v > 0) ts_ws_bytes_ = (size_t)v;
+    if (const char *e = getenv("RR_PGO_QUERY_TRACE")) ts_trace_ = std::atoi(e) != 0;
     n_lin_blocks_ = (int)(((int64_t)n_list_ * LIN_GROUP + LIN_THREADS - 1) / LIN_THREADS);
     lin_blocks_pull_ = n_lin_blocks_;
     edge_lin_ = getenv("RR_PGO_EDGE_LINEARIZE") != nullptr && !is3d_ && !sharded_ && g_.n_edges() > 0;
@@ -2867,12 +2873,17 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
 
 
   // ---- queries over the factor: what rr_pgo_marginals, rr_pgo_covariances, rr_pgo_gate_edges and rr_pgo_gate_joint share
-  void require_f64_unsharded_lds_factor(const char *who) const {
+  // lds_only: rr_pgo_marginals, and the other queries while rr_pgo_set_query_big_fronts is off
+  void require_f64_unsharded_lds_factor(const char *who, bool lds_only) const {
     const std::string w = who;
     if (sharded_ || world_ > 1) throw ApiError(RR_PGO_EUNSUPPORTED, w + ": sharded handle (a rank holds a part of the factor only)");
     if (!f64_) throw ApiError(RR_PGO_EUNSUPPORTED, w + ": F32 / MIXED handle (a single-precision factor of a matrix of condition ~1e10 has no meaningful inverse): create the handle with RR_PGO_F64");
-    if (sym_.n_big > 0) throw ApiError(RR_PGO_EUNSUPPORTED, w + ": " + std::to_string(sym_.n_big) + " fronts beyond LDS (n_big_fronts must be 0)");
+    if (sym_.n_big > 0 && lds_only)
+      throw ApiError(RR_PGO_EUNSUPPORTED, w + ": " + std::to_string(sym_.n_big) + " fronts beyond LDS (n_big_fronts must be 0)" +
+                                              (w == "rr_pgo_marginals" ? ": use rr_pgo_covariances with rr_pgo_set_query_big_fronts" : ""));
   }
+  void set_query_big_fronts(int on) override { query_big_ = on != 0; }
+  int query_big_fronts() const override { return query_big_ ? 1 : 0; }
   // depth of every front, front of every permuted column, the four events of a call: made once
   void tree_tables(const char *who) {
     if (!front_depth_.empty()) return;
@@ -2954,7 +2965,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
 
   void marginals(int nq, const int32_t *na, const int32_t *nb, const int64_t *off, double *out) override {
     static constexpr const char *who = "rr_pgo_marginals";
-    require_f64_unsharded_lds_factor(who);
+    require_f64_unsharded_lds_factor(who, true);
     if constexpr (f64_) {
       marginals_prepare(who);
       const Symbolic &sym = sym_;
@@ -3033,6 +3044,9 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   struct TsPlan {
     std::vector<TsTask> tasks;                 // by level, deepest first
     std::vector<int32_t> child, unit, czrow, level_ptr;
+    std::vector<int32_t> big_ptr;              // per level: its first task beyond LDS (LDS tasks first, then these)
+    std::vector<TsSlab> slab;                  // the slabs of rows below of the tasks beyond LDS, by level
+    std::vector<int32_t> slab_ptr;             // per level, into slab
     std::vector<CovQuery> query;
     int64_t zrows = 0, urows = 0;
     int n_chunks = 0;
@@ -3053,7 +3067,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
       m.parent = sym.sn_parent[f];
       m.loff = sym.sn_loff[f];
       m.rel_ptr = sym.rel_ptr[f];
-      max_n = std::max<int64_t>(max_n, (int64_t)m.nc + m.nr);
+      if (!sym.sn_big[f]) max_n = std::max<int64_t>(max_n, (int64_t)m.nc + m.nr);   // (a front beyond LDS keeps its block in the workspace)
     }
     ts_lds_ = (size_t)max_n * TS_LD * sizeof(T);
     if (ts_lds_ + 256 * sizeof(T) > (size_t)160 * 1024)
@@ -3147,7 +3161,10 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     const int nt = (int)tmp.size();
     std::vector<int32_t> order((size_t)nt), newidx((size_t)nt);
     for (int i = 0; i < nt; i++) order[i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return front_depth_[tmp[x].front] > front_depth_[tmp[y].front]; });
+    std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) {   // within a level the LDS tasks, then those beyond LDS
+      const int fx = tmp[x].front, fy = tmp[y].front;
+      return front_depth_[fx] != front_depth_[fy] ? front_depth_[fx] > front_depth_[fy] : sym.sn_big[fx] < sym.sn_big[fy];
+    });
     pl.tasks.resize((size_t)nt);
     pl.level_ptr.assign(1, 0);
     for (int i = 0; i < nt; i++) {
@@ -3156,6 +3173,15 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
       if (i > 0 && front_depth_[pl.tasks[i].front] != front_depth_[pl.tasks[i - 1].front]) pl.level_ptr.push_back(i);
     }
     pl.level_ptr.push_back(nt);
+    pl.slab_ptr.assign(1, 0);
+    for (size_t l = 0; l + 1 < pl.level_ptr.size(); l++) {
+      int i = pl.level_ptr[l];
+      while (i < pl.level_ptr[l + 1] && !sym.sn_big[pl.tasks[i].front]) i++;
+      pl.big_ptr.push_back(i);
+      for (; i < pl.level_ptr[l + 1]; i++)
+        for (int r0 = 0; r0 < sym.sn_nrows[pl.tasks[i].front]; r0 += TSB_SLAB) pl.slab.push_back(TsSlab{i, r0});
+      pl.slab_ptr.push_back((int32_t)pl.slab.size());
+    }
     for (int32_t &c : pl.child) c = newidx[c];
     pl.query.resize((size_t)(q1 - q0));
     for (int q = q0; q < q1; q++) {
@@ -3178,6 +3204,34 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     }
   }
 
+  // RR_PGO_QUERY_TRACE=1: one line per pass, one per active front of the pass (by level, deepest first; over the chunks: a
+  // front active in several chunks is listed once) and one per distinct queried node
+  void trace_plan(const char *who, int q0, int q1, const int32_t *na, const int32_t *nb, const TsPlan &pl, size_t ws) const {
+    const Symbolic &sym = sym_;
+    int n_big = 0, n_launch = 0;
+    for (const TsTask &t : pl.tasks) n_big += sym.sn_big[t.front];
+    for (size_t l = 0; l + 1 < pl.level_ptr.size(); l++)
+      n_launch += (pl.big_ptr[l] > pl.level_ptr[l]) + (pl.level_ptr[l + 1] > pl.big_ptr[l]) + (pl.slab_ptr[l + 1] > pl.slab_ptr[l]);
+    std::fprintf(stderr, "query trace: %s pass [%d, %d): %d chunks, %zu tasks (%d beyond LDS), %zu slabs, %zu levels, %d forward launches, %zu bytes\n",
+                 who, q0, q1, pl.n_chunks, pl.tasks.size(), n_big, pl.slab.size(), pl.level_ptr.size() - 1, n_launch, ws);
+    std::vector<char> seen((size_t)sym.S, 0);
+    for (size_t l = 0; l + 1 < pl.level_ptr.size(); l++)
+      for (int i = pl.level_ptr[l]; i < pl.level_ptr[l + 1]; i++) {
+        const int f = pl.tasks[i].front;
+        if (seen[f]) continue;
+        seen[f] = 1;
+        std::fprintf(stderr, "query trace:   front %d depth %d nc %d nr %d parent %d children %d %s\n", f, front_depth_[f], sym.sn_ncols[f],
+                     sym.sn_nrows[f], sym.sn_parent[f], sym.child_ptr[f + 1] - sym.child_ptr[f], sym.sn_big[f] ? "beyond-LDS" : "LDS");
+      }
+    std::vector<char> told((size_t)g_.n_nodes(), 0);
+    for (int q = q0; q < q1; q++)
+      for (int v : {na[q], nb[q]})
+        if (!told[v]) {
+          told[v] = 1;
+          std::fprintf(stderr, "query trace:   node %d front %d\n", v, front_of(v));
+        }
+  }
+
   template <typename U> void ts_grow(DevBuf<U> &b, size_t count) {
     if (b.p && b.n >= count) return;
     ArenaScope scope(nullptr);   // a buffer of its own: freed when it grows and with the handle
@@ -3194,6 +3248,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     ts_fill(ts_child_, pl.child);
     ts_fill(ts_unit_, pl.unit);
     ts_fill(ts_czrow_, pl.czrow);
+    if (!pl.slab.empty()) ts_fill(ts_slab_, pl.slab);
     ts_grow(ts_z_, (size_t)pl.zrows * TS_MC);
     ts_grow(ts_u_, (size_t)pl.urows * TS_MC);
   }
@@ -3210,9 +3265,11 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     a.U = ts_u_.p;
     if constexpr (std::is_same<T, double>::value)
       for (size_t l = 0; l + 1 < pl.level_ptr.size(); l++) {
-        const int begin = pl.level_ptr[l], count = pl.level_ptr[l + 1] - begin;
-        if (count <= 0) continue;
-        hipLaunchKernelGGL((k_tree_fwd<T>), dim3((unsigned)count), dim3(TS_THREADS), ts_lds_, stream_, a, begin);
+        const int begin = pl.level_ptr[l], big = pl.big_ptr[l], end = pl.level_ptr[l + 1];
+        if (big > begin) hipLaunchKernelGGL((k_tree_fwd<T>), dim3((unsigned)(big - begin)), dim3(TS_THREADS), ts_lds_, stream_, a, begin);
+        if (end > big) hipLaunchKernelGGL((k_tree_fwd_big<T>), dim3((unsigned)(end - big)), dim3(TSB_THREADS), 0, stream_, a, big);
+        const int s0 = pl.slab_ptr[l], ns = pl.slab_ptr[l + 1] - s0;
+        if (ns > 0) hipLaunchKernelGGL((k_tree_fwd_big_update<T>), dim3((unsigned)ns), dim3(TSB_THREADS), 0, stream_, a, (const TsSlab *)ts_slab_.p, s0);
       }
     check_launch("k_tree_fwd");
   }
@@ -3260,6 +3317,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
         todo.emplace_back(u0, mid);
         continue;
       }
+      if (ts_trace_) trace_plan(who, q0, q1, a, b, pl, ws);
       ts_stage(pl);
       stage(q0, q1, pl);
       if (!first) HIPCHK(hipEventRecord(query_ev_[1], stream_));
@@ -3288,7 +3346,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   // ---- covariances of arbitrary node pairs (include/rr_pgo.h, rr_pgo_covariances; treesolve.hip.h, k_cov_pairs)
   void covariances(int nq, const int32_t *na, const int32_t *nb, const int64_t *off, double *out) override {
     static constexpr const char *who = "rr_pgo_covariances";
-    require_f64_unsharded_lds_factor(who);
+    require_f64_unsharded_lds_factor(who, !query_big_);
     if constexpr (f64_) {
       covariances_prepare(who);
       tree_query(who, "pair", nq, na, nb, off, query_ms_[Q_COVARIANCES], false, [&](int q0, int q1, const TsPlan &pl) {
@@ -3315,13 +3373,14 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   void cross_covariances(int n_row, const int32_t *row_node, int n_col, const int32_t *col_node, const int64_t *roff,
                          const int64_t *coff, double *out) override {
     static constexpr const char *who = "rr_pgo_cross_covariances";
-    require_f64_unsharded_lds_factor(who);
+    require_f64_unsharded_lds_factor(who, !query_big_);
     if constexpr (f64_) {
       covariances_prepare(who);
       const Symbolic &sym = sym_;
       const int S_ = sym.S;
       const int64_t R = roff[n_row], C = coff[n_col];
-      // ---- the backward-active fronts by depth, root level first (within a level: descending front index, as sel_order_)
+      // ---- the backward-active fronts by depth, root level first (within a level: the LDS fronts in descending front index, as
+      // sel_order_, then the fronts beyond LDS)
       std::vector<int32_t> fvrow((size_t)S_, -1), order, level_ptr;
       if (!row_node) std::fill(fvrow.begin(), fvrow.end(), 0);
       else
@@ -3333,10 +3392,20 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
         if (fvrow[f] == 0) level_ptr[(size_t)front_depth_[f] + 1]++;
       for (int d = 0; d <= max_depth; d++) level_ptr[(size_t)d + 1] += level_ptr[d];
       order.resize((size_t)level_ptr[(size_t)max_depth + 1]);
+      std::vector<int32_t> big_ptr(level_ptr.begin() + 1, level_ptr.end());   // per level: its first front beyond LDS (LDS fronts first)
       {
         std::vector<int32_t> fill(level_ptr.begin(), level_ptr.end() - 1);
         for (int f = S_ - 1; f >= 0; f--)
-          if (fvrow[f] == 0) order[(size_t)fill[front_depth_[f]]++] = f;
+          if (fvrow[f] == 0 && sym.sn_big[f]) order[(size_t)--big_ptr[front_depth_[f]]] = f;
+        for (int f = S_ - 1; f >= 0; f--)
+          if (fvrow[f] == 0 && !sym.sn_big[f]) order[(size_t)fill[front_depth_[f]]++] = f;
+      }
+      std::vector<TsSlab> slab;               // the slabs of pivot rows of the fronts beyond LDS, by level
+      std::vector<int32_t> slab_ptr(1, 0);
+      for (int d = 0; d <= max_depth; d++) {
+        for (int i = big_ptr[d]; i < level_ptr[(size_t)d + 1]; i++)
+          for (int r0 = 0; r0 < sym.sn_ncols[order[i]]; r0 += TSB_SLAB) slab.push_back(TsSlab{order[i], r0});
+        slab_ptr.push_back((int32_t)slab.size());
       }
       int64_t vrows = 0;   // rows of V per chunk
       for (int32_t f : order) {
@@ -3367,11 +3436,20 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
         a.V = ts_v_.p;
         a.vrows = vrows;
         a.S = S_;
+        if (ts_trace_) {
+          int n_launch = 0;
+          for (size_t l = 0; l + 1 < level_ptr.size(); l++)
+            n_launch += (big_ptr[l] > level_ptr[l]) + (level_ptr[l + 1] > big_ptr[l]) + (slab_ptr[l + 1] > slab_ptr[l]);
+          std::fprintf(stderr, "query trace:   backward: %zu fronts, %zu slabs, %d launches\n", order.size(), slab.size(), n_launch);
+        }
         if constexpr (std::is_same<T, double>::value)
           for (size_t l = 0; l + 1 < level_ptr.size(); l++) {
-            const int begin = level_ptr[l], count = level_ptr[l + 1] - begin;
-            if (count <= 0) continue;
-            hipLaunchKernelGGL((k_tree_bwd<T>), dim3((unsigned)count, (unsigned)pl.n_chunks), dim3(TS_THREADS), ts_lds_, stream_, a, begin);
+            const int begin = level_ptr[l], big = big_ptr[l], end = level_ptr[l + 1];
+            const unsigned nch = (unsigned)pl.n_chunks;
+            if (big > begin) hipLaunchKernelGGL((k_tree_bwd<T>), dim3((unsigned)(big - begin), nch), dim3(TS_THREADS), ts_lds_, stream_, a, begin);
+            const int s0 = slab_ptr[l], ns = slab_ptr[l + 1] - s0;
+            if (ns > 0) hipLaunchKernelGGL((k_tree_bwd_big_gemv<T>), dim3((unsigned)ns, nch), dim3(TSB_THREADS), 0, stream_, a, (const TsSlab *)cross_slab_.p, s0);
+            if (end > big) hipLaunchKernelGGL((k_tree_bwd_big<T>), dim3((unsigned)(end - big), nch), dim3(TSB_THREADS), 0, stream_, a, big);
           }
         check_launch("k_tree_bwd");
       };
@@ -3386,6 +3464,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
         }
         ts_fill(cross_order_, order);
         ts_fill(cross_fvrow_, fvrow);
+        if (!slab.empty()) ts_fill(cross_slab_, slab);
         ts_fill(cross_rsrc_, rsrc);
         ts_fill(cross_csrc_, csrc);
         ts_grow(ts_v_, (size_t)pl.n_chunks * (size_t)vrows * TS_MC);
@@ -3415,7 +3494,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   void gate_edges(int n, const int32_t *from, const int32_t *to, const int64_t *soff, std::vector<GateCand> &cand, double *d2,
                   double *chi2, double *innov) override {
     static constexpr const char *who = "rr_pgo_gate_edges";
-    require_f64_unsharded_lds_factor(who);
+    require_f64_unsharded_lds_factor(who, !query_big_);
     if constexpr (f64_) {
       covariances_prepare(who);
       auto n_innov = [&](int c0, int c1) { return innov ? (size_t)(soff[c1] - soff[c0]) : 0; };
@@ -3452,11 +3531,11 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
 
   // ---- audit of the graph's own edges (include/rr_pgo.h, rr_pgo_check_edges; treesolve.hip.h, k_check_edges): the gate's plan
   // and records, for edges of the graph; the robust kind and delta travel in the arguments
-  void refuse_factor_query(const char *who) const override { require_f64_unsharded_lds_factor(who); }
+  void refuse_factor_query(const char *who) const override { require_f64_unsharded_lds_factor(who, !query_big_); }
   void check_edges(int n, const int32_t *from, const int32_t *to, const int64_t *soff, std::vector<GateCand> &cand, double *d2,
                    double *red, double *chi2, double *resid) override {
     static constexpr const char *who = "rr_pgo_check_edges";
-    require_f64_unsharded_lds_factor(who);
+    require_f64_unsharded_lds_factor(who, !query_big_);
     if constexpr (f64_) {
       covariances_prepare(who);
       auto n_resid = [&](int c0, int c1) { return resid ? (size_t)(soff[c1] - soff[c0]) : 0; };
@@ -3501,7 +3580,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   void gate_joint(int n_sets, const int32_t *set_ptr, const int32_t *from, const int32_t *to, const int32_t *dim,
                   const int64_t *ioff, std::vector<GateCand> &cand, double *d2, double *prefix, double *innov) override {
     static constexpr const char *who = "rr_pgo_gate_joint";
-    require_f64_unsharded_lds_factor(who);
+    require_f64_unsharded_lds_factor(who, !query_big_);
     if constexpr (f64_) {
       covariances_prepare(who);
       const Symbolic &sym = sym_;
@@ -4212,6 +4291,7 @@ static void extend_handle(rr_pgo *h, int32_t n_new_nodes, const int32_t *node_ki
   }
   if (h->engine->priors().n() > 0) apply_priors(*nh, h->engine->priors());   // node indices do not change
   if (!h->engine->fixed().empty()) nh->engine->set_fixed(h->engine->fixed(), h->engine->fixed_keep_anchor());   // new nodes are free
+  nh->engine->set_query_big_fronts(h->engine->query_big_fronts());
   // ---- the swap: nothing below can fail.  The old engine (its stream drained above, the copy out of its buffers waited for)
   // goes with nh.  Every field changes sides (the engines refer to the pointees of g and symp, which do not move).
   std::swap(*h, *nh);
@@ -4261,6 +4341,7 @@ static void remove_handle(rr_pgo *h, int32_t n_remove, const int32_t *edge) {
   }
   if (h->engine->priors().n() > 0) apply_priors(*nh, h->engine->priors());   // node indices do not change
   if (!h->engine->fixed().empty()) nh->engine->set_fixed(h->engine->fixed(), h->engine->fixed_keep_anchor());
+  nh->engine->set_query_big_fronts(h->engine->query_big_fronts());
   // ---- the swap, as in extend_handle: nothing below can fail
   std::swap(*h, *nh);
   h->remove_ms[0] = t1 - t0;
@@ -4691,6 +4772,12 @@ int rr_pgo_set_fixed(rr_pgo *h, int32_t n_fixed, const int32_t *node, int32_t ke
   nodes.erase(std::unique(nodes.begin(), nodes.end()), nodes.end());   // a node listed twice counts once
   return guarded([&] { h->engine->set_fixed(nodes, keep_anchor); });
 }
+
+int rr_pgo_set_query_big_fronts(rr_pgo *h, int32_t on) {
+  if (!h) { g_last_error = "rr_pgo_set_query_big_fronts: no handle"; return RR_PGO_EINVAL; }
+  return guarded([&] { h->engine->set_query_big_fronts(on); });
+}
+int32_t rr_pgo_get_query_big_fronts(const rr_pgo *h) { return h ? (int32_t)h->engine->query_big_fronts() : 0; }
 
 int32_t rr_pgo_num_fixed(const rr_pgo *h) { return h ? (int32_t)h->engine->fixed().size() : 0; }
 

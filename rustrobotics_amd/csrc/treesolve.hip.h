@@ -12,6 +12,8 @@
 //   k_gate_joint  one workgroup per set of candidate edges: their joint distance from the same Z
 //   k_tree_bwd    one workgroup per (chunk, backward-active front), one launch per level, root level first: X = L^-T Z
 //   k_cross_gather  the rectangular block Sigma[rows, cols] out of X (the end of this file)
+//   k_tree_fwd_big, k_tree_fwd_big_update, k_tree_bwd_big_gemv, k_tree_bwd_big   the two solves of a front beyond LDS, whose
+//                 block stays in the workspace (before k_cross_gather; DESIGN.md 4r, rr_pgo_set_query_big_fronts)
 //
 // Columns.  The distinct queried nodes are ordered by (front, pivot column) -- fronts are numbered in elimination order, so
 // neighbours share paths -- and packed, whole nodes at a time, into chunks of TS_MC = 32 columns (unused columns stay zero).
@@ -872,6 +874,306 @@ __global__ void __launch_bounds__(TS_THREADS) k_tree_bwd(TsBwdArgs<T> a, int beg
   // ---- V = [X_P; X_R], what the children gather from
   T *Vg = a.V + (vbase + a.fvrow[f]) * TS_MC;
   for (int e = tid; e < n * TS_MC; e += TS_THREADS) Vg[e] = B[(e >> 5) * LD + (e & 31)];
+}
+
+// ---- fronts beyond LDS (rr_pgo_set_query_big_fronts)
+//
+// The right-hand block of such a front does not fit in LDS beside nothing: it lives where the plan puts it anyway, its nc
+// pivot rows in Z (forward) and its nr rows below in U, or its nc + nr rows in V (backward).  The panel is addressed as an
+// LDS front's is; the inverses of its diagonal blocks are 32 x 32: winv[wblk * 256 + b * 1024 + c * 32 + j] = W_b(j, c).
+//
+//   k_tree_fwd_big         one workgroup per (chunk, active front): zero, gather the children, unit entries, pivot square
+//   k_tree_fwd_big_update  one workgroup per (chunk, front, slab of TSB_SLAB rows below): U = B_R - L_21 Y_P
+//   k_tree_bwd_big_gemv    one workgroup per (chunk, front, slab of TSB_SLAB pivot rows): T = Y_P - L_21^T X_R into V
+//   k_tree_bwd_big         one workgroup per (chunk, front): the pivot square from the right, and X_R into V
+// A level of the tree is the launch of its LDS fronts as before, then these for its fronts beyond LDS.  Only launches order
+// the work: a kernel reads what an earlier launch wrote, or what its own workgroup wrote behind a __syncthreads().
+//
+// Determinism.  As above: a scalar of Z, U or V is one wave's, blocks ascend going forward and descend going backward, k
+// ascends inside a block and over the rows below, children come in ascending front order.  A tile's wave and a slab's
+// workgroup are chosen by the row alone, and neither enters the order of the row's operations.
+constexpr int TSB_THREADS = 512;
+constexpr int TSB_SLAB = 16 * (TSB_THREADS / 64);   // rows of a slab: one 16-row tile per wave, both column tiles
+constexpr int TSB_KP = 64;                          // rows below staged in LDS per piece (k_tree_bwd_big_gemv)
+static_assert(TSB_KP % 4 == 0, "a piece is whole MFMA steps, so the pieces do not change how k is grouped");
+
+struct TsSlab {
+  int32_t item;                   // forward: the task; backward: the front
+  int32_t row0;                   // first row of the slab among the rows below (forward) / the pivot rows (backward)
+};
+
+template <typename T>
+__global__ void __launch_bounds__(TSB_THREADS) k_tree_fwd_big(TsArgs<T> a, int begin) {
+  using MM = Mfma16<T>;
+  constexpr int NW = TSB_THREADS / 64, LD = TS_LD, NCT = TS_MC / 16;
+  __shared__ T ws[1024];                 // W_b: ws[c * 32 + j] = W_b(j, c)
+  __shared__ T yb[32 * LD];              // Y_b, the B operand of the block's updates
+  const int tid = threadIdx.x, lane = tid & 63, li = lane & 15, lk = lane >> 4;
+  const int wave = wave_index();
+  const TsTask t = a.tasks[begin + blockIdx.x];
+  const TsMeta m = a.meta[t.front];
+  const int nc = m.nc, nr = m.nr, n = nc + nr, M = n + 1;
+  const T *Lg = a.lvals + m.loff;
+  const T *Wg = a.winv + (int64_t)m.wblk * 256;
+  T *Zg = a.Z + (int64_t)t.zrow * TS_MC, *Ug = a.U + (int64_t)t.urow * TS_MC;
+  for (int e = tid; e < nc * TS_MC; e += TSB_THREADS) Zg[e] = 0;
+  for (int e = tid; e < nr * TS_MC; e += TSB_THREADS) Ug[e] = 0;
+  __syncthreads();
+  // ---- the update blocks of the active children through their rel maps, one child after the other
+  for (int c = 0; c < t.n_child; c++) {
+    const TsTask ct = a.tasks[a.child[t.child_ptr + c]];
+    const TsMeta cm = a.meta[ct.front];
+    const int32_t *rel = a.rel + cm.rel_ptr;
+    const T *Uc = a.U + (int64_t)ct.urow * TS_MC;
+    for (int e = tid; e < cm.nr * TS_MC; e += TSB_THREADS) {
+      const int row = rel[e >> 5];
+      if ((unsigned)row < (unsigned)n) {
+        T *d = row < nc ? Zg + (int64_t)row * TS_MC : Ug + (int64_t)(row - nc) * TS_MC;
+        d[e & 31] += Uc[e];
+      }
+    }
+    __syncthreads();
+  }
+  // ---- unit entries of the chunk's nodes whose pivot columns are here
+  for (int e = tid; e < t.n_unit; e += TSB_THREADS) {
+    const int u = a.unit[t.unit_ptr + e];
+    Zg[(int64_t)(u >> 5) * TS_MC + (u & 31)] += (T)1;
+  }
+  __syncthreads();
+  // ---- pivot square, right-looking by 32-column blocks: Y_b = W_b B_b, then B_i -= L_ib Y_b for the later pivot rows
+  for (int b = 0; b < ((nc + 31) >> 5); b++) {
+    const int c0 = 32 * b, cw = min(32, nc - c0), t0 = c0 + 32;
+    for (int e = tid; e < 1024; e += TSB_THREADS) ws[e] = Wg[(int64_t)b * 1024 + e];
+    __syncthreads();
+    if (wave < NCT) {   // a column tile of the block is one wave's: read whole, then written
+      const int col = 16 * wave + li;
+      typename MM::Acc y0 = {0, 0, 0, 0}, y1 = {0, 0, 0, 0};
+      T bv[8];
+#pragma unroll
+      for (int s = 0; s < 8; s++) bv[s] = Zg[(int64_t)(c0 + min(4 * s + lk, cw - 1)) * TS_MC + col];
+#pragma unroll
+      for (int s = 0; s < 8; s++) {
+        const int k = 4 * s + lk;
+        const T bk = k < cw ? bv[s] : (T)0;
+        // W is lower triangular; rows past a partial block are padding
+        y0 = MM::mma((k <= li && li < cw) ? ws[k * 32 + li] : (T)0, bk, y0);
+        y1 = MM::mma((k <= 16 + li && 16 + li < cw) ? ws[k * 32 + 16 + li] : (T)0, bk, y1);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        const int i = MM::row(lane, r);
+        yb[i * LD + col] = y0[r];
+        yb[(16 + i) * LD + col] = y1[r];
+        if (i < cw) Zg[(int64_t)(c0 + i) * TS_MC + col] = y0[r];
+        if (16 + i < cw) Zg[(int64_t)(c0 + 16 + i) * TS_MC + col] = y1[r];
+      }
+    }
+    __syncthreads();
+    if (t0 < nc) {   // (so this block is a full one)
+      const int nti = (nc - t0 + 15) >> 4;
+      for (int tile = wave; tile < nti * NCT; tile += NW) {
+        const int ib = tile / NCT, jb = tile - ib * NCT;
+        const int i0 = t0 + 16 * ib, col = 16 * jb + li;
+        typename MM::Acc acc;
+#pragma unroll
+        for (int r = 0; r < 4; r++) acc[r] = Zg[(int64_t)min(i0 + MM::row(lane, r), nc - 1) * TS_MC + col];
+        const T *La = Lg + (int64_t)c0 * M + min(i0 + li, nc - 1);   // rows past nc of the last tile are computed and dropped
+        T lv[8];
+#pragma unroll
+        for (int s = 0; s < 8; s++) lv[s] = La[(int64_t)(4 * s + lk) * M];
+#pragma unroll
+        for (int s = 0; s < 8; s++) acc = MM::mma(-lv[s], yb[(4 * s + lk) * LD + col], acc);
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+          const int row = i0 + MM::row(lane, r);
+          if (row < nc) Zg[(int64_t)row * TS_MC + col] = acc[r];
+        }
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// The rows below of one slab: a wave holds 16 rows x TS_MC columns in two accumulators over all nc columns of the panel and
+// writes them once.  L goes from lvals straight into the A operand, Y_P from the front's rows of Z into the B operands.
+template <typename T>
+__global__ void __launch_bounds__(TSB_THREADS) k_tree_fwd_big_update(TsArgs<T> a, const TsSlab *slab, int begin) {
+  using MM = Mfma16<T>;
+  const int lane = threadIdx.x & 63, li = lane & 15, lk = lane >> 4;
+  const TsSlab s = slab[begin + blockIdx.x];
+  const TsTask t = a.tasks[s.item];
+  const TsMeta m = a.meta[t.front];
+  const int nc = m.nc, nr = m.nr, M = nc + nr + 1;
+  const int r0 = s.row0 + 16 * wave_index();
+  if (r0 >= nr) return;   // (no barrier below)
+  const T *Lg = a.lvals + m.loff;
+  const T *Zg = a.Z + (int64_t)t.zrow * TS_MC;
+  T *Ug = a.U + (int64_t)t.urow * TS_MC;
+  typename MM::Acc acc0, acc1;
+#pragma unroll
+  for (int r = 0; r < 4; r++) {
+    const T *u = Ug + (int64_t)min(r0 + MM::row(lane, r), nr - 1) * TS_MC;
+    acc0[r] = u[li];
+    acc1[r] = u[16 + li];
+  }
+  const T *La = Lg + nc + min(r0 + li, nr - 1);   // rows past nr of the last tile are computed and dropped
+  for (int k4 = 0; k4 < nc; k4 += 4) {
+    const int k = k4 + lk, kc = min(k, nc - 1);
+    const T lv = La[(int64_t)kc * M];
+    const T av = k < nc ? -lv : (T)0;
+    const T *z = Zg + (int64_t)kc * TS_MC;
+    acc0 = MM::mma(av, z[li], acc0);
+    acc1 = MM::mma(av, z[16 + li], acc1);
+  }
+#pragma unroll
+  for (int r = 0; r < 4; r++) {
+    const int row = r0 + MM::row(lane, r);
+    if (row < nr) {
+      Ug[(int64_t)row * TS_MC + li] = acc0[r];
+      Ug[(int64_t)row * TS_MC + 16 + li] = acc1[r];
+    }
+  }
+}
+
+// T = Y_P - L21^T X_R for one slab of pivot rows, into the front's pivot rows of V.  X_R is gathered from the parent's block
+// through the rel map, TSB_KP rows below at a time, into LDS; A(i, k) = L(nc + k, i): a lane's consecutive k are consecutive
+// scalars of one panel column.  A root (no rows below) copies Y_P.
+template <typename T>
+__global__ void __launch_bounds__(TSB_THREADS) k_tree_bwd_big_gemv(TsBwdArgs<T> a, const TsSlab *slab, int begin) {
+  using MM = Mfma16<T>;
+  constexpr int LD = TS_LD;
+  __shared__ T xs[TSB_KP * LD];
+  const int tid = threadIdx.x, lane = tid & 63, li = lane & 15, lk = lane >> 4;
+  const TsSlab s = slab[begin + blockIdx.x];
+  const int f = s.item, chunk = blockIdx.y;
+  const TsMeta m = a.meta[f];
+  const int nc = m.nc, nr = m.nr, M = nc + nr + 1;
+  const int64_t vbase = (int64_t)chunk * a.vrows;
+  T *Vf = a.V + (vbase + a.fvrow[f]) * TS_MC;
+  const int i0 = s.row0 + 16 * wave_index();
+  const bool mine = i0 < nc;   // (every wave stages X_R)
+  typename MM::Acc acc0 = {0, 0, 0, 0}, acc1 = {0, 0, 0, 0};
+  // ---- Y_P: the front's rows of Z where the chunk's forward plan holds the front, else zero
+  const int zr = a.czrow[(int64_t)chunk * a.S + f];
+  if (mine && zr >= 0) {
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      const T *z = a.Z + (int64_t)(zr + min(i0 + MM::row(lane, r), nc - 1)) * TS_MC;
+      acc0[r] = z[li];
+      acc1[r] = z[16 + li];
+    }
+  }
+  const int p = m.parent;
+  const int pn = p >= 0 ? a.meta[p].nc + a.meta[p].nr : 0;
+  const T *Vp = a.V + (vbase + (p >= 0 ? a.fvrow[p] : 0)) * TS_MC;
+  const int32_t *rel = a.rel + m.rel_ptr;
+  const T *Lc = a.lvals + m.loff + (int64_t)min(i0 + li, nc - 1) * M + nc;   // rows past nc of the last tile are computed and dropped
+  for (int k0 = 0; k0 < nr; k0 += TSB_KP) {
+    const int kp = min(TSB_KP, nr - k0);
+    if (k0 > 0) __syncthreads();   // the piece before has been read
+    for (int e = tid; e < kp * TS_MC; e += TSB_THREADS) {
+      const int row = rel[k0 + (e >> 5)];
+      xs[(e >> 5) * LD + (e & 31)] = (unsigned)row < (unsigned)pn ? Vp[(int64_t)row * TS_MC + (e & 31)] : (T)0;
+    }
+    __syncthreads();
+    if (mine)
+      for (int k4 = 0; k4 < kp; k4 += 4) {
+        const int k = k4 + lk, kc = min(k, kp - 1);
+        const T lv = Lc[k0 + kc];
+        const T av = k < kp ? -lv : (T)0;
+        acc0 = MM::mma(av, xs[kc * LD + li], acc0);
+        acc1 = MM::mma(av, xs[kc * LD + 16 + li], acc1);
+      }
+  }
+  if (mine) {
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      const int row = i0 + MM::row(lane, r);
+      if (row < nc) {
+        Vf[(int64_t)row * TS_MC + li] = acc0[r];
+        Vf[(int64_t)row * TS_MC + 16 + li] = acc1[r];
+      }
+    }
+  }
+}
+
+// The pivot rows of V hold T (k_tree_bwd_big_gemv).  By 32-column blocks from the right: X_b = W_b^T T_b, then
+// T_j -= L_bj^T X_b for the earlier blocks; the rows below are copied from the parent's block, so V = [X_P; X_R] is what a
+// child -- in LDS or beyond -- gathers from.
+template <typename T>
+__global__ void __launch_bounds__(TSB_THREADS) k_tree_bwd_big(TsBwdArgs<T> a, int begin) {
+  using MM = Mfma16<T>;
+  constexpr int NW = TSB_THREADS / 64, LD = TS_LD, NCT = TS_MC / 16;
+  __shared__ T ws[1024];                 // W_b: ws[c * 32 + j] = W_b(j, c) = W_b^T(c, j)
+  __shared__ T xb[32 * LD];              // X_b, the B operand of the block's updates
+  const int tid = threadIdx.x, lane = tid & 63, li = lane & 15, lk = lane >> 4;
+  const int wave = wave_index();
+  const int f = a.order[begin + blockIdx.x], chunk = blockIdx.y;
+  const TsMeta m = a.meta[f];
+  const int nc = m.nc, nr = m.nr, M = nc + nr + 1;
+  const T *Lg = a.lvals + m.loff;
+  const T *Wg = a.winv + (int64_t)m.wblk * 256;
+  const int64_t vbase = (int64_t)chunk * a.vrows;
+  T *Vf = a.V + (vbase + a.fvrow[f]) * TS_MC;
+  // ---- X_R: the parent's block through this front's rel map (a root has no rows below)
+  if (nr > 0) {
+    const int p = m.parent;
+    const int pn = p >= 0 ? a.meta[p].nc + a.meta[p].nr : 0;
+    const T *Vp = a.V + (vbase + (p >= 0 ? a.fvrow[p] : 0)) * TS_MC;
+    const int32_t *rel = a.rel + m.rel_ptr;
+    for (int e = tid; e < nr * TS_MC; e += TSB_THREADS) {
+      const int row = rel[e >> 5];
+      Vf[(int64_t)nc * TS_MC + e] = (unsigned)row < (unsigned)pn ? Vp[(int64_t)row * TS_MC + (e & 31)] : (T)0;
+    }
+  }
+  for (int b = ((nc + 31) >> 5) - 1; b >= 0; b--) {
+    const int c0 = 32 * b, cw = min(32, nc - c0);
+    for (int e = tid; e < 1024; e += TSB_THREADS) ws[e] = Wg[(int64_t)b * 1024 + e];
+    __syncthreads();
+    if (wave < NCT) {   // a column tile of the block is one wave's: read whole, then written
+      const int col = 16 * wave + li;
+      typename MM::Acc x0 = {0, 0, 0, 0}, x1 = {0, 0, 0, 0};
+      T bv[8];
+#pragma unroll
+      for (int s = 0; s < 8; s++) bv[s] = Vf[(int64_t)(c0 + min(4 * s + lk, cw - 1)) * TS_MC + col];
+#pragma unroll
+      for (int s = 0; s < 8; s++) {
+        const int k = 4 * s + lk;
+        const T bk = k < cw ? bv[s] : (T)0;
+        // W^T is upper triangular; rows past a partial block are padding
+        x0 = MM::mma((li <= k && k < cw) ? ws[li * 32 + k] : (T)0, bk, x0);
+        x1 = MM::mma((16 + li <= k && k < cw) ? ws[(16 + li) * 32 + k] : (T)0, bk, x1);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        const int i = MM::row(lane, r);
+        xb[i * LD + col] = x0[r];
+        xb[(16 + i) * LD + col] = x1[r];
+        if (i < cw) Vf[(int64_t)(c0 + i) * TS_MC + col] = x0[r];
+        if (16 + i < cw) Vf[(int64_t)(c0 + 16 + i) * TS_MC + col] = x1[r];
+      }
+    }
+    __syncthreads();
+    for (int tile = wave; tile < 2 * b * NCT; tile += NW) {   // (the earlier blocks are full ones)
+      const int ib = tile / NCT, jb = tile - ib * NCT;
+      const int i0 = 16 * ib, col = 16 * jb + li;
+      typename MM::Acc acc;
+#pragma unroll
+      for (int r = 0; r < 4; r++) acc[r] = Vf[(int64_t)(i0 + MM::row(lane, r)) * TS_MC + col];
+      const T *Lc = Lg + (int64_t)(i0 + li) * M + c0;
+      T lv[8];
+#pragma unroll
+      for (int s = 0; s < 8; s++) lv[s] = Lc[min(4 * s + lk, cw - 1)];
+#pragma unroll
+      for (int s = 0; s < 8; s++) {
+        const int k = 4 * s + lk;
+        acc = MM::mma(k < cw ? -lv[s] : (T)0, xb[k * LD + col], acc);   // (rows of X_b past cw are zero)
+      }
+#pragma unroll
+      for (int r = 0; r < 4; r++) Vf[(int64_t)(i0 + MM::row(lane, r)) * TS_MC + col] = acc[r];
+    }
+    __syncthreads();
+  }
 }
 
 template <typename T> struct CrossArgs {

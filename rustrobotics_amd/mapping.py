@@ -376,6 +376,17 @@ class PoseGraph:
         _check(_lib.load().rr_pgo_get_fixed(self._h, _ip(out) if len(out) else None))
         return out
 
+    # -- factor queries on fronts beyond LDS (include/rr_pgo.h, "factor queries on fronts beyond LDS") --
+    @property
+    def query_big_fronts(self):
+        """Whether covariance_blocks, cross_covariances, gate_edges, gate_joint and check_edges answer on a graph with fronts
+        beyond LDS (stats()["n_big_fronts"] != 0).  Off by default: such graphs are refused.  extend and remove_edges keep it."""
+        return bool(_lib.load().rr_pgo_get_query_big_fronts(self._h))
+
+    @query_big_fronts.setter
+    def query_big_fronts(self, on):
+        _check(_lib.load().rr_pgo_set_query_big_fronts(self._h, 1 if on else 0))
+
     # -- marginal covariances (include/rr_pgo.h, "marginal covariances") -----------------
     def marginal_blocks(self, node_a=None, node_b=None):
         """rr_pgo_marginals as it is: (values, offsets) of the queried blocks of Sigma = H^-1 at the current state.
