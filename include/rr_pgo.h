@@ -299,11 +299,23 @@ int rr_pgo_get_fixed(const rr_pgo *h, int32_t *out); /* ascending node indices, 
  * untouched.  A non-positive pivot: RR_PGO_ENOTSPD.
  * RR_PGO_EUNSUPPORTED (the message says which): sharded handles, RR_PGO_F32 / RR_PGO_MIXED handles, graphs with fronts
  * beyond LDS (rr_pgo_stats::n_big_fronts != 0; there the message points to rr_pgo_covariances with
- * rr_pgo_set_query_big_fronts). */
+ * rr_pgo_set_query_big_fronts) unless rr_pgo_set_marginals_big_fronts, below, is on: then every sentence above holds on
+ * such graphs too.  RR_PGO_ENOMEM (only with that switch, on the first call): the device has no room for the selected
+ * inverse or the workspace of the fronts beyond LDS; the message holds the bytes, the handle stays usable. */
 int rr_pgo_marginals(rr_pgo *h, int32_t n_query, const int32_t *node_a, const int32_t *node_b,
                      double *out, int64_t *out_offset, int64_t *n_vals);
 /* ms[3]: HIP-event times of the last rr_pgo_marginals call -- linearise + factor, selected inverse, gather. */
 int rr_pgo_marginals_times(const rr_pgo *h, double *ms);
+/* Let rr_pgo_marginals answer on graphs with fronts beyond LDS.  Default 0: such graphs are refused as before, same code,
+ * same message (a test of the earlier interface pins it), so the capability is asked for per handle.  With the switch on, a
+ * front beyond LDS keeps its part of the selected inverse in device memory and is inverted by kernels of its own
+ * (DESIGN.md 4s): one launch ahead of the tree's levels and up to three more per level that holds such a front; the
+ * results do not depend on the schedule, so two calls at one state give the same bits.  On a handle without such fronts
+ * the switch changes no bit and no launch.  The setter is RR_PGO_OK on every handle (RR_PGO_EINVAL: no handle); sharded and
+ * RR_PGO_F32 / RR_PGO_MIXED handles keep their own refusals, which are checked first.  Independent of
+ * rr_pgo_set_query_big_fronts: neither call reads the other's switch.  rr_pgo_extend and rr_pgo_remove_edges carry it. */
+int rr_pgo_set_marginals_big_fronts(rr_pgo *h, int32_t on);
+int32_t rr_pgo_get_marginals_big_fronts(const rr_pgo *h);   /* 0 or 1; 0 without a handle */
 
 /* Covariance blocks of ARBITRARY node pairs: block q is Sigma(node_a[q], node_b[q]), d_a x d_b row-major, for any two
  * valid nodes -- joined by an edge or far apart in the elimination tree (a == b: the node's diagonal block).  Same H (the
@@ -472,7 +484,7 @@ int rr_pgo_check_edges_times(const rr_pgo *h, double *ms);
  * holds such a front; every "bit for bit" sentence of the five queries holds on these graphs too.  On a handle without such
  * fronts the switch changes no bit of any result and no launch.  The setter is RR_PGO_OK on every handle (RR_PGO_EINVAL:
  * no handle); sharded and RR_PGO_F32 / RR_PGO_MIXED handles keep their own refusals, which are checked first.
- * rr_pgo_extend and rr_pgo_remove_edges carry the switch.  rr_pgo_marginals does not read it and keeps refusing such graphs.
+ * rr_pgo_extend and rr_pgo_remove_edges carry the switch.  rr_pgo_marginals does not read it: its own switch is rr_pgo_set_marginals_big_fronts.
  * Captured graphs, the state, the Levenberg-Marquardt lambda and the robust, prior and fixed settings are untouched. */
 int rr_pgo_set_query_big_fronts(rr_pgo *h, int32_t on);
 int32_t rr_pgo_get_query_big_fronts(const rr_pgo *h);   /* 0 or 1; 0 without a handle */
@@ -499,7 +511,7 @@ int32_t rr_pgo_get_query_big_fronts(const rr_pgo *h);   /* 0 or 1; 0 without a h
  * (rr_pgo_get_graph shows them, the analysis sees what a fresh handle on that graph would).
  * Carried over: the solver option; the robust kernel's kind and delta; its edge mask, extended with 1 for every new edge (a
  * fresh closure is robustified; a NULL mask stays NULL); the prior list of rr_pgo_set_priors with its robust flags and
- * keep_anchor (node indices do not change); the rr_pgo_set_query_big_fronts switch.  NOT carried: captured graphs, the tree and selected-inverse tables of
+ * keep_anchor (node indices do not change); the rr_pgo_set_query_big_fronts and rr_pgo_set_marginals_big_fronts switches.  NOT carried: captured graphs, the tree and selected-inverse tables of
  * the queries, rr_pgo_set_state's memo of the previous state, the Levenberg-Marquardt lambda and the *_times of earlier calls;
  * rr_pgo_stream may return another stream.  Pointers from an earlier rr_pgo_get_graph become invalid.
  * Atomic: the new graph, analysis and engine are built completely and then swapped in; the old stream is synchronised before
@@ -527,7 +539,7 @@ int rr_pgo_extend_times(const rr_pgo *h, double *ms);
  * under the environment as it is at the call -- except that the device state of every node is the old device state bit for
  * bit (copied device to device, as rr_pgo_extend carries it).
  * Carried over: the solver option; the robust kernel's kind and delta; its edge mask with the removed entries cut out (a NULL
- * mask stays NULL); the prior list with its robust flags; the fixed set; both keep_anchor settings; the rr_pgo_set_query_big_fronts switch.  NOT carried: what
+ * mask stays NULL); the prior list with its robust flags; the fixed set; both keep_anchor settings; the rr_pgo_set_query_big_fronts and rr_pgo_set_marginals_big_fronts switches.  NOT carried: what
  * rr_pgo_extend does not carry.  Atomic as rr_pgo_extend: any failure leaves the handle as it was, with the same bits.
  * RR_PGO_EINVAL, decided before anything changes: n_remove < 0, null edge with n_remove > 0, an index out of range, a node
  * left without any edge (the message names the node).  A removal that only disconnects the graph is the caller's

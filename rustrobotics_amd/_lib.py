@@ -41,6 +41,7 @@ EXPORTS = (
     "rr_pgo_extend", "rr_pgo_extend_times", "rr_pgo_set_priors", "rr_pgo_num_priors", "rr_pgo_prior_errors",
     "rr_pgo_set_fixed", "rr_pgo_num_fixed", "rr_pgo_get_fixed",
     "rr_pgo_set_query_big_fronts", "rr_pgo_get_query_big_fronts",
+    "rr_pgo_set_marginals_big_fronts", "rr_pgo_get_marginals_big_fronts",
 )
 
 
@@ -169,6 +170,9 @@ def load():
     L.rr_pgo_set_query_big_fronts.argtypes = [vp, C.c_int32]
     L.rr_pgo_get_query_big_fronts.argtypes = [vp]
     L.rr_pgo_get_query_big_fronts.restype = C.c_int32
+    L.rr_pgo_set_marginals_big_fronts.argtypes = [vp, C.c_int32]
+    L.rr_pgo_get_marginals_big_fronts.argtypes = [vp]
+    L.rr_pgo_get_marginals_big_fronts.restype = C.c_int32
     if L.rr_pgo_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH} speaks ABI version {L.rr_pgo_abi_version()}, this mirror {ABI_VERSION}: rebuild the library")
     _lib = L

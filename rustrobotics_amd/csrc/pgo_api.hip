@@ -300,6 +300,8 @@ struct EngineBase {
   virtual void refuse_factor_query(const char *who) const = 0;   // what every factor query refuses, before its arguments are read
   virtual void set_query_big_fronts(int on) = 0;                  // rr_pgo_set_query_big_fronts / rr_pgo_get_query_big_fronts
   virtual int query_big_fronts() const = 0;
+  virtual void set_marginals_big_fronts(int on) = 0;              // rr_pgo_set_marginals_big_fronts / rr_pgo_get_marginals_big_fronts
+  virtual int marginals_big_fronts() const = 0;
   // rr_pgo_gate_joint (arguments checked; set s is the records [set_ptr[s], set_ptr[s + 1]) of from / to / cand, the sets
   // expanded one after the other; dim: D_s; ioff: [n_sets + 1] offsets of the sets' S in innov; prefix and innov may be null) /
   // rr_pgo_gate_joint_times
@@ -534,6 +536,14 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   std::vector<int64_t> sel_soff_;
   size_t sel_lds_ = 0;
   bool sel_ready_ = false;
+  // fronts beyond LDS in the selected inverse (rr_pgo_set_marginals_big_fronts): per level the LDS fronts
+  // come first in sel_order_, and the tiles of the others' kernels follow each other, launch by launch, in sel_tile_
+  bool marg_big_ = false;
+  std::vector<int32_t> sel_big_ptr_;     // per level: its first front beyond LDS in sel_order_
+  std::vector<int32_t> sel_tile_ptr_;    // ranges of sel_tile_: k_selinv_big_z, _y, _zz; then per level: k_selinv_big_rp, _pp
+  DevBuf<SelBig> sel_big_;
+  DevBuf<SelTile> sel_tile_;
+  DevBuf<T> sel_work_;                   // Z and Y of every front beyond LDS
   // covariances of arbitrary pairs (treesolve.hip.h; rr_pgo_covariances): the per-front records are made on the first call,
   // in the arena; the plan of a call and its workspace live in buffers of their own that only grow
   DevBuf<TsMeta> ts_meta_;
@@ -2873,7 +2883,8 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
 
 
   // ---- queries over the factor: what rr_pgo_marginals, rr_pgo_covariances, rr_pgo_gate_edges and rr_pgo_gate_joint share
-  // lds_only: rr_pgo_marginals, and the other queries while rr_pgo_set_query_big_fronts is off
+  // lds_only: rr_pgo_marginals while rr_pgo_set_marginals_big_fronts is off, the other queries while
+  // rr_pgo_set_query_big_fronts is off
   void require_f64_unsharded_lds_factor(const char *who, bool lds_only) const {
     const std::string w = who;
     if (sharded_ || world_ > 1) throw ApiError(RR_PGO_EUNSUPPORTED, w + ": sharded handle (a rank holds a part of the factor only)");
@@ -2884,6 +2895,8 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   }
   void set_query_big_fronts(int on) override { query_big_ = on != 0; }
   int query_big_fronts() const override { return query_big_ ? 1 : 0; }
+  void set_marginals_big_fronts(int on) override { marg_big_ = on != 0; }
+  int marginals_big_fronts() const override { return marg_big_ ? 1 : 0; }
   // depth of every front, front of every permuted column, the four events of a call: made once
   void tree_tables(const char *who) {
     if (!front_depth_.empty()) return;
@@ -2921,9 +2934,11 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     size_t lds_elems = 0;
     for (int f = 0; f < S_; f++) {
       const int64_t nc = sym.sn_ncols[f], nr = sym.sn_nrows[f];
-      if (nc + nr > SELINV_MAX_ROWS) throw ApiError(RR_PGO_EUNSUPPORTED, std::string(who) + ": a front of " + std::to_string(nc + nr) + " rows exceeds what one workgroup holds");
       const int64_t image = (nc + nr) * nc + nr * (nr + 1) / 2;
-      lds_elems = std::max(lds_elems, (size_t)image);
+      if (!sym.sn_big[f]) {   // (a front beyond LDS keeps its image in svals: k_selinv_big_*)
+        if (nc + nr > SELINV_MAX_ROWS) throw ApiError(RR_PGO_EUNSUPPORTED, std::string(who) + ": a front of " + std::to_string(nc + nr) + " rows exceeds what one workgroup holds");
+        lds_elems = std::max(lds_elems, (size_t)image);
+      }
       sel_soff_[f + 1] = sel_soff_[f] + ((image + 3) & ~(int64_t)3);
     }
     for (int f = 0; f < S_; f++) {
@@ -2947,16 +2962,80 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     std::vector<int32_t> order;
     sel_level_ptr_.assign(1, 0);
     const int max_depth = *std::max_element(front_depth_.begin(), front_depth_.end());
+    // a level is two ranges: its LDS fronts, then its fronts beyond LDS with the tiles of their kernels
+    std::vector<SelBig> big;
+    std::vector<SelTile> tile;
+    std::vector<int32_t> big_of((size_t)S_, -1);
+    int64_t work_elems = 0;
+    for (int f = S_ - 1; f >= 0; f--)
+      if (sym.sn_big[f]) {
+        const int64_t nc = sym.sn_ncols[f], nr = sym.sn_nrows[f];
+        big_of[f] = (int32_t)big.size();
+        big.push_back(SelBig{f, 0, work_elems, work_elems + nc * nc});
+        work_elems += nc * (nc + nr);
+      }
+    auto below = [&](int f) {    // 128 rows below x 32 columns: k_selinv_big_y
+      for (int r0 = 0; r0 < sym.sn_nrows[f]; r0 += SELB_SLAB)
+        for (int c0 = 0; c0 < sym.sn_ncols[f]; c0 += SELB_COLS) tile.push_back(SelTile{big_of[f], r0, c0, 0});
+    };
+    auto strips = [&](int f) {   // 16 rows below x 256 columns: k_selinv_big_rp
+      for (int r0 = 0; r0 < sym.sn_nrows[f]; r0 += 16)
+        for (int c0 = 0; c0 < sym.sn_ncols[f]; c0 += SELB_RP_COLS) tile.push_back(SelTile{big_of[f], r0, c0, 0});
+    };
+    auto square = [&](int f) {   // the lower triangle of the pivot square: k_selinv_big_zz, k_selinv_big_pp
+      for (int r0 = 0; r0 < sym.sn_ncols[f]; r0 += SELB_SLAB)
+        for (int c0 = 0; c0 < sym.sn_ncols[f] && c0 < r0 + SELB_SLAB; c0 += SELB_COLS) tile.push_back(SelTile{big_of[f], r0, c0, 0});
+    };
+    sel_tile_ptr_.assign(1, 0);
+    for (int pass = 0; pass < 3; pass++) {   // ahead of the levels: Z by block rows, Y, Z^T Z
+      for (const SelBig &b : big) {
+        if (pass == 0)
+          for (int r = 0; r < (sym.sn_ncols[b.front] + 31) / 32; r++) tile.push_back(SelTile{big_of[b.front], r, 0, 0});
+        else if (pass == 1) below(b.front);
+        else square(b.front);
+      }
+      sel_tile_ptr_.push_back((int32_t)tile.size());
+    }
+    sel_big_ptr_.clear();
     for (int d = 0; d <= max_depth; d++) {
       for (int f = S_ - 1; f >= 0; f--)
-        if (front_depth_[f] == d) order.push_back(f);
+        if (front_depth_[f] == d && !sym.sn_big[f]) order.push_back(f);
+      sel_big_ptr_.push_back((int32_t)order.size());
+      for (int f = S_ - 1; f >= 0; f--)
+        if (front_depth_[f] == d && sym.sn_big[f]) order.push_back(f);
       sel_level_ptr_.push_back((int32_t)order.size());
+      for (int pass = 0; pass < 2; pass++) {   // k_selinv_big_rp, k_selinv_big_pp: nothing for a front without rows below
+        for (int k = sel_big_ptr_.back(); k < sel_level_ptr_.back(); k++)
+          if (sym.sn_nrows[order[k]] > 0) pass == 0 ? strips(order[k]) : square(order[k]);
+        sel_tile_ptr_.push_back((int32_t)tile.size());
+      }
     }
-    {
+    if (big.empty()) {
       ArenaScope scope(&arena_);   // like every other buffer of the handle: back to the pool with it
       sel_meta_.upload(meta);
       sel_order_.upload(order);
       svals_.alloc((size_t)sel_soff_[S_] + 4);
+    } else {
+      // the images and the workspace of fronts beyond LDS are of the factor's size: buffers of their own, so that a device
+      // without room for them is an answer (nothing of the handle has changed by then), not a failed arena chunk
+      auto own = [&](DevBuf<T> &buf, size_t count, const char *what) {
+        buf.alloc(0);
+        T *p = nullptr;
+        if (hipMalloc((void **)&p, count * sizeof(T)) != hipSuccess) {
+          (void)hipGetLastError();
+          throw ApiError(RR_PGO_ENOMEM, std::string(who) + ": " + std::to_string(count * sizeof(T)) + " bytes for " + what + " of the fronts beyond LDS");
+        }
+        buf.p = p;
+        buf.n = count;
+        buf.owned = true;
+      };
+      own(svals_, (size_t)sel_soff_[S_] + 4, "the selected inverse");
+      own(sel_work_, (size_t)work_elems + 4, "the workspace");
+      ArenaScope scope(&arena_);
+      sel_meta_.upload(meta);
+      sel_order_.upload(order);
+      sel_big_.upload(big);
+      sel_tile_.upload(tile);
     }
     if constexpr (std::is_same<T, double>::value)
       HIPCHK(hipFuncSetAttribute((const void *)k_selinv_level<T, SELINV_THREADS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sel_lds_));
@@ -2965,7 +3044,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
 
   void marginals(int nq, const int32_t *na, const int32_t *nb, const int64_t *off, double *out) override {
     static constexpr const char *who = "rr_pgo_marginals";
-    require_f64_unsharded_lds_factor(who, true);
+    require_f64_unsharded_lds_factor(who, !marg_big_);
     if constexpr (f64_) {
       marginals_prepare(who);
       const Symbolic &sym = sym_;
@@ -3018,10 +3097,24 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
       a.lvals = lvals_.p;
       a.winv = winv_.p;
       a.svals = svals_.p;
+      SelBigArgs<T> ab;
+      ab.s = a;
+      ab.big = sel_big_.p;
+      ab.tile = sel_tile_.p;
+      ab.work = sel_work_.p;
+      // ranges of sel_tile_: Z, Y, Z^T Z of every front beyond LDS (they need nothing from a parent), then two per level
+      auto big_launch = [&](auto kernel, int threads, size_t r) {
+        const int first = sel_tile_ptr_[r], count = sel_tile_ptr_[r + 1] - first;
+        if (count > 0) hipLaunchKernelGGL(kernel, dim3((unsigned)count), dim3((unsigned)threads), 0, stream_, ab, first);
+      };
+      big_launch(k_selinv_big_z<T>, SELB_Z_THREADS, 0);
+      big_launch(k_selinv_big_y<T>, SELB_THREADS, 1);
+      big_launch(k_selinv_big_zz<T>, SELB_THREADS, 2);
       for (size_t l = 0; l + 1 < sel_level_ptr_.size(); l++) {
-        const int begin = sel_level_ptr_[l], count = sel_level_ptr_[l + 1] - begin;
-        if (count <= 0) continue;
-        hipLaunchKernelGGL((k_selinv_level<T, SELINV_THREADS>), dim3((unsigned)count), dim3(SELINV_THREADS), sel_lds_, stream_, a, begin);
+        const int begin = sel_level_ptr_[l], count = sel_big_ptr_[l] - begin;
+        if (count > 0) hipLaunchKernelGGL((k_selinv_level<T, SELINV_THREADS>), dim3((unsigned)count), dim3(SELINV_THREADS), sel_lds_, stream_, a, begin);
+        big_launch(k_selinv_big_rp<T>, SELB_THREADS, 3 + 2 * l);
+        big_launch(k_selinv_big_pp<T>, SELB_THREADS, 4 + 2 * l);
       }
       check_launch("k_selinv_level");
       HIPCHK(hipEventRecord(query_ev_[2], stream_));
@@ -4292,6 +4385,7 @@ static void extend_handle(rr_pgo *h, int32_t n_new_nodes, const int32_t *node_ki
   if (h->engine->priors().n() > 0) apply_priors(*nh, h->engine->priors());   // node indices do not change
   if (!h->engine->fixed().empty()) nh->engine->set_fixed(h->engine->fixed(), h->engine->fixed_keep_anchor());   // new nodes are free
   nh->engine->set_query_big_fronts(h->engine->query_big_fronts());
+  nh->engine->set_marginals_big_fronts(h->engine->marginals_big_fronts());
   // ---- the swap: nothing below can fail.  The old engine (its stream drained above, the copy out of its buffers waited for)
   // goes with nh.  Every field changes sides (the engines refer to the pointees of g and symp, which do not move).
   std::swap(*h, *nh);
@@ -4342,6 +4436,7 @@ static void remove_handle(rr_pgo *h, int32_t n_remove, const int32_t *edge) {
   if (h->engine->priors().n() > 0) apply_priors(*nh, h->engine->priors());   // node indices do not change
   if (!h->engine->fixed().empty()) nh->engine->set_fixed(h->engine->fixed(), h->engine->fixed_keep_anchor());
   nh->engine->set_query_big_fronts(h->engine->query_big_fronts());
+  nh->engine->set_marginals_big_fronts(h->engine->marginals_big_fronts());
   // ---- the swap, as in extend_handle: nothing below can fail
   std::swap(*h, *nh);
   h->remove_ms[0] = t1 - t0;
@@ -4778,6 +4873,12 @@ int rr_pgo_set_query_big_fronts(rr_pgo *h, int32_t on) {
   return guarded([&] { h->engine->set_query_big_fronts(on); });
 }
 int32_t rr_pgo_get_query_big_fronts(const rr_pgo *h) { return h ? (int32_t)h->engine->query_big_fronts() : 0; }
+
+int rr_pgo_set_marginals_big_fronts(rr_pgo *h, int32_t on) {
+  if (!h) { g_last_error = "rr_pgo_set_marginals_big_fronts: no handle"; return RR_PGO_EINVAL; }
+  return guarded([&] { h->engine->set_marginals_big_fronts(on); });
+}
+int32_t rr_pgo_get_marginals_big_fronts(const rr_pgo *h) { return h ? (int32_t)h->engine->marginals_big_fronts() : 0; }
 
 int32_t rr_pgo_num_fixed(const rr_pgo *h) { return h ? (int32_t)h->engine->fixed().size() : 0; }
 

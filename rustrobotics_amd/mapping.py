@@ -387,6 +387,16 @@ class PoseGraph:
     def query_big_fronts(self, on):
         _check(_lib.load().rr_pgo_set_query_big_fronts(self._h, 1 if on else 0))
 
+    @property
+    def marginals_big_fronts(self):
+        """Whether marginal_blocks answers on a graph with fronts beyond LDS (stats()["n_big_fronts"] != 0).  Off by default:
+        such graphs are refused.  Independent of query_big_fronts.  extend and remove_edges keep it."""
+        return bool(_lib.load().rr_pgo_get_marginals_big_fronts(self._h))
+
+    @marginals_big_fronts.setter
+    def marginals_big_fronts(self, on):
+        _check(_lib.load().rr_pgo_set_marginals_big_fronts(self._h, 1 if on else 0))
+
     # -- marginal covariances (include/rr_pgo.h, "marginal covariances") -----------------
     def marginal_blocks(self, node_a=None, node_b=None):
         """rr_pgo_marginals as it is: (values, offsets) of the queried blocks of Sigma = H^-1 at the current state.
