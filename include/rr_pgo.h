@@ -61,7 +61,8 @@ enum {
 enum { RR_PGO_GAUSS_NEWTON = 0, RR_PGO_LEVENBERG_MARQUARDT = 1 };
 /* enum Node variants, :147-154 ; enum Edge variants, :20-26 */
 enum { RR_PGO_NODE_SE2 = 0, RR_PGO_NODE_XY = 1, RR_PGO_NODE_SE3 = 2, RR_PGO_NODE_XYZ = 3 };
-enum { RR_PGO_EDGE_SE2 = 0, RR_PGO_EDGE_SE2_XY = 1, RR_PGO_EDGE_SE3 = 2, RR_PGO_EDGE_SE3_XYZ = 3 };
+enum { RR_PGO_EDGE_SE2 = 0, RR_PGO_EDGE_SE2_XY = 1, RR_PGO_EDGE_SE3 = 2, RR_PGO_EDGE_SE3_XYZ = 3,
+       RR_PGO_EDGE_SE2_BEARING = 4, RR_PGO_EDGE_SE2_RANGE = 6 };   /* 5 and 7 are reserved: unknown kinds at every entry point */
 /* 3-D point landmarks: RR_PGO_NODE_XYZ and RR_PGO_EDGE_SE3_XYZ (build-defined; the reference has none).
  *   node   state x y z, 3 scalars of the step, additive: l <- l + sign * dl, no renormalisation.
  *   edge   from an SE3 pose (t, q) to an XYZ landmark l, measurement z = x y z, information 6 values (3 x 3 upper triangle,
@@ -79,6 +80,40 @@ enum { RR_PGO_EDGE_SE2 = 0, RR_PGO_EDGE_SE2_XY = 1, RR_PGO_EDGE_SE3 = 2, RR_PGO_
  *   g2o text: VERTEX_TRACKXYZ id x y z; EDGE_SE3_TRACKXYZ from to param_id x y z i11 i12 i13 i22 i23 i33 (param_id: an
  *   unsigned integer, otherwise ignored); PARAMS_SE3OFFSET id x y z qx qy qz qw is accepted only as exactly 0 0 0 0 0 0 1 --
  *   any other offset is RR_PGO_EPARSE, "sensor offsets are not supported": a deliberate restriction. */
+/* Bearing-only and range-only landmark edges: RR_PGO_EDGE_SE2_BEARING and RR_PGO_EDGE_SE2_RANGE (the range-bearing model of
+ * the reference's src/models/measurement.rs, one measurement at a time).  Both go from an SE2 pose (t, theta) to an XY landmark
+ * l; any other endpoints are RR_PGO_EINVAL, and with a 3-D node the graph is "mixed 2D / 3D".
+ *   edge   1 measurement value z, 1 information value omega > 0; the error has ONE scalar.  With d = l - t, p = R(theta)^T d
+ *          and rho = |d|:
+ *            bearing  z in radians, e = wrap(atan2(p_y, p_x) - z) into (-pi, pi] -- evaluated without a modulo: the
+ *                     measurement is kept as (cos z, sin z), as poses keep their angle, and e = atan2 of p rotated by -z;
+ *                     de/dt = (d_y, -d_x) / rho^2, de/dtheta = -1, de/dl = (-d_y, d_x) / rho^2
+ *            range    z >= 0 in the units of t, e = rho - z; de/dt = -d / rho, de/dtheta = 0, de/dl = d / rho
+ *          under the library's additive 2-D increments (x, y, theta) and (l_x, l_y); the tests pin both Jacobians to central
+ *          differences in 50-digit arithmetic.
+ *   domain rho = 0 (the landmark at the pose) is outside the domain of both kinds: keeping every observed landmark away from
+ *          the pose that saw it is the CALLER'S precondition; the kernels carry no guard (rho = 0 gives NaN).
+ *   graph  rr_pgo_graph_desc packs 1 measurement and 1 information value per such edge.  Neither kind is a pose-pose edge:
+ *          neither sets rr_pgo_anchor_node.  A bearing and a range edge between the same pair are two edges (two terms of one
+ *          block); a combined kind with a correlated 2 x 2 information matrix does not exist.
+ *   prior  there are no bearing or range priors: a prior stays the edge of the node's own kind.
+ *   extend (guess mode) a bearing or range edge yields NO step -- one scalar does not place a landmark.  A new landmark that
+ *          only such edges reach is the refusal "has no initial value" naming the node; one that also has an SE2_XY edge from
+ *          a ready pose is guessed from that edge.
+ *   gate / check / joint: d_e = 1, S and R are 1 x 1; the `to` node's block keeps its 2 scalars.  A call of rr_pgo_gate_edges,
+ *          rr_pgo_gate_joint or rr_pgo_check_edges runs ONE kernel instantiation, chosen by the whole call: the one that knows the
+ *          two kinds when the handle's graph has such an edge or the call holds such a record, the one every other call always
+ *          ran otherwise.  Within an instantiation every bitwise guarantee of the three calls holds as stated (order, repeats,
+ *          the rest of the list, a cut of the plan).  The one exception: on a handle WITHOUT such edges, an SE2 or SE2_XY
+ *          candidate's outputs in a call that also holds a bearing or range candidate agree with its outputs in a call that
+ *          holds none to rounding, not bit for bit -- two instantiations promise no common bits.  On a handle with such edges
+ *          every call runs the same instantiation and there is no exception.
+ *   Handles in RR_PGO_F64, RR_PGO_F32 and RR_PGO_MIXED.  RR_PGO_EUNSUPPORTED: a sharded handle on a graph with one of the
+ *   kinds, and such a graph under RR_PGO_EDGE_LINEARIZE (at rr_pgo_create / rr_pgo_load_g2o / rr_pgo_extend: the
+ *   edge-parallel experiment forms are not taught the kinds, as they are not taught priors or fixed nodes).
+ *   g2o text: EDGE_BEARING_SE2_XY from to z omega is g2o's own tag; EDGE_RANGE_SE2_XY from to z omega is build-defined by
+ *   analogy (stock g2o has no 2-D range tag).  A non-positive omega is RR_PGO_EPARSE there, RR_PGO_EINVAL from rr_pgo_create
+ *   and rr_pgo_extend. */
 /* arithmetic type of the device path (the reference is f64 throughout).
  * RR_PGO_MIXED: state, measurements, error / Jacobians / gradient and chi2 in f64; H, its factor and
  * the solve in f32.  The gradient is exact, so Gauss-Newton converges to the f64 minimum while the
@@ -96,8 +131,9 @@ typedef struct rr_pgo_graph_desc {
   const int32_t *edge_kind;   /* [n_edges] RR_PGO_EDGE_*, file order (order defines the prior, :330-336) */
   const int32_t *edge_from;   /* [n_edges] dense node index (lut/nodes lookups of :312-320 done by the caller) */
   const int32_t *edge_to;
-  const double *edge_meas;    /* packed in edge order: SE2 x,y,theta | SE2_XY x,y | SE3 x,y,z,qx,qy,qz,qw | SE3_XYZ x,y,z */
-  const double *edge_info;    /* packed upper triangles, row-major: 6 | 3 | 21 | 6 values (g2o.rs:82,100,117) */
+  const double *edge_meas;    /* packed in edge order: SE2 x,y,theta | SE2_XY x,y | SE3 x,y,z,qx,qy,qz,qw | SE3_XYZ x,y,z |
+                                 SE2_BEARING z | SE2_RANGE z */
+  const double *edge_info;    /* packed upper triangles, row-major: 6 | 3 | 21 | 6 | 1 | 1 values (g2o.rs:82,100,117) */
 } rr_pgo_graph_desc;
 
 typedef struct rr_pgo_options {
@@ -505,7 +541,7 @@ int32_t rr_pgo_get_query_big_fronts(const rr_pgo *h);   /* 0 or 1; 0 without a h
  * alone: the ready set starts as the old nodes; the new edges are scanned in order, again and again, until a scan adds no
  * step; an edge with exactly one ready endpoint whose other endpoint is a new node not yet ready is a step when it determines
  * that node -- to = from (+) z for every kind (SE2: X_to = X_from Z; SE2_XY and SE3_XYZ: l = t + R z; SE3: X_to = X_from Z), from = to (+) z^-1
- * for pose-pose edges only -- and makes it ready.  A new node no step reaches is RR_PGO_EINVAL (the message names it), decided
+ * for pose-pose edges only -- and makes it ready (SE2_BEARING and SE2_RANGE edges are never a step).  A new node no step reaches is RR_PGO_EINVAL (the message names it), decided
  * before anything changes.  One kernel (k_guess_nodes) executes the steps in the state's arithmetic type, dependent steps in
  * list order, (cos, sin) and quaternions renormalised; the guessed values of the new nodes are copied into the host graph
  * (rr_pgo_get_graph shows them, the analysis sees what a fresh handle on that graph would).

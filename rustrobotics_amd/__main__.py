@@ -30,7 +30,7 @@
       (row vertex, column vertex) block: the two ids, d_r, d_c, the d_r x d_c values row-major -- and the call's three times
 
   --gate FILE  (example mode): after the optimisation, gate the candidate edges of FILE -- EDGE_SE2 / EDGE_SE2_XY /
-      EDGE_SE3:QUAT lines in the loader's field order, between vertex ids of the loaded graph, not part of it -- and print
+      EDGE_BEARING_SE2_XY / EDGE_RANGE_SE2_XY / EDGE_SE3:QUAT / EDGE_SE3_TRACKXYZ lines in the loader's field order, between vertex ids of the loaded graph, not part of it -- and print
       one line per candidate: ids, Mahalanobis distance d2, e^T Omega e, accept / reject at the 0.95 chi-square quantile
       (rr_pgo_gate_edges).  With --accept the accepted candidates are then added to the live handle (rr_pgo_extend), the
       optimisation runs again, and chi2 before and after is printed
@@ -138,7 +138,8 @@ def write_cross(g, path, columns, rows):
           f"linearise + factor {t[0]:.3f} ms, forward + backward solve {t[1]:.3f} ms, gather + copy {t[2]:.3f} ms")
 
 
-GATE_TAGS = {"EDGE_SE2": 0, "EDGE_SE2_XY": 1, "EDGE_SE3:QUAT": 2, "EDGE_SE3_TRACKXYZ": 3}
+GATE_TAGS = {"EDGE_SE2": 0, "EDGE_SE2_XY": 1, "EDGE_SE3:QUAT": 2, "EDGE_SE3_TRACKXYZ": 3,
+             "EDGE_BEARING_SE2_XY": 4, "EDGE_RANGE_SE2_XY": 6}   # (the range tag is build-defined: include/rr_pgo.h)
 
 
 _PARAM_ID = {"EDGE_SE3_TRACKXYZ": ", a parameter id"}   # what the messages about such a line add
@@ -175,7 +176,8 @@ def parse_gate_file(path, index, sets=None, flag="--gate"):
                 sets.append((no, members))
                 continue
             if tok[0] not in GATE_TAGS:
-                raise SystemExit(f"{flag}: {path}:{no}: unknown tag {tok[0]!r} (EDGE_SE2, EDGE_SE2_XY or EDGE_SE3:QUAT)")
+                raise SystemExit(f"{flag}: {path}:{no}: unknown tag {tok[0]!r} (EDGE_SE2, EDGE_SE2_XY, EDGE_BEARING_SE2_XY, EDGE_RANGE_SE2_XY, "
+                                 "EDGE_SE3:QUAT or EDGE_SE3_TRACKXYZ)")
             k = GATE_TAGS[tok[0]]
             nm, ni = GATE_MEAS_LEN[k], GATE_INFO_LEN[k]
             try:
@@ -287,7 +289,8 @@ def parse_extend_file(path, index, n_nodes=None, flag="--extend"):
                 continue
             if tok[0] not in GATE_TAGS:
                 raise SystemExit(f"{flag}: {path}:{no}: unknown tag {tok[0]!r} (VERTEX_SE2, VERTEX_XY, VERTEX_SE3:QUAT, "
-                                 "EDGE_SE2, EDGE_SE2_XY or EDGE_SE3:QUAT)")
+                                 "VERTEX_TRACKXYZ, EDGE_SE2, EDGE_SE2_XY, EDGE_BEARING_SE2_XY, EDGE_RANGE_SE2_XY, EDGE_SE3:QUAT or "
+                                 "EDGE_SE3_TRACKXYZ)")
             k = GATE_TAGS[tok[0]]
             nm, ni = GATE_MEAS_LEN[k], GATE_INFO_LEN[k]
             try:

@@ -6,6 +6,8 @@
 //     EDGE_SE3:QUAT, anything else is an error (unimplemented!() at :138);
 //   * build-defined, the reference has none: VERTEX_TRACKXYZ, EDGE_SE3_TRACKXYZ and an identity PARAMS_SE3OFFSET
 //     (3-D point landmarks, include/rr_pgo.h);
+//   * EDGE_BEARING_SE2_XY (g2o's own tag) and EDGE_RANGE_SE2_XY (build-defined by analogy: stock g2o has no 2-D range tag):
+//     `from to z omega`, one measurement and one information value, which must be positive;
 //   * scalar offsets grow by 3 / 2 / 6 (TRACKXYZ: 3) in vertex FILE order (:60-77);
 //   * edges keep FILE order (:94-95,111-112,135-136);
 //   * information matrices are given as row-major upper triangles (:82,100,117).
@@ -81,7 +83,7 @@ std::string HostGraph::finalize() {
   node_state_off.assign(N, 0);
   int off = 0;
   int64_t soff = 0;
-  has_se3 = has_2d = has_xyz = false;
+  has_se3 = has_2d = has_xyz = has_br = false;
   for (int i = 0; i < N; i++) {
     int k = node_kind[i];
     if (k < NODE_SE2 || k > NODE_XYZ) return "bad node kind";
@@ -101,18 +103,16 @@ std::string HostGraph::finalize() {
   anchor_node = -1;
   for (int k = 0; k < E; k++) {
     int ek = edge_kind[k];
-    if (ek < EDGE_SE2 || ek > EDGE_SE3_XYZ) return "bad edge kind";
+    if (!edge_kind_known(ek)) return "bad edge kind";
     int a = edge_from[k], b = edge_to[k];
     if (a < 0 || a >= N || b < 0 || b >= N)
       return "edge " + std::to_string(k) + " references an unknown vertex";
     int ka = node_kind[a], kb = node_kind[b];
-    bool ok = (ek == EDGE_SE2 && ka == NODE_SE2 && kb == NODE_SE2) ||
-              (ek == EDGE_SE2_XY && ka == NODE_SE2 && kb == NODE_XY) ||
-              (ek == EDGE_SE3 && ka == NODE_SE3 && kb == NODE_SE3) ||
-              (ek == EDGE_SE3_XYZ && ka == NODE_SE3 && kb == NODE_XYZ);
+    bool ok = edge_endpoints_ok(ek, ka, kb);
     if (!ok)  // unreachable!() in the reference, pose_graph_optimization.rs:315-320,342-347
       return "edge " + std::to_string(k) + ": endpoint kinds do not match the edge kind";
     if (a == b) return "edge " + std::to_string(k) + " is a self loop";
+    if (edge_is_br(ek)) has_br = true;
     edge_meas_off[k] = mo;
     edge_info_off[k] = io;
     mo += edge_meas_len(ek);
@@ -122,6 +122,9 @@ std::string HostGraph::finalize() {
   }
   if ((int64_t)edge_meas.size() != mo) return "edge_meas length does not match edge kinds";
   if ((int64_t)edge_info.size() != io) return "edge_info length does not match edge kinds";
+  for (int k = 0; k < E; k++)   // (a 1 x 1 information matrix: positive definite is positive)
+    if (edge_is_br(edge_kind[k]) && !(edge_info[edge_info_off[k]] > 0.0))
+      return "edge " + std::to_string(k) + ": the information value of a bearing or range edge must be positive";
   return "";
 }
 
@@ -165,6 +168,8 @@ void parse_part(const char *text, size_t begin, size_t end, ParsedPart &out) {
     else if (tok[0] == "EDGE_SE2") { kind = EDGE_SE2; nvals = 9; is_edge = true; }
     else if (tok[0] == "EDGE_SE2_XY") { kind = EDGE_SE2_XY; nvals = 5; is_edge = true; }
     else if (tok[0] == "EDGE_SE3:QUAT") { kind = EDGE_SE3; nvals = 28; is_edge = true; }
+    else if (tok[0] == "EDGE_BEARING_SE2_XY") { kind = EDGE_SE2_BEARING; nvals = 2; is_edge = true; }
+    else if (tok[0] == "EDGE_RANGE_SE2_XY") { kind = EDGE_SE2_RANGE; nvals = 2; is_edge = true; }
     else if (tok[0] == "VERTEX_TRACKXYZ") { kind = NODE_XYZ; nvals = 3; }
     else if (tok[0] == "EDGE_SE3_TRACKXYZ") { kind = EDGE_SE3_XYZ; nvals = 9; is_edge = true; is_track = true; }
     else if (tok[0] == "PARAMS_SE3OFFSET") {
@@ -193,6 +198,7 @@ void parse_part(const char *text, size_t begin, size_t end, ParsedPart &out) {
     for (int i = 0; i < nvals; i++)
       if (!to_f64(tok[first + i], v[i])) return fail("bad number '" + std::string(tok[first + i]) + "'");
 
+    if (is_edge && edge_is_br(kind) && !(v[1] > 0.0)) return fail("the information value must be positive");
     if (!is_edge) {
       out.node_kind.push_back(kind);
       out.node_id.push_back(id0);
@@ -288,6 +294,10 @@ std::string load_g2o(const char *path, HostGraph &g, bool &io_error) {
     for (size_t k = 0; k < E; k++)
       if (g.edge_kind[k] == EDGE_SE3_XYZ && (g.node_kind[g.edge_from[k]] != NODE_SE3 || g.node_kind[g.edge_to[k]] != NODE_XYZ))
         return "line " + std::to_string(edge_line[k]) + ": EDGE_SE3_TRACKXYZ goes from an SE3 pose to an XYZ landmark";
+    for (size_t k = 0; k < E; k++)
+      if (edge_is_br(g.edge_kind[k]) && (g.node_kind[g.edge_from[k]] != NODE_SE2 || g.node_kind[g.edge_to[k]] != NODE_XY))
+        return "line " + std::to_string(edge_line[k]) + (g.edge_kind[k] == EDGE_SE2_BEARING ? ": EDGE_BEARING_SE2_XY" : ": EDGE_RANGE_SE2_XY") +
+               " goes from an SE2 pose to an XY landmark";
   }
   return g.finalize();
 }

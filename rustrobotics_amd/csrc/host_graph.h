@@ -9,13 +9,22 @@
 namespace rrpgo {
 
 enum NodeKind : int32_t { NODE_SE2 = 0, NODE_XY = 1, NODE_SE3 = 2, NODE_XYZ = 3 };
-enum EdgeKind : int32_t { EDGE_SE2 = 0, EDGE_SE2_XY = 1, EDGE_SE3 = 2, EDGE_SE3_XYZ = 3 };
+// 5 and 7 are reserved: unknown kinds everywhere
+enum EdgeKind : int32_t { EDGE_SE2 = 0, EDGE_SE2_XY = 1, EDGE_SE3 = 2, EDGE_SE3_XYZ = 3, EDGE_SE2_BEARING = 4, EDGE_SE2_RANGE = 6 };
+inline bool edge_kind_known(int kind) { return (kind >= EDGE_SE2 && kind <= EDGE_SE2_BEARING) || kind == EDGE_SE2_RANGE; }
+// bearing-only and range-only edges SE2 pose -> XY landmark: ONE error scalar, one measurement value, one information value
+inline bool edge_is_br(int kind) { return kind == EDGE_SE2_BEARING || kind == EDGE_SE2_RANGE; }
 
 inline int node_dim(int kind) { return kind == NODE_SE2 ? 3 : kind == NODE_XY ? 2 : kind == NODE_XYZ ? 3 : 6; }
 inline int node_state_len(int kind) { return kind == NODE_SE2 ? 3 : kind == NODE_XY ? 2 : kind == NODE_XYZ ? 3 : 7; }
-inline int edge_dim(int kind) { return kind == EDGE_SE2 ? 3 : kind == EDGE_SE2_XY ? 2 : kind == EDGE_SE3_XYZ ? 3 : 6; }
-inline int edge_meas_len(int kind) { return kind == EDGE_SE2 ? 3 : kind == EDGE_SE2_XY ? 2 : kind == EDGE_SE3_XYZ ? 3 : 7; }
-inline int edge_info_len(int kind) { return kind == EDGE_SE2 ? 6 : kind == EDGE_SE2_XY ? 3 : kind == EDGE_SE3_XYZ ? 6 : 21; }
+inline int edge_dim(int kind) { return edge_is_br(kind) ? 1 : kind == EDGE_SE2 ? 3 : kind == EDGE_SE2_XY ? 2 : kind == EDGE_SE3_XYZ ? 3 : 6; }
+inline int edge_meas_len(int kind) { return edge_is_br(kind) ? 1 : kind == EDGE_SE2 ? 3 : kind == EDGE_SE2_XY ? 2 : kind == EDGE_SE3_XYZ ? 3 : 7; }
+inline int edge_info_len(int kind) { return edge_is_br(kind) ? 1 : kind == EDGE_SE2 ? 6 : kind == EDGE_SE2_XY ? 3 : kind == EDGE_SE3_XYZ ? 6 : 21; }
+// the endpoint kinds an edge kind asks for
+inline bool edge_endpoints_ok(int ek, int ka, int kb) {
+  return (ek == EDGE_SE2 && ka == NODE_SE2 && kb == NODE_SE2) || ((ek == EDGE_SE2_XY || edge_is_br(ek)) && ka == NODE_SE2 && kb == NODE_XY) ||
+         (ek == EDGE_SE3 && ka == NODE_SE3 && kb == NODE_SE3) || (ek == EDGE_SE3_XYZ && ka == NODE_SE3 && kb == NODE_XYZ);
+}
 inline bool node_is_3d(int kind) { return kind == NODE_SE3 || kind == NODE_XYZ; }
 // a prior on a node is the edge of the node's own kind from a fixed identity pose (rr_pgo_set_priors)
 inline int prior_edge_kind(int node_kind) {
@@ -54,6 +63,18 @@ inline int pack_state(int kind, const double *s, double p[8]) {
   }
   return node_state_len(kind);
 }
+// The device form of an edge's measurement by EDGE kind.  The node numbering serves kinds 0 .. 3 as it is; a bearing z is packed
+// as poses pack their angle, a range as it is, and lane 3 carries the kind (4 or 6, exact in every arithmetic type): the lane is
+// zero in every SE2_XY record, and the code of the SE2_XY error reads lanes 0 and 1 alone.
+//   BEARING  cos z, sin z, 0, 4 | -      RANGE  z, 0, 0, 6 | -
+inline int pack_meas(int edge_kind, const double *m, double p[8]) {
+  if (!edge_is_br(edge_kind)) return pack_state(edge_kind, m, p);
+  for (int t = 0; t < 8; t++) p[t] = 0.0;
+  if (edge_kind == EDGE_SE2_BEARING) { p[0] = std::cos(m[0]); p[1] = std::sin(m[0]); }
+  else p[0] = m[0];
+  p[3] = (double)edge_kind;
+  return 1;
+}
 // the inverse (the angle of (cos, sin); the quaternion as it is); returns how many scalars it wrote
 inline int unpack_state(int kind, const double p[8], double *s) {
   s[0] = p[0]; s[1] = p[1];
@@ -82,6 +103,7 @@ struct HostGraph {
   int32_t anchor_node = -1; // from-node of the first pose-pose edge (prior, :330-336)
   bool has_se3 = false, has_2d = false;   // has_se3: the graph is 3-D (SE3 poses, XYZ landmarks)
   bool has_xyz = false;                   // ... and has XYZ landmarks
+  bool has_br = false;                    // a 2-D graph with bearing-only or range-only edges
 
   int n_nodes() const { return (int)node_kind.size(); }
   int n_edges() const { return (int)edge_kind.size(); }

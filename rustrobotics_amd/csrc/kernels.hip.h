@@ -147,8 +147,9 @@ __device__ __forceinline__ bool opt_stopped(const int *err) { return err && err[
 template <typename TC> struct EdgeRec {
   int32_t from, to;
   int64_t slot;                        // (offset into hvals << 1) | transposed
-  typename VecT<TC>::V4 meas;          // SE2: x, y, cos, sin | SE2_XY: x, y, 0, 0
-  typename VecT<TC>::V4 info_a;        // i11 i12 i13 i22
+  typename VecT<TC>::V4 meas;          // SE2: x, y, cos, sin | SE2_XY: x, y, 0, 0 | SE2_BEARING: cos z, sin z, 0, 4 | SE2_RANGE: z, 0, 0, 6
+                                       // (lane 3 of a landmark edge: its sub-kind, read by the BR kernels alone; pack_meas, host_graph.h)
+  typename VecT<TC>::V4 info_a;        // i11 i12 i13 i22 (SE2_BEARING / SE2_RANGE: omega, 0, 0, 0)
   typename VecT<TC>::V2 info_b;        // i23 i33
 };
 static_assert(sizeof(EdgeRec<float>) == 64 && sizeof(EdgeRec<double>) == 128, "EdgeRec is four / eight sixteen-byte loads of one line");
@@ -256,6 +257,39 @@ __device__ __forceinline__ void edge_linearize_2d(int kind, const typename VecT<
     B[0][0] = r;  B[0][1] = i;  B[0][2] = 0;
     B[1][0] = -i; B[1][1] = r;  B[1][2] = 0;
     B[2][0] = 0;  B[2][1] = 0;  B[2][2] = 0;
+  }
+}
+
+// Bearing-only and range-only edges SE2 pose x1 = (t, theta) -> XY landmark x2 = l (RR_PGO_EDGE_SE2_BEARING / _RANGE;
+// include/rr_pgo.h).  The error has ONE scalar: e, A and B come zero padded to 3 and 3 x 3 with row 0 alone populated, so the
+// frame of k_linearize_br takes them as it takes an SE2_XY edge's.  With d = l - t, p = R(theta)^T d, rho = |d|:
+//   bearing (z.w == 4, z = (cos m, sin m, -, 4)):  e = atan2 of p rotated by -m, which is wrap(atan2(p_y, p_x) - m) into
+//     (-pi, pi] without a modulo;  de/dt = (d_y, -d_x) / rho^2,  de/dtheta = -1,  de/dl = (-d_y, d_x) / rho^2
+//   range   (z.w == 6, z = (m, -, -, 6)):          e = rho - m;  de/dt = -d / rho,  de/dtheta = 0,  de/dl = d / rho
+// rho = 0 (the landmark at the pose) is outside the domain: the caller's precondition, no guard here.
+template <typename T>
+__device__ __forceinline__ void edge_linearize_2d_br(const typename VecT<T>::V4 &x1, const typename VecT<T>::V4 &x2,
+                                                     const typename VecT<T>::V4 &z, T e[3], T A[3][3], T B[3][3]) {
+  const T dx = x2.x - x1.x, dy = x2.y - x1.y;
+  const T r2 = dx * dx + dy * dy;
+#pragma unroll
+  for (int i = 0; i < 3; i++)
+#pragma unroll
+    for (int j = 0; j < 3; j++) { A[i][j] = 0; B[i][j] = 0; }
+  e[1] = 0; e[2] = 0;
+  if (z.w == (T)4) {
+    const T px = x1.z * dx + x1.w * dy, py = -x1.w * dx + x1.z * dy;
+    e[0] = atan2(z.x * py - z.y * px, z.x * px + z.y * py);
+    const T ir2 = (T)1 / r2;
+    const T gx = dy * ir2, gy = dx * ir2;
+    A[0][0] = gx;  A[0][1] = -gy; A[0][2] = -1;
+    B[0][0] = -gx; B[0][1] = gy;
+  } else {
+    const T rho = sqrt(r2), ir = (T)1 / rho;
+    e[0] = rho - z.x;
+    const T ux = dx * ir, uy = dy * ir;
+    A[0][0] = -ux; A[0][1] = -uy;
+    B[0][0] = ux;  B[0][1] = uy;
   }
 }
 
@@ -684,13 +718,26 @@ template <typename A> __device__ __forceinline__ void opt_publish_chi2_in_last_b
 template <typename TO, typename T, int RK = ROBUST_NONE, int D = 3, bool PR = false>
 __global__ void __launch_bounds__(LIN_THREADS) k_linearize(LinArgs<TO, T> a) {
   constexpr bool LM = false;
+  constexpr bool BR = false;
 #include "linearize_pull.inc"
 }
 // the pull form of a 3-D graph with XYZ landmarks
 template <typename TO, typename T, int RK = ROBUST_NONE, bool PR = false>
 __global__ void __launch_bounds__(LIN_THREADS) k_linearize_lm(LinArgs<TO, T> a) {
   constexpr bool LM = true;
+  constexpr bool BR = false;
   constexpr int D = 6;
+#include "linearize_pull.inc"
+}
+// the pull form of a 2-D graph with bearing-only or range-only edges (RR_PGO_EDGE_SE2_BEARING / _RANGE): the D = 3 frame, and
+// behind `if constexpr (BR)` the one statement that evaluates such an edge (edge_linearize_2d_br, zero padded: row 0 of e, A, B
+// and W[0][0] alone are populated; the record's information lanes hold (omega, 0, 0, 0 | 0, 0), so info_2d unpacks the padded W
+// as it is).  The stores are the SE2_XY ones.  A handle whose graph has no such edge launches k_linearize<..., 3, ...> as ever.
+template <typename TO, typename T, int RK = ROBUST_NONE, bool PR = false>
+__global__ void __launch_bounds__(LIN_THREADS) k_linearize_br(LinArgs<TO, T> a) {
+  constexpr bool LM = false;
+  constexpr bool BR = true;
+  constexpr int D = 3;
 #include "linearize_pull.inc"
 }
 
@@ -1010,6 +1057,27 @@ template <typename TC, bool LM = false> __global__ void __launch_bounds__(256) k
     edge_linearize_3d<TC>(0, ti, qi, tj, qj, tz, qz, e, J);
     s = edge_chi2_3d<TC>(W, e);
   }
+  TC wt = 1;
+  if (!a.mask || a.mask[k]) {
+    if (a.kind == ROBUST_HUBER) wt = robust_weight<ROBUST_HUBER, TC>(s, a.delta, a.delta2);
+    else if (a.kind == ROBUST_CAUCHY) wt = robust_weight<ROBUST_CAUCHY, TC>(s, a.delta, a.delta2);
+  }
+  a.s_out[k] = (double)s;
+  if (a.w_out) a.w_out[k] = (double)wt;
+}
+
+// k_edge_errors of a 2-D graph with bearing-only / range-only edges (a landmark edge whose measurement holds its kind in lane 3):
+// a kernel of its own, so that k_edge_errors<TC, LM> keeps its name and its code.  The error code of k_linearize_br, in TC.
+template <typename TC> __global__ void __launch_bounds__(256) k_edge_errors_br(EdgeErrArgs<TC> a) {
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  if (k >= a.n_edges) return;
+  const EdgeRec<TC> rec = a.e_rec[k];
+  TC W[3][3], e[3], A[3][3], B[3][3];
+  info_2d<TC>(rec, W);
+  const int lmk = a.node_dim[rec.to] == 2 ? 1 : 0;
+  if (lmk && rec.meas.w != (TC)0) edge_linearize_2d_br<TC>(a.pose[rec.from], a.pose[rec.to], rec.meas, e, A, B);
+  else edge_linearize_2d<TC>(lmk, a.pose[rec.from], a.pose[rec.to], rec.meas, e, A, B);
+  const TC s = edge_chi2_2d<TC>(W, e);
   TC wt = 1;
   if (!a.mask || a.mask[k]) {
     if (a.kind == ROBUST_HUBER) wt = robust_weight<ROBUST_HUBER, TC>(s, a.delta, a.delta2);

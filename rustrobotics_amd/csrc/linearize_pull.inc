@@ -1,6 +1,7 @@
 // linearize_pull.inc -- the body of k_linearize and of k_linearize_lm (kernels.hip.h includes it inside each of the two kernels,
 // behind `constexpr bool LM`; TO, T, RK, D, PR and the argument `a` are the kernel's).  Every LM path is behind `if constexpr (LM)`
 // and every such statement keeps the LM = false text in its else branch, so k_linearize compiles what it always did.
+// k_linearize_br includes it too, behind `constexpr bool BR` (D = 3: a 2-D graph with bearing-only / range-only edges), by the same rule.
   using V4 = typename VecT<T>::V4;
   constexpr int NV = D / 3;             // V4s per node and per measurement
   constexpr int NT = D * (D + 1) / 2;   // lower triangle of the diagonal block, row-major: (0,0),(1,0),(1,1),...
@@ -48,6 +49,10 @@
         const V4 other = a.pose[inc.y];
         info_2d<T>(rec, W);
         T A[3][3];
+        if constexpr (BR) {   // a bearing or range edge: a landmark edge whose measurement holds its kind in lane 3 (SE2_XY: 0)
+          if (((ent >> 1) & 1) && rec.meas.w != (T)0) edge_linearize_2d_br<T>(role ? other : self[0], role ? self[0] : other, rec.meas, e, A, B2);
+          else edge_linearize_2d<T>((ent >> 1) & 1, role ? other : self[0], role ? self[0] : other, rec.meas, e, A, B2);
+        } else
         edge_linearize_2d<T>((ent >> 1) & 1, role ? other : self[0], role ? self[0] : other, rec.meas, e, A, B2);
 #pragma unroll
         for (int r = 0; r < 3; r++)

@@ -398,6 +398,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   DevBuf<S> e_info3_;   // SE(3): 21 information entries per edge
   bool is3d_ = false;
   bool has_lm_ = false;   // a 3-D graph with XYZ landmarks: the LM kernels (k_linearize_lm, k_update_lm) run
+  bool has_br_ = false;   // a 2-D graph with bearing-only / range-only edges: the BR kernels (k_linearize_br, k_edge_errors_br) run
   // sharding over ranks
   int rank_ = 0, world_ = 1;
   bool sharded_ = false;            // driven by rr_pgo_stage (world_size > 1, or opt.sharded with one rank)
@@ -643,6 +644,11 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     has_lm_ = g.has_xyz;
     if (has_lm_ && sharded_)
       throw ApiError(RR_PGO_EUNSUPPORTED, "sharded handle on a graph with XYZ landmarks (the ranks' exchange of SE(3) fronts is not taught the 3-scalar nodes)");
+    has_br_ = g.has_br;
+    if (has_br_ && sharded_)
+      throw ApiError(RR_PGO_EUNSUPPORTED, "sharded handle on a graph with bearing-only or range-only edges (the ranks' linearisation is not taught them)");
+    if (has_br_ && getenv("RR_PGO_EDGE_LINEARIZE") != nullptr)
+      throw ApiError(RR_PGO_EUNSUPPORTED, "RR_PGO_EDGE_LINEARIZE on a graph with bearing-only or range-only edges (the edge-parallel linearisation forms are not taught them)");
     std::vector<uint8_t> ndim(N);
     for (int i = 0; i < N; i++) ndim[i] = (uint8_t)node_dim(g.node_kind[i]);
     node_dim_.upload(ndim);
@@ -668,6 +674,13 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
             pack_v4(EDGE_SE2, &g.edge_meas[g.edge_meas_off[k]], &r.meas);
             r.info_a = V4{(S)w[0], (S)w[1], (S)w[2], (S)w[3]};
             r.info_b = V2{(S)w[4], (S)w[5]};
+          } else if (has_br_ && edge_is_br(g.edge_kind[k])) {
+            // one scalar: the measurement with its kind in lane 3 (pack_meas), omega as W[0][0] of the zero-padded information
+            double pm[8];
+            pack_meas(g.edge_kind[k], &g.edge_meas[g.edge_meas_off[k]], pm);
+            r.meas = V4{(S)pm[0], (S)pm[1], (S)pm[2], (S)pm[3]};
+            r.info_a = V4{(S)w[0], (S)0, (S)0, (S)0};
+            r.info_b = V2{(S)0, (S)0};
           } else {
             pack_v4(EDGE_SE2_XY, &g.edge_meas[g.edge_meas_off[k]], &r.meas);
             r.info_a = V4{(S)w[0], (S)w[1], (S)0, (S)w[2]};
@@ -704,7 +717,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
       const int pf = world_ > 1 ? sym.node_part[g.edge_from[k]] : 0, pt = world_ > 1 ? sym.node_part[g.edge_to[k]] : 0;
       const int owns = (pf >= 0 ? pf : pt >= 0 ? pt : 0) == rank_ ? 1 : 0;
       const int offd = role == 0 && (owns || (pf < 0 && pt < 0)) ? 1 : 0;
-      inc[q] = int2{(k << 4) | (offd << 3) | (owns << 2) | ((g.edge_kind[k] == EDGE_SE2_XY || g.edge_kind[k] == EDGE_SE3_XYZ ? 1 : 0) << 1) | role,
+      inc[q] = int2{(k << 4) | (offd << 3) | (owns << 2) | ((g.edge_kind[k] == EDGE_SE2_XY || g.edge_kind[k] == EDGE_SE3_XYZ || edge_is_br(g.edge_kind[k]) ? 1 : 0) << 1) | role,
                     role ? g.edge_from[k] : g.edge_to[k]};
     }
     inc_ptr_.upload(sym.inc_ptr);
@@ -1905,6 +1918,11 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
       else hipLaunchKernelGGL((k_linearize_lm<T, S, RK, false>), dim3(n_lin_blocks_), dim3(LIN_THREADS), 0, stream_, la);
       return;
     }
+    if (has_br_) {   // a 2-D graph with bearing-only / range-only edges: the BR instantiations (every other 2-D handle launches the kernels it always did)
+      if (priors_.n() > 0) hipLaunchKernelGGL((k_linearize_br<T, S, RK, true>), dim3(n_lin_blocks_), dim3(LIN_THREADS), 0, stream_, la);
+      else hipLaunchKernelGGL((k_linearize_br<T, S, RK, false>), dim3(n_lin_blocks_), dim3(LIN_THREADS), 0, stream_, la);
+      return;
+    }
     if (priors_.n() > 0) {   // (a handle without priors launches the kernels it always did)
       if (is3d_) hipLaunchKernelGGL((k_linearize<T, S, RK, 6, true>), dim3(n_lin_blocks_), dim3(LIN_THREADS), 0, stream_, la);
       else hipLaunchKernelGGL((k_linearize<T, S, RK, 3, true>), dim3(n_lin_blocks_), dim3(LIN_THREADS), 0, stream_, la);
@@ -2740,6 +2758,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     a.s_out = out.p;
     a.w_out = out.p + E;
     if (has_lm_) hipLaunchKernelGGL((k_edge_errors<S, true>), dim3((E + 255) / 256), dim3(256), 0, stream_, a);
+    else if (has_br_) hipLaunchKernelGGL((k_edge_errors_br<S>), dim3((E + 255) / 256), dim3(256), 0, stream_, a);
     else hipLaunchKernelGGL((k_edge_errors<S>), dim3((E + 255) / 256), dim3(256), 0, stream_, a);
     check_launch("k_edge_errors");
     std::vector<double> host(2 * (size_t)E);
@@ -3582,6 +3601,12 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     }
   }
 
+  // a record of kind RR_PGO_EDGE_SE2_BEARING / _RANGE among the call's records (the whole call decides, not a cut of its plan)
+  static bool cand_has_br(const std::vector<GateCand> &cand) {
+    for (const GateCand &c : cand)
+      if (edge_is_br(c.kind)) return true;
+    return false;
+  }
   // ---- Mahalanobis gate of candidate edges (include/rr_pgo.h, rr_pgo_gate_edges; treesolve.hip.h, k_gate_pairs): the plan
   // of the candidates' nodes is the covariance plan of the pairs (from, to)
   void gate_edges(int n, const int32_t *from, const int32_t *to, const int64_t *soff, std::vector<GateCand> &cand, double *d2,
@@ -3590,6 +3615,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     require_f64_unsharded_lds_factor(who, !query_big_);
     if constexpr (f64_) {
       covariances_prepare(who);
+      const bool br = has_br_ || cand_has_br(cand);   // the BR kernel: the graph or the call holds a bearing / range edge
       auto n_innov = [&](int c0, int c1) { return innov ? (size_t)(soff[c1] - soff[c0]) : 0; };
       tree_query(who, "candidate", n, from, to, soff, query_ms_[Q_GATE], true, [&](int c0, int c1, const TsPlan &pl) {
         const size_t nc = (size_t)(c1 - c0);
@@ -3614,6 +3640,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
         a.sout = innov ? ts_out_.p + 2 * nc : nullptr;
         a.S = sym_.S;
         if (has_lm_) hipLaunchKernelGGL((k_gate_pairs<T, 6, true>), dim3((unsigned)nc), dim3(COV_THREADS), 0, stream_, a);
+        else if (br) hipLaunchKernelGGL((k_gate_pairs<T, 3, true>), dim3((unsigned)nc), dim3(COV_THREADS), 0, stream_, a);
         else if (is3d_) hipLaunchKernelGGL((k_gate_pairs<T, 6>), dim3((unsigned)nc), dim3(COV_THREADS), 0, stream_, a);
         else hipLaunchKernelGGL((k_gate_pairs<T, 3>), dim3((unsigned)nc), dim3(COV_THREADS), 0, stream_, a);
         check_launch("k_gate_pairs");
@@ -3631,6 +3658,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     require_f64_unsharded_lds_factor(who, !query_big_);
     if constexpr (f64_) {
       covariances_prepare(who);
+      const bool br = has_br_ || cand_has_br(cand);   // the BR kernel: the graph or the call holds a bearing / range edge
       auto n_resid = [&](int c0, int c1) { return resid ? (size_t)(soff[c1] - soff[c0]) : 0; };
       tree_query(who, "edge", n, from, to, soff, query_ms_[Q_CHECK], true, [&](int c0, int c1, const TsPlan &pl) {
         const size_t nc = (size_t)(c1 - c0);
@@ -3659,6 +3687,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
         a.S = sym_.S;
         a.rkind = robust_kind_;
         if (has_lm_) hipLaunchKernelGGL((k_check_edges<T, 6, true>), dim3((unsigned)nc), dim3(COV_THREADS), 0, stream_, a);
+        else if (br) hipLaunchKernelGGL((k_check_edges<T, 3, true>), dim3((unsigned)nc), dim3(COV_THREADS), 0, stream_, a);
         else if (is3d_) hipLaunchKernelGGL((k_check_edges<T, 6>), dim3((unsigned)nc), dim3(COV_THREADS), 0, stream_, a);
         else hipLaunchKernelGGL((k_check_edges<T, 3>), dim3((unsigned)nc), dim3(COV_THREADS), 0, stream_, a);
         check_launch("k_check_edges");
@@ -3676,6 +3705,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     require_f64_unsharded_lds_factor(who, !query_big_);
     if constexpr (f64_) {
       covariances_prepare(who);
+      const bool br = has_br_ || cand_has_br(cand);   // the BR kernel: the graph or the call holds a bearing / range edge
       const Symbolic &sym = sym_;
       const int n = n_sets > 0 ? set_ptr[n_sets] : 0;
       const std::vector<int64_t> no_off((size_t)n + 1, 0);   // (a pair's record carries no output offset here)
@@ -3752,6 +3782,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
         a.prefix = ts_out_.p + ns;
         a.sout = innov ? ts_out_.p + ns + nc : nullptr;
         if (has_lm_) hipLaunchKernelGGL((k_gate_joint<T, 6, true>), dim3((unsigned)ns), dim3(COV_THREADS), 0, stream_, a);
+        else if (br) hipLaunchKernelGGL((k_gate_joint<T, 3, true>), dim3((unsigned)ns), dim3(COV_THREADS), 0, stream_, a);
         else if (is3d_) hipLaunchKernelGGL((k_gate_joint<T, 6>), dim3((unsigned)ns), dim3(COV_THREADS), 0, stream_, a);
         else hipLaunchKernelGGL((k_gate_joint<T, 3>), dim3((unsigned)ns), dim3(COV_THREADS), 0, stream_, a);
         check_launch("k_gate_joint");
@@ -4241,6 +4272,7 @@ static int plan_guess_steps(const HostGraph &g, int n_old, int e_old, std::vecto
     for (int k = e_old; k < E; k++) {
       const int f = g.edge_from[k], t = g.edge_to[k], ek = g.edge_kind[k];
       int src, dst, op;
+      if (edge_is_br(ek)) continue;   // one scalar does not place a landmark: a bearing or range edge yields no step
       if (ready[f] && !ready[t] && t >= n_old) {
         src = f; dst = t;
         op = ek == EDGE_SE2 ? GUESS_SE2 : ek == EDGE_SE2_XY ? GUESS_XY : ek == EDGE_SE3_XYZ ? GUESS_XYZ : GUESS_SE3;
@@ -4332,13 +4364,11 @@ static void extend_handle(rr_pgo *h, int32_t n_new_nodes, const int32_t *node_ki
   for (int k = 0; k < n_new_edges; k++) {
     const std::string who = "rr_pgo_extend: new edge " + std::to_string(k) + " (edge " + std::to_string(e_old + k) + ")";
     const int ek = edge_kind[k], a = edge_from[k], b = edge_to[k];
-    if (ek < EDGE_SE2 || ek > EDGE_SE3_XYZ) throw ApiError(RR_PGO_EINVAL, who + ": bad edge kind " + std::to_string(ek));
+    if (!edge_kind_known(ek)) throw ApiError(RR_PGO_EINVAL, who + ": bad edge kind " + std::to_string(ek));
     if (a < 0 || a >= n_total || b < 0 || b >= n_total) throw ApiError(RR_PGO_EINVAL, who + " references an unknown vertex");
     if (a == b) throw ApiError(RR_PGO_EINVAL, who + " is a self loop");
     const int ka = g.node_kind[a], kb = g.node_kind[b];
-    const bool ok = (ek == EDGE_SE2 && ka == NODE_SE2 && kb == NODE_SE2) || (ek == EDGE_SE2_XY && ka == NODE_SE2 && kb == NODE_XY) ||
-                    (ek == EDGE_SE3 && ka == NODE_SE3 && kb == NODE_SE3) || (ek == EDGE_SE3_XYZ && ka == NODE_SE3 && kb == NODE_XYZ);
-    if (!ok) throw ApiError(RR_PGO_EINVAL, who + ": endpoint kinds do not match the edge kind");
+    if (!edge_endpoints_ok(ek, ka, kb)) throw ApiError(RR_PGO_EINVAL, who + ": endpoint kinds do not match the edge kind");
     g.edge_kind.push_back(ek);
     g.edge_from.push_back(a);
     g.edge_to.push_back(b);
@@ -4538,7 +4568,7 @@ int rr_pgo_create(const rr_pgo_graph_desc *d, const rr_pgo_options *opt, rr_pgo 
     g.edge_to.assign(d->edge_to, d->edge_to + d->n_edges);
     size_t nm = 0, ni = 0;
     for (int k = 0; k < d->n_edges; k++) {
-      if (g.edge_kind[k] < EDGE_SE2 || g.edge_kind[k] > EDGE_SE3_XYZ) throw ApiError(RR_PGO_EINVAL, "bad edge kind");
+      if (!edge_kind_known(g.edge_kind[k])) throw ApiError(RR_PGO_EINVAL, "bad edge kind");
       nm += edge_meas_len(g.edge_kind[k]);
       ni += edge_info_len(g.edge_kind[k]);
     }
@@ -4768,7 +4798,7 @@ static int gate_candidates(const char *api, const rr_pgo *h, int32_t n_cand, con
     const std::string who = std::string(api) + ": " + what + " " + std::to_string(c) + ": ";
     auto bad = [&](const std::string &what) { g_last_error = who + what; return RR_PGO_EINVAL; };
     const int kind = edge_kind[c], a = edge_from[c], b = edge_to[c];
-    if (kind != EDGE_SE2 && kind != EDGE_SE2_XY && kind != EDGE_SE3 && kind != EDGE_SE3_XYZ) return bad("unknown edge kind " + std::to_string(kind));
+    if (!edge_kind_known(kind)) return bad("unknown edge kind " + std::to_string(kind));
     if (a < 0 || a >= N || b < 0 || b >= N) return bad("node index out of range");
     if (a == b) return bad("from == to");
     const int ka = g.node_kind[a], kb = g.node_kind[b];
@@ -4776,6 +4806,8 @@ static int gate_candidates(const char *api, const rr_pgo *h, int32_t n_cand, con
     if (kind == EDGE_SE2_XY && (ka != NODE_SE2 || kb != NODE_XY)) return bad("an SE2_XY edge goes from an SE2 pose to an XY landmark");
     if (kind == EDGE_SE3 && (ka != NODE_SE3 || kb != NODE_SE3)) return bad("an SE3 edge needs two SE3 poses");
     if (kind == EDGE_SE3_XYZ && (ka != NODE_SE3 || kb != NODE_XYZ)) return bad("an SE3_XYZ edge goes from an SE3 pose to an XYZ landmark");
+    if (kind == EDGE_SE2_BEARING && (ka != NODE_SE2 || kb != NODE_XY)) return bad("an SE2_BEARING edge goes from an SE2 pose to an XY landmark");
+    if (kind == EDGE_SE2_RANGE && (ka != NODE_SE2 || kb != NODE_XY)) return bad("an SE2_RANGE edge goes from an SE2 pose to an XY landmark");
     const int nm = edge_meas_len(kind), ni = edge_info_len(kind), de = edge_dim(kind);
     const double *m = edge_meas + mo, *w = edge_info + io;
     mo += nm;
@@ -4788,7 +4820,7 @@ static int gate_candidates(const char *api, const rr_pgo *h, int32_t n_cand, con
     gc.na = a;
     gc.nb = b;
     if (kind == EDGE_SE3 && !(quat_norm(m + 3) > 0.0)) return bad("zero quaternion in the measurement");
-    pack_state(kind, m, gc.meas);
+    pack_meas(kind, m, gc.meas);
     // Omega from its packed upper triangle; Omega^-1 = L^-T L^-1 from its Cholesky factor
     double L[36] = {0}, Li[36] = {0};
     for (int i = 0, t = 0; i < de; i++)

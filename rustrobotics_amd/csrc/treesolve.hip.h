@@ -235,6 +235,7 @@ struct GateCand {
   int32_t fa, fb;                 // the fronts of a and of b
   int32_t na, nb, kind, pad;      // the two nodes; RR_PGO_EDGE_*
   double meas[8];                 // 2-D: x, y, cos, sin | SE(3): t (3), -, q (4, normalised) | SE3_XYZ: x, y, z, then zeros
+                                  // SE2_BEARING: cos z, sin z, 0, 4 | SE2_RANGE: z, 0, 0, 6 (pack_meas, host_graph.h)
   double info[36], cov[36];       // Omega and Omega^-1, row stride D (3 or 6), zero padded
 };
 static_assert(sizeof(GateCand) == 712, "GateCand is one 712-byte record");
@@ -251,9 +252,18 @@ template <typename T> struct GateArgs {
 
 // error dimension of a candidate of RR_PGO_EDGE_* `kind` in a graph of pose dimension D; a landmark edge's `to` node has as many scalars
 // LM: the kernel instantiation of a 3-D graph with XYZ landmarks (kind 3 occurs); false is the code of every other handle
+// LM with D == 3 ("BR" below): the kernel instantiation of a 2-D call with bearing-only / range-only records (kinds 4 and 6 occur:
+// one error scalar, while the `to` node, an XY landmark, has two -- gate_to_dim).  The flag's second meaning keeps the names and
+// the code of the instantiations that exist: <T, 3, false> stays what every other 2-D call launches.
 template <int D, bool LM> __device__ __forceinline__ int gate_edge_dim(int kind) {
-  if constexpr (LM) return kind == 3 ? 3 : D;
+  if constexpr (LM && D == 3) return kind == 4 || kind == 6 ? 1 : kind == 1 ? 2 : D;
+  else if constexpr (LM) return kind == 3 ? 3 : D;
   else return kind == 1 ? 2 : D;
+}
+// scalars of the candidate's `to` node: d_e everywhere but for a bearing or range record
+template <int D, bool LM> __device__ __forceinline__ int gate_to_dim(int kind) {
+  if constexpr (LM && D == 3) return kind == 0 ? D : 2;
+  else return gate_edge_dim<D, LM>(kind);
 }
 
 // A candidate's error e and Jacobians A, B (row-major D x D) at the current state, by the linearisation's own code.
@@ -265,6 +275,10 @@ __device__ __forceinline__ void gate_linearize(const GateCand *q, const typename
     if (role == 0) {
       const V4 z = {(T)q->meas[0], (T)q->meas[1], (T)q->meas[2], (T)q->meas[3]};
       T e[3], A[3][3], B[3][3];
+      if constexpr (LM) {   // (D == 3: the BR instantiation)
+        if (q->kind == 4 || q->kind == 6) edge_linearize_2d_br<T>(pose[q->na], pose[q->nb], z, e, A, B);   // zero padded, row 0 alone
+        else edge_linearize_2d<T>(q->kind, pose[q->na], pose[q->nb], z, e, A, B);
+      } else
       edge_linearize_2d<T>(q->kind, pose[q->na], pose[q->nb], z, e, A, B);
 #pragma unroll
       for (int i = 0; i < 3; i++) {
@@ -344,7 +358,7 @@ __global__ void __launch_bounds__(COV_THREADS) k_gate_pairs(GateArgs<T> a) {
   const GateCand *q = a.cand + blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63, slice = wave_index();
   const int kind = q->kind;
-  const int de = gate_edge_dim<D, LM>(kind), db = de, ntri = de * (de + 1) / 2;
+  const int de = gate_edge_dim<D, LM>(kind), db = gate_to_dim<D, LM>(kind), ntri = de * (de + 1) / 2;
   if (lane == 0 && slice < 2) gate_linearize<T, D, LM>(q, a.pose, slice, se, sA, sB);
   __syncthreads();
   // ---- entry t = (i, j), j <= i, of the lower triangle; lanes past the triangle repeat its last entry
@@ -444,7 +458,7 @@ __global__ void __launch_bounds__(COV_THREADS) k_check_edges(CheckArgs<T> a) {
   const GateCand *q = a.cand + blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63, slice = wave_index();
   const int kind = q->kind;
-  const int de = gate_edge_dim<D, LM>(kind), db = de, ntri = de * (de + 1) / 2;
+  const int de = gate_edge_dim<D, LM>(kind), db = gate_to_dim<D, LM>(kind), ntri = de * (de + 1) / 2;
   if (lane == 0 && slice < 2) gate_linearize<T, D, LM>(q, a.pose, slice, se, sA, sB);
   __syncthreads();
   if (tid == 0) {
@@ -610,7 +624,7 @@ __global__ void __launch_bounds__(COV_THREADS) k_gate_joint(JointArgs<T> a) {
   T Ai[D], Bi[D];
   int cola[D], colb[D];
   {
-    const int i = live ? s_i[lane] : 0, db = gate_edge_dim<D, LM>(cq[c].kind);
+    const int i = live ? s_i[lane] : 0, db = gate_to_dim<D, LM>(cq[c].kind);
 #pragma unroll
     for (int k = 0; k < D; k++) {
       Ai[k] = live ? sA[c * D * D + i * D + k] : (T)0;

@@ -34,23 +34,25 @@ class PoseGraphError(RuntimeError):
 
 
 # 0.95 quantiles of the chi-square distribution with 2, 3 and 6 degrees of freedom (the default gate), and the error
-# dimension, measurement length and packed information length of an edge by kind (RR_PGO_EDGE_SE2, _SE2_XY, _SE3, _SE3_XYZ)
-CHI2_95_2, CHI2_95_3, CHI2_95_6 = 5.991, 7.815, 12.592
-GATE_DEFAULT_THRESHOLD = {0: CHI2_95_3, 1: CHI2_95_2, 2: CHI2_95_6, 3: CHI2_95_3}
+# dimension, measurement length and packed information length of an edge by kind (RR_PGO_EDGE_SE2, _SE2_XY, _SE3, _SE3_XYZ,
+# _SE2_BEARING = 4, _SE2_RANGE = 6; 5 and 7 are reserved, unknown kinds: the 0 at index 5 is a place holder nothing reads)
+CHI2_95_1, CHI2_95_2, CHI2_95_3, CHI2_95_6 = 3.841, 5.991, 7.815, 12.592
+GATE_DEFAULT_THRESHOLD = {0: CHI2_95_3, 1: CHI2_95_2, 2: CHI2_95_6, 3: CHI2_95_3, 4: CHI2_95_1, 6: CHI2_95_1}
 # ... and with 1 .. 48 degrees of freedom (CHI2_95[d]; the default of PoseGraph.gate_joint_accept: d = D_s)
 CHI2_95 = (None,
            3.841, 5.991, 7.815, 9.488, 11.070, 12.592, 14.067, 15.507, 16.919, 18.307, 19.675, 21.026,
            22.362, 23.685, 24.996, 26.296, 27.587, 28.869, 30.144, 31.410, 32.671, 33.924, 35.172, 36.415,
            37.652, 38.885, 40.113, 41.337, 42.557, 43.773, 44.985, 46.194, 47.400, 48.602, 49.802, 50.998,
            52.192, 53.384, 54.572, 55.758, 56.942, 58.124, 59.304, 60.481, 61.656, 62.830, 64.001, 65.171)
-GATE_EDGE_DIM = (3, 2, 6, 3)
-GATE_MEAS_LEN = (3, 2, 7, 3)
-GATE_INFO_LEN = (6, 3, 21, 6)
+GATE_EDGE_DIM = (3, 2, 6, 3, 1, 0, 1)
+GATE_MEAS_LEN = (3, 2, 7, 3, 1, 0, 1)
+GATE_INFO_LEN = (6, 3, 21, 6, 1, 0, 1)
 # the same by node kind (RR_PGO_NODE_SE2, _XY, _SE3, _XYZ): scalars of the step and of the state; a node's state has the
 # length of the measurement of the edge of its kind
 NODE_DIM = (3, 2, 6, 3)
-NODE_STATE_LEN = GATE_MEAS_LEN
-KNOWN_KINDS = (0, 1, 2, 3)
+NODE_STATE_LEN = (3, 2, 7, 3)
+KNOWN_KINDS = (0, 1, 2, 3, 4, 6)      # edge kinds
+KNOWN_NODE_KINDS = (0, 1, 2, 3)
 
 
 def gate_thresholds(edge_kind, threshold=None):
@@ -523,7 +525,8 @@ class PoseGraph:
     def gate_edges(self, edge_kind, edge_from, edge_to, edge_meas, edge_info, return_innovation=False):
         """rr_pgo_gate_edges: (d2, chi2) of candidate edges that are not part of the graph, in rr_pgo_graph_desc packing --
         d2 = e^T S^-1 e with S = Omega^-1 + J Sigma J^T at the current state, chi2 = e^T Omega e.  With return_innovation
-        also the list of the d_e x d_e matrices S."""
+        also the list of the d_e x d_e matrices S (1 x 1 for an SE2_BEARING or SE2_RANGE candidate, which packs one
+        measurement value and one information value)."""
         L = _lib.load()
         kind = np.ascontiguousarray(edge_kind, np.int32)
         a = np.ascontiguousarray(edge_from, np.int32)
@@ -551,7 +554,8 @@ class PoseGraph:
 
     def gate(self, edge_kind, edge_from, edge_to, edge_meas, edge_info, threshold=None):
         """Boolean mask d2 <= threshold of the candidates (True: accept).  threshold: a scalar, a mapping from edge kind
-        (0 SE2, 1 SE2_XY, 2 SE3, 3 SE3_XYZ) to a scalar, or None: the 0.95 chi-square quantile of the edge's dimension."""
+        (0 SE2, 1 SE2_XY, 2 SE3, 3 SE3_XYZ, 4 SE2_BEARING, 6 SE2_RANGE) to a scalar, or None: the 0.95 chi-square quantile
+        of the edge's dimension (3.841 for the two one-scalar kinds)."""
         d2, _ = self.gate_edges(edge_kind, edge_from, edge_to, edge_meas, edge_info)
         return d2 <= gate_thresholds(edge_kind, threshold)
 
@@ -628,7 +632,7 @@ class PoseGraph:
         st = ids = None
         if node_state is not None:
             st = np.ascontiguousarray(node_state, np.float64).ravel()
-            if np.all(np.isin(nk, KNOWN_KINDS)) and len(st) != int(np.sum(np.take(GATE_MEAS_LEN, nk))):
+            if np.all(np.isin(nk, KNOWN_NODE_KINDS)) and len(st) != int(np.sum(np.take(NODE_STATE_LEN, nk))):
                 raise ValueError("node_state does not have the length the node kinds ask for")
         if node_id is not None:
             ids = np.ascontiguousarray(node_id, np.uint32).ravel()
