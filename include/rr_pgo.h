@@ -250,6 +250,71 @@ int rr_pgo_set_robust_kernel(rr_pgo *h, int32_t kind, double delta, const int32_
  * Edges only: the priors of rr_pgo_set_priors have rr_pgo_prior_errors. */
 int rr_pgo_edge_errors(rr_pgo *h, double *chi2_out, double *weight_out);
 
+/* ---- truncated least squares and graduated non-convexity (build-defined) ----
+ * A fourth kernel, with a continuation parameter mu > 0 beside delta (written c below).  With lo = mu / (mu + 1) c^2 and
+ * hi = (mu + 1) / mu c^2:
+ *   s <= lo  (and s < 0)   w = 1                               rho = s
+ *   lo < s < hi            w = c sqrt(mu (mu + 1) / s) - mu    rho = 2 c sqrt(s mu (mu + 1)) - mu (c^2 + s)
+ *   s >= hi                w = 0                               rho = c^2
+ * w = rho' everywhere, w is continuous, and outside the band the weights are EXACTLY 0 and 1.  As mu grows the band closes
+ * on c^2: the surrogate goes from (nearly) least squares to truncated least squares, rho = min(s, c^2) (Yang, Antonante,
+ * Tzoumas, Carlone: "Graduated non-convexity for robust spatial perception", RA-L 2020).
+ * Everything said above for the robust kernels holds: IRLS, the mask, flagged priors, chi2 = sum rho, the arithmetic types.
+ * An edge of weight 0 adds nothing to H and b; the sparsity pattern and the analysis stay as they are.  A node whose every
+ * edge has weight 0 leaves H singular there: the iteration returns RR_PGO_ENOTSPD with the state as before it.  That is the
+ * caller's precondition: mask the loop closures and leave the odometry chain at weight 1 (edge_mask[k] = |from - to| > 1).
+ * rr_pgo_check_edges on an edge of weight exactly 0: d2, redundancy and R are NaN (Omega_w^-1 does not exist), chi2_out
+ * stays e^T Omega e, no other edge's output changes; query such an edge with rr_pgo_gate_edges as the candidate it now is.
+ * RR_PGO_ROBUST_TLS is what rr_pgo_get_robust reports; rr_pgo_set_robust_kernel does NOT accept it (EINVAL, as ever), and
+ * with kinds 0..2 replaces it (the constant is defined below, before the driver's structs). */
+/* As rr_pgo_set_robust_kernel (mask copied, stream synchronised, captured graphs dropped); accepted on sharded handles.
+ * EINVAL, before anything changes: delta or mu not finite or <= 0. */
+int rr_pgo_set_robust_tls(rr_pgo *h, double delta, double mu, const int32_t *edge_mask);
+/* mu alone: no mask upload, no allocation; every later launch reads the new value (captured iterations are captured anew).
+ * EINVAL unless the handle's kernel is RR_PGO_ROBUST_TLS, or mu not finite or <= 0. */
+int rr_pgo_set_robust_mu(rr_pgo *h, double mu);
+/* The handle's kernel; any pointer may be NULL.  mu = 0 for the kinds other than TLS, delta = 1 for NONE.  rr_pgo_extend and
+ * rr_pgo_remove_edges carry kind, delta, mu and the mask (a new edge is robustified, the mask of removed edges goes). */
+int rr_pgo_get_robust(const rr_pgo *h, int32_t *kind, double *delta, double *mu);
+
+#define RR_PGO_ROBUST_TLS 3   /* reported by rr_pgo_get_robust; NOT accepted by rr_pgo_set_robust_kernel */
+typedef struct rr_pgo_gnc_options {
+  double delta;              /* c; c^2 is the caller's chi-square quantile of the edge dimension */
+  double mu_factor;          /* > 1; default 1.4 */
+  int32_t max_stages;        /* >= 1; default 100 */
+  int32_t inner_iterations;  /* iterations of the handle's solver per stage, >= 1; default 1 */
+  int32_t final_iterations;  /* closing iterations at the last mu under the stop rule, >= 0; default 20 */
+  int32_t reserved[11];      /* zero */
+} rr_pgo_gnc_options;
+/* the defaults above; delta = 1 */
+void rr_pgo_default_gnc_options(rr_pgo_gnc_options *opt);
+typedef struct rr_pgo_gnc_result {
+  int32_t n_stages, converged;          /* converged: 1 = a stage ended with every masked weight exactly 0 or 1 */
+  int32_t n_rejected, n_fractional;     /* masked edges with w == 0 / 0 < w < 1 at the end */
+  int32_t final_iterations_run;
+  double mu0, mu_last, r2_max, cost_last;
+} rr_pgo_gnc_result;
+/* Optimise a graph that holds outliers, from the current state:
+ *   1. scan: r2_max = the largest s over the masked edges, clamped at 0
+ *   2. mu0 = c^2 / (2 r2_max - c^2) when 2 r2_max > c^2 (every masked weight starts inside the band or at 1), else mu0 = 1
+ *      (every masked weight is exactly 1: the first stage is a plain step)
+ *   3. stage t: TLS (c, mu_t, mask); inner_iterations iterations exactly as rr_pgo_optimize runs them (stop rule and
+ *      Levenberg-Marquardt's decisions included; each stage is one such call); scan; stop when no masked weight is fractional
+ *      or t + 1 == max_stages, else mu_{t+1} = mu_factor mu_t
+ *   4. final_iterations iterations under the stop rule at the last mu, and a last scan
+ *   5. the handle keeps the TLS kernel at mu_last: rr_pgo_edge_errors' weights name the rejected edges (w == 0),
+ *      rr_pgo_remove_edges takes them out, every query sees the final weights.
+ * edge_mask as for rr_pgo_set_robust_tls (NULL: every edge -- see the precondition above).  stage_mu / stage_cost: [max_stages],
+ * may be NULL: mu_t and sum rho (over all edges, at mu_t) after stage t.  cost_last: sum rho after step 4.  A scan is one pass
+ * on the device and one synchronisation; nothing per edge comes back to the host inside the loop.
+ * ENOTSPD propagates as from rr_pgo_optimize, the state that of the last completed iteration, the kernel at that stage's mu
+ * (res holds n_stages completed, mu0 and mu_last).  EUNSUPPORTED: sharded handles.  EINVAL, before anything changes: NULL opt
+ * or res, options out of their ranges, reserved not zero. */
+int rr_pgo_optimize_gnc(rr_pgo *h, const rr_pgo_gnc_options *opt, const int32_t *edge_mask, rr_pgo_gnc_result *res,
+                        double *stage_mu, double *stage_cost);
+/* ms[3]: HIP-event time of the last rr_pgo_optimize_gnc call's scans, stages and closing iterations */
+int rr_pgo_gnc_times(const rr_pgo *h, double *ms);
+
 /* ---- absolute priors on poses and landmarks (build-defined; the reference has only the anchor term) ----
  * A prior on node i is the edge of the node's own kind from a FIXED identity pose to node i: an SE2 pose takes an
  * RR_PGO_EDGE_SE2 term, an XY landmark an RR_PGO_EDGE_SE2_XY term, an SE3 pose an RR_PGO_EDGE_SE3 term, an XYZ landmark an

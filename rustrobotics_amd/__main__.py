@@ -9,6 +9,12 @@
   --robust huber:DELTA | cauchy:DELTA  (both modes): a robust kernel on every edge (include/rr_pgo.h); the errors printed
       are then the robust cost
 
+  --gnc DELTA[:loops|all]  (example mode): instead of the plain optimisation, graduated non-convexity on truncated least squares
+      (rr_pgo_optimize_gnc): DELTA^2 is the chi-square quantile beyond which an edge is an outlier (3.3682 for 0.99 at 3 degrees
+      of freedom); `loops` (the default) robustifies the edges with |from - to| > 1 and trusts the odometry, `all` every edge
+      (a node whose every edge is rejected then ends the run: not positive definite).  Prints the stages, mu0, mu_last and
+      the indices of the rejected edges; everything printed afterwards sees the final weights
+
   --priors FILE  (both modes): absolute priors (rr_pgo_set_priors), one per line: NODE_ID (the g2o vertex id), then the
       measurement and the upper triangle of the information matrix in g2o's order for the node's kind (SE2 pose: x y theta
       and 6 values; XY landmark: x y and 3; SE3 pose: x y z qx qy qz qw and 21); `#` starts a comment.  A vertex may be
@@ -68,6 +74,38 @@ def _robust_arg(text):
     if kind not in ("huber", "cauchy") or not sep or not (d > 0 and d != float("inf")):
         raise argparse.ArgumentTypeError(f"expected huber:DELTA or cauchy:DELTA with DELTA > 0, got {text!r}")
     return kind, d
+
+
+def _gnc_arg(text):
+    delta, sep, which = text.partition(":")
+    which = which.strip().lower() if sep else "loops"
+    try:
+        d = float(delta)
+    except ValueError:
+        d = float("nan")
+    if which not in ("loops", "all") or not (d > 0 and d != float("inf")):
+        raise argparse.ArgumentTypeError(f"expected DELTA, DELTA:loops or DELTA:all with DELTA > 0, got {text!r}")
+    return d, which
+
+
+def gnc_report(g, delta, which):
+    import numpy as np
+    mask = None
+    if which == "loops":
+        _, _, _, ef, et, _, _ = g.graph_arrays()
+        mask = (np.abs(ef.astype(np.int64) - et.astype(np.int64)) > 1).astype(np.int32)
+    print(f"Loaded graph with {g.num_nodes} nodes and {g.num_edges} edges")
+    print(f"graduated non-convexity, truncated least squares: delta {delta:g}, "
+          f"{'every edge' if mask is None else f'{int(mask.sum())} loop closures'} robustified")
+    res = g.optimize_gnc(delta, mask)
+    for t, (mu, cost) in enumerate(zip(res["stage_mu"], res["stage_cost"])):
+        print(f"stage {t:3} : mu = {mu:.6g}, cost = {cost:.5f}")
+    _, w = g.edge_errors()
+    rejected = np.flatnonzero((w == 0.0) & (mask != 0 if mask is not None else True))
+    print(f"{res['n_stages']} stages ({'converged' if res['converged'] else 'NOT converged: fractional weights remain'}), "
+          f"mu0 {res['mu0']:.6g}, mu_last {res['mu_last']:.6g}, {res['final_iterations_run']} closing iterations, "
+          f"final cost {res['cost_last']:.9g}")
+    print(f"{res['n_rejected']} edges rejected, {res['n_fractional']} fractional: {' '.join(str(int(k)) for k in rejected)}")
 
 
 def write_marginals(g, path):
@@ -452,6 +490,8 @@ def main(argv=None):
     ap.add_argument("--repeats", type=int, default=20)
     ap.add_argument("--robust", type=_robust_arg, default=None, metavar="KIND:DELTA",
                     help="robust kernel on every edge: huber:DELTA or cauchy:DELTA")
+    ap.add_argument("--gnc", type=_gnc_arg, default=None, metavar="DELTA[:loops|all]",
+                    help="optimise by graduated non-convexity on truncated least squares; loops (default): edges with |from - to| > 1")
     ap.add_argument("--priors", metavar="FILE", default=None,
                     help="absolute priors, one per line: NODE_ID, measurement, upper triangle of the information")
     ap.add_argument("--free-anchor", action="store_true",
@@ -490,6 +530,8 @@ def main(argv=None):
         ap.error("--cross needs --columns ID,ID,...")
     if (a.columns or a.rows) and not a.cross:
         ap.error("--columns and --rows need --cross FILE")
+    if a.gnc and (a.bench or a.robust):
+        ap.error("--gnc is an optimisation of its own: not with --bench or --robust")
     if a.guess and not a.extend:
         ap.error("--guess needs --extend FILE")
     if a.free_anchor and not (a.priors or a.fix):
@@ -514,7 +556,10 @@ def main(argv=None):
             print(f"{g.num_priors} priors from {a.priors}" + (", anchor term dropped" if a.free_anchor else ""))
         if a.fix:
             print(f"{g.num_fixed} vertices held fixed" + (", anchor term dropped" if a.free_anchor else ""))
-        g.optimize(50 if a.iterations is None else a.iterations, True, a.plot)
+        if a.gnc:
+            gnc_report(g, *a.gnc)
+        else:
+            g.optimize(50 if a.iterations is None else a.iterations, True, a.plot)
         if a.priors:
             print_prior_share(g)
         if a.marginals:

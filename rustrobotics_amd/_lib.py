@@ -17,6 +17,7 @@ OK, EINVAL, EIO, EPARSE, ENODEVICE, ENOTSPD, ENOMEM, EUNSUPPORTED, ETIMEOUT = 0,
 ABI_VERSION = 4   # RR_PGO_ABI_VERSION this mirror was written against (load() checks the library's)
 F64, F32, MIXED = 0, 1, 2
 ROBUST_NONE, ROBUST_HUBER, ROBUST_CAUCHY = 0, 1, 2   # RR_PGO_ROBUST_* (rr_pgo_set_robust_kernel)
+ROBUST_TLS = 3   # RR_PGO_ROBUST_TLS: reported by rr_pgo_get_robust, set through rr_pgo_set_robust_tls (not a ROBUST_KERNELS entry)
 ROBUST_KERNELS = {None: ROBUST_NONE, "none": ROBUST_NONE, "huber": ROBUST_HUBER, "cauchy": ROBUST_CAUCHY}
 PRECISIONS = {"f64": F64, "f32": F32, "mixed": MIXED}
 GATE_JOINT_MAX_DIM, GATE_JOINT_MAX_CAND = 48, 16   # RR_PGO_GATE_JOINT_MAX_DIM / _MAX_CAND
@@ -42,6 +43,8 @@ EXPORTS = (
     "rr_pgo_set_fixed", "rr_pgo_num_fixed", "rr_pgo_get_fixed",
     "rr_pgo_set_query_big_fronts", "rr_pgo_get_query_big_fronts",
     "rr_pgo_set_marginals_big_fronts", "rr_pgo_get_marginals_big_fronts",
+    "rr_pgo_set_robust_tls", "rr_pgo_set_robust_mu", "rr_pgo_get_robust", "rr_pgo_default_gnc_options",
+    "rr_pgo_optimize_gnc", "rr_pgo_gnc_times",
 )
 
 
@@ -69,6 +72,17 @@ class Stats(C.Structure):
         ("bytes_update", C.c_double), ("bytes_chi2", C.c_double), ("big_update_flops", C.c_double),
         ("big_flow_flops", C.c_double), ("stored_factor_bytes", C.c_double), ("abi_version", C.c_int32), ("lds_dataflow", C.c_int32),
     ]
+
+
+class GncOptions(C.Structure):
+    _fields_ = [("delta", C.c_double), ("mu_factor", C.c_double), ("max_stages", C.c_int32), ("inner_iterations", C.c_int32),
+                ("final_iterations", C.c_int32), ("reserved", C.c_int32 * 11)]
+
+
+class GncResult(C.Structure):
+    _fields_ = [("n_stages", C.c_int32), ("converged", C.c_int32), ("n_rejected", C.c_int32), ("n_fractional", C.c_int32),
+                ("final_iterations_run", C.c_int32), ("mu0", C.c_double), ("mu_last", C.c_double), ("r2_max", C.c_double),
+                ("cost_last", C.c_double)]
 
 
 _lib = None
@@ -142,6 +156,13 @@ def load():
     L.rr_pgo_debug_withhold.argtypes = [vp, C.c_int32]
     L.rr_pgo_set_robust_kernel.argtypes = [vp, C.c_int32, C.c_double, ip]
     L.rr_pgo_edge_errors.argtypes = [vp, dp, dp]
+    L.rr_pgo_set_robust_tls.argtypes = [vp, C.c_double, C.c_double, ip]
+    L.rr_pgo_set_robust_mu.argtypes = [vp, C.c_double]
+    L.rr_pgo_get_robust.argtypes = [vp, ip, dp, dp]
+    L.rr_pgo_default_gnc_options.argtypes = [C.POINTER(GncOptions)]
+    L.rr_pgo_default_gnc_options.restype = None
+    L.rr_pgo_optimize_gnc.argtypes = [vp, C.POINTER(GncOptions), ip, C.POINTER(GncResult), dp, dp]
+    L.rr_pgo_gnc_times.argtypes = [vp, dp]
     L.rr_pgo_marginals.argtypes = [vp, C.c_int32, ip, ip, dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.rr_pgo_marginals_times.argtypes = [vp, dp]
     L.rr_pgo_covariances.argtypes = [vp, C.c_int32, ip, ip, dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]

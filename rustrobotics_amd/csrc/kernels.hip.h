@@ -201,6 +201,10 @@ template <typename T, typename TC = T> struct LinArgs {
   const uint8_t *prior_robust;           // per prior: 1 = robustified while a kernel is set
   // fixed nodes (rr_pgo_set_fixed; read by every instantiation of k_linearize): per node, 1 = held constant; null = none
   const uint8_t *fixed;
+  // truncated least squares (rr_pgo_set_robust_tls; read by the RK = ROBUST_TLS instantiations alone): the band's ends
+  // lo = mu / (mu + 1) c^2 and hi = (mu + 1) / mu c^2, c sqrt(mu (mu + 1)) and mu; c^2 is robust_delta2.  Behind every older
+  // field: those keep their kernarg offsets.
+  TC tls_lo, tls_hi, tls_cs, tls_mu;
 };
 template <typename A> __device__ __forceinline__ void opt_reset_in_first_thread(const A &a) {
   if (a.reset_ctrl && blockIdx.x == 0 && threadIdx.x == 0) {
@@ -490,16 +494,31 @@ __device__ __forceinline__ void prior_linearize_3d_point(const T l[3], const T z
 
 // Robust kernels (include/rr_pgo.h, rr_pgo_set_robust_kernel): rho(s) and the IRLS weight w = rho'(s) at s = e^T W e.
 // A template argument of the linearisation kernels: the NONE instantiation is the plain least-squares code.
-enum : int { ROBUST_NONE = 0, ROBUST_HUBER = 1, ROBUST_CAUCHY = 2 };
-template <int RK, typename T> __device__ __forceinline__ T robust_weight(T s, T delta, T delta2) {
+// ROBUST_TLS (rr_pgo_set_robust_tls): truncated least squares with the continuation parameter mu of graduated non-convexity.
+// With c = delta: w = 1, rho = s up to lo = mu / (mu + 1) c^2; w = 0, rho = c^2 from hi = (mu + 1) / mu c^2 on; in between
+// w = c sqrt(mu (mu + 1) / s) - mu and rho = 2 c sqrt(s mu (mu + 1)) - mu (c^2 + s).  The host passes lo, hi, cs = c sqrt(mu (mu + 1))
+// and mu; the other kinds ignore them.  Outside the band the weights are the constants 0 and 1, not rounded values.
+enum : int { ROBUST_NONE = 0, ROBUST_HUBER = 1, ROBUST_CAUCHY = 2, ROBUST_TLS = 3 };
+template <int RK, typename T>
+__device__ __forceinline__ T robust_weight(T s, T delta, T delta2, T lo = (T)0, T hi = (T)0, T cs = (T)0, T mu = (T)0) {
   if (RK == ROBUST_HUBER) return s > delta2 ? delta / sqrt(s) : (T)1;
   if (RK == ROBUST_CAUCHY) return s > (T)0 ? (T)1 / ((T)1 + s / delta2) : (T)1;
+  if (RK == ROBUST_TLS) return s <= lo ? (T)1 : s >= hi ? (T)0 : cs / sqrt(s) - mu;
   return (T)1;
 }
-template <int RK, typename T> __device__ __forceinline__ T robust_rho(T s, T delta, T delta2) {
+template <int RK, typename T>
+__device__ __forceinline__ T robust_rho(T s, T delta, T delta2, T lo = (T)0, T hi = (T)0, T cs = (T)0, T mu = (T)0) {
   if (RK == ROBUST_HUBER) return s > delta2 ? (T)2 * delta * sqrt(s) - delta2 : s;
   if (RK == ROBUST_CAUCHY) return s > (T)0 ? delta2 * log1p(s / delta2) : s;
+  if (RK == ROBUST_TLS) return s <= lo ? s : s >= hi ? delta2 : (T)2 * cs * sqrt(s) - mu * (delta2 + s);
   return s;
+}
+// the robust weight under a kind known at run time only (k_edge_errors, k_prior_errors, k_check_edges, k_tls_scan)
+template <typename T> __device__ __forceinline__ T robust_weight_rt(int kind, T s, T delta, T delta2, T lo, T hi, T cs, T mu) {
+  if (kind == ROBUST_HUBER) return robust_weight<ROBUST_HUBER, T>(s, delta, delta2);
+  if (kind == ROBUST_CAUCHY) return robust_weight<ROBUST_CAUCHY, T>(s, delta, delta2);
+  if (kind == ROBUST_TLS) return robust_weight<ROBUST_TLS, T>(s, delta, delta2, lo, hi, cs, mu);
+  return (T)1;
 }
 
 template <typename T> __device__ __forceinline__ T group_sum8(T v) {   // sum over the LIN_GROUP lanes of a node
@@ -1024,6 +1043,7 @@ template <typename TC> struct EdgeErrArgs {
   TC delta, delta2;
   const uint8_t *mask;                   // null: every edge
   double *s_out, *w_out;
+  TC tls_lo, tls_hi, tls_cs, tls_mu;     // ROBUST_TLS: as LinArgs
 };
 template <typename TC, bool LM = false> __global__ void __launch_bounds__(256) k_edge_errors(EdgeErrArgs<TC> a) {
   const int k = blockIdx.x * 256 + threadIdx.x;
@@ -1058,10 +1078,7 @@ template <typename TC, bool LM = false> __global__ void __launch_bounds__(256) k
     s = edge_chi2_3d<TC>(W, e);
   }
   TC wt = 1;
-  if (!a.mask || a.mask[k]) {
-    if (a.kind == ROBUST_HUBER) wt = robust_weight<ROBUST_HUBER, TC>(s, a.delta, a.delta2);
-    else if (a.kind == ROBUST_CAUCHY) wt = robust_weight<ROBUST_CAUCHY, TC>(s, a.delta, a.delta2);
-  }
+  if (!a.mask || a.mask[k]) wt = robust_weight_rt<TC>(a.kind, s, a.delta, a.delta2, a.tls_lo, a.tls_hi, a.tls_cs, a.tls_mu);
   a.s_out[k] = (double)s;
   if (a.w_out) a.w_out[k] = (double)wt;
 }
@@ -1079,10 +1096,7 @@ template <typename TC> __global__ void __launch_bounds__(256) k_edge_errors_br(E
   else edge_linearize_2d<TC>(lmk, a.pose[rec.from], a.pose[rec.to], rec.meas, e, A, B);
   const TC s = edge_chi2_2d<TC>(W, e);
   TC wt = 1;
-  if (!a.mask || a.mask[k]) {
-    if (a.kind == ROBUST_HUBER) wt = robust_weight<ROBUST_HUBER, TC>(s, a.delta, a.delta2);
-    else if (a.kind == ROBUST_CAUCHY) wt = robust_weight<ROBUST_CAUCHY, TC>(s, a.delta, a.delta2);
-  }
+  if (!a.mask || a.mask[k]) wt = robust_weight_rt<TC>(a.kind, s, a.delta, a.delta2, a.tls_lo, a.tls_hi, a.tls_cs, a.tls_mu);
   a.s_out[k] = (double)s;
   if (a.w_out) a.w_out[k] = (double)wt;
 }
@@ -1100,6 +1114,7 @@ template <typename TC> struct PriorErrArgs {
   TC delta, delta2;
   const uint8_t *robust;                 // per prior
   double *s_out, *w_out;
+  TC tls_lo, tls_hi, tls_cs, tls_mu;     // ROBUST_TLS: as LinArgs
 };
 template <typename TC, bool LM = false> __global__ void __launch_bounds__(256) k_prior_errors(PriorErrArgs<TC> a) {
   const int p = blockIdx.x * 256 + threadIdx.x;
@@ -1124,12 +1139,88 @@ template <typename TC, bool LM = false> __global__ void __launch_bounds__(256) k
     s = edge_chi2_3d<TC>(W, e);
   }
   TC wt = 1;
-  if (a.robust[p]) {
-    if (a.kind == ROBUST_HUBER) wt = robust_weight<ROBUST_HUBER, TC>(s, a.delta, a.delta2);
-    else if (a.kind == ROBUST_CAUCHY) wt = robust_weight<ROBUST_CAUCHY, TC>(s, a.delta, a.delta2);
-  }
+  if (a.robust[p]) wt = robust_weight_rt<TC>(a.kind, s, a.delta, a.delta2, a.tls_lo, a.tls_hi, a.tls_cs, a.tls_mu);
   a.s_out[p] = (double)s;
   a.w_out[p] = (double)wt;
+}
+
+// rr_pgo_optimize_gnc's scan: what the driver decides a stage on, from the (s, w) the k_edge_errors family has
+// just left on the device, without a per-edge copy to the host.  out[0] = the largest s over the masked edges (clamped at 0),
+// out[1] = masked edges with 0 < w < 1, out[2] = masked edges with w == 0, out[3] = sum of rho over ALL edges (s where the
+// mask is off), rho in TC like the linearisation's chi2 terms.  A thread takes one edge; a workgroup's four values are reduced
+// by a fixed shuffle tree, and the workgroup that finishes last adds the partials, thread t those of workgroups t, t + 256, ...,
+// through the same tree: the same bits at one state whatever the order the workgroups ran in.
+template <typename TC> struct TlsScanArgs {
+  int n_edges;
+  const double *s, *w;                   // k_edge_errors' output
+  const uint8_t *mask;                   // null: every edge
+  TC delta2, tls_lo, tls_hi, tls_cs, tls_mu;
+  double *partial;                       // [4 * gridDim.x]
+  int *blocks_done;                      // zero between launches
+  double *out;                           // [4], host-visible
+};
+struct TlsScanVal { double r2, rho; int frac, rej; };
+__device__ __forceinline__ TlsScanVal tls_scan_block_reduce(TlsScanVal v, TlsScanVal *scratch) {   // valid in thread 0; 256 threads
+  for (int o = 32; o > 0; o >>= 1) {
+    v.r2 = fmax(v.r2, __shfl_down(v.r2, o));
+    v.rho += __shfl_down(v.rho, o);
+    v.frac += __shfl_down(v.frac, o);
+    v.rej += __shfl_down(v.rej, o);
+  }
+  const int wave = wave_index(), lane = threadIdx.x & 63;
+  __syncthreads();
+  if (lane == 0) scratch[wave] = v;
+  __syncthreads();
+  TlsScanVal r = scratch[0];
+  if (threadIdx.x == 0)
+    for (int k = 1; k < 4; k++) {
+      r.r2 = fmax(r.r2, scratch[k].r2);
+      r.rho += scratch[k].rho;
+      r.frac += scratch[k].frac;
+      r.rej += scratch[k].rej;
+    }
+  return r;
+}
+template <typename TC> __global__ void __launch_bounds__(256) k_tls_scan(TlsScanArgs<TC> a) {
+  __shared__ TlsScanVal scratch[4];
+  __shared__ int is_last;
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  TlsScanVal v{0.0, 0.0, 0, 0};
+  if (k < a.n_edges) {
+    const double s = a.s[k], w = a.w[k];
+    if (!a.mask || a.mask[k]) {
+      v.r2 = fmax(s, 0.0);
+      v.rho = (double)robust_rho<ROBUST_TLS, TC>((TC)s, (TC)0, a.delta2, a.tls_lo, a.tls_hi, a.tls_cs, a.tls_mu);
+      v.frac = w > 0.0 && w < 1.0 ? 1 : 0;
+      v.rej = w == 0.0 ? 1 : 0;
+    } else {
+      v.rho = s;
+    }
+  }
+  v = tls_scan_block_reduce(v, scratch);
+  if (threadIdx.x == 0) {
+    double *p = a.partial + 4 * (size_t)blockIdx.x;
+    p[0] = v.r2; p[1] = (double)v.frac; p[2] = (double)v.rej; p[3] = v.rho;
+    __threadfence();
+    is_last = atomicAdd(a.blocks_done, 1) == (int)gridDim.x - 1;
+  }
+  __syncthreads();
+  if (!is_last) return;
+  __threadfence();
+  TlsScanVal t{0.0, 0.0, 0, 0};
+  for (int i = threadIdx.x; i < (int)gridDim.x; i += 256) {
+    const double *p = a.partial + 4 * (size_t)i;
+    t.r2 = fmax(t.r2, p[0]);
+    t.frac += (int)p[1];
+    t.rej += (int)p[2];
+    t.rho += p[3];
+  }
+  t = tls_scan_block_reduce(t, scratch);
+  if (threadIdx.x == 0) {
+    *a.blocks_done = 0;
+    a.out[0] = t.r2; a.out[1] = (double)t.frac; a.out[2] = (double)t.rej; a.out[3] = t.rho;
+    __threadfence_system();
+  }
 }
 
 // rr_pgo_extend without node_state: initial values of appended nodes, composed on the device from a pose that is already

@@ -83,7 +83,7 @@
         s_rob = edge_chi2<D, T>(W, e);
         rob = !a.robust_mask || a.robust_mask[k];
         if (rob) {   // masked-off edges keep W as it is
-          const T w = robust_weight<RK, T>(s_rob, a.robust_delta, a.robust_delta2);
+          const T w = robust_weight<RK, T>(s_rob, a.robust_delta, a.robust_delta2, a.tls_lo, a.tls_hi, a.tls_cs, a.tls_mu);
 #pragma unroll
           for (int i = 0; i < D; i++)
 #pragma unroll
@@ -119,7 +119,7 @@
         if constexpr (RK == ROBUST_NONE) {
           if (owns) chi += (double)edge_chi2<D, T>(W, e);   // every edge's term is owned by one rank
         } else {
-          if (owns) chi += (double)(rob ? robust_rho<RK, T>(s_rob, a.robust_delta, a.robust_delta2) : s_rob);
+          if (owns) chi += (double)(rob ? robust_rho<RK, T>(s_rob, a.robust_delta, a.robust_delta2, a.tls_lo, a.tls_hi, a.tls_cs, a.tls_mu) : s_rob);
         }
         if (a.write_system && (ent & 8)) {
           // ---- per dimension: the off-diagonal block H[from rows, to cols] = A^T W B and where it goes
@@ -216,7 +216,7 @@
           s_rob = edge_chi2<D, T>(W, e);
           rob = a.prior_robust[p] != 0;
           if (rob) {
-            const T w = robust_weight<RK, T>(s_rob, a.robust_delta, a.robust_delta2);
+            const T w = robust_weight<RK, T>(s_rob, a.robust_delta, a.robust_delta2, a.tls_lo, a.tls_hi, a.tls_cs, a.tls_mu);
 #pragma unroll
             for (int i = 0; i < D; i++)
 #pragma unroll
@@ -248,7 +248,7 @@
           for (int i = 0; i < D; i++) bv[i] += row_dot<D, T>(JW[i], e, 1);
         }
         if constexpr (RK == ROBUST_NONE) chi += (double)edge_chi2<D, T>(W, e);
-        else chi += (double)(rob ? robust_rho<RK, T>(s_rob, a.robust_delta, a.robust_delta2) : s_rob);
+        else chi += (double)(rob ? robust_rho<RK, T>(s_rob, a.robust_delta, a.robust_delta2, a.tls_lo, a.tls_hi, a.tls_cs, a.tls_mu) : s_rob);
       }
     }
   }

@@ -275,7 +275,11 @@ struct EngineBase {
   virtual void stage(int stage, double lambda, int lm) = 0;
   virtual void read_last_scalars(double *chi, double *norm) = 0;
   virtual void debug_withhold(int mode) = 0;   // failure injection for the dataflow launches (rr_pgo_debug_withhold)
-  virtual void set_robust(int kind, double delta, const int32_t *mask) = 0;   // rr_pgo_set_robust_kernel (arguments checked)
+  virtual void set_robust(int kind, double delta, double mu, const int32_t *mask) = 0;   // rr_pgo_set_robust_kernel / rr_pgo_set_robust_tls (arguments checked; mu: ROBUST_TLS alone)
+  virtual void set_robust_mu(double mu) = 0;                                   // rr_pgo_set_robust_mu (arguments checked)
+  // rr_pgo_optimize_gnc (arguments checked) / rr_pgo_gnc_times
+  virtual void optimize_gnc(int solver, const rr_pgo_gnc_options &opt, const int32_t *mask, rr_pgo_gnc_result *res, double *stage_mu, double *stage_cost) = 0;
+  virtual void gnc_times(double *ms) const = 0;
   virtual void edge_errors(double *s_out, double *w_out) = 0;                  // rr_pgo_edge_errors
   virtual void refuse_priors(const char *who) const = 0;                       // EUNSUPPORTED where priors cannot be held
   virtual void set_priors(const PriorSet &ps) = 0;                             // rr_pgo_set_priors (arguments checked)
@@ -324,6 +328,7 @@ struct EngineBase {
   // the first n_nodes nodes of the state from src (device memory of the same arithmetic type), on this engine's stream; waits
   virtual void adopt_state(const void *src, size_t n_nodes, double *ms) = 0;
   virtual void robust_setting(int *kind, double *delta, bool *masked, std::vector<int32_t> &mask) const = 0;
+  virtual double robust_mu() const = 0;   // of ROBUST_TLS, 0 under every other kind
   int n_launches_per_iter = 0;
   // rr_pgo_launch_counts: iterations put on the stream as plain launches / as replays of the captured hipGraph / as items of
   // the device-side loop, and instantiations of that graph.  Host-side, counted where the launches are enqueued.
@@ -598,6 +603,13 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   // robust kernel (rr_pgo_set_robust_kernel): ROBUST_* of kernels.hip.h, delta, per-edge mask (empty: every edge)
   int robust_kind_ = ROBUST_NONE;
   double robust_delta_ = 1.0;
+  double robust_mu_ = 0.0;           // ROBUST_TLS: the continuation parameter (0 under every other kind)
+  // rr_pgo_optimize_gnc: k_edge_errors' (s, w) and k_tls_scan's partials on the device, the scan's four numbers in host-coherent
+  // memory, the time of the last call's scans / stages / closing iterations
+  DevBuf<double> gnc_sw_, gnc_partial_;
+  DevBuf<int> gnc_done_;
+  PinnedBuf<double> gnc_host_;
+  double gnc_ms_[3] = {0, 0, 0};
   DevBuf<uint8_t> robust_mask_;
   std::vector<uint8_t> robust_mask_host_;
   // priors (rr_pgo_set_priors): the caller's list, and its device form -- CSR by node, records in CSR order (a node's priors
@@ -1805,6 +1817,15 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     a.robust_delta = (S)robust_delta_;
     a.robust_delta2 = (S)(robust_delta_ * robust_delta_);
     a.robust_mask = robust_mask_.n ? robust_mask_.p : nullptr;
+    const TlsParams p = tls_params();
+    a.tls_lo = (S)p.lo; a.tls_hi = (S)p.hi; a.tls_cs = (S)p.cs; a.tls_mu = (S)p.mu;
+  }
+  // ROBUST_TLS: what the host precomputes from (delta, mu) for every kernel that reads the weight (zeros under the other kinds)
+  struct TlsParams { double lo, hi, cs, mu; };
+  TlsParams tls_params() const {
+    if (robust_kind_ != ROBUST_TLS) return TlsParams{0.0, 0.0, 0.0, 0.0};
+    const double c2 = robust_delta_ * robust_delta_, mu = robust_mu_;
+    return TlsParams{mu / (mu + 1.0) * c2, (mu + 1.0) / mu * c2, robust_delta_ * std::sqrt(mu * (mu + 1.0)), mu};
   }
   void prior_fields(LinArgs<T, S> &a) const {   // (read by the PR instantiations alone: launch_pull)
     a.prior_ptr = prior_ptr_.p;
@@ -1907,6 +1928,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     } else {
       if (robust_kind_ == ROBUST_HUBER) launch_pull<ROBUST_HUBER>(la);
       else if (robust_kind_ == ROBUST_CAUCHY) launch_pull<ROBUST_CAUCHY>(la);
+      else if (robust_kind_ == ROBUST_TLS) launch_pull<ROBUST_TLS>(la);
       else launch_pull<ROBUST_NONE>(la);
     }
     check_launch("k_linearize");
@@ -2552,6 +2574,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     *masked = !robust_mask_host_.empty();
     mask.assign(robust_mask_host_.begin(), robust_mask_host_.end());
   }
+  double robust_mu() const override { return robust_kind_ == ROBUST_TLS ? robust_mu_ : 0.0; }
 
   void assemble(double lambda, int lm, std::vector<double> &hv, std::vector<double> &b) override {
     refuse_rank_partial("rr_pgo_assemble");
@@ -2718,7 +2741,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   }
 
   // ---- robust kernels (include/rr_pgo.h, rr_pgo_set_robust_kernel)
-  void set_robust(int kind, double delta, const int32_t *mask) override {
+  void set_robust(int kind, double delta, double mu, const int32_t *mask) override {
     std::vector<uint8_t> m;
     if (kind != ROBUST_NONE && mask) {
       m.resize((size_t)g_.n_edges());
@@ -2729,6 +2752,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     robust_mask_host_ = m;                   // (rr_pgo_extend carries the setting to the grown graph's engine)
     robust_kind_ = kind;
     robust_delta_ = kind != ROBUST_NONE ? delta : 1.0;
+    robust_mu_ = kind == ROBUST_TLS ? mu : 0.0;
     // the captured graphs hold the old kernel and its arguments
     drop_graphs();
     // the edge-parallel experiment forms have no robust instantiation: the pull form runs while a kernel is set
@@ -2736,12 +2760,102 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     edge_lin_wave_ = edge_lin_wave_env_ && kind == ROBUST_NONE;
     n_lin_blocks_ = edge_lin_ ? lin_blocks_edge_ : lin_blocks_pull_;
   }
+  // mu alone (rr_pgo_set_robust_mu): a kernel argument of every later launch.  The captured graphs hold the old value: dropped
+  // (behind whatever replay is still on the stream), so the next iteration captures anew.  No mask upload, no allocation.
+  void set_robust_mu(double mu) override {
+    if (robust_kind_ != ROBUST_TLS) throw ApiError(RR_PGO_EINVAL, "rr_pgo_set_robust_mu: the handle's robust kernel is not RR_PGO_ROBUST_TLS");
+    bool captured = gn_exec_ != nullptr;
+    for (hipGraphExec_t e : stage_exec_) captured = captured || e != nullptr;
+    if (captured) {
+      HIPCHK(hipStreamSynchronize(stream_));
+      drop_graphs();
+    }
+    robust_mu_ = mu;
+  }
+  // ---- graduated non-convexity on truncated least squares (include/rr_pgo.h, rr_pgo_optimize_gnc)
+  // One scan: the k_edge_errors family into device memory, k_tls_scan over it, ONE synchronisation, four numbers read.
+  struct TlsScan { double r2_max, rho; int frac, rej; };
+  TlsScan tls_scan() {
+    const int E = g_.n_edges(), nb = (E + 255) / 256;
+    launch_edge_errors(gnc_sw_.p, gnc_sw_.p + E);
+    TlsScanArgs<S> a;
+    a.n_edges = E;
+    a.s = gnc_sw_.p;
+    a.w = gnc_sw_.p + E;
+    a.mask = robust_mask_.n ? robust_mask_.p : nullptr;
+    const TlsParams p = tls_params();
+    a.delta2 = (S)(robust_delta_ * robust_delta_);
+    a.tls_lo = (S)p.lo; a.tls_hi = (S)p.hi; a.tls_cs = (S)p.cs; a.tls_mu = (S)p.mu;
+    a.partial = gnc_partial_.p;
+    a.blocks_done = gnc_done_.p;
+    a.out = gnc_host_.p;
+    hipLaunchKernelGGL((k_tls_scan<S>), dim3((unsigned)nb), dim3(256), 0, stream_, a);
+    check_launch("k_tls_scan");
+    HIPCHK(hipStreamSynchronize(stream_));
+    return TlsScan{gnc_host_[0], gnc_host_[3], (int)gnc_host_[1], (int)gnc_host_[2]};
+  }
+  // the loop of the header, statement by statement; the iterations go through optimize(), the path of rr_pgo_optimize
+  void optimize_gnc(int solver, const rr_pgo_gnc_options &o, const int32_t *mask, rr_pgo_gnc_result *res, double *stage_mu,
+                    double *stage_cost) override {
+    if (sharded_ || world_ > 1) throw ApiError(RR_PGO_EUNSUPPORTED, "rr_pgo_optimize_gnc on a sharded handle");
+    const int E = g_.n_edges();
+    if (E == 0) throw ApiError(RR_PGO_EINVAL, "rr_pgo_optimize_gnc: the graph has no edge");
+    const size_t nb = ((size_t)E + 255) / 256;
+    if (gnc_sw_.n < 2 * (size_t)E) gnc_sw_.alloc(2 * (size_t)E);
+    if (gnc_partial_.n < 4 * nb) gnc_partial_.alloc(4 * nb);
+    if (!gnc_done_.p) { gnc_done_.alloc(1); gnc_done_.zero(); }
+    if (!gnc_host_.p) gnc_host_.alloc(4);
+    *res = rr_pgo_gnc_result{};
+    double ms[3] = {0, 0, 0};
+    TlsScan sc{};
+    auto scan = [&] { ms[0] += timed_ms([&] { sc = tls_scan(); }); };
+    std::vector<double> errors((size_t)std::max(o.inner_iterations, o.final_iterations) + 2);
+    int ne = 0;
+    const double c2 = o.delta * o.delta;
+    set_robust(ROBUST_TLS, o.delta, 1.0, mask);   // (the mask goes up once; the stages change mu alone)
+    scan();
+    res->r2_max = sc.r2_max;
+    res->mu0 = 2.0 * sc.r2_max > c2 ? c2 / (2.0 * sc.r2_max - c2) : 1.0;
+    double mu = res->mu0;
+    for (int t = 0;; t++) {
+      set_robust_mu(mu);
+      res->mu_last = mu;
+      ms[1] += timed_ms([&] { optimize(solver, o.inner_iterations, errors.data(), &ne, nullptr); });
+      scan();
+      if (stage_mu) stage_mu[t] = mu;
+      if (stage_cost) stage_cost[t] = sc.rho;
+      res->n_stages = t + 1;
+      if (sc.frac == 0) { res->converged = 1; break; }
+      if (t + 1 == o.max_stages) break;
+      mu *= o.mu_factor;
+    }
+    if (o.final_iterations > 0) {
+      ms[2] += timed_ms([&] { optimize(solver, o.final_iterations, errors.data(), &ne, nullptr); });
+      res->final_iterations_run = ne - 1;
+      scan();
+    }
+    res->n_rejected = sc.rej;
+    res->n_fractional = sc.frac;
+    res->cost_last = sc.rho;
+    for (int k = 0; k < 3; k++) gnc_ms_[k] = ms[k];
+  }
+  void gnc_times(double *ms) const override { for (int k = 0; k < 3; k++) ms[k] = gnc_ms_[k]; }
   void edge_errors(double *s_out, double *w_out) override {
     if (sharded_) throw ApiError(RR_PGO_EUNSUPPORTED, "rr_pgo_edge_errors on a sharded handle");
     const int E = g_.n_edges();
     if (E == 0) return;
     DevBuf<double> out;
     out.alloc(2 * (size_t)E);
+    launch_edge_errors(out.p, out.p + E);
+    std::vector<double> host(2 * (size_t)E);
+    HIPCHK(hipMemcpyAsync(host.data(), out.p, host.size() * sizeof(double), hipMemcpyDeviceToHost, stream_));
+    HIPCHK(hipStreamSynchronize(stream_));
+    std::memcpy(s_out, host.data(), E * sizeof(double));
+    if (w_out) std::memcpy(w_out, host.data() + E, E * sizeof(double));
+  }
+  // (s, w) of every edge into device memory: rr_pgo_edge_errors, and the scan of rr_pgo_optimize_gnc
+  void launch_edge_errors(double *s_dev, double *w_dev) {
+    const int E = g_.n_edges();
     EdgeErrArgs<S> a;
     a.n_edges = E;
     a.is3d = is3d_ ? (has_lm_ ? 2 : 1) : 0;
@@ -2755,17 +2869,14 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     a.delta = (S)robust_delta_;
     a.delta2 = (S)(robust_delta_ * robust_delta_);
     a.mask = robust_mask_.n ? robust_mask_.p : nullptr;
-    a.s_out = out.p;
-    a.w_out = out.p + E;
+    a.s_out = s_dev;
+    a.w_out = w_dev;
+    const TlsParams p = tls_params();
+    a.tls_lo = (S)p.lo; a.tls_hi = (S)p.hi; a.tls_cs = (S)p.cs; a.tls_mu = (S)p.mu;
     if (has_lm_) hipLaunchKernelGGL((k_edge_errors<S, true>), dim3((E + 255) / 256), dim3(256), 0, stream_, a);
     else if (has_br_) hipLaunchKernelGGL((k_edge_errors_br<S>), dim3((E + 255) / 256), dim3(256), 0, stream_, a);
     else hipLaunchKernelGGL((k_edge_errors<S>), dim3((E + 255) / 256), dim3(256), 0, stream_, a);
     check_launch("k_edge_errors");
-    std::vector<double> host(2 * (size_t)E);
-    HIPCHK(hipMemcpyAsync(host.data(), out.p, host.size() * sizeof(double), hipMemcpyDeviceToHost, stream_));
-    HIPCHK(hipStreamSynchronize(stream_));
-    std::memcpy(s_out, host.data(), E * sizeof(double));
-    if (w_out) std::memcpy(w_out, host.data() + E, E * sizeof(double));
   }
 
   // ---- priors (include/rr_pgo.h, rr_pgo_set_priors)
@@ -2886,6 +2997,8 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     a.delta = (S)robust_delta_;
     a.delta2 = (S)(robust_delta_ * robust_delta_);
     a.robust = prior_robust_.p;
+    const TlsParams tp = tls_params();
+    a.tls_lo = (S)tp.lo; a.tls_hi = (S)tp.hi; a.tls_cs = (S)tp.cs; a.tls_mu = (S)tp.mu;
     a.s_out = out.p;
     a.w_out = out.p + P;
     if (has_lm_) hipLaunchKernelGGL((k_prior_errors<S, true>), dim3((P + 255) / 256), dim3(256), 0, stream_, a);
@@ -3686,6 +3799,8 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
         a.delta2 = (T)(robust_delta_ * robust_delta_);
         a.S = sym_.S;
         a.rkind = robust_kind_;
+        const TlsParams tp = tls_params();
+        a.tls_lo = (T)tp.lo; a.tls_hi = (T)tp.hi; a.tls_cs = (T)tp.cs; a.tls_mu = (T)tp.mu;
         if (has_lm_) hipLaunchKernelGGL((k_check_edges<T, 6, true>), dim3((unsigned)nc), dim3(COV_THREADS), 0, stream_, a);
         else if (br) hipLaunchKernelGGL((k_check_edges<T, 3, true>), dim3((unsigned)nc), dim3(COV_THREADS), 0, stream_, a);
         else if (is3d_) hipLaunchKernelGGL((k_check_edges<T, 6>), dim3((unsigned)nc), dim3(COV_THREADS), 0, stream_, a);
@@ -4410,7 +4525,7 @@ static void extend_handle(rr_pgo *h, int32_t n_new_nodes, const int32_t *node_ki
   h->engine->robust_setting(&rk, &rdelta, &masked, mask);
   if (rk != ROBUST_NONE) {
     if (masked) mask.resize((size_t)g.n_edges(), 1);   // a fresh closure is robustified
-    nh->engine->set_robust(rk, rdelta, masked ? mask.data() : nullptr);
+    nh->engine->set_robust(rk, rdelta, h->engine->robust_mu(), masked ? mask.data() : nullptr);
   }
   if (h->engine->priors().n() > 0) apply_priors(*nh, h->engine->priors());   // node indices do not change
   if (!h->engine->fixed().empty()) nh->engine->set_fixed(h->engine->fixed(), h->engine->fixed_keep_anchor());   // new nodes are free
@@ -4461,7 +4576,7 @@ static void remove_handle(rr_pgo *h, int32_t n_remove, const int32_t *edge) {
   if (rk != ROBUST_NONE) {
     if (masked)
       for (int k : keep) kept_mask.push_back(mask[k]);
-    nh->engine->set_robust(rk, rdelta, masked ? kept_mask.data() : nullptr);
+    nh->engine->set_robust(rk, rdelta, h->engine->robust_mu(), masked ? kept_mask.data() : nullptr);
   }
   if (h->engine->priors().n() > 0) apply_priors(*nh, h->engine->priors());   // node indices do not change
   if (!h->engine->fixed().empty()) nh->engine->set_fixed(h->engine->fixed(), h->engine->fixed_keep_anchor());
@@ -4668,7 +4783,63 @@ int rr_pgo_set_robust_kernel(rr_pgo *h, int32_t kind, double delta, const int32_
     return RR_PGO_EINVAL;
   }
   static_assert(RR_PGO_ROBUST_HUBER == ROBUST_HUBER && RR_PGO_ROBUST_CAUCHY == ROBUST_CAUCHY, "robust kernel numbering");
-  return guarded([&] { h->engine->set_robust(kind, delta, edge_mask); });
+  return guarded([&] { h->engine->set_robust(kind, delta, 0.0, edge_mask); });
+}
+
+int rr_pgo_set_robust_tls(rr_pgo *h, double delta, double mu, const int32_t *edge_mask) {
+  if (!h) { g_last_error = "null argument"; return RR_PGO_EINVAL; }
+  if (!(std::isfinite(delta) && delta > 0.0) || !(std::isfinite(mu) && mu > 0.0)) {
+    g_last_error = "rr_pgo_set_robust_tls: delta and mu must be finite and > 0";
+    return RR_PGO_EINVAL;
+  }
+  static_assert(RR_PGO_ROBUST_TLS == ROBUST_TLS, "robust kernel numbering");
+  return guarded([&] { h->engine->set_robust(ROBUST_TLS, delta, mu, edge_mask); });
+}
+
+int rr_pgo_set_robust_mu(rr_pgo *h, double mu) {
+  if (!h) { g_last_error = "null argument"; return RR_PGO_EINVAL; }
+  if (!(std::isfinite(mu) && mu > 0.0)) { g_last_error = "rr_pgo_set_robust_mu: mu must be finite and > 0"; return RR_PGO_EINVAL; }
+  return guarded([&] { h->engine->set_robust_mu(mu); });
+}
+
+int rr_pgo_get_robust(const rr_pgo *h, int32_t *kind, double *delta, double *mu) {
+  if (!h) { g_last_error = "null argument"; return RR_PGO_EINVAL; }
+  return guarded([&] {
+    int rk = ROBUST_NONE;
+    double rdelta = 1.0;
+    bool masked = false;
+    std::vector<int32_t> mask;
+    h->engine->robust_setting(&rk, &rdelta, &masked, mask);
+    if (kind) *kind = rk;
+    if (delta) *delta = rdelta;
+    if (mu) *mu = h->engine->robust_mu();
+  });
+}
+
+void rr_pgo_default_gnc_options(rr_pgo_gnc_options *opt) {
+  if (!opt) return;
+  std::memset(opt, 0, sizeof(*opt));
+  opt->delta = 1.0;
+  opt->mu_factor = 1.4;
+  opt->max_stages = 100;
+  opt->inner_iterations = 1;
+  opt->final_iterations = 20;
+}
+
+int rr_pgo_optimize_gnc(rr_pgo *h, const rr_pgo_gnc_options *opt, const int32_t *edge_mask, rr_pgo_gnc_result *res,
+                        double *stage_mu, double *stage_cost) {
+  if (!h || !opt || !res) { g_last_error = "null argument"; return RR_PGO_EINVAL; }
+  bool ok = std::isfinite(opt->delta) && opt->delta > 0.0 && std::isfinite(opt->mu_factor) && opt->mu_factor > 1.0 &&
+            opt->max_stages >= 1 && opt->inner_iterations >= 1 && opt->final_iterations >= 0;
+  for (int32_t r : opt->reserved) ok = ok && r == 0;
+  if (!ok) { g_last_error = "rr_pgo_optimize_gnc: option out of range"; return RR_PGO_EINVAL; }
+  return guarded([&] { h->engine->optimize_gnc(h->opt.solver, *opt, edge_mask, res, stage_mu, stage_cost); });
+}
+
+int rr_pgo_gnc_times(const rr_pgo *h, double *ms) {
+  if (!h || !ms) { g_last_error = "null argument"; return RR_PGO_EINVAL; }
+  h->engine->gnc_times(ms);
+  return RR_PGO_OK;
 }
 
 int rr_pgo_edge_errors(rr_pgo *h, double *chi2_out, double *weight_out) {

@@ -444,12 +444,14 @@ template <typename T> struct CheckArgs {
   double *d2, *chi2, *red, *rout; // rout null: R is not asked for
   T delta, delta2;                // of the robust kernel
   int32_t S, rkind;               // rkind: ROBUST_*
+  T tls_lo, tls_hi, tls_cs, tls_mu;   // ROBUST_TLS: as LinArgs
 };
 
 // One workgroup per queried edge; D as in k_gate_pairs, and the same walk.  Lane 0 of wave 0 has s = e^T Omega e and w(s) ready
 // (the linearisation's own robust_weight) when the slices are added: entry (i, j) of the lower triangle is
 // Omega^-1(i, j) / w - P(i, j), mirrored, so R is symmetric bit for bit.  r is summed row by row, column by column, by one
-// lane.  A non-positive pivot of R (an edge at r near 0, or one whose residual the rest of the graph determines in some
+// lane.  An edge whose weight is exactly 0 (ROBUST_TLS beyond its band) gave H nothing: its R, r and d2 are NaN, chi2 stays
+// e^T Omega e, and it is queried with rr_pgo_gate_edges as the candidate it now is.  A non-positive pivot of R (an edge at r near 0, or one whose residual the rest of the graph determines in some
 // directions only: rounding decides) gives d2 = NaN; r and R are written all the same.
 template <typename T, int D, bool LM = false>
 __global__ void __launch_bounds__(COV_THREADS) k_check_edges(CheckArgs<T> a) {
@@ -471,10 +473,7 @@ __global__ void __launch_bounds__(COV_THREADS) k_check_edges(CheckArgs<T> a) {
     }
     const T c2 = edge_chi2<D, T>(W, e);
     T w = 1;
-    if (q->pad & 1) {
-      if (a.rkind == ROBUST_HUBER) w = robust_weight<ROBUST_HUBER, T>(c2, a.delta, a.delta2);
-      else if (a.rkind == ROBUST_CAUCHY) w = robust_weight<ROBUST_CAUCHY, T>(c2, a.delta, a.delta2);
-    }
+    if (q->pad & 1) w = robust_weight_rt<T>(a.rkind, c2, a.delta, a.delta2, a.tls_lo, a.tls_hi, a.tls_cs, a.tls_mu);
     a.chi2[blockIdx.x] = (double)c2;
     sw[0] = w;
   }
@@ -506,7 +505,8 @@ __global__ void __launch_bounds__(COV_THREADS) k_check_edges(CheckArgs<T> a) {
     T s = part[tid];
 #pragma unroll
     for (int k = 1; k < NS; k++) s += part[k * 32 + tid];
-    const T r = (T)q->cov[i * D + j] / sw[0] - s;
+    // w == 0 exactly (truncated least squares): the edge is not part of H and Omega_w^-1 does not exist -- R, r and d2 are NaN
+    const T r = sw[0] == (T)0 ? (T)__builtin_nan("") : (T)q->cov[i * D + j] / sw[0] - s;
     sS[i * D + j] = r;
     sS[j * D + i] = r;
   }

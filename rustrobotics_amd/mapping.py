@@ -307,6 +307,57 @@ class PoseGraph:
         _check(_lib.load().rr_pgo_set_robust_kernel(self._h, _lib.ROBUST_KERNELS[key], float(delta),
                                                     None if mask is None else _ip(mask)))
 
+    def _edge_mask(self, edge_mask):
+        if edge_mask is None:
+            return None
+        mask = np.ascontiguousarray(edge_mask).astype(np.int32)
+        if mask.shape != (self.num_edges,):
+            raise ValueError("edge_mask needs one entry per edge")
+        return mask
+
+    # -- truncated least squares and graduated non-convexity (include/rr_pgo.h, rr_pgo_optimize_gnc) ----
+    def set_robust_tls(self, delta, mu=1.0, edge_mask=None):
+        """Truncated least squares with continuation parameter mu as the handle's robust kernel: w = 1 up to
+        mu / (mu + 1) delta^2, w = 0 from (mu + 1) / mu delta^2 on, delta sqrt(mu (mu + 1) / s) - mu in between."""
+        mask = self._edge_mask(edge_mask)
+        _check(_lib.load().rr_pgo_set_robust_tls(self._h, float(delta), float(mu), None if mask is None else _ip(mask)))
+
+    def set_robust_mu(self, mu):
+        """mu of the truncated-least-squares kernel alone (the mask and delta stay)."""
+        _check(_lib.load().rr_pgo_set_robust_mu(self._h, float(mu)))
+
+    @property
+    def robust_setting(self):
+        """(kind, delta, mu) of the handle's robust kernel: kind 0 none, 1 huber, 2 cauchy, 3 truncated least squares; mu is 0
+        for the kinds without one."""
+        kind, delta, mu = C.c_int32(), C.c_double(), C.c_double()
+        _check(_lib.load().rr_pgo_get_robust(self._h, C.byref(kind), C.byref(delta), C.byref(mu)))
+        return kind.value, delta.value, mu.value
+
+    def optimize_gnc(self, delta, edge_mask=None, mu_factor=1.4, max_stages=100, inner_iterations=1, final_iterations=20):
+        """rr_pgo_optimize_gnc: graduated non-convexity on truncated least squares from the current state.  delta^2 is the
+        chi-square quantile beyond which a masked edge (None: every edge; usually the loop closures) counts as an outlier.
+        Returns a dict of the result fields plus stage_mu and stage_cost (one entry per stage run).  The handle keeps the
+        kernel at mu_last: edge_errors()[1] == 0 names the rejected edges."""
+        L = _lib.load()
+        opt = _lib.GncOptions()
+        L.rr_pgo_default_gnc_options(C.byref(opt))
+        opt.delta, opt.mu_factor = float(delta), float(mu_factor)
+        opt.max_stages, opt.inner_iterations, opt.final_iterations = int(max_stages), int(inner_iterations), int(final_iterations)
+        mask = self._edge_mask(edge_mask)
+        res = _lib.GncResult()
+        n = max(opt.max_stages, 1)
+        stage_mu, stage_cost = np.zeros(n), np.zeros(n)
+        _check(L.rr_pgo_optimize_gnc(self._h, C.byref(opt), None if mask is None else _ip(mask), C.byref(res), _dp(stage_mu),
+                                     _dp(stage_cost)))
+        out = {name: getattr(res, name) for name, _ in _lib.GncResult._fields_}
+        out["stage_mu"], out["stage_cost"] = stage_mu[:res.n_stages].copy(), stage_cost[:res.n_stages].copy()
+        return out
+
+    def gnc_times(self):
+        """HIP-event milliseconds of the last optimize_gnc call: (scans, stages, closing iterations)."""
+        return self._times(_lib.load().rr_pgo_gnc_times)
+
     def edge_errors(self):
         """(s, w): e^T Omega e of every edge at the current state and its robust weight (1 without a kernel), file order."""
         s, w = np.zeros(self.num_edges), np.zeros(self.num_edges)
@@ -674,7 +725,8 @@ class PoseGraph:
                 k = c if idx is None else int(idx[c])
                 W = np.zeros((dims[c], dims[c]))
                 W[np.triu_indices(dims[c])] = ei[io[k]:io[k + 1]]
-                rmin[c] = directional_redundancy(out["R"][c], W + np.triu(W, 1).T, red[c])
+                # (an edge of weight exactly 0 under truncated least squares: R is NaN, and so is every figure of it)
+                rmin[c] = directional_redundancy(out["R"][c], W + np.triu(W, 1).T, red[c]) if np.isfinite(out["R"][c]).all() else np.nan
             out["redundancy_min"] = rmin
         return out
 
