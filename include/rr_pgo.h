@@ -385,6 +385,41 @@ int rr_pgo_set_fixed(rr_pgo *h, int32_t n_fixed, const int32_t *node, int32_t ke
 int32_t rr_pgo_num_fixed(const rr_pgo *h);           /* distinct fixed nodes */
 int rr_pgo_get_fixed(const rr_pgo *h, int32_t *out); /* ascending node indices, rr_pgo_num_fixed entries */
 
+/* ---- initialisation from the measurements (build-defined; the reference has none) ----------
+ * rr_pgo_initialize(h, RR_PGO_INIT_CHORDAL) replaces the state of every free node by the chordal relaxation of the graph
+ * (Carlone, Tron, Daniilidis, Dellaert, ICRA 2015): linear least squares for the rotations, a projection onto SO(d),
+ * linear least squares for the positions.  It reads the graph, the prior list and the HELD nodes' states, nothing else of
+ * the current state.  Every edge takes full weight: the robust kernel, its mask and the TLS weights play no part.
+ * HELD nodes are the fixed nodes (rr_pgo_set_fixed) and, while BOTH keep_anchor settings say keep, rr_pgo_anchor_node.
+ * They are constants taken from the current state -- held exactly, not by the 1e7 term -- and their state bits do not change.
+ * With Omega an edge's or prior's information, translation first; Omega_tt its upper-left d x d block, Omega_rot the rest:
+ *   SE(3)  1. over M_i in R^(3x3), i a free pose, M_c = R_c for a held pose c:
+ *               min  sum_{SE3 edges (i,j)} k_ij |M_i R_ij - M_j|_F^2  +  sum_{priors p on pose i} k_p |M_i - R_zp|_F^2 ,
+ *               k = trace(Omega_rot) / 3
+ *          2. R_i = U diag(1, 1, det(U V^T)) V^T  of  M_i = U S V^T  (the nearest rotation in the Frobenius norm)
+ *          3. over t_i (free poses) and l (free XYZ landmarks), with |v|^2_W = v^T W v and the R_i of step 2 or the held ones:
+ *               min  sum_{SE3 edges} |R_i^T (t_j - t_i) - t_ij|^2_Omega_tt  +  sum_{SE3_XYZ edges} |R_i^T (l_j - t_i) - z|^2_Omega
+ *                  + sum_{pose priors} |R_z^T (t_i - t_z)|^2_Omega_tt       +  sum_{landmark priors} |l - z|^2_Omega
+ *             (the translation-rotation cross block of Omega is ignored)
+ *   SE(2)  the same scheme with u_i = (cos, sin) in R^2: min sum k |Rot(theta_ij) u_i - u_j|^2 + sum k_p |u_i - u_zp|^2,
+ *          k = Omega_theta,theta; the projection is u / |u|; positions as above with the 2 x 2 Omega_tt, SE2_XY edges and
+ *          XY-landmark priors.  SE2_BEARING and SE2_RANGE edges take no part (one scalar places nothing).
+ * A free pose gets (t, R) -- SE(3): a unit quaternion with q_w >= 0 --, a free landmark its position.  All three precisions;
+ * RR_PGO_F32 / RR_PGO_MIXED solve with the single-precision factor, without the gauge transfer.
+ * Untouched: the robust setting, the prior list, the fixed set, the Levenberg-Marquardt lambda, the solver, captured graphs
+ * and the two big-front switches (rr_pgo_set_query_big_fronts, rr_pgo_set_marginals_big_fronts).
+ * Failures; after each of them the state is what it was before the call, bit for bit:
+ *   RR_PGO_EINVAL        unknown method; a free landmark with no SE2_XY / SE3_XYZ edge and no prior (the message names it)
+ *   RR_PGO_EUNSUPPORTED  sharded handles
+ *   RR_PGO_ENOTSPD       a stage's system is singular: a set of poses connected by pose-pose edges with no held pose and
+ *                        no pose prior (decided before anything runs), or a non-positive pivot in a stage's factorisation
+ *   device errors and RR_PGO_ETIMEOUT propagate as from rr_pgo_optimize
+ * The call synchronises with the device once per stage. */
+enum { RR_PGO_INIT_CHORDAL = 0 };
+int rr_pgo_initialize(rr_pgo *h, int32_t method);
+/* ms[3]: HIP-event time of the last call's rotation stage(s) incl. projection, position stage, and the whole call */
+int rr_pgo_initialize_times(const rr_pgo *h, double *ms);
+
 /* ---- marginal covariances (build-defined; the reference has none) ----------
  * Blocks of Sigma = H^-1 at the current state (H as rr_pgo_linearize_solve(h, 0, 0) builds it: anchor prior 1e7 included,
  * lambda = 0, robust weights included while a kernel is set; with a prior list, rr_pgo_set_priors, H is the one with the

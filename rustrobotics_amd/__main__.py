@@ -25,6 +25,11 @@
       covariances and gates printed afterwards are conditional on them.  With --free-anchor the fixed set (plus any
       priors) fixes the gauge.  Applied before --robust and the optimisation
 
+  --init chordal  (both modes): before the optimisation, replace the state of every free vertex by the chordal relaxation of
+      the graph (rr_pgo_initialize: relaxed rotations, projection onto SO(d), positions); fixed vertices and the kept anchor
+      stay.  Applied after --priors and --fix, which it reads, and before --robust, which it ignores.  The example mode
+      prints chi2 before and after the initialisation and the call's three times
+
   --marginals FILE  (example mode): after the optimisation, one line per node -- id, d, the upper triangle of its d x d
       covariance block (rr_pgo_marginals; f64 handles whose fronts all live in LDS)
 
@@ -498,6 +503,8 @@ def main(argv=None):
                     help="with --priors and / or --fix: drop the 1e7 term on the anchor node, they alone fix the gauge")
     ap.add_argument("--fix", type=_ids_arg, metavar="ID,ID,...", default=None,
                     help="hold these g2o vertex ids constant: they never move, covariances and gates are conditional on them")
+    ap.add_argument("--init", choices=["chordal"], default=None,
+                    help="before the optimisation: initialise every free vertex from the measurements (chordal relaxation)")
     ap.add_argument("--marginals", metavar="FILE", default=None,
                     help="after the optimisation write every node's covariance block: id, d, upper triangle")
     ap.add_argument("--joint", type=_ids_arg, metavar="ID,ID,...", default=None,
@@ -537,6 +544,7 @@ def main(argv=None):
     if a.free_anchor and not (a.priors or a.fix):
         ap.error("--free-anchor needs --priors FILE or --fix ID,ID,...")
     solver = PoseGraphSolver[a.solver]
+    report_init = not a.bench
 
     def new():
         g = PoseGraph.new(a.file, solver, precision=a.precision)
@@ -544,6 +552,13 @@ def main(argv=None):
             apply_priors_file(g, a.priors, a.free_anchor)
         if a.fix:
             g.set_fixed(fix_indices(a.fix, _node_index(g)), keep_anchor=not a.free_anchor)
+        if a.init:
+            before = g.global_error() if report_init else None
+            g.initialize(a.init)
+            if report_init:
+                ms = g.initialize_times()
+                print(f"{a.init} initialisation: chi2 before {before:.9g}, after {g.global_error():.9g} "
+                      f"(rotations {ms[0]:.3f} ms, positions {ms[1]:.3f} ms, call {ms[2]:.3f} ms)")
         if a.robust:
             g.set_robust_kernel(*a.robust)
         return g

@@ -45,6 +45,7 @@ EXPORTS = (
     "rr_pgo_set_marginals_big_fronts", "rr_pgo_get_marginals_big_fronts",
     "rr_pgo_set_robust_tls", "rr_pgo_set_robust_mu", "rr_pgo_get_robust", "rr_pgo_default_gnc_options",
     "rr_pgo_optimize_gnc", "rr_pgo_gnc_times",
+    "rr_pgo_initialize", "rr_pgo_initialize_times",
 )
 
 
@@ -163,6 +164,8 @@ def load():
     L.rr_pgo_default_gnc_options.restype = None
     L.rr_pgo_optimize_gnc.argtypes = [vp, C.POINTER(GncOptions), ip, C.POINTER(GncResult), dp, dp]
     L.rr_pgo_gnc_times.argtypes = [vp, dp]
+    L.rr_pgo_initialize.argtypes = [vp, C.c_int32]
+    L.rr_pgo_initialize_times.argtypes = [vp, dp]
     L.rr_pgo_marginals.argtypes = [vp, C.c_int32, ip, ip, dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.rr_pgo_marginals_times.argtypes = [vp, dp]
     L.rr_pgo_covariances.argtypes = [vp, C.c_int32, ip, ip, dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]

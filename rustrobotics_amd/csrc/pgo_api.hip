@@ -31,6 +31,7 @@
 #include "flow.hip.h"
 #include "lds_flow.hip.h"
 #include "selinv.hip.h"
+#include "chordal.hip.h"
 #include "treesolve.hip.h"
 #include "symbolic.h"
 #include "host_threads.h"
@@ -289,6 +290,8 @@ struct EngineBase {
   virtual void set_fixed(const std::vector<int32_t> &nodes, int keep_anchor) = 0;   // rr_pgo_set_fixed (distinct, ascending, checked)
   virtual const std::vector<int32_t> &fixed() const = 0;
   virtual int fixed_keep_anchor() const = 0;
+  virtual void initialize(int method) = 0;                       // rr_pgo_initialize / rr_pgo_initialize_times
+  virtual void initialize_times(double *ms) const = 0;
   // rr_pgo_marginals (arguments checked; off: [nq + 1] offsets of the blocks in out) / rr_pgo_marginals_times
   virtual void marginals(int nq, const int32_t *na, const int32_t *nb, const int64_t *off, double *out) = 0;
   // rr_pgo_covariances (arguments checked; off as for marginals) / rr_pgo_covariances_times
@@ -627,6 +630,12 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   std::vector<uint8_t> fixed_host_;    // [n_nodes] while the set is non-empty (the queries' plans read it)
   int fixed_keep_anchor_ = 1;
   DevBuf<uint8_t> fixed_;
+  // rr_pgo_initialize (chordal.hip.h): the projected rotations per node, the exported solution of the first rotation stage
+  // (3-D), the events around the stages and the last call's times; buffers and events are made by the first call
+  DevBuf<S> chordal_rot_;
+  DevBuf<T> chordal_sol_;
+  EventHolder chordal_ev_[4];
+  double chordal_ms_[3] = {0, 0, 0};
   DevBuf<V4> guess_stage_;           // rr_pgo_extend's initial guess: the old state and the new nodes behind it (made by that call)
   int host_counter_ = 0;             // mirrors the device slot counter
 
@@ -2978,6 +2987,133 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   int fixed_keep_anchor() const override { return fixed_keep_anchor_; }
   bool is_fixed(int v) const { return !fixed_host_.empty() && fixed_host_[(size_t)v] != 0; }
 
+  // ---- rr_pgo_initialize (include/rr_pgo.h; chordal.hip.h): the chordal relaxation from the measurements.
+  // Two (2-D) or three (3-D) linear stages on the pattern of H, each linearised by k_chordal_lin and factored and solved by
+  // the handle's own launches, eagerly and without the gauge term (a held node makes the systems definite); the solved
+  // vector of each is exported in reference order and its error flag read before the next stage is enqueued.  The state is
+  // written by ONE launch, k_chordal_place, behind the last clean flag: every refusal and failure leaves it as it was.
+  int chordal_anchor() const { return (priors_.keep_anchor && fixed_keep_anchor_) ? g_.anchor_node : -1; }
+  ChordalArgs<T, S> chordal_args() const {
+    ChordalArgs<T, S> a;
+    a.n_nodes = g_.n_nodes();
+    a.pose = pose_.p;
+    a.e_rec = e_rec_.p;
+    a.e_meas = e_meas_.p;
+    a.e_info = e_info3_.p;
+    a.e_slot = e_slot_.p;
+    a.inc_ptr = inc_ptr_.p;
+    a.inc_list = inc_list_.p;
+    a.node_dim = node_dim_.p;
+    a.node_offset = node_offset_.p;
+    a.diag_off = diag_off_.p;
+    a.hvals = hvals_.p;
+    a.b = b_.p;
+    a.zero_words = lds_flow_ ? dep_flags_.p : nullptr;
+    a.n_zero_words = lds_flow_ ? 2 * sym_.S + 64 : 0;
+    a.fill_words = lds_flow_ ? reinterpret_cast<unsigned *>(x_ptr_) : nullptr;
+    a.n_fill_words = lds_flow_ ? (int)((size_t)g_.dim * sizeof(T) / 4) : 0;
+    a.prior_ptr = priors_.n() > 0 ? prior_ptr_.p : nullptr;
+    a.prior_rec = prior_rec_.p;
+    a.prior_meas = prior_meas_.p;
+    a.prior_info = prior_info3_.p;
+    a.fixed = fixed_nodes_.empty() ? nullptr : fixed_.p;
+    a.anchor = chordal_anchor();
+    a.rot = chordal_rot_.p;
+    return a;
+  }
+  template <int STAGE> void chordal_stage() {
+    const ChordalArgs<T, S> a = chordal_args();
+    const unsigned nb = (unsigned)(((int64_t)g_.n_nodes() * LIN_GROUP + LIN_THREADS - 1) / LIN_THREADS);
+    if (is3d_) hipLaunchKernelGGL((k_chordal_lin<T, S, 6, STAGE>), dim3(nb), dim3(LIN_THREADS), 0, stream_, a);
+    else if constexpr (STAGE != 1) hipLaunchKernelGGL((k_chordal_lin<T, S, 3, STAGE>), dim3(nb), dim3(LIN_THREADS), 0, stream_, a);
+    check_launch("k_chordal_lin");
+    launch_factor_range(0, sym_.steps.size(), false);
+    launch_solve();
+    launch_step(false, STEP_EXPORT);   // the solved vector in reference order (dx_ref_), the state untouched
+    check_device_error();              // waits; a singular stage throws RR_PGO_ENOTSPD here
+  }
+  void initialize(int method) override {
+    if (sharded_ || world_ > 1)
+      throw ApiError(RR_PGO_EUNSUPPORTED, "rr_pgo_initialize: sharded handle (the relaxed systems are not split over ranks)");
+    if (method != RR_PGO_INIT_CHORDAL) throw ApiError(RR_PGO_EINVAL, "rr_pgo_initialize: unknown method " + std::to_string(method));
+    const int N = g_.n_nodes();
+    const int anchor = chordal_anchor();
+    {   // every free landmark needs a term that places it
+      std::vector<uint8_t> placed((size_t)N, 0);
+      for (int k = 0; k < g_.n_edges(); k++)
+        if (g_.edge_kind[k] == EDGE_SE2_XY || g_.edge_kind[k] == EDGE_SE3_XYZ) placed[(size_t)g_.edge_to[k]] = 1;
+      for (int32_t v : priors_.node) placed[(size_t)v] = 1;
+      for (int i = 0; i < N; i++) {
+        const int kind = g_.node_kind[i];
+        if ((kind == NODE_XY || kind == NODE_XYZ) && !placed[(size_t)i] && !is_fixed(i) && i != anchor)
+          throw ApiError(RR_PGO_EINVAL, "rr_pgo_initialize: landmark node " + std::to_string(i) + " (id " + std::to_string(g_.node_id[(size_t)i]) +
+                                            ") is free and has neither an SE2_XY / SE3_XYZ edge nor a prior: nothing places it");
+      }
+    }
+    {   // every set of poses connected by pose-pose edges needs a held pose or a pose prior: without one the rotation stage's
+      // matrix is a singular block Laplacian, whose last pivot is zero in exact arithmetic only -- decided here, not by rounding
+      std::vector<int32_t> root((size_t)N);
+      for (int i = 0; i < N; i++) root[(size_t)i] = i;
+      auto find = [&](int v) {
+        while (root[(size_t)v] != v) { root[(size_t)v] = root[(size_t)root[(size_t)v]]; v = root[(size_t)v]; }
+        return v;
+      };
+      for (int k = 0; k < g_.n_edges(); k++)
+        if (g_.edge_kind[k] == EDGE_SE2 || g_.edge_kind[k] == EDGE_SE3) root[(size_t)find(g_.edge_from[k])] = find(g_.edge_to[k]);
+      std::vector<uint8_t> grounded((size_t)N, 0);
+      auto is_pose = [&](int v) { return g_.node_kind[(size_t)v] == NODE_SE2 || g_.node_kind[(size_t)v] == NODE_SE3; };
+      for (int i = 0; i < N; i++)
+        if (is_pose(i) && (is_fixed(i) || i == anchor)) grounded[(size_t)find(i)] = 1;
+      for (int32_t v : priors_.node)
+        if (is_pose(v)) grounded[(size_t)find(v)] = 1;
+      for (int i = 0; i < N; i++)
+        if (is_pose(i) && !grounded[(size_t)find(i)])
+          throw ApiError(RR_PGO_ENOTSPD, "rr_pgo_initialize: the poses connected to node " + std::to_string(i) +
+                                             " hold neither a fixed node, a kept anchor nor a pose prior: the relaxed systems are singular");
+    }
+    if (!chordal_rot_.p) {
+      chordal_rot_.alloc((size_t)N * (is3d_ ? 9 : 2));
+      if (is3d_) chordal_sol_.alloc((size_t)g_.dim);
+      for (EventHolder &e : chordal_ev_) e.create(hipEventDefault);
+    }
+    for (double &m : chordal_ms_) m = 0;
+    clear_stop_word();
+    ChordalNodeArgs<T, S> na;
+    na.n_nodes = N;
+    na.is3d = is3d_ ? 1 : 0;
+    na.pose = pose_.p;
+    na.node_dim = node_dim_.p;
+    na.node_offset = node_offset_.p;
+    na.fixed = fixed_nodes_.empty() ? nullptr : fixed_.p;
+    na.anchor = anchor;
+    na.sol_a = is3d_ ? chordal_sol_.p : dx_ref_.p;
+    na.sol_b = dx_ref_.p;
+    na.rot = chordal_rot_.p;
+    const unsigned nb = (unsigned)((N + 255) / 256);
+    HIPCHK(hipEventRecord(chordal_ev_[0], stream_));
+    chordal_stage<0>();
+    if (is3d_) {
+      HIPCHK(hipMemcpyAsync(chordal_sol_.p, dx_ref_.p, (size_t)g_.dim * sizeof(T), hipMemcpyDeviceToDevice, stream_));
+      chordal_stage<1>();
+    }
+    hipLaunchKernelGGL((k_chordal_project<T, S>), dim3(nb), dim3(256), 0, stream_, na);
+    check_launch("k_chordal_project");
+    HIPCHK(hipEventRecord(chordal_ev_[1], stream_));
+    chordal_stage<2>();
+    HIPCHK(hipEventRecord(chordal_ev_[2], stream_));
+    na.sol_a = dx_ref_.p;
+    hipLaunchKernelGGL((k_chordal_place<T, S>), dim3(nb), dim3(256), 0, stream_, na);
+    check_launch("k_chordal_place");
+    HIPCHK(hipEventRecord(chordal_ev_[3], stream_));
+    HIPCHK(hipStreamSynchronize(stream_));
+    float t01 = 0, t12 = 0, t03 = 0;
+    HIPCHK(hipEventElapsedTime(&t01, chordal_ev_[0], chordal_ev_[1]));
+    HIPCHK(hipEventElapsedTime(&t12, chordal_ev_[1], chordal_ev_[2]));
+    HIPCHK(hipEventElapsedTime(&t03, chordal_ev_[0], chordal_ev_[3]));
+    chordal_ms_[0] = t01; chordal_ms_[1] = t12; chordal_ms_[2] = t03;
+  }
+  void initialize_times(double *ms) const override { for (int k = 0; k < 3; k++) ms[k] = chordal_ms_[k]; }
+
   void prior_errors(double *s_out, double *w_out) override {
     refuse_priors("rr_pgo_prior_errors");
     const int P = priors_.n();
@@ -5082,6 +5218,17 @@ int rr_pgo_set_marginals_big_fronts(rr_pgo *h, int32_t on) {
   return guarded([&] { h->engine->set_marginals_big_fronts(on); });
 }
 int32_t rr_pgo_get_marginals_big_fronts(const rr_pgo *h) { return h ? (int32_t)h->engine->marginals_big_fronts() : 0; }
+
+int rr_pgo_initialize(rr_pgo *h, int32_t method) {
+  if (!h) { g_last_error = "rr_pgo_initialize: no handle"; return RR_PGO_EINVAL; }
+  return guarded([&] { h->engine->initialize(method); });
+}
+
+int rr_pgo_initialize_times(const rr_pgo *h, double *ms) {
+  if (!h || !ms) { g_last_error = "null argument"; return RR_PGO_EINVAL; }
+  h->engine->initialize_times(ms);
+  return RR_PGO_OK;
+}
 
 int32_t rr_pgo_num_fixed(const rr_pgo *h) { return h ? (int32_t)h->engine->fixed().size() : 0; }
 

@@ -429,6 +429,23 @@ class PoseGraph:
         _check(_lib.load().rr_pgo_get_fixed(self._h, _ip(out) if len(out) else None))
         return out
 
+    # -- initialisation from the measurements (include/rr_pgo.h, rr_pgo_initialize) ------------
+    INIT_METHODS = {"chordal": 0}
+
+    def initialize(self, method="chordal"):
+        """rr_pgo_initialize: replace the state of every free node by the chordal relaxation of the graph (relaxed rotations,
+        projection onto SO(d), positions).  Fixed nodes and a kept anchor are held at their current state; the robust setting
+        plays no part.  method: "chordal", or the C enum's integer."""
+        if isinstance(method, str):
+            if method not in self.INIT_METHODS:
+                raise ValueError(f"unknown initialisation method {method!r}: 'chordal'")
+            method = self.INIT_METHODS[method]
+        _check(_lib.load().rr_pgo_initialize(self._h, int(method)))
+
+    def initialize_times(self):
+        """HIP-event milliseconds of the last initialize call: (rotation stages with the projection, position stage, whole call)."""
+        return self._times(_lib.load().rr_pgo_initialize_times)
+
     # -- factor queries on fronts beyond LDS (include/rr_pgo.h, "factor queries on fronts beyond LDS") --
     @property
     def query_big_fronts(self):
