@@ -273,8 +273,8 @@ int rr_pgo_set_robust_tls(rr_pgo *h, double delta, double mu, const int32_t *edg
 /* mu alone: no mask upload, no allocation; every later launch reads the new value (captured iterations are captured anew).
  * EINVAL unless the handle's kernel is RR_PGO_ROBUST_TLS, or mu not finite or <= 0. */
 int rr_pgo_set_robust_mu(rr_pgo *h, double mu);
-/* The handle's kernel; any pointer may be NULL.  mu = 0 for the kinds other than TLS, delta = 1 for NONE.  rr_pgo_extend and
- * rr_pgo_remove_edges carry kind, delta, mu and the mask (a new edge is robustified, the mask of removed edges goes). */
+/* The handle's kernel; any pointer may be NULL.  mu = 0 for the kinds other than TLS, delta = 1 for NONE.  Carried by
+ * rr_pgo_extend and rr_pgo_remove_edges (the list under rr_pgo_extend). */
 int rr_pgo_get_robust(const rr_pgo *h, int32_t *kind, double *delta, double *mu);
 
 #define RR_PGO_ROBUST_TLS 3   /* reported by rr_pgo_get_robust; NOT accepted by rr_pgo_set_robust_kernel */
@@ -338,6 +338,7 @@ int rr_pgo_gnc_times(const rr_pgo *h, double *ms);
  * queries below.  The state, the Levenberg-Marquardt lambda and the robust setting are untouched; captured graphs are
  * dropped, as by rr_pgo_set_robust_kernel.  On RR_PGO_F32 / RR_PGO_MIXED handles whose Gauss-Newton steps use the gauge
  * transfer (a big root front), that transfer is off while the list is non-empty: the system is then the one described here.
+ * Carried by rr_pgo_extend and rr_pgo_remove_edges (the list under rr_pgo_extend).
  * RR_PGO_EINVAL, decided before anything changes, the message names the prior: n_priors < 0, a null required pointer, a
  * node out of range, a non-finite value, Omega not positive definite, an SE3 measurement whose quaternion has zero norm.
  * RR_PGO_EUNSUPPORTED (the message says which): sharded handles; handles created under RR_PGO_EDGE_LINEARIZE=1 or =2 (the
@@ -377,7 +378,7 @@ int rr_pgo_prior_errors(rr_pgo *h, double *s_out, double *weight_out /* may be N
  * rr_pgo_marginals, rr_pgo_covariances, rr_pgo_gate_edges, rr_pgo_gate_joint: Sigma is the covariance conditional on the
  * fixed nodes, (H_ff)^-1 on the free nodes; every block with a fixed node in it, its own diagonal block included, is
  * returned as zeros; a gate candidate with a fixed endpoint a gets S = Omega^-1 + B Sigma_bb B^T, one with both S = Omega^-1.
- * rr_pgo_extend carries the set and keep_anchor; old indices do not change, new nodes are free.
+ * Carried by rr_pgo_extend and rr_pgo_remove_edges (the list under rr_pgo_extend).
  * RR_PGO_EINVAL, decided before anything changes, the message names the entry: n_fixed < 0, null node with n_fixed > 0, a
  * node out of range.  RR_PGO_EUNSUPPORTED (the message says which): sharded handles; handles created under
  * RR_PGO_EDGE_LINEARIZE=1 or =2. */
@@ -645,11 +646,16 @@ int32_t rr_pgo_get_query_big_fronts(const rr_pgo *h);   /* 0 or 1; 0 without a h
  * before anything changes.  One kernel (k_guess_nodes) executes the steps in the state's arithmetic type, dependent steps in
  * list order, (cos, sin) and quaternions renormalised; the guessed values of the new nodes are copied into the host graph
  * (rr_pgo_get_graph shows them, the analysis sees what a fresh handle on that graph would).
- * Carried over: the solver option; the robust kernel's kind and delta; its edge mask, extended with 1 for every new edge (a
- * fresh closure is robustified; a NULL mask stays NULL); the prior list of rr_pgo_set_priors with its robust flags and
- * keep_anchor (node indices do not change); the rr_pgo_set_query_big_fronts and rr_pgo_set_marginals_big_fronts switches.  NOT carried: captured graphs, the tree and selected-inverse tables of
- * the queries, rr_pgo_set_state's memo of the previous state, the Levenberg-Marquardt lambda and the *_times of earlier calls;
- * rr_pgo_stream may return another stream.  Pointers from an earlier rr_pgo_get_graph become invalid.
+ * Carried over -- by this call and by rr_pgo_remove_edges, the two calls that rebuild a handle; this is the one list:
+ *   the solver option;
+ *   the robust kernel: kind, delta, the mu of RR_PGO_ROBUST_TLS, and the edge mask re-indexed to the new edges -- here the
+ *     old entries followed by 1 for every new edge (a fresh closure is robustified); a NULL mask stays NULL;
+ *   the prior list of rr_pgo_set_priors with its robust flags and keep_anchor (node indices do not change);
+ *   the fixed set of rr_pgo_set_fixed with its keep_anchor (new nodes are free);
+ *   the rr_pgo_set_query_big_fronts and rr_pgo_set_marginals_big_fronts switches.
+ * NOT carried: captured graphs, the tree and selected-inverse tables of the queries, rr_pgo_set_state's memo of the previous
+ * state, the Levenberg-Marquardt lambda and the *_times of earlier calls; rr_pgo_stream may return another stream.  Pointers
+ * from an earlier rr_pgo_get_graph become invalid.
  * Atomic: the new graph, analysis and engine are built completely and then swapped in; the old stream is synchronised before
  * the old engine goes.  Any failure -- RR_PGO_EINVAL below, RR_PGO_ENOMEM, a HIP error (RR_PGO_ENODEVICE) -- leaves the handle
  * as it was, usable, with the same bits.
@@ -674,9 +680,9 @@ int rr_pgo_extend_times(const rr_pgo *h, double *ms);
  * After the call the handle is the handle rr_pgo_create would return for the remaining graph, with the handle's options and
  * under the environment as it is at the call -- except that the device state of every node is the old device state bit for
  * bit (copied device to device, as rr_pgo_extend carries it).
- * Carried over: the solver option; the robust kernel's kind and delta; its edge mask with the removed entries cut out (a NULL
- * mask stays NULL); the prior list with its robust flags; the fixed set; both keep_anchor settings; the rr_pgo_set_query_big_fronts and rr_pgo_set_marginals_big_fronts switches.  NOT carried: what
- * rr_pgo_extend does not carry.  Atomic as rr_pgo_extend: any failure leaves the handle as it was, with the same bits.
+ * Carried over and NOT carried: the list under rr_pgo_extend, with one difference -- the robust kernel's edge mask keeps the
+ * entries of the remaining edges, in their order.  Atomic as rr_pgo_extend: any failure leaves the handle as it was, with the
+ * same bits.
  * RR_PGO_EINVAL, decided before anything changes: n_remove < 0, null edge with n_remove > 0, an index out of range, a node
  * left without any edge (the message names the node).  A removal that only disconnects the graph is the caller's
  * responsibility, as with keep_anchor == 0: the system then ends as RR_PGO_ENOTSPD, and redundancy_out of rr_pgo_check_edges

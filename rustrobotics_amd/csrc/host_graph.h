@@ -147,6 +147,16 @@ inline std::vector<int32_t> copy_without_edges(const HostGraph &og, const char *
   return keep;
 }
 
+// rr_pgo_extend / rr_pgo_remove_edges: the robust edge mask of a rebuilt graph.  origin[k] is the old index of new edge k, -1
+// for an edge the old graph did not have (a fresh edge is robustified: 1).  An empty mask (every edge) stays empty.
+inline std::vector<uint8_t> reindex_edge_mask(const std::vector<uint8_t> &mask, const std::vector<int32_t> &origin) {
+  std::vector<uint8_t> out;
+  if (mask.empty()) return out;
+  out.reserve(origin.size());
+  for (const int32_t k : origin) out.push_back(k < 0 ? 1 : mask[(size_t)k]);
+  return out;
+}
+
 // parse_g2o, g2o.rs:35-143.  Returns "" or an error message; io_error set when
 // the file could not be read (Err(io) in the reference) as opposed to malformed.
 std::string load_g2o(const char *path, HostGraph &g, bool &io_error);

@@ -251,6 +251,29 @@ struct PriorSet {
   int n() const { return (int)node.size(); }
 };
 
+// What a handle has been told since it was created, as its setters normalised it.  rr_pgo_extend and rr_pgo_remove_edges
+// build a new engine and carry this record to it: carry_settings is the ONE place that enumerates the fields, so a new
+// field is carried by adding it there.  (The engine's device copies and derived host tables are not settings.)
+struct HandleSettings {
+  // robust kernel (rr_pgo_set_robust_kernel / rr_pgo_set_robust_tls): ROBUST_* of kernels.hip.h; delta is 1 under ROBUST_NONE;
+  // mu is ROBUST_TLS's continuation parameter, 0 under every other kind; the per-edge mask (empty: every edge)
+  int robust_kind = ROBUST_NONE;
+  double robust_delta = 1.0, robust_mu = 0.0;
+  std::vector<uint8_t> robust_mask;
+  PriorSet priors;                  // rr_pgo_set_priors: the caller's list (keep_anchor is 1 while it is empty)
+  std::vector<int32_t> fixed;       // rr_pgo_set_fixed: the distinct nodes in ascending order
+  int fixed_keep_anchor = 1;        // (1 while the set is empty)
+  bool query_big = false;           // rr_pgo_set_query_big_fronts: fronts beyond LDS go to the k_tree_*_big kernels
+  bool marg_big = false;            // rr_pgo_set_marginals_big_fronts: ... and to the k_selinv_big_* kernels
+};
+
+// an edge mask of the ABI in the record's form: one byte per edge, 0 or 1; null: empty (every edge)
+static std::vector<uint8_t> mask_bytes(const int32_t *mask, int n_edges) {
+  std::vector<uint8_t> m(mask ? (size_t)n_edges : 0);
+  for (size_t k = 0; k < m.size(); k++) m[k] = mask[k] != 0 ? 1 : 0;
+  return m;
+}
+
 struct EngineBase {
   enum Query { Q_MARGINALS, Q_COVARIANCES, Q_GATE, Q_GATE_JOINT, Q_CROSS, Q_CHECK, N_QUERY };   // the factor queries, in the order of their ABI functions
   virtual ~EngineBase() = default;
@@ -276,7 +299,9 @@ struct EngineBase {
   virtual void stage(int stage, double lambda, int lm) = 0;
   virtual void read_last_scalars(double *chi, double *norm) = 0;
   virtual void debug_withhold(int mode) = 0;   // failure injection for the dataflow launches (rr_pgo_debug_withhold)
-  virtual void set_robust(int kind, double delta, double mu, const int32_t *mask) = 0;   // rr_pgo_set_robust_kernel / rr_pgo_set_robust_tls (arguments checked; mu: ROBUST_TLS alone)
+  virtual const HandleSettings &settings() const = 0;   // what the setters below have left: read by the ABI's getters and by the carry
+  // rr_pgo_set_robust_kernel / rr_pgo_set_robust_tls (arguments checked; mu: ROBUST_TLS alone; mask: in the record's form)
+  virtual void set_robust(int kind, double delta, double mu, std::vector<uint8_t> mask) = 0;
   virtual void set_robust_mu(double mu) = 0;                                   // rr_pgo_set_robust_mu (arguments checked)
   // rr_pgo_optimize_gnc (arguments checked) / rr_pgo_gnc_times
   virtual void optimize_gnc(int solver, const rr_pgo_gnc_options &opt, const int32_t *mask, rr_pgo_gnc_result *res, double *stage_mu, double *stage_cost) = 0;
@@ -284,12 +309,9 @@ struct EngineBase {
   virtual void edge_errors(double *s_out, double *w_out) = 0;                  // rr_pgo_edge_errors
   virtual void refuse_priors(const char *who) const = 0;                       // EUNSUPPORTED where priors cannot be held
   virtual void set_priors(const PriorSet &ps) = 0;                             // rr_pgo_set_priors (arguments checked)
-  virtual const PriorSet &priors() const = 0;
   virtual void prior_errors(double *s_out, double *w_out) = 0;                 // rr_pgo_prior_errors
   virtual void refuse_fixed(const char *who) const = 0;                        // EUNSUPPORTED where fixed nodes cannot be held
   virtual void set_fixed(const std::vector<int32_t> &nodes, int keep_anchor) = 0;   // rr_pgo_set_fixed (distinct, ascending, checked)
-  virtual const std::vector<int32_t> &fixed() const = 0;
-  virtual int fixed_keep_anchor() const = 0;
   virtual void initialize(int method) = 0;                       // rr_pgo_initialize / rr_pgo_initialize_times
   virtual void initialize_times(double *ms) const = 0;
   // rr_pgo_marginals (arguments checked; off: [nq + 1] offsets of the blocks in out) / rr_pgo_marginals_times
@@ -305,10 +327,8 @@ struct EngineBase {
   virtual void check_edges(int n, const int32_t *from, const int32_t *to, const int64_t *soff, std::vector<GateCand> &cand,
                            double *d2, double *red, double *chi2, double *resid) = 0;
   virtual void refuse_factor_query(const char *who) const = 0;   // what every factor query refuses, before its arguments are read
-  virtual void set_query_big_fronts(int on) = 0;                  // rr_pgo_set_query_big_fronts / rr_pgo_get_query_big_fronts
-  virtual int query_big_fronts() const = 0;
-  virtual void set_marginals_big_fronts(int on) = 0;              // rr_pgo_set_marginals_big_fronts / rr_pgo_get_marginals_big_fronts
-  virtual int marginals_big_fronts() const = 0;
+  virtual void set_query_big_fronts(int on) = 0;                  // rr_pgo_set_query_big_fronts
+  virtual void set_marginals_big_fronts(int on) = 0;              // rr_pgo_set_marginals_big_fronts
   // rr_pgo_gate_joint (arguments checked; set s is the records [set_ptr[s], set_ptr[s + 1]) of from / to / cand, the sets
   // expanded one after the other; dim: D_s; ioff: [n_sets + 1] offsets of the sets' S in innov; prefix and innov may be null) /
   // rr_pgo_gate_joint_times
@@ -330,8 +350,6 @@ struct EngineBase {
   virtual const void *guess_dev() const = 0;
   // the first n_nodes nodes of the state from src (device memory of the same arithmetic type), on this engine's stream; waits
   virtual void adopt_state(const void *src, size_t n_nodes, double *ms) = 0;
-  virtual void robust_setting(int *kind, double *delta, bool *masked, std::vector<int32_t> &mask) const = 0;
-  virtual double robust_mu() const = 0;   // of ROBUST_TLS, 0 under every other kind
   int n_launches_per_iter = 0;
   // rr_pgo_launch_counts: iterations put on the stream as plain launches / as replays of the captured hipGraph / as items of
   // the device-side loop, and instantiations of that graph.  Host-side, counted where the launches are enqueued.
@@ -547,7 +565,6 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   bool sel_ready_ = false;
   // fronts beyond LDS in the selected inverse (rr_pgo_set_marginals_big_fronts): per level the LDS fronts
   // come first in sel_order_, and the tiles of the others' kernels follow each other, launch by launch, in sel_tile_
-  bool marg_big_ = false;
   std::vector<int32_t> sel_big_ptr_;     // per level: its first front beyond LDS in sel_order_
   std::vector<int32_t> sel_tile_ptr_;    // ranges of sel_tile_: k_selinv_big_z, _y, _zz; then per level: k_selinv_big_rp, _pp
   DevBuf<SelBig> sel_big_;
@@ -559,7 +576,6 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   size_t ts_lds_ = 0;
   size_t ts_ws_bytes_ = TS_WS_BYTES;   // bound of Z + U of one pass (RR_PGO_TS_WS_BYTES=<n>, read at creation)
   bool ts_ready_ = false;
-  bool query_big_ = false;             // rr_pgo_set_query_big_fronts: fronts beyond LDS go to the k_tree_*_big kernels
   bool ts_trace_ = false;              // RR_PGO_QUERY_TRACE=1, read at creation: every pass of a tree query describes its plan on stderr
   DevBuf<TsTask> ts_tasks_;
   DevBuf<TsSlab> ts_slab_, cross_slab_;   // slabs of the fronts beyond LDS, by level: rows below (forward), pivot rows (backward)
@@ -603,32 +619,25 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   bool edge_lin_wave_ = false;      // RR_PGO_EDGE_LINEARIZE=2: k_linearize_wave_edges (one WAVEFRONT per edge, operands staged in LDS, LDS-reduced scatter-add)
   bool edge_lin_env_ = false, edge_lin_wave_env_ = false;   // what the knob asked for (a robust kernel runs the pull form)
   int lin_blocks_pull_ = 0, lin_blocks_edge_ = 0;            // n_lin_blocks_ of the pull form / of the edge-parallel form
-  // robust kernel (rr_pgo_set_robust_kernel): ROBUST_* of kernels.hip.h, delta, per-edge mask (empty: every edge)
-  int robust_kind_ = ROBUST_NONE;
-  double robust_delta_ = 1.0;
-  double robust_mu_ = 0.0;           // ROBUST_TLS: the continuation parameter (0 under every other kind)
+  HandleSettings settings_;          // everything the setters were told (the robust kernel, the priors, the fixed nodes, the big-front switches)
   // rr_pgo_optimize_gnc: k_edge_errors' (s, w) and k_tls_scan's partials on the device, the scan's four numbers in host-coherent
   // memory, the time of the last call's scans / stages / closing iterations
   DevBuf<double> gnc_sw_, gnc_partial_;
   DevBuf<int> gnc_done_;
   PinnedBuf<double> gnc_host_;
   double gnc_ms_[3] = {0, 0, 0};
-  DevBuf<uint8_t> robust_mask_;
-  std::vector<uint8_t> robust_mask_host_;
-  // priors (rr_pgo_set_priors): the caller's list, and its device form -- CSR by node, records in CSR order (a node's priors
+  DevBuf<uint8_t> robust_mask_;      // the robust kernel's per-edge mask on the device (none: every edge)
+  // priors (rr_pgo_set_priors): the device form of settings_.priors -- CSR by node, records in CSR order (a node's priors
   // in the call's order).  The buffers live in the arena and only grow (DevBuf::n is their capacity).
-  PriorSet priors_;
   std::vector<int32_t> prior_order_;   // CSR position -> index in the call
   DevBuf<int32_t> prior_ptr_, prior_node_;
   DevBuf<EdgeRec<S>> prior_rec_;       // SE(2)
   DevBuf<V4> prior_meas_;              // SE(3)
   DevBuf<S> prior_info3_;              // SE(3)
   DevBuf<uint8_t> prior_robust_;
-  // fixed nodes (rr_pgo_set_fixed): the distinct nodes in ascending order, and one byte per node on the device (arena;
+  // fixed nodes (rr_pgo_set_fixed): settings_.fixed as one byte per node, on the host and on the device (arena;
   // allocated by the first non-empty set).  While the set is empty k_linearize and k_update get a null pointer.
-  std::vector<int32_t> fixed_nodes_;
   std::vector<uint8_t> fixed_host_;    // [n_nodes] while the set is non-empty (the queries' plans read it)
-  int fixed_keep_anchor_ = 1;
   DevBuf<uint8_t> fixed_;
   // rr_pgo_initialize (chordal.hip.h): the projected rotations per node, the exported solution of the first rotation stage
   // (3-D), the events around the stages and the last call's times; buffers and events are made by the first call
@@ -1773,7 +1782,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   // Gauss-Newton with a single-precision factor: no anchor prior, the root front carries the gauge term
   // (not with priors: the gauge term assumes that H without the anchor term is singular along the SE(2) gauge)
   // (nor with fixed nodes, rr_pgo_set_fixed: their identity rows are no part of that singular system)
-  bool gauge_rule(int lm, bool reference_prior = false) const { return gauge_ok_ && !lm && !reference_prior && priors_.n() == 0 && fixed_nodes_.empty(); }
+  bool gauge_rule(int lm, bool reference_prior = false) const { return gauge_ok_ && !lm && !reference_prior && settings_.priors.n() == 0 && settings_.fixed.empty(); }
   static Lin lin_chi2() { return Lin{0, false, 0, 0.0}; }
   Lin lin_system(double lambda, int lm) const { return Lin{1, gauge_rule(lm), lm, lambda}; }
   Lin lin_reference_system(double lambda, int lm) const { return Lin{1, gauge_rule(lm, true), lm, lambda}; }   // rr_pgo_assemble: always the anchor prior
@@ -1800,7 +1809,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     a.hvals = hvals_.p;
     a.b = b_.p;
     a.chi2_partial = chi_partial_.p;
-    a.anchor = ((m.write_system && m.gauge) || !priors_.keep_anchor || !fixed_keep_anchor_) ? -1 : g_.anchor_node;
+    a.anchor = ((m.write_system && m.gauge) || !settings_.priors.keep_anchor || !settings_.fixed_keep_anchor) ? -1 : g_.anchor_node;
     a.lambda = m.lm ? (S)m.lambda : (S)0;
     a.write_system = m.write_system;
     a.adds_diag = norm_counts_.p;
@@ -1819,12 +1828,12 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     a.blocks_done = blocks_done_.p + 1;
     robust_fields(a);
     prior_fields(a);
-    a.fixed = fixed_nodes_.empty() ? nullptr : fixed_.p;   // (every instantiation reads it)
+    a.fixed = settings_.fixed.empty() ? nullptr : fixed_.p;   // (every instantiation reads it)
     return a;
   }
   void robust_fields(LinArgs<T, S> &a) const {
-    a.robust_delta = (S)robust_delta_;
-    a.robust_delta2 = (S)(robust_delta_ * robust_delta_);
+    a.robust_delta = (S)settings_.robust_delta;
+    a.robust_delta2 = (S)(settings_.robust_delta * settings_.robust_delta);
     a.robust_mask = robust_mask_.n ? robust_mask_.p : nullptr;
     const TlsParams p = tls_params();
     a.tls_lo = (S)p.lo; a.tls_hi = (S)p.hi; a.tls_cs = (S)p.cs; a.tls_mu = (S)p.mu;
@@ -1832,9 +1841,9 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   // ROBUST_TLS: what the host precomputes from (delta, mu) for every kernel that reads the weight (zeros under the other kinds)
   struct TlsParams { double lo, hi, cs, mu; };
   TlsParams tls_params() const {
-    if (robust_kind_ != ROBUST_TLS) return TlsParams{0.0, 0.0, 0.0, 0.0};
-    const double c2 = robust_delta_ * robust_delta_, mu = robust_mu_;
-    return TlsParams{mu / (mu + 1.0) * c2, (mu + 1.0) / mu * c2, robust_delta_ * std::sqrt(mu * (mu + 1.0)), mu};
+    if (settings_.robust_kind != ROBUST_TLS) return TlsParams{0.0, 0.0, 0.0, 0.0};
+    const double c2 = settings_.robust_delta * settings_.robust_delta, mu = settings_.robust_mu;
+    return TlsParams{mu / (mu + 1.0) * c2, (mu + 1.0) / mu * c2, settings_.robust_delta * std::sqrt(mu * (mu + 1.0)), mu};
   }
   void prior_fields(LinArgs<T, S> &a) const {   // (read by the PR instantiations alone: launch_pull)
     a.prior_ptr = prior_ptr_.p;
@@ -1935,9 +1944,9 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
       else hipLaunchKernelGGL((k_linearize_edges<T, S>), dim3(n_lin_blocks_), dim3(LIN_THREADS), 0, stream_, la, g_.n_edges());
       if (m.write_system) hipLaunchKernelGGL((k_lin_finish<T, S>), dim3(nb), dim3(256), 0, stream_, la);
     } else {
-      if (robust_kind_ == ROBUST_HUBER) launch_pull<ROBUST_HUBER>(la);
-      else if (robust_kind_ == ROBUST_CAUCHY) launch_pull<ROBUST_CAUCHY>(la);
-      else if (robust_kind_ == ROBUST_TLS) launch_pull<ROBUST_TLS>(la);
+      if (settings_.robust_kind == ROBUST_HUBER) launch_pull<ROBUST_HUBER>(la);
+      else if (settings_.robust_kind == ROBUST_CAUCHY) launch_pull<ROBUST_CAUCHY>(la);
+      else if (settings_.robust_kind == ROBUST_TLS) launch_pull<ROBUST_TLS>(la);
       else launch_pull<ROBUST_NONE>(la);
     }
     check_launch("k_linearize");
@@ -1945,16 +1954,16 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   }
   template <int RK> void launch_pull(const LinArgs<T, S> &la) {   // the pull form of either dimension under robust kernel RK
     if (has_lm_) {   // a 3-D graph with XYZ landmarks: the LM instantiations (a pure SE(3) handle launches the kernels it always did)
-      if (priors_.n() > 0) hipLaunchKernelGGL((k_linearize_lm<T, S, RK, true>), dim3(n_lin_blocks_), dim3(LIN_THREADS), 0, stream_, la);
+      if (settings_.priors.n() > 0) hipLaunchKernelGGL((k_linearize_lm<T, S, RK, true>), dim3(n_lin_blocks_), dim3(LIN_THREADS), 0, stream_, la);
       else hipLaunchKernelGGL((k_linearize_lm<T, S, RK, false>), dim3(n_lin_blocks_), dim3(LIN_THREADS), 0, stream_, la);
       return;
     }
     if (has_br_) {   // a 2-D graph with bearing-only / range-only edges: the BR instantiations (every other 2-D handle launches the kernels it always did)
-      if (priors_.n() > 0) hipLaunchKernelGGL((k_linearize_br<T, S, RK, true>), dim3(n_lin_blocks_), dim3(LIN_THREADS), 0, stream_, la);
+      if (settings_.priors.n() > 0) hipLaunchKernelGGL((k_linearize_br<T, S, RK, true>), dim3(n_lin_blocks_), dim3(LIN_THREADS), 0, stream_, la);
       else hipLaunchKernelGGL((k_linearize_br<T, S, RK, false>), dim3(n_lin_blocks_), dim3(LIN_THREADS), 0, stream_, la);
       return;
     }
-    if (priors_.n() > 0) {   // (a handle without priors launches the kernels it always did)
+    if (settings_.priors.n() > 0) {   // (a handle without priors launches the kernels it always did)
       if (is3d_) hipLaunchKernelGGL((k_linearize<T, S, RK, 6, true>), dim3(n_lin_blocks_), dim3(LIN_THREADS), 0, stream_, la);
       else hipLaunchKernelGGL((k_linearize<T, S, RK, 3, true>), dim3(n_lin_blocks_), dim3(LIN_THREADS), 0, stream_, la);
       return;
@@ -2161,7 +2170,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     u.export_only = export_only ? 1 : 0;
     u.err = dx_ref_in ? nullptr : err_.p;
     u.gate = gate;
-    u.fixed = fixed_nodes_.empty() ? nullptr : fixed_.p;
+    u.fixed = settings_.fixed.empty() ? nullptr : fixed_.p;
     u.fin = fin;
     if (has_lm_) hipLaunchKernelGGL((k_update_lm<T, S>), dim3(n_upd_blocks_), dim3(UPD_THREADS), 0, stream_, u);
     else if (is3d_) hipLaunchKernelGGL((k_update<T, S, 6>), dim3(n_upd_blocks_), dim3(UPD_THREADS), 0, stream_, u);
@@ -2577,13 +2586,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     if (n_nodes > (size_t)g_.n_nodes()) throw ApiError(RR_PGO_EINVAL, "internal: more nodes adopted than the graph has");
     *ms = timed_ms([&] { copy_words16(src, pose_.p, n_nodes * pose_node_bytes()); });
   }
-  void robust_setting(int *kind, double *delta, bool *masked, std::vector<int32_t> &mask) const override {
-    *kind = robust_kind_;
-    *delta = robust_delta_;
-    *masked = !robust_mask_host_.empty();
-    mask.assign(robust_mask_host_.begin(), robust_mask_host_.end());
-  }
-  double robust_mu() const override { return robust_kind_ == ROBUST_TLS ? robust_mu_ : 0.0; }
+  const HandleSettings &settings() const override { return settings_; }
 
   void assemble(double lambda, int lm, std::vector<double> &hv, std::vector<double> &b) override {
     refuse_rank_partial("rr_pgo_assemble");
@@ -2750,18 +2753,15 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   }
 
   // ---- robust kernels (include/rr_pgo.h, rr_pgo_set_robust_kernel)
-  void set_robust(int kind, double delta, double mu, const int32_t *mask) override {
-    std::vector<uint8_t> m;
-    if (kind != ROBUST_NONE && mask) {
-      m.resize((size_t)g_.n_edges());
-      for (int k = 0; k < g_.n_edges(); k++) m[k] = mask[k] != 0 ? 1 : 0;
-    }
+  void set_robust(int kind, double delta, double mu, std::vector<uint8_t> m) override {   // m: empty, or 0 / 1 per edge
+    if (kind == ROBUST_NONE) m.clear();
+    if (!m.empty() && m.size() != (size_t)g_.n_edges()) throw ApiError(RR_PGO_EINVAL, "internal: robust mask of another graph");
     HIPCHK(hipStreamSynchronize(stream_));   // launches already enqueued read the old mask
     robust_mask_.upload(m);                  // (empty: freed, every edge)
-    robust_mask_host_ = m;                   // (rr_pgo_extend carries the setting to the grown graph's engine)
-    robust_kind_ = kind;
-    robust_delta_ = kind != ROBUST_NONE ? delta : 1.0;
-    robust_mu_ = kind == ROBUST_TLS ? mu : 0.0;
+    settings_.robust_mask = std::move(m);
+    settings_.robust_kind = kind;
+    settings_.robust_delta = kind != ROBUST_NONE ? delta : 1.0;
+    settings_.robust_mu = kind == ROBUST_TLS ? mu : 0.0;
     // the captured graphs hold the old kernel and its arguments
     drop_graphs();
     // the edge-parallel experiment forms have no robust instantiation: the pull form runs while a kernel is set
@@ -2772,14 +2772,14 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   // mu alone (rr_pgo_set_robust_mu): a kernel argument of every later launch.  The captured graphs hold the old value: dropped
   // (behind whatever replay is still on the stream), so the next iteration captures anew.  No mask upload, no allocation.
   void set_robust_mu(double mu) override {
-    if (robust_kind_ != ROBUST_TLS) throw ApiError(RR_PGO_EINVAL, "rr_pgo_set_robust_mu: the handle's robust kernel is not RR_PGO_ROBUST_TLS");
+    if (settings_.robust_kind != ROBUST_TLS) throw ApiError(RR_PGO_EINVAL, "rr_pgo_set_robust_mu: the handle's robust kernel is not RR_PGO_ROBUST_TLS");
     bool captured = gn_exec_ != nullptr;
     for (hipGraphExec_t e : stage_exec_) captured = captured || e != nullptr;
     if (captured) {
       HIPCHK(hipStreamSynchronize(stream_));
       drop_graphs();
     }
-    robust_mu_ = mu;
+    settings_.robust_mu = mu;
   }
   // ---- graduated non-convexity on truncated least squares (include/rr_pgo.h, rr_pgo_optimize_gnc)
   // One scan: the k_edge_errors family into device memory, k_tls_scan over it, ONE synchronisation, four numbers read.
@@ -2793,7 +2793,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     a.w = gnc_sw_.p + E;
     a.mask = robust_mask_.n ? robust_mask_.p : nullptr;
     const TlsParams p = tls_params();
-    a.delta2 = (S)(robust_delta_ * robust_delta_);
+    a.delta2 = (S)(settings_.robust_delta * settings_.robust_delta);
     a.tls_lo = (S)p.lo; a.tls_hi = (S)p.hi; a.tls_cs = (S)p.cs; a.tls_mu = (S)p.mu;
     a.partial = gnc_partial_.p;
     a.blocks_done = gnc_done_.p;
@@ -2821,7 +2821,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     std::vector<double> errors((size_t)std::max(o.inner_iterations, o.final_iterations) + 2);
     int ne = 0;
     const double c2 = o.delta * o.delta;
-    set_robust(ROBUST_TLS, o.delta, 1.0, mask);   // (the mask goes up once; the stages change mu alone)
+    set_robust(ROBUST_TLS, o.delta, 1.0, mask_bytes(mask, g_.n_edges()));   // (the mask goes up once; the stages change mu alone)
     scan();
     res->r2_max = sc.r2_max;
     res->mu0 = 2.0 * sc.r2_max > c2 ? c2 / (2.0 * sc.r2_max - c2) : 1.0;
@@ -2868,15 +2868,15 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     EdgeErrArgs<S> a;
     a.n_edges = E;
     a.is3d = is3d_ ? (has_lm_ ? 2 : 1) : 0;
-    a.kind = robust_kind_;
+    a.kind = settings_.robust_kind;
     a.e_rec = e_rec_.p;
     a.pose = pose_.p;
     a.e_idx = e_idx_.p;
     a.e_meas = e_meas_.p;
     a.e_info = e_info3_.p;
     a.node_dim = node_dim_.p;
-    a.delta = (S)robust_delta_;
-    a.delta2 = (S)(robust_delta_ * robust_delta_);
+    a.delta = (S)settings_.robust_delta;
+    a.delta2 = (S)(settings_.robust_delta * settings_.robust_delta);
     a.mask = robust_mask_.n ? robust_mask_.p : nullptr;
     a.s_out = s_dev;
     a.w_out = w_dev;
@@ -2955,13 +2955,12 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
       upload_grow(prior_info3_, info);
       upload_grow(prior_robust_, rob);
     }
-    priors_ = ps;
-    if (P == 0) priors_.keep_anchor = 1;
+    settings_.priors = ps;
+    if (P == 0) settings_.priors.keep_anchor = 1;
     prior_order_.swap(order);
     // the captured graphs hold the old kernel and its arguments
     drop_graphs();
   }
-  const PriorSet &priors() const override { return priors_; }
 
   // ---- fixed nodes (include/rr_pgo.h, rr_pgo_set_fixed)
   void refuse_fixed(const char *who) const override {
@@ -2977,14 +2976,12 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     HIPCHK(hipStreamSynchronize(stream_));   // launches already enqueued read the old set
     if (!nodes.empty()) upload_grow(fixed_, flag);
     else flag.clear();
-    fixed_nodes_ = nodes;
+    settings_.fixed = nodes;
     fixed_host_.swap(flag);
-    fixed_keep_anchor_ = nodes.empty() ? 1 : (keep_anchor != 0 ? 1 : 0);
+    settings_.fixed_keep_anchor = nodes.empty() ? 1 : (keep_anchor != 0 ? 1 : 0);
     // the captured graphs hold the old kernel and its arguments
     drop_graphs();
   }
-  const std::vector<int32_t> &fixed() const override { return fixed_nodes_; }
-  int fixed_keep_anchor() const override { return fixed_keep_anchor_; }
   bool is_fixed(int v) const { return !fixed_host_.empty() && fixed_host_[(size_t)v] != 0; }
 
   // ---- rr_pgo_initialize (include/rr_pgo.h; chordal.hip.h): the chordal relaxation from the measurements.
@@ -2992,7 +2989,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   // the handle's own launches, eagerly and without the gauge term (a held node makes the systems definite); the solved
   // vector of each is exported in reference order and its error flag read before the next stage is enqueued.  The state is
   // written by ONE launch, k_chordal_place, behind the last clean flag: every refusal and failure leaves it as it was.
-  int chordal_anchor() const { return (priors_.keep_anchor && fixed_keep_anchor_) ? g_.anchor_node : -1; }
+  int chordal_anchor() const { return (settings_.priors.keep_anchor && settings_.fixed_keep_anchor) ? g_.anchor_node : -1; }
   ChordalArgs<T, S> chordal_args() const {
     ChordalArgs<T, S> a;
     a.n_nodes = g_.n_nodes();
@@ -3012,11 +3009,11 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     a.n_zero_words = lds_flow_ ? 2 * sym_.S + 64 : 0;
     a.fill_words = lds_flow_ ? reinterpret_cast<unsigned *>(x_ptr_) : nullptr;
     a.n_fill_words = lds_flow_ ? (int)((size_t)g_.dim * sizeof(T) / 4) : 0;
-    a.prior_ptr = priors_.n() > 0 ? prior_ptr_.p : nullptr;
+    a.prior_ptr = settings_.priors.n() > 0 ? prior_ptr_.p : nullptr;
     a.prior_rec = prior_rec_.p;
     a.prior_meas = prior_meas_.p;
     a.prior_info = prior_info3_.p;
-    a.fixed = fixed_nodes_.empty() ? nullptr : fixed_.p;
+    a.fixed = settings_.fixed.empty() ? nullptr : fixed_.p;
     a.anchor = chordal_anchor();
     a.rot = chordal_rot_.p;
     return a;
@@ -3042,7 +3039,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
       std::vector<uint8_t> placed((size_t)N, 0);
       for (int k = 0; k < g_.n_edges(); k++)
         if (g_.edge_kind[k] == EDGE_SE2_XY || g_.edge_kind[k] == EDGE_SE3_XYZ) placed[(size_t)g_.edge_to[k]] = 1;
-      for (int32_t v : priors_.node) placed[(size_t)v] = 1;
+      for (int32_t v : settings_.priors.node) placed[(size_t)v] = 1;
       for (int i = 0; i < N; i++) {
         const int kind = g_.node_kind[i];
         if ((kind == NODE_XY || kind == NODE_XYZ) && !placed[(size_t)i] && !is_fixed(i) && i != anchor)
@@ -3064,7 +3061,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
       auto is_pose = [&](int v) { return g_.node_kind[(size_t)v] == NODE_SE2 || g_.node_kind[(size_t)v] == NODE_SE3; };
       for (int i = 0; i < N; i++)
         if (is_pose(i) && (is_fixed(i) || i == anchor)) grounded[(size_t)find(i)] = 1;
-      for (int32_t v : priors_.node)
+      for (int32_t v : settings_.priors.node)
         if (is_pose(v)) grounded[(size_t)find(v)] = 1;
       for (int i = 0; i < N; i++)
         if (is_pose(i) && !grounded[(size_t)find(i)])
@@ -3084,7 +3081,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
     na.pose = pose_.p;
     na.node_dim = node_dim_.p;
     na.node_offset = node_offset_.p;
-    na.fixed = fixed_nodes_.empty() ? nullptr : fixed_.p;
+    na.fixed = settings_.fixed.empty() ? nullptr : fixed_.p;
     na.anchor = anchor;
     na.sol_a = is3d_ ? chordal_sol_.p : dx_ref_.p;
     na.sol_b = dx_ref_.p;
@@ -3116,22 +3113,22 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
 
   void prior_errors(double *s_out, double *w_out) override {
     refuse_priors("rr_pgo_prior_errors");
-    const int P = priors_.n();
+    const int P = settings_.priors.n();
     if (P == 0) return;
     DevBuf<double> out;
     out.alloc(2 * (size_t)P);
     PriorErrArgs<S> a;
     a.n_priors = P;
     a.is3d = is3d_ ? (has_lm_ ? 2 : 1) : 0;
-    a.kind = robust_kind_;
+    a.kind = settings_.robust_kind;
     a.node = prior_node_.p;
     a.rec = prior_rec_.p;
     a.pose = pose_.p;
     a.meas = prior_meas_.p;
     a.info = prior_info3_.p;
     a.node_dim = node_dim_.p;
-    a.delta = (S)robust_delta_;
-    a.delta2 = (S)(robust_delta_ * robust_delta_);
+    a.delta = (S)settings_.robust_delta;
+    a.delta2 = (S)(settings_.robust_delta * settings_.robust_delta);
     a.robust = prior_robust_.p;
     const TlsParams tp = tls_params();
     a.tls_lo = (S)tp.lo; a.tls_hi = (S)tp.hi; a.tls_cs = (S)tp.cs; a.tls_mu = (S)tp.mu;
@@ -3161,10 +3158,8 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
       throw ApiError(RR_PGO_EUNSUPPORTED, w + ": " + std::to_string(sym_.n_big) + " fronts beyond LDS (n_big_fronts must be 0)" +
                                               (w == "rr_pgo_marginals" ? ": use rr_pgo_covariances with rr_pgo_set_query_big_fronts" : ""));
   }
-  void set_query_big_fronts(int on) override { query_big_ = on != 0; }
-  int query_big_fronts() const override { return query_big_ ? 1 : 0; }
-  void set_marginals_big_fronts(int on) override { marg_big_ = on != 0; }
-  int marginals_big_fronts() const override { return marg_big_ ? 1 : 0; }
+  void set_query_big_fronts(int on) override { settings_.query_big = on != 0; }
+  void set_marginals_big_fronts(int on) override { settings_.marg_big = on != 0; }
   // depth of every front, front of every permuted column, the four events of a call: made once
   void tree_tables(const char *who) {
     if (!front_depth_.empty()) return;
@@ -3312,7 +3307,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
 
   void marginals(int nq, const int32_t *na, const int32_t *nb, const int64_t *off, double *out) override {
     static constexpr const char *who = "rr_pgo_marginals";
-    require_f64_unsharded_lds_factor(who, !marg_big_);
+    require_f64_unsharded_lds_factor(who, !settings_.marg_big);
     if constexpr (f64_) {
       marginals_prepare(who);
       const Symbolic &sym = sym_;
@@ -3707,7 +3702,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   // ---- covariances of arbitrary node pairs (include/rr_pgo.h, rr_pgo_covariances; treesolve.hip.h, k_cov_pairs)
   void covariances(int nq, const int32_t *na, const int32_t *nb, const int64_t *off, double *out) override {
     static constexpr const char *who = "rr_pgo_covariances";
-    require_f64_unsharded_lds_factor(who, !query_big_);
+    require_f64_unsharded_lds_factor(who, !settings_.query_big);
     if constexpr (f64_) {
       covariances_prepare(who);
       tree_query(who, "pair", nq, na, nb, off, query_ms_[Q_COVARIANCES], false, [&](int q0, int q1, const TsPlan &pl) {
@@ -3734,7 +3729,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   void cross_covariances(int n_row, const int32_t *row_node, int n_col, const int32_t *col_node, const int64_t *roff,
                          const int64_t *coff, double *out) override {
     static constexpr const char *who = "rr_pgo_cross_covariances";
-    require_f64_unsharded_lds_factor(who, !query_big_);
+    require_f64_unsharded_lds_factor(who, !settings_.query_big);
     if constexpr (f64_) {
       covariances_prepare(who);
       const Symbolic &sym = sym_;
@@ -3861,7 +3856,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   void gate_edges(int n, const int32_t *from, const int32_t *to, const int64_t *soff, std::vector<GateCand> &cand, double *d2,
                   double *chi2, double *innov) override {
     static constexpr const char *who = "rr_pgo_gate_edges";
-    require_f64_unsharded_lds_factor(who, !query_big_);
+    require_f64_unsharded_lds_factor(who, !settings_.query_big);
     if constexpr (f64_) {
       covariances_prepare(who);
       const bool br = has_br_ || cand_has_br(cand);   // the BR kernel: the graph or the call holds a bearing / range edge
@@ -3900,11 +3895,11 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
 
   // ---- audit of the graph's own edges (include/rr_pgo.h, rr_pgo_check_edges; treesolve.hip.h, k_check_edges): the gate's plan
   // and records, for edges of the graph; the robust kind and delta travel in the arguments
-  void refuse_factor_query(const char *who) const override { require_f64_unsharded_lds_factor(who, !query_big_); }
+  void refuse_factor_query(const char *who) const override { require_f64_unsharded_lds_factor(who, !settings_.query_big); }
   void check_edges(int n, const int32_t *from, const int32_t *to, const int64_t *soff, std::vector<GateCand> &cand, double *d2,
                    double *red, double *chi2, double *resid) override {
     static constexpr const char *who = "rr_pgo_check_edges";
-    require_f64_unsharded_lds_factor(who, !query_big_);
+    require_f64_unsharded_lds_factor(who, !settings_.query_big);
     if constexpr (f64_) {
       covariances_prepare(who);
       const bool br = has_br_ || cand_has_br(cand);   // the BR kernel: the graph or the call holds a bearing / range edge
@@ -3931,10 +3926,10 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
         a.chi2 = ts_out_.p + nc;
         a.red = ts_out_.p + 2 * nc;
         a.rout = resid ? ts_out_.p + 3 * nc : nullptr;
-        a.delta = (T)robust_delta_;
-        a.delta2 = (T)(robust_delta_ * robust_delta_);
+        a.delta = (T)settings_.robust_delta;
+        a.delta2 = (T)(settings_.robust_delta * settings_.robust_delta);
         a.S = sym_.S;
-        a.rkind = robust_kind_;
+        a.rkind = settings_.robust_kind;
         const TlsParams tp = tls_params();
         a.tls_lo = (T)tp.lo; a.tls_hi = (T)tp.hi; a.tls_cs = (T)tp.cs; a.tls_mu = (T)tp.mu;
         if (has_lm_) hipLaunchKernelGGL((k_check_edges<T, 6, true>), dim3((unsigned)nc), dim3(COV_THREADS), 0, stream_, a);
@@ -3953,7 +3948,7 @@ template <typename T, typename S = T> class Engine final : public EngineBase {
   void gate_joint(int n_sets, const int32_t *set_ptr, const int32_t *from, const int32_t *to, const int32_t *dim,
                   const int64_t *ioff, std::vector<GateCand> &cand, double *d2, double *prefix, double *innov) override {
     static constexpr const char *who = "rr_pgo_gate_joint";
-    require_f64_unsharded_lds_factor(who, !query_big_);
+    require_f64_unsharded_lds_factor(who, !settings_.query_big);
     if constexpr (f64_) {
       covariances_prepare(who);
       const bool br = has_br_ || cand_has_br(cand);   // the BR kernel: the graph or the call holds a bearing / range edge
@@ -4571,9 +4566,42 @@ static double prior_bytes(const rr_pgo &h, const PriorSet &ps) {
   return bytes;
 }
 static void apply_priors(rr_pgo &h, const PriorSet &ps) {
-  const double before = prior_bytes(h, h.engine->priors());
+  const double before = prior_bytes(h, h.engine->settings().priors);
   h.engine->set_priors(ps);
-  h.stats.bytes_linearize += prior_bytes(h, h.engine->priors()) - before;
+  h.stats.bytes_linearize += prior_bytes(h, h.engine->settings().priors) - before;
+}
+
+// The settings of a handle's engine applied to the engine of the graph rebuilt from it (HandleSettings: the one list of what
+// is carried).  origin: the old index of every edge of nh's graph, -1 for a new one.  Node indices do not change, so the
+// priors and the fixed set go over as they are (new nodes are free); a setting still at its default skips its setter.
+static void carry_settings(const HandleSettings &s, rr_pgo &nh, const std::vector<int32_t> &origin) {
+  if (s.robust_kind != ROBUST_NONE) nh.engine->set_robust(s.robust_kind, s.robust_delta, s.robust_mu, reindex_edge_mask(s.robust_mask, origin));
+  if (s.priors.n() > 0) apply_priors(nh, s.priors);   // (through the statistics: bytes_linearize)
+  if (!s.fixed.empty()) nh.engine->set_fixed(s.fixed, s.fixed_keep_anchor);
+  nh.engine->set_query_big_fronts(s.query_big);
+  nh.engine->set_marginals_big_fronts(s.marg_big);
+}
+
+// The tail of rr_pgo_extend and rr_pgo_remove_edges: nh holds the finalized new graph and nothing else.  Its analysis and its
+// engine are built completely, the first n_state nodes of the state come from `state` (device memory of h's engine, whose
+// stream the caller has drained), the settings are carried, and only then the handles change sides: a throw leaves *h as it
+// was.  ms (rr_pgo::extend_ms or remove_ms): analysis, engine (host wall clock), ms_dev plus the state copy (HIP events).
+static void rebuild_and_swap(rr_pgo *h, std::unique_ptr<rr_pgo> nh, const std::vector<int32_t> &origin, const void *state, size_t n_state,
+                             double ms_dev, double (rr_pgo::*ms)[3]) {
+  const double t0 = now_ms();
+  analyze_handle(*nh, &h->opt, 0.0);
+  const double t1 = now_ms();
+  build_engine(*nh);
+  const double t2 = now_ms();
+  double t = 0;
+  nh->engine->adopt_state(state, n_state, &t);
+  carry_settings(h->engine->settings(), *nh, origin);
+  // ---- the swap: nothing below can fail.  The old engine (its stream drained by the caller, the copy out of its buffers waited
+  // for) goes with nh.  Every field changes sides (the engines refer to the pointees of g and symp, which do not move).
+  std::swap(*h, *nh);
+  (h->*ms)[0] = t1 - t0;
+  (h->*ms)[1] = t2 - t1;
+  (h->*ms)[2] = ms_dev + t;
 }
 
 static void extend_handle(rr_pgo *h, int32_t n_new_nodes, const int32_t *node_kind, const uint32_t *node_id, const double *node_state,
@@ -4640,43 +4668,17 @@ static void extend_handle(rr_pgo *h, int32_t n_new_nodes, const int32_t *node_ki
   }
   // ---- from here on the device.  The old stream is drained: its last launches wrote the state that is carried.
   HIPCHK(hipStreamSynchronize(h->engine->stream()));
-  double ms_dev = 0, t = 0;
-  if (guess) {
-    // (before the analysis, which reads the positions: on the OLD engine's stream, into a staging buffer of the grown state)
-    h->engine->guess_nodes(steps, tree_ptr, n_old, n_total, g.has_se3, g.node_kind.data() + n_old, g.node_state.data() + state_old, &t);
-    ms_dev += t;
-  }
-  const double t0 = now_ms();
-  analyze_handle(*nh, &h->opt, 0.0);
-  const double t1 = now_ms();
-  build_engine(*nh);
-  const double t2 = now_ms();
-  if (guess) nh->engine->adopt_state(h->engine->guess_dev(), (size_t)n_total, &t);
-  else nh->engine->adopt_state(h->engine->pose_dev(), (size_t)n_old, &t);
-  ms_dev += t;
-  int rk = ROBUST_NONE;
-  double rdelta = 1.0;
-  bool masked = false;
-  std::vector<int32_t> mask;
-  h->engine->robust_setting(&rk, &rdelta, &masked, mask);
-  if (rk != ROBUST_NONE) {
-    if (masked) mask.resize((size_t)g.n_edges(), 1);   // a fresh closure is robustified
-    nh->engine->set_robust(rk, rdelta, h->engine->robust_mu(), masked ? mask.data() : nullptr);
-  }
-  if (h->engine->priors().n() > 0) apply_priors(*nh, h->engine->priors());   // node indices do not change
-  if (!h->engine->fixed().empty()) nh->engine->set_fixed(h->engine->fixed(), h->engine->fixed_keep_anchor());   // new nodes are free
-  nh->engine->set_query_big_fronts(h->engine->query_big_fronts());
-  nh->engine->set_marginals_big_fronts(h->engine->marginals_big_fronts());
-  // ---- the swap: nothing below can fail.  The old engine (its stream drained above, the copy out of its buffers waited for)
-  // goes with nh.  Every field changes sides (the engines refer to the pointees of g and symp, which do not move).
-  std::swap(*h, *nh);
-  h->extend_ms[0] = t1 - t0;
-  h->extend_ms[1] = t2 - t1;
-  h->extend_ms[2] = ms_dev;
+  double ms_dev = 0;
+  // (before the analysis, which reads the positions: on the OLD engine's stream, into a staging buffer of the grown state)
+  if (guess) h->engine->guess_nodes(steps, tree_ptr, n_old, n_total, g.has_se3, g.node_kind.data() + n_old, g.node_state.data() + state_old, &ms_dev);
+  std::vector<int32_t> origin((size_t)g.n_edges(), -1);   // the old edges keep their indices, the new ones follow
+  for (int k = 0; k < e_old; k++) origin[(size_t)k] = k;
+  rebuild_and_swap(h, std::move(nh), origin, guess ? h->engine->guess_dev() : h->engine->pose_dev(), (size_t)(guess ? n_total : n_old), ms_dev,
+                   &rr_pgo::extend_ms);
 }
 
-// rr_pgo_remove_edges behind its argument checks: the graph without the listed edges, its analysis and engine built completely,
-// the device state and the settings carried as rr_pgo_extend carries them, then the swap
+// rr_pgo_remove_edges behind its argument checks: the graph without the listed edges, then rebuild_and_swap with the surviving
+// edges' old indices
 static void remove_handle(rr_pgo *h, int32_t n_remove, const int32_t *edge) {
   const HostGraph &og = *h->g;
   const int N = og.n_nodes(), E = og.n_edges();
@@ -4697,32 +4699,7 @@ static void remove_handle(rr_pgo *h, int32_t n_remove, const int32_t *edge) {
   if (!err.empty()) throw ApiError(RR_PGO_EINVAL, "rr_pgo_remove_edges: " + err);
   // ---- from here on the device.  The old stream is drained: its last launches wrote the state that is carried.
   HIPCHK(hipStreamSynchronize(h->engine->stream()));
-  const double t0 = now_ms();
-  analyze_handle(*nh, &h->opt, 0.0);
-  const double t1 = now_ms();
-  build_engine(*nh);
-  const double t2 = now_ms();
-  double ms_dev = 0;
-  nh->engine->adopt_state(h->engine->pose_dev(), (size_t)N, &ms_dev);
-  int rk = ROBUST_NONE;
-  double rdelta = 1.0;
-  bool masked = false;
-  std::vector<int32_t> mask, kept_mask;
-  h->engine->robust_setting(&rk, &rdelta, &masked, mask);
-  if (rk != ROBUST_NONE) {
-    if (masked)
-      for (int k : keep) kept_mask.push_back(mask[k]);
-    nh->engine->set_robust(rk, rdelta, h->engine->robust_mu(), masked ? kept_mask.data() : nullptr);
-  }
-  if (h->engine->priors().n() > 0) apply_priors(*nh, h->engine->priors());   // node indices do not change
-  if (!h->engine->fixed().empty()) nh->engine->set_fixed(h->engine->fixed(), h->engine->fixed_keep_anchor());
-  nh->engine->set_query_big_fronts(h->engine->query_big_fronts());
-  nh->engine->set_marginals_big_fronts(h->engine->marginals_big_fronts());
-  // ---- the swap, as in extend_handle: nothing below can fail
-  std::swap(*h, *nh);
-  h->remove_ms[0] = t1 - t0;
-  h->remove_ms[1] = t2 - t1;
-  h->remove_ms[2] = ms_dev;
+  rebuild_and_swap(h, std::move(nh), keep, h->engine->pose_dev(), (size_t)N, 0.0, &rr_pgo::remove_ms);
 }
 
 }  // namespace
@@ -4919,7 +4896,7 @@ int rr_pgo_set_robust_kernel(rr_pgo *h, int32_t kind, double delta, const int32_
     return RR_PGO_EINVAL;
   }
   static_assert(RR_PGO_ROBUST_HUBER == ROBUST_HUBER && RR_PGO_ROBUST_CAUCHY == ROBUST_CAUCHY, "robust kernel numbering");
-  return guarded([&] { h->engine->set_robust(kind, delta, 0.0, edge_mask); });
+  return guarded([&] { h->engine->set_robust(kind, delta, 0.0, mask_bytes(edge_mask, h->g->n_edges())); });
 }
 
 int rr_pgo_set_robust_tls(rr_pgo *h, double delta, double mu, const int32_t *edge_mask) {
@@ -4929,7 +4906,7 @@ int rr_pgo_set_robust_tls(rr_pgo *h, double delta, double mu, const int32_t *edg
     return RR_PGO_EINVAL;
   }
   static_assert(RR_PGO_ROBUST_TLS == ROBUST_TLS, "robust kernel numbering");
-  return guarded([&] { h->engine->set_robust(ROBUST_TLS, delta, mu, edge_mask); });
+  return guarded([&] { h->engine->set_robust(ROBUST_TLS, delta, mu, mask_bytes(edge_mask, h->g->n_edges())); });
 }
 
 int rr_pgo_set_robust_mu(rr_pgo *h, double mu) {
@@ -4941,14 +4918,10 @@ int rr_pgo_set_robust_mu(rr_pgo *h, double mu) {
 int rr_pgo_get_robust(const rr_pgo *h, int32_t *kind, double *delta, double *mu) {
   if (!h) { g_last_error = "null argument"; return RR_PGO_EINVAL; }
   return guarded([&] {
-    int rk = ROBUST_NONE;
-    double rdelta = 1.0;
-    bool masked = false;
-    std::vector<int32_t> mask;
-    h->engine->robust_setting(&rk, &rdelta, &masked, mask);
-    if (kind) *kind = rk;
-    if (delta) *delta = rdelta;
-    if (mu) *mu = h->engine->robust_mu();
+    const HandleSettings &s = h->engine->settings();
+    if (kind) *kind = s.robust_kind;
+    if (delta) *delta = s.robust_delta;
+    if (mu) *mu = s.robust_mu;
   });
 }
 
@@ -5188,7 +5161,7 @@ int rr_pgo_set_priors(rr_pgo *h, int32_t n_priors, const int32_t *node, const do
   return guarded([&] { apply_priors(*h, ps); });
 }
 
-int32_t rr_pgo_num_priors(const rr_pgo *h) { return h ? h->engine->priors().n() : 0; }
+int32_t rr_pgo_num_priors(const rr_pgo *h) { return h ? h->engine->settings().priors.n() : 0; }
 
 int rr_pgo_set_fixed(rr_pgo *h, int32_t n_fixed, const int32_t *node, int32_t keep_anchor) {
   if (!h) { g_last_error = "null argument"; return RR_PGO_EINVAL; }
@@ -5211,13 +5184,13 @@ int rr_pgo_set_query_big_fronts(rr_pgo *h, int32_t on) {
   if (!h) { g_last_error = "rr_pgo_set_query_big_fronts: no handle"; return RR_PGO_EINVAL; }
   return guarded([&] { h->engine->set_query_big_fronts(on); });
 }
-int32_t rr_pgo_get_query_big_fronts(const rr_pgo *h) { return h ? (int32_t)h->engine->query_big_fronts() : 0; }
+int32_t rr_pgo_get_query_big_fronts(const rr_pgo *h) { return h && h->engine->settings().query_big ? 1 : 0; }
 
 int rr_pgo_set_marginals_big_fronts(rr_pgo *h, int32_t on) {
   if (!h) { g_last_error = "rr_pgo_set_marginals_big_fronts: no handle"; return RR_PGO_EINVAL; }
   return guarded([&] { h->engine->set_marginals_big_fronts(on); });
 }
-int32_t rr_pgo_get_marginals_big_fronts(const rr_pgo *h) { return h ? (int32_t)h->engine->marginals_big_fronts() : 0; }
+int32_t rr_pgo_get_marginals_big_fronts(const rr_pgo *h) { return h && h->engine->settings().marg_big ? 1 : 0; }
 
 int rr_pgo_initialize(rr_pgo *h, int32_t method) {
   if (!h) { g_last_error = "rr_pgo_initialize: no handle"; return RR_PGO_EINVAL; }
@@ -5230,11 +5203,11 @@ int rr_pgo_initialize_times(const rr_pgo *h, double *ms) {
   return RR_PGO_OK;
 }
 
-int32_t rr_pgo_num_fixed(const rr_pgo *h) { return h ? (int32_t)h->engine->fixed().size() : 0; }
+int32_t rr_pgo_num_fixed(const rr_pgo *h) { return h ? (int32_t)h->engine->settings().fixed.size() : 0; }
 
 int rr_pgo_get_fixed(const rr_pgo *h, int32_t *out) {
   if (!h) { g_last_error = "null argument"; return RR_PGO_EINVAL; }
-  const std::vector<int32_t> &f = h->engine->fixed();
+  const std::vector<int32_t> &f = h->engine->settings().fixed;
   if (!f.empty() && !out) { g_last_error = "rr_pgo_get_fixed: null argument (out is required)"; return RR_PGO_EINVAL; }
   if (!f.empty()) std::memcpy(out, f.data(), f.size() * sizeof(int32_t));
   return RR_PGO_OK;
@@ -5351,12 +5324,9 @@ int rr_pgo_check_edges(rr_pgo *h, int32_t n_query, const int32_t *edge, double *
   std::vector<GateCand> cand;
   std::vector<int64_t> soff;
   if (const int rc = gate_candidates(api, h, n_query, kind.data(), from.data(), to.data(), meas.data(), info.data(), cand, soff, "query")) return rc;
-  int rk = ROBUST_NONE;
-  double rdelta = 1.0;
-  bool masked = false;
-  std::vector<int32_t> mask;
-  h->engine->robust_setting(&rk, &rdelta, &masked, mask);
-  for (int q = 0; q < n_query; q++) cand[q].pad = rk != ROBUST_NONE && (!masked || mask[edge ? edge[q] : q]) ? 1 : 0;
+  const HandleSettings &rs = h->engine->settings();   // (the mask is read in place)
+  for (int q = 0; q < n_query; q++)
+    cand[q].pad = rs.robust_kind != ROBUST_NONE && (rs.robust_mask.empty() || rs.robust_mask[edge ? edge[q] : q]) ? 1 : 0;
   const int rc = guarded([&] { h->engine->check_edges(n_query, from.data(), to.data(), soff.data(), cand, d2_out, redundancy_out, chi2_out, resid_out); });
   if (rc == RR_PGO_OK && resid_offset) std::copy(soff.begin(), soff.end(), resid_offset);
   return rc;

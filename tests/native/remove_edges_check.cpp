@@ -1,5 +1,6 @@
 // The host-only part of rr_pgo_remove_edges (csrc/host_graph.h, csrc/g2o_loader.cpp), on the CPU: the orphan check, the
-// compaction of what remains and the anchor rule of HostGraph::finalize.  Prints "ok" and returns 0, or says what failed.
+// compaction of what remains, the anchor rule of HostGraph::finalize, and the re-indexing of the robust edge mask that
+// rr_pgo_extend shares with it.  Prints "ok" and returns 0, or says what failed.
 #include <cstdio>
 #include <vector>
 
@@ -60,6 +61,27 @@ int main() {
     if (g.edge_meas[(size_t)g.edge_meas_off[q]] != k + 0.25 || g.edge_info[(size_t)g.edge_info_off[q]] != 100.0 + k) return fail("a survivor's measurement and information");
   }
   if (g.edge_meas.size() != 2 + 3 * 3 + 2 * 2 || g.edge_info.size() != 3 + 3 * 6 + 2 * 3) return fail("packed lengths");
+  // reindex_edge_mask, the robust mask of a rebuilt graph, for the two shapes of `origin` its callers have: rr_pgo_extend's
+  // (0 .. E - 1, then -1 per new edge) and rr_pgo_remove_edges' (`keep` above)
+  const std::vector<uint8_t> none, mask = {1, 0, 0, 1, 1, 0, 1, 0};
+  std::vector<int32_t> grown((size_t)E + 3, -1);
+  for (int k = 0; k < E; k++) grown[(size_t)k] = k;
+  if (!reindex_edge_mask(none, grown).empty() || !reindex_edge_mask(none, keep).empty()) return fail("an empty mask (every edge) stays empty");
+  if (reindex_edge_mask(mask, grown) != std::vector<uint8_t>{1, 0, 0, 1, 1, 0, 1, 0, 1, 1, 1}) return fail("extend: the old entries, then 1 per new edge");
+  grown.resize((size_t)E);
+  if (reindex_edge_mask(mask, grown) != mask) return fail("extend without a new edge: the mask as it was");
+  const std::vector<uint8_t> kept = reindex_edge_mask(mask, keep);
+  if (kept.size() != keep.size()) return fail("remove: one entry per surviving edge");
+  for (size_t q = 0; q < keep.size(); q++)
+    if (kept[q] != mask[(size_t)keep[q]]) return fail("remove: mask[keep]");
+  if (kept != std::vector<uint8_t>{1, 0, 1, 1, 1, 0}) return fail("remove: the survivors' entries in their order");
+  // a removal list with duplicates in any order flags each edge once: `keep` is ascending and without repeats, and so is the mask's
+  std::vector<char> gone2((size_t)E, 0);
+  for (int k : {7, 0, 7, 3, 0}) gone2[(size_t)k] = 1;
+  HostGraph g2;
+  const std::vector<int32_t> keep2 = copy_without_edges(og, gone2.data(), g2);
+  if (keep2 != std::vector<int32_t>{1, 2, 4, 5, 6}) return fail("duplicates count once, order kept");
+  if (reindex_edge_mask(mask, keep2) != std::vector<uint8_t>{0, 0, 1, 0, 1}) return fail("remove with duplicates: mask[keep]");
   std::printf("ok\n");
   return 0;
 }

@@ -136,6 +136,79 @@ def test_robust_mask_priors_fixed_set_and_solver_are_carried(api):
     assert np.array_equal(c.edge_errors()[1], wc0[keep]) and np.any(wc0[keep] < 1.0)
 
 
+def test_every_setting_at_once_through_extend_then_remove(api):
+    """A handle dressed with every setting there is -- a masked kernel, priors with robust flags and keep_anchor off, a fixed
+    set with keep_anchor off, both big-front switches -- goes through extend and then remove_edges of exactly the added edges.
+    After the extend it is a fresh handle on the grown graph dressed alike, the mask extended by ones; after the removal it
+    is the twin that was never rebuilt: every comparison is of bits.  A second pass reads the getters alone under truncated
+    least squares, so that mu is seen to survive (delta as in tests/test_gnc_gpu.py's carry test; mu there is the last stage
+    of a run, mu0 * 1.4^k: any such value does, the getter must return its bits)."""
+    from extend_cases import closures_only
+    from priors_reference import random_priors
+    PoseGraph = api[0]
+    c = closures_only("simulation-pose-landmark", K_EDGES)
+    ek, ef, et, em, ei, _, _ = c.addition
+    nk = np.asarray(c.base[0])
+    poses, lms = np.flatnonzero(nk == 0), np.flatnonzero(nk == 1)
+    node, meas, info = random_priors(np.random.default_rng(5), c.base, [int(poses[3]), int(poses[len(poses) // 2]), int(lms[0])])
+    fixed = sorted(int(v) for v in (poses[10], poses[11], lms[-1]))
+    mask = (np.arange(c.e_base) % 3 != 0).astype(np.int32)
+    grown_mask = np.concatenate([mask, np.ones(K_EDGES, np.int32)])
+    added = np.arange(c.e_base, c.e_base + K_EDGES)
+
+    def dress(g, m, tls=None):
+        if tls:
+            g.set_robust_tls(*tls, m)
+        else:
+            g.set_robust_kernel("cauchy", 1.0, m)
+        g.set_priors(node, meas, info, robust=[1, 0, 1], keep_anchor=False)
+        g.set_fixed(fixed, keep_anchor=False)
+        g.query_big_fronts = True
+        g.marginals_big_fronts = True
+
+    def told(g):
+        """what the getters say, and what the settings do to the errors at the current state"""
+        return (g.global_error(), *g.edge_errors(), *g.prior_errors(), np.array(g.robust_setting), g.num_priors, g.fixed_nodes(),
+                g.query_big_fronts, g.marginals_big_fronts)
+
+    def same(x, y):
+        assert len(x) == len(y) and all(np.array_equal(p, q) for p, q in zip(x, y))
+
+    a, twin, fresh = PoseGraph.from_arrays(*c.base), PoseGraph.from_arrays(*c.base), PoseGraph.from_arrays(*c.grown)
+    dress(a, mask)
+    dress(twin, mask)
+    dress(fresh, grown_mask)
+    a.optimize(2)
+    s = a.state()
+    for g in (a, twin, fresh):    # all three get the SAME array through set_state, so that all hold the same bits
+        g.set_state(s)
+    assert a.extend(ek, ef, et, em, ei) == (c.n_base, c.e_base)
+    same_graph(a, fresh)
+    ta = told(a)
+    assert ta[5].tolist() == [2, 1.0, 0.0] and ta[6] == 3 and list(ta[7]) == fixed and ta[8] is True and ta[9] is True
+    assert np.all(ta[2][:c.e_base][mask == 0] == 1.0) and np.any(ta[2] < 1.0) and np.any(ta[4] < 1.0) and ta[4][1] == 1.0
+    same(ta, told(fresh))
+    a.remove_edges(added)
+    same_graph(a, twin)
+    same(told(a), told(twin))
+    ea, na = a.optimize(3, return_norms=True)
+    eb, nb = twin.optimize(3, return_norms=True)
+    assert np.array_equal(ea, eb) and np.array_equal(na, nb) and np.array_equal(a.state(), twin.state())
+    assert np.all(np.isfinite(ea))
+    # the getters and the errors alone (no iteration) under truncated least squares
+    tls = (3.3682, 1.4 ** 9)
+    t, t_twin, t_fresh = PoseGraph.from_arrays(*c.base), PoseGraph.from_arrays(*c.base), PoseGraph.from_arrays(*c.grown)
+    dress(t, mask, tls)
+    dress(t_twin, mask, tls)
+    dress(t_fresh, grown_mask, tls)
+    t.extend(ek, ef, et, em, ei)
+    assert t.robust_setting == (3, *tls)
+    same(told(t), told(t_fresh))
+    t.remove_edges(added)
+    assert t.robust_setting == (3, *tls)
+    same(told(t), told(t_twin))
+
+
 # ---- 4. the anchor
 @pytest.mark.parametrize("name", ["triangle", "clique5", "landmarks-1-3"])
 def test_anchor_moves_when_the_first_pose_pose_edge_goes(api, name):
